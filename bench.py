@@ -23,9 +23,14 @@ milliseconds under load to leave its idle clock state (measured: 10 warm-up + 50
 picks, an untimed device warm-up (--prewarm-ms, default 60 ms of launches) precedes the W warm-up steps; the timed
 region is still exactly K steps between barrier + synchronize.
 
-After -- and outside -- the timed region, rank 0 at N = 1 also reports: `parity_rel_err` (one trajectory of the timed kernel's
-output against the C oracle), `cpu_baseline` (C port, all granted cores) and `cpu_baseline_numpy` (single-process NumPy
-batched restatement), and `secondary` (bounded runs of BASELINE configs[2], [3], [4]; tools/secondary_bench.py).
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the result line (at N > 1 also the result
+all-gather, unless --no-gather).  With --full, after -- and
+outside -- the timed region, rank 0 at N = 1 also reports: `parity_rel_err` (one trajectory of the timed kernel's output against
+the C oracle), `cpu_baseline` (C port, all granted cores) and `cpu_baseline_numpy` (single-process NumPy batched restatement),
+and `secondary` (bounded runs of BASELINE configs[2], [3], [4]; tools/secondary_bench.py); at N > 1, `secondary_sharded`.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path returned in its last step (rank 0's shard) as
+DIR/<name>.npy (dump_outputs below).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 --backend gloo --stub-step replaces the HIP launch by a CPU tensor op: the CPU rehearsal of the launcher / barrier /
 max-over-ranks / all-gather code path (tests/test_bench_launcher_cpu.py).  Its line is marked "stub": true and is not a
@@ -225,6 +230,39 @@ def cpu_baseline_numpy(batch, T, n, m, target_seconds=4.0):
                       f"numpy.linalg.solve, Python loop over T), one process"}
 
 
+# what work.results() holds, in order: the arrays a caller of the timed path receives
+OUTPUT_NAMES = {"lqr": ("L",), "n64": ("L",), "ilqr": ("xTraj", "uTraj", "L", "J", "converged"),
+                "ddp": ("xTraj", "uTraj", "L", "J", "converged"), "mpc": ("u0", "xTraj", "uTraj", "optimal")}
+DUMP_BUDGET_BYTES = 63 * 10 ** 6       # the 64 MB cap on a dump, less room for the .npy headers
+
+
+def dump_outputs(work, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """The results of the last timed step as <out_dir>/<name>.npy: float32 arrays stay float32, everything else is written as
+    float64.  When all of them together exceed `budget` bytes, every array is cut to the same fixed, seeded sample of items along
+    the batch axis (ascending order), so two builds run with the same arguments write the same items.  Returns what was written."""
+    import numpy as np
+    import torch
+    arrays = []
+    for name, x in zip(OUTPUT_NAMES[work.name], work.results()):
+        t = torch.as_tensor(x)
+        dt = torch.float32 if t.dtype == torch.float32 else torch.float64
+        arrays.append((name, t, dt))
+    items = arrays[0][1].shape[0]
+    per_item = sum((t[0].numel() if items else 0) * (4 if dt == torch.float32 else 8) for _, t, dt in arrays)
+    keep = items if per_item * items <= budget else max(1, budget // per_item)
+    idx = None
+    if keep < items:
+        idx = np.sort(np.random.default_rng(seed).choice(items, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, t, dt in arrays:
+        if idx is not None:
+            t = t.index_select(0, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
+        files.append(name + ".npy")
+    return {"dir": out_dir, "files": files, "items": int(keep), "of_items": int(items)}
+
+
 def parity_of_timed_output(work, ntraj=4):
     """Checker leg: the first `ntraj` trajectories of the LAST timed launch's gains against oracle/riccati_oracle.c."""
     import numpy as np
@@ -251,9 +289,15 @@ def parse_args(argv):
     ap.add_argument("--T", type=int, default=None)
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--m", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the post-timing check of the kernel's output against the C oracle")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bounded runs of BASELINE configs[2..4] after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the parity check against the C oracle, the CPU baselines and the bounded runs of "
+                         "BASELINE configs[2..4] (secondary at N = 1, secondary_sharded at N > 1); a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0's "
+                         "shard; float32 / float64; a fixed seeded sample of items when the whole exceeds 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true", help="(with --full) skip the post-timing check of the kernel's output against the C oracle")
+    ap.add_argument("--no-secondary", action="store_true", help="(with --full) skip the bounded runs of BASELINE configs[2..4] after the timed region")
     ap.add_argument("--secondary-budget-s", type=float, default=25.0)
     ap.add_argument("--prewarm-ms", type=float, default=60.0,
                     help="untimed device warm-up before the W warm-up steps: launches until this much time has passed, so that a "
@@ -537,6 +581,9 @@ def run_rank(args):
     comm = Comm(dist, world, torch.device("cpu") if host_staged else work.dev)
     comm.host_staged = host_staged
     elapsed, kern_ms, nev = timed_steps(work, comm, steps, warmup, args.prewarm_ms)
+    if rank == 0 and args.dump_outputs:
+        d = dump_outputs(work, args.dump_outputs)
+        print(f"bench.py: wrote {', '.join(d['files'])} to {d['dir']} ({d['items']} of {d['of_items']} items)", file=sys.stderr)
     job_units = comm.reduce(float(work.units_per_step), "sum")      # ragged shards: the job's units are the sum over ranks
     devices = comm.names(work.device_name())
 
@@ -606,10 +653,10 @@ def run_rank(args):
             res["secondary_sharded"] = sharded
         if parity is not None:
             res["parity_rel_err"] = parity
-        if world == 1 and args.workload == "lqr" and not args.no_cpu_baseline:
+        if args.full and world == 1 and args.workload == "lqr" and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(batch, T, n, m)
             res["cpu_baseline_numpy"] = cpu_baseline_numpy(batch, T, n, m)
-        if world == 1 and args.workload == "lqr" and not work.stub and not args.no_secondary:
+        if args.full and world == 1 and args.workload == "lqr" and not work.stub and not args.no_secondary:
             del work.sets                      # free the 1.15 GB of headline inputs before the secondary workloads
             torch.cuda.empty_cache()
             from tools import secondary_bench
@@ -632,11 +679,11 @@ def run_rank(args):
         if args.workload == "n64" and "error" not in legs["gather"]:
             legs["gather"]["overlap"] = overlapped_gather_leg(work, comm)
 
-    if rank == 0 and args.workload == "lqr" and not work.stub and not args.no_parity:
+    if args.full and rank == 0 and args.workload == "lqr" and not work.stub and not args.no_parity:
         legs["parity"] = parity_of_timed_output(work)      # checker leg (oracle/riccati_oracle.c), after the timing; rank-local, no collective
 
     # N > 1, headline workload: the configs BASELINE defines as multi-GPU, strong-sharded over the same ranks (every rank takes part)
-    if world > 1 and args.workload == "lqr" and not args.no_secondary:
+    if args.full and world > 1 and args.workload == "lqr" and not args.no_secondary:
         legs["sharded"] = sharded_secondary(args, comm, world, rank, local_rank, work, dog)
     if dist.is_initialized():
         if dog:

@@ -113,9 +113,9 @@ def test_every_workload_shards_and_gathers(workload, ranks, scaling, batch):
 
 
 def test_headline_at_two_ranks_carries_the_sharded_configs():
-    """N > 1 with the default workload: after the headline, configs[2], [3] (iLQR and DDP) and [4] run strong-sharded over the
-    same ranks, each with its result gather -- what a driver SCALE pass over N = 1, 2, 4, 8 records for them."""
-    out = _run([sys.executable, BENCH, "--gpus", "2"] + STUB, _clean_env())
+    """N > 1 with the default workload and --full: after the headline, configs[2], [3] (iLQR and DDP) and [4] run strong-sharded
+    over the same ranks, each with its result gather -- what a driver SCALE pass over N = 1, 2, 4, 8 records for them."""
+    out = _run([sys.executable, BENCH, "--gpus", "2", "--full"] + STUB, _clean_env())
     assert out.returncode == 0, out.stderr[-2000:]
     res = _one_json_line(out.stdout)
     sh = res["secondary_sharded"]
@@ -125,8 +125,60 @@ def test_headline_at_two_ranks_carries_the_sharded_configs():
         assert e["scaling"] == "strong" and e["job_items"] == 16 and e["items_rank0"] == 8 and e["value"] > 0
         assert "error" not in e["allgather"] and e["allgather"]["items"] == 16
     assert "overlap" in sh["configs[4]_n64"]["allgather"]
-    out = _run([sys.executable, BENCH, "--gpus", "2", "--no-secondary"] + STUB, _clean_env())
+    out = _run([sys.executable, BENCH, "--gpus", "2", "--full", "--no-secondary"] + STUB, _clean_env())
     assert out.returncode == 0 and "secondary_sharded" not in _one_json_line(out.stdout)
+    out = _run([sys.executable, BENCH, "--gpus", "2"] + STUB, _clean_env())           # a plain run: the headline alone
+    assert out.returncode == 0 and "secondary_sharded" not in _one_json_line(out.stdout)
+
+
+def test_plain_single_rank_line_has_only_the_headline():
+    """`--gpus 1` without --full: no parity check, CPU baselines or secondary configs (they cost tens of seconds each)"""
+    out = _run([sys.executable, BENCH, "--gpus", "1", "--backend", "gloo", "--stub-step", "--steps", "3", "--warmup", "1", "--batch", "6",
+                "--T", "5"], _clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    res = _one_json_line(out.stdout)
+    assert res["steps"] == 3 and res["ms_per_step"] > 0
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in res
+    for key in ("cpu_baseline", "cpu_baseline_numpy", "parity_rel_err", "secondary", "secondary_sharded"):
+        assert key not in res
+
+
+@pytest.mark.parametrize("workload,names", [("lqr", ["L"]), ("ilqr", ["xTraj", "uTraj", "L", "J", "converged"]),
+                                            ("mpc", ["u0", "xTraj", "uTraj", "optimal"])])
+def test_dump_outputs_writes_the_last_step(workload, names, tmp_path):
+    """--dump-outputs DIR: the result tuple of the timed path's last step, one float .npy per array, equal to what the step computed
+    (the stub's values are a known function of the item index)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from tools import workloads as wl
+    out = _run([sys.executable, BENCH, "--gpus", "1", "--workload", workload, "--dump-outputs", str(tmp_path)] + STUB, _clean_env())
+    assert out.returncode == 0, out.stderr[-2000:]
+    _one_json_line(out.stdout)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(n + ".npy" for n in names)
+    for name, ref in zip(names, wl.StubWorkload.expected(workload, 6, T=5)):
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype in (np.float32, np.float64)
+        assert np.array_equal(got, ref.double().numpy())
+
+
+def test_dump_outputs_samples_a_large_result_the_same_way_every_time(tmp_path):
+    """past the byte budget every array keeps the same fixed, seeded rows, in ascending order"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from tools import workloads as wl
+    work = wl.StubWorkload("ilqr", 0, 40, 40, rank=0, T=5)
+    work.step(0)
+    per_item = 8 * (6 * 12 + 5 * 4 + 5 * 4 * 12 + 1 + 1)
+    a = bench.dump_outputs(work, str(tmp_path / "a"), budget=10 * per_item)
+    b = bench.dump_outputs(work, str(tmp_path / "b"), budget=10 * per_item)
+    assert a["items"] == 10 and a["of_items"] == 40
+    rows = (np.load(tmp_path / "a" / "xTraj.npy").reshape(10, -1)[:, 0] // 1000).astype(int)   # the stub's item g starts at 1000 g
+    assert list(rows) == sorted(set(rows))
+    for name, full in zip(bench.OUTPUT_NAMES["ilqr"], wl.StubWorkload.expected("ilqr", 40, T=5)):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.array_equal(x, y) and np.array_equal(x, full.double().numpy()[rows])
 
 
 def test_strong_scaling_of_the_headline_and_force_dist():
