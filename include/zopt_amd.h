@@ -447,6 +447,27 @@ int zm_mpc_solve_relaxed_f64(const double* A, const double* B, const double* K, 
                              int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj, int32_t* status,
                              int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream);
 
+/* Per-problem data (reference: zopt/mpcUtils.py:14-81, class lqrMpc, one problem per object there): P problems of the same
+ * (N, n, m), each with its own A, B, Q, R, Qf, bounds and penalty, set up and solved in one launch each.
+ * zm_mpc_setup_batched_f64: the tables of zm_mpc_setup_f64 for every problem p and level l, bit for bit those of P * L calls of it
+ *     (one workgroup per (p, l), the same arithmetic).
+ *     in : A (P,n,n) B (P,n,m) Q (P,n,n) R (P,m,m) Qf (P,n,n) rho (P,L) -- the penalty of each (problem, level)   [device]
+ *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m), problem-major (one problem's levels are contiguous)                    [device] */
+int zm_mpc_setup_batched_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
+                             const double* rho, int64_t P, int L, int N, int n, int m, double* K, double* Minv, void* stream);
+/* zm_mpc_solve_batched_f64: zm_mpc_solve_relaxed_f64 with per-problem data.  Instance i solves problem problem[i] in [0, P): A (P,n,n),
+ * B (P,n,m), K / Minv (P,n_levels,N,...) from zm_mpc_setup_batched_f64, bounds (P,n) / (P,m), rho (P) -- the penalty of level0 of
+ * each problem (the levels are rho[p] * rho_step^(l - level0)); x0, workspace and outputs as in zm_mpc_solve_relaxed_f64.  Same
+ * dispatch (16 lanes per instance where the shape and horizon fit it and ZOPT_AMD_MPC_PATH is not `lane`, else one lane per instance at
+ * the fixed penalty of level0), same bits per instance as a zm_mpc_solve_relaxed_f64 call on its problem alone.  Reads the index map
+ * back to the host to check it (ZM_EINVAL for an index outside [0, P)), so the call waits for the work queued on `stream` before it. */
+int zm_mpc_solve_batched_f64(const double* A, const double* B, const double* K, const double* Minv, int n_levels, int level0,
+                             double rho_step, double alpha, const double* x_lb, const double* x_ub, const double* u_lb,
+                             const double* u_ub, const double* x0, const double* rho, const int32_t* problem, int64_t P,
+                             double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace,
+                             double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N,
+                             int n, int m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

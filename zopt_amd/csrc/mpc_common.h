@@ -32,7 +32,15 @@ struct MpcTabs {
     const double *A, *B, *K, *Minv, *x_lb, *x_ub, *u_lb, *u_ub;
 };
 
+// per-problem data (zm_mpc_solve_batched_f64): instance i solves problem prob[i] in [0, P), whose A, B, bounds and tables sit at
+// p x their single-problem size in the MpcTabs arrays (tables: p x n_levels levels), with the penalty rho[p]
+struct MpcProb {
+    const int* prob;
+    const double* rho;
+};
+
 // mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.
 int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, int n, int m, hipStream_t st);
+int mpc_wave_dispatch_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st);
 
 }  // namespace zm
