@@ -67,3 +67,104 @@ def random_ilqr_model(batch: int, T: int, n: int, m: int, seed: int = 0):
     v_x = rng.standard_normal((batch, n))
     v = rng.standard_normal(batch)
     return (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Hard-spectrum designs for the DARE and the finite-horizon sweep: each generator returns (A, B, Q, R), float64 arrays with a leading
+# batch axis, with ONE known hard feature (tests/test_hp_reference.py asserts that each generator has it).
+def _stable_block(rng, k, rho):
+    G = rng.standard_normal((k, k))
+    return rho * G / np.max(np.abs(np.linalg.eigvals(G)))
+
+
+def _spd(rng, k):
+    M = rng.standard_normal((k, k))
+    return M @ M.T / k + np.eye(k)
+
+
+def slow_unreachable_mode(batch: int, n: int, m: int, seed: int = 0, lam: float = 0.999, coupling: float = 0.0):
+    """A random stable block (rho = 0.6) on states 0..n-2 plus a slow stable mode lam on state n-1 that the input cannot reach
+    (B[n-1] = 0, A[n-1, :n-1] = 0); Q = R = I.  Its value entry 1/(1 - lam^2) ~ 500 dominates P, but with coupling = 0 the gain does
+    not see it at all.  coupling > 0: the slow state drives the block (A[:n-1, n-1] ~ coupling), so the gain converges as slowly."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = np.zeros((batch, n, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _stable_block(rng, n - 1, 0.6)
+        A[i, :n - 1, n - 1] = coupling * rng.standard_normal(n - 1)
+        A[i, n - 1, n - 1] = lam
+        B[i, :n - 1] = rng.standard_normal((n - 1, m))
+    return A, B, np.tile(np.eye(n), (batch, 1, 1)), np.tile(np.eye(m), (batch, 1, 1))
+
+
+def weakly_detectable_unstable(batch: int, n: int, m: int, seed: int = 0, lam: float = 1.001, q: float = 1e-6):
+    """An unstable mode lam on state n-1, reached by B, weighted by only q in Q: the optimal loop mirrors it to ~1/lam, so the closed
+    loop's spectral radius is ~0.999 and value iteration converges slowly after a long transient."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = rng.standard_normal((batch, n, m))
+    Q = np.zeros((batch, n, n))
+    R = np.empty((batch, m, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _stable_block(rng, n - 1, 0.6)
+        A[i, n - 1, n - 1] = lam
+        Q[i, :n - 1, :n - 1] = _spd(rng, n - 1)
+        Q[i, n - 1, n - 1] = q
+        R[i] = _spd(rng, m)
+    return A, B, Q, R
+
+
+def marginally_stabilisable(batch: int, n: int, m: int, seed: int = 0, lam: float = 1.02, b: float = 1e-2):
+    """An unstable mode lam on state n-1 that only input 0 reaches, through B[n-1, 0] = b: stabilising it costs ~1/b^2, so its value
+    entry is large and the gain's column n-1 is large."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = np.empty((batch, n, m))
+    Q = np.empty((batch, n, n))
+    R = np.empty((batch, m, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _stable_block(rng, n - 1, 0.6)
+        A[i, n - 1, n - 1] = lam
+        B[i, :n - 1] = rng.standard_normal((n - 1, m))
+        B[i, n - 1] = 0.0
+        B[i, n - 1, 0] = b
+        Q[i] = _spd(rng, n)
+        R[i] = _spd(rng, m)
+    return A, B, Q, R
+
+
+def cheap_control(batch: int, n: int, m: int, seed: int = 0):
+    """R = 1e-8 I on an unstable random system (rho(A) = 1.2): R + B^T V B is dominated by B^T V B."""
+    A, B, Q, _ = random_lti_systems(batch, n, m, seed=seed, rho=1.2)
+    return A, B, Q, np.tile(1e-8 * np.eye(m), (batch, 1, 1))
+
+
+def expensive_control(batch: int, n: int, m: int, seed: int = 0):
+    """R = 1e8 I on an unstable random system (rho(A) = 1.05): the gain is tiny and the unstable modes are only just mirrored."""
+    A, B, Q, _ = random_lti_systems(batch, n, m, seed=seed, rho=1.05)
+    return A, B, Q, np.tile(1e8 * np.eye(m), (batch, 1, 1))
+
+
+def badly_scaled(batch: int, n: int, m: int, seed: int = 0, rho: float = 1.05):
+    """A random system in coordinates x' = D x, D = diag(logspace(-2, 2, n)): D A D^-1, D B, D^-T Q D^-1, R.  The solution is
+    P' = D^-1 P D^-1, L' = L D^-1: entries over eight decades."""
+    A, B, Q, R = random_lti_systems(batch, n, m, seed=seed, rho=rho)
+    d = np.logspace(-2, 2, n)
+    return A * d[:, None] / d[None, :], B * d[:, None], Q / d[:, None] / d[None, :], R
+
+
+# name -> generator (batch, n, m, seed) of the hard-spectrum families above
+HARD_DARE = {
+    "slow_unreachable": slow_unreachable_mode,
+    "slow_coupled": lambda batch, n, m, seed=0: slow_unreachable_mode(batch, n, m, seed=seed, coupling=1e-3),
+    "weakly_detectable": weakly_detectable_unstable,
+    "marginally_stabilisable": marginally_stabilisable,
+    "cheap_control": cheap_control,
+    "expensive_control": expensive_control,
+    "badly_scaled": badly_scaled,
+}
+
+
+def hard_dare(name: str, n: int, m: int, batch: int = 2):
+    """The seeded batch of HARD_DARE[name] at (n, m) that both the CPU property tests and the GPU tests use."""
+    return HARD_DARE[name](batch, n, m, seed=1000 + 97 * n + m)

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""CPU check: the gfx950 ISA of every MPC kernel that exists at a base revision is unchanged in the working tree.
+"""CPU check: the gfx950 ISA of every selected kernel that exists at a base revision is unchanged in the working tree.
 
-Compiles mpc.hip and mpc_wave.hip of both trees to assembly (`hipcc --cuda-device-only -S`, the flags of tests/test_dpp_hazards.py; no
-GPU needed), cuts out every kernel of the base (mpc_setup_kernel, mpc_solve_kernel, mpc_solve_wave_kernel instantiations) and
-compares its instruction text with the same symbol's in the working tree.  Basic-block labels carry the function's ordinal in the
-file (.LBB<f>_<b>), which moves when kernels are added before it, so the ordinal is dropped before comparing.
+Compiles the given sources (default mpc.hip and mpc_wave.hip) of both trees to assembly (`hipcc --cuda-device-only -S`, the flags of
+tests/test_dpp_hazards.py; no GPU needed), cuts out every kernel of the base whose symbol matches the regex (default: the
+mpc_setup_kernel, mpc_solve_kernel, mpc_solve_wave_kernel instantiations) and compares its instruction text with the same symbol's
+in the working tree.  Basic-block labels carry the function's ordinal in the file (.LBB<f>_<b>), which moves when kernels are added
+before it, so the ordinal is dropped before comparing.
 
     python tools/mpc_isa_identity.py [--base HEAD]
+    # every lqr_backward_tiled instantiation with DARE = false (the last template flag: ...Lb0EE):
+    python tools/mpc_isa_identity.py --src lqr_backward_tiled_f32.hip lqr_backward_tiled_f64.hip \
+        --kernels 'lqr_backward_tiled.*Lb[01]ELb[01]ELb0EE'
 """
 import argparse
 import os
@@ -43,9 +47,9 @@ def functions(asm):
     return out
 
 
-def compile_tree(csrc, out_dir):
+def compile_tree(csrc, out_dir, sources):
     res = {}
-    for src in SOURCES:
+    for src in sources:
         out = os.path.join(out_dir, src + ".s")
         p = subprocess.run([HIPCC] + FLAGS + [os.path.join(csrc, src), "-o", out], capture_output=True, text=True)
         if p.returncode != 0:
@@ -57,7 +61,10 @@ def compile_tree(csrc, out_dir):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", default="HEAD", help="git revision whose kernels must be reproduced")
+    ap.add_argument("--src", nargs="+", default=list(SOURCES), help="sources under zopt_amd/csrc to compile")
+    ap.add_argument("--kernels", default=KERNELS.pattern, help="regex on the (mangled) symbol: the kernels to compare")
     args = ap.parse_args()
+    kernels = re.compile(args.kernels)
     with tempfile.TemporaryDirectory() as tmp:
         base_tree = os.path.join(tmp, "base")
         os.makedirs(base_tree)
@@ -65,9 +72,9 @@ def main():
         subprocess.run(["tar", "-x", "-C", base_tree], input=tar.stdout, check=True)
         os.makedirs(os.path.join(tmp, "b"))
         os.makedirs(os.path.join(tmp, "w"))
-        base = compile_tree(os.path.join(base_tree, "zopt_amd", "csrc"), os.path.join(tmp, "b"))
-        work = compile_tree(os.path.join(ROOT, "zopt_amd", "csrc"), os.path.join(tmp, "w"))
-    names = sorted(k for k in base if KERNELS.search(k))
+        base = compile_tree(os.path.join(base_tree, "zopt_amd", "csrc"), os.path.join(tmp, "b"), args.src)
+        work = compile_tree(os.path.join(ROOT, "zopt_amd", "csrc"), os.path.join(tmp, "w"), args.src)
+    names = sorted(k for k in base if kernels.search(k))
     bad = 0
     for k in names:
         same = work.get(k) == base[k]

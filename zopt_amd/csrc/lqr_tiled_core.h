@@ -262,14 +262,23 @@ __device__ unsigned long long zm_tiled_stamps[12];
 // of one step's loads is exposed once per ~20 us step, which costs far less than spilling a second operand set.
 // DARE (discreteInfiniteHorizonLqr for large states, zopt/lqrUtils.py:176-204): the same step iterated on TIME-INVARIANT operands -- A, B,
 // Q, R are (batch, ., .) without a time axis, T is the iteration cap, L (batch, m, n) is overwritten every iteration -- from V = Q until
-// the gain stops changing: max|L_k - L_{k-1}| <= tol max|L_k| (tested every 8th iteration, or a stall at the rounding floor); then
-// P <- V (batch, n, n) and iters <- +k (converged) / -k (cap reached), as zm_dare_f64 documents.
+// the VALUE stops changing: max|V' - V| <= tol max|V'| (tested every 8th iteration and on the last allowed one, or a stall at the
+// rounding floor; a converged gain alone is not enough: it does not see a slow mode that the input cannot reach); then P <- V'
+// (batch, n, n) and iters <- +k (converged) / -k (cap reached), as zm_dare_f64 documents.
 template <class S>
 struct TiledDareArgs {
     S* P;
     int* iters;
     S tol;
 };
+
+// DARE: V at the head of a tested iteration, lane-private in LDS (word r of tile t of lane l at [(4 t + r) * 64 + l]: no exchange
+// between lanes, so no barrier); V itself is overwritten by Q during the step.  Only the DARE instantiations call this.
+template <class S, int NT>
+__device__ __forceinline__ S* tiled_dare_vhead() {
+    __shared__ S vh[NT * NT * 4 * 64];
+    return vh;
+}
 
 template <class TR, int NT, bool EXACT, bool PREFETCH = true, bool DARE = false>
 __global__ __launch_bounds__(64) void lqr_backward_tiled(const typename TR::S* __restrict__ A, const typename TR::S* __restrict__ B,
@@ -314,15 +323,10 @@ __global__ __launch_bounds__(64) void lqr_backward_tiled(const typename TR::S* _
         if constexpr (PREFETCH) Fn[K][NT] = load_tile<TR, EXACT>(Bb + k0 * nm, n, m, K, 0, g, c);
     }
     if constexpr (PREFETCH) Rn = load_tile<TR, EXACT>(Rb + k0 * mm, m, m, 0, 0, g, c, S(1));
-    // DARE: the previous iteration's gain (this lane's column), convergence state
-    S xprev[DARE ? 16 : 1];
+    // DARE: convergence state
     S dprev = TR::huge();
     int stall = 0, iters_done = 0;
-    bool stop = false, conv = false;
-    if constexpr (DARE) {
-#pragma unroll
-        for (int u_ = 0; u_ < 16; ++u_) xprev[u_] = S(0);
-    }
+    bool conv = false;
 
 #ifdef ZM_TILED_LAB
     unsigned long long zt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, zt_last;
@@ -330,6 +334,19 @@ __global__ __launch_bounds__(64) void lqr_backward_tiled(const typename TR::S* _
 #endif
     for (int kk_ = T - 1; kk_ >= 0; --kk_) {
         const int k = DARE ? 0 : kk_;          // time index of this step's operands and of L_k
+        // DARE: is this iteration (number T - kk_) tested?  Then keep its V for max|V' - V| (wave-uniform)
+        const bool dchk = DARE && (((T - kk_) & 7) == 0 || kk_ == 0);
+        if constexpr (DARE) {
+            if (dchk) {
+                S* vh = tiled_dare_vhead<S, NT>();
+#pragma unroll
+                for (int I = 0; I < NT; ++I)
+#pragma unroll
+                    for (int J = 0; J < NT; ++J)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) vh[((I * NT + J) * 4 + r) * 64 + lane] = V[I][J][r];
+            }
+        }
         if constexpr (PREFETCH) {
 #pragma unroll
             for (int K = 0; K < NT; ++K)
@@ -549,37 +566,6 @@ __global__ __launch_bounds__(64) void lqr_backward_tiled(const typename TR::S* _
             t_lds_sync();
 #undef S_
         }
-        if constexpr (DARE) {   // has the gain stopped changing?  (wave-uniform decision; the step is finished either way)
-            ++iters_done;
-            if ((iters_done & 7) == 0 || kk_ == 0) {
-                S dmax = S(0), smax = S(0);
-#pragma unroll
-                for (int u_ = 0; u_ < 16; ++u_) {
-                    const S d_ = TR::abs(x[u_] - xprev[u_]), a_ = TR::abs(x[u_]);
-                    dmax = (lane < n && d_ > dmax) || (lane < n && !(d_ == d_)) ? d_ : dmax;      // NaN sticks
-                    smax = (lane < n && a_ > smax) ? a_ : smax;
-                }
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const S od = __shfl_xor(dmax, off, 64), os = __shfl_xor(smax, off, 64);
-                    dmax = (od > dmax || !(od == od)) ? od : dmax;
-                    smax = os > smax ? os : smax;
-                }
-                if (!(dmax > dr.tol * smax)) {           // converged (or NaN: stop; the caller sees the non-finite gain)
-                    conv = true;
-                    stop = true;
-                } else {
-                    stall = (dmax >= dprev && dmax <= S(1e-9) * smax) ? stall + 1 : 0;   // rounding floor reached
-                    if (stall >= 3) {
-                        conv = true;
-                        stop = true;
-                    }
-                    dprev = dmax;
-                }
-            }
-#pragma unroll
-            for (int u_ = 0; u_ < 16; ++u_) xprev[u_] = x[u_];
-        }
         // L_k to HBM (row u: 64 consecutive floats across the wave), -L back to LDS (b128) for the tile reads
         if (lane < n) {
 #pragma unroll
@@ -639,8 +625,42 @@ __global__ __launch_bounds__(64) void lqr_backward_tiled(const typename TR::S* _
             }
         t_lds_sync();  // Sc / Tb are rewritten by the next step
         ZT_STAMP(6)   // -RL, Acl, W, V' (464 MFMAs)
-        if constexpr (DARE) {
-            if (stop) break;
+        if constexpr (DARE) {   // has the value stopped changing?  (wave-uniform decision)
+            ++iters_done;
+            if (dchk) {
+                const S* vh = tiled_dare_vhead<S, NT>();
+                S dmax = S(0), smax = S(0);
+#pragma unroll
+                for (int I = 0; I < NT; ++I)
+#pragma unroll
+                    for (int J = 0; J < NT; ++J)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const bool in = 16 * I + TR::row(g, r) < n && 16 * J + c < n;
+                            const S v_ = V[I][J][r];
+                            const S d_ = TR::abs(v_ - vh[((I * NT + J) * 4 + r) * 64 + lane]), a_ = TR::abs(v_);
+                            dmax = in && (d_ > dmax || !(d_ == d_)) ? d_ : dmax;      // NaN sticks
+                            smax = in && a_ > smax ? a_ : smax;
+                        }
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const S od = __shfl_xor(dmax, off, 64), os = __shfl_xor(smax, off, 64);
+                    dmax = (od > dmax || !(od == od)) ? od : dmax;
+                    smax = os > smax ? os : smax;
+                }
+                // converged (or NaN: stop; the caller sees the non-finite gain).  An overflowing V (an unstable mode the input
+                // cannot reach) is not convergence: iterate on until it turns the gain into NaN.
+                if (!(dmax == dmax) || (!(dmax > dr.tol * smax) && smax <= TR::huge())) {
+                    conv = true;
+                    break;
+                }
+                stall = (dmax >= dprev && dmax <= S(1e-9) * smax) ? stall + 1 : 0;   // rounding floor reached
+                if (stall >= 3) {
+                    conv = true;
+                    break;
+                }
+                dprev = dmax;
+            }
         }
     }
     if constexpr (DARE) {

@@ -108,8 +108,8 @@ def discreteInfiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=200000, return_val
     Arguments
     ---------
         A : (..., n, n)    B : (..., n, m)    Q : (..., n, n)    R : (..., m, m)     (n <= 64, m <= 16: the tile-16 register
-            kernel up to n <= 12, m <= 4, the fp64 MFMA tile kernel on time-invariant operands beyond -- it stops when the GAIN no
-            longer changes, `max|L_k - L_{k-1}| <= tol max|L_k|`)
+            kernel up to n <= 12, m <= 4, the fp64 MFMA tile kernel on time-invariant operands beyond; both stop when the VALUE no
+            longer changes, `max|V' - V| <= tol max|V'|`)
 
     Returns
     -------
