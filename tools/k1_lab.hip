@@ -45,6 +45,22 @@ int main(int argc, char** argv) {
     CHK(hipMalloc(&L, nB * 8));
     for (int i = 0; i < 4; ++i) CHK(hipMalloc(&Lr[i], nB * 8));
     if (argc > 1) rot = atoi(argv[1]);   // rotate the output over 4 buffers (314 MB > Infinity Cache)
+    if (argc > 2) {   // inputs from files instead: DIR/{A,B,Q,R}{0,1}.bin, fp64 (4096, 50, .., ..) as bench.py builds them
+        std::vector<double> h(nA);
+        const char* nm[4] = {"A", "B", "Q", "R"};
+        for (int s = 0; s < 2; ++s)
+            for (int k = 0; k < 4; ++k) {
+                const size_t cnt = k == 1 ? nB : k == 3 ? nR : nA;
+                char path[512];
+                snprintf(path, sizeof path, "%s/%s%d.bin", argv[2], nm[k], s);
+                FILE* f = fopen(path, "rb");
+                if (!f || fread(h.data(), 8, cnt, f) != cnt) { printf("cannot read %s\n", path); exit(1); }
+                fclose(f);
+                double* dst = k == 0 ? A[s] : k == 1 ? B[s] : k == 2 ? Q[s] : R[s];
+                CHK(hipMemcpy(dst, h.data(), cnt * 8, hipMemcpyHostToDevice));
+            }
+        printf("inputs: %s\n", argv[2]);
+    }
     int lcount = 0;
     CHK(hipDeviceSynchronize());
     using namespace zm;
@@ -56,6 +72,7 @@ int main(int argc, char** argv) {
         {"compiler-only LDS sync (X bit 21)", lqr_backward_dma_f64<12, 4, 3, true, (1 << 21), 1, 4>, 1},
         {"L2-resident                      ", lqr_backward_dma_f64<12, 4, 3, true, 1, 1, 4>, 1},
         {"L2-resident, compiler-only sync  ", lqr_backward_dma_f64<12, 4, 3, true, 1 | (1 << 21), 1, 4>, 1},
+        {"memory only (X bit 32)           ", lqr_backward_dma_f64<12, 4, 3, true, 32, 1, 4>, 1},
     };
     auto launch = [&](kern_t k, int blocks, int set, size_t dyn, int W = 1) {
         hipLaunchKernelGGL(k, dim3(blocks / W), dim3(64 * W), dyn, 0, A[set], B[set], Q[set], R[set], rot ? Lr[(lcount++) & 3] : L, T, (long)blocks);
@@ -72,6 +89,17 @@ int main(int argc, char** argv) {
             size_t bad = 0, nan = 0;
             for (size_t i = 0; i < nB; ++i) { bad += (memcmp(&ref[i], &got[i], 8) != 0); nan += (ref[i] != ref[i]); }
             printf("bitwise check %s: %zu of %zu differ (reference has %zu NaN)\n", vs[v].name, bad, nB, nan);
+        }
+    }
+    {   // wave-steps of the product's arithmetic that take the pivoted re-solve (X bit 22), per input set
+        kern_t k = (kern_t)lqr_backward_dma_f64<12, 4, 3, true, (1 << 22), 1, 4>;
+        for (int s = 0; s < 2; ++s) {
+            unsigned long long z[8] = {0};
+            CHK(hipMemcpyToSymbol(HIP_SYMBOL(zm_k1_stamps), z, sizeof(z)));
+            launch(k, batch, s, 0, 1);
+            CHK(hipDeviceSynchronize());
+            CHK(hipMemcpyFromSymbol(z, HIP_SYMBOL(zm_k1_stamps), sizeof(z)));
+            printf("pivoted re-solves (X bit 22), input set %d: %llu of %d wave-steps\n", s, z[6], batch * T);
         }
     }
     hipEvent_t e0, e1;

@@ -15,8 +15,10 @@
 //              which idle DMA lanes fill from a zero source (no per-step masking instructions).
 //   Y  = V^T F                    3 MFMA     F = [A_k | B_k]
 //   G  = Y^T F + [0 ; R]          3 MFMA     rows n.. of G = [B^T V A | R + B^T V B]
-//   L  = solve(Suu, Sux)          4 x 16 tile through LDS; lane-local elimination WITHOUT row exchanges when every
-//                                 multiplier is <= 4 in magnitude (checked, wave-uniform), else the pivoted LU
+//   L  = solve(Suu, Sux)          4 x 16 tile through LDS; every lane expands one 3x3 cofactor of Suu, 1 v_mfma_f64_4x4x4_4b
+//                                 gives adj(Suu) [Sux | Suu], scaled by 1/det(Suu); when the Suu columns of that product are
+//                                 not det(Suu) I to 2^-45 (checked, wave-uniform), the pivoted LU instead
+//   (k = 0: L_0 is the last output, the wave returns after storing it)
 //   [Acl ; -R L] = [A ; 0] + [B ; R] (-L)     1 MFMA   (stacked A operand: rows < n give A - B L, rows n.. give -R L)
 //   W  = V^T Acl = Y_A + Y_B (-L) 1 MFMA     (Y_B = V^T B is already in Y; transposed through LDS off the critical path)
 //   V' = Q + (-L)^T (-R L) + W^T Acl         4 MFMA
@@ -72,7 +74,8 @@ __device__ __forceinline__ void dma_issue(DmaState<N, M, D, ES>& a, char* slot) 
 
 // X: diagnostic bits for tools/k1_lab.hip (0 in the product): 1 = every block loads the inputs of trajectory blockIdx % 64 (the
 // working set then sits in L2: compute time without HBM latency / bandwidth), 2 = no s_setprio around the solve,
-// 4 = s_memtime stamps per segment, summed into zm_k1_stamps (diagnostic build only: the stamps' waits forbid overlaps).
+// 4 = s_memtime stamps per segment, summed into zm_k1_stamps (diagnostic build only: the stamps' waits forbid overlaps),
+// bit 22 = count the wave-steps that take the pivoted re-solve in zm_k1_stamps[6].
 #ifdef ZM_K1_LAB
 __device__ unsigned long long zm_k1_stamps[8];
 #define ZM_STAMP(var)                                                                          \
@@ -175,6 +178,21 @@ __global__ __launch_bounds__(64 * W, WPS) void lqr_backward_dma_f64(const IO* __
     const int oYBa = YBO + (g * M + (c & 3)) * 8;           // Y_B[4s+g][c & 3] (+ s*4*M*8): A operand of the 4x4x4 blocks (G4)
     const bool vL = cA;                                     // (g < M always: M == 4)
     IO* pL = L + ((((X >> 19) & 1) ? (traj & 63) : traj) * T + (T - 1)) * nm + g * N + c;
+    // The 3x3 minor of Suu that lane (g, c) expands for the cofactor C[g][c & 3]: rows != g, columns != c & 3, read from the exchange
+    // tile (Suu[i][j] = exch[16 i + N + j]).  The sign (-1)^(g + c&3) is folded in by swapping the minor's last two rows.
+    int mo[3][3];
+    {
+        const int cc = c & 3;
+        int mr[3] = {g == 0 ? 1 : 0, g <= 1 ? 2 : 1, g <= 2 ? 3 : 2};
+        const int mc[3] = {cc == 0 ? 1 : 0, cc <= 1 ? 2 : 1, cc <= 2 ? 3 : 2};
+        if ((g + cc) & 1) { const int t = mr[1]; mr[1] = mr[2]; mr[2] = t; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int l = 0; l < 3; ++l) mo[k][l] = EXCH + (mr[k] * 16 + N + mc[l]) * 8;
+    }
+    const bool cS = (c >= N) && (c < N + M);                // lanes holding Suu[g][c - N]: they test the residual
+    const double eye = (cS && g == c - N) ? 1.0 : 0.0;      // I[g][c - N] there
 
     // prologue: fill the ring with steps T-1 .. T-D
 #pragma unroll
@@ -256,30 +274,53 @@ __global__ __launch_bounds__(64 * W, WPS) void lqr_backward_dma_f64(const IO* __
             }
 
             ZM_STAMP(st2)
-            // m x m solve: 4 x 16 tile through LDS, every lane reads Suu (broadcast) and its own RHS column
+            // m x m solve by cofactors: 4 x 16 tile through LDS, every lane reads its own 3x3 minor of Suu
             exch[g * 16 + c] = srow;
             k1_lds_sync<((X >> 21) & 1) != 0>();
-            double S[4][4], b[4], x[4];
+            double mi[3][3];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
+            for (int k = 0; k < 3; ++k)
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) S[i][jj] = exch[i * 16 + N + jj];
-                b[i] = exch[i * 16 + c];
-            }
+                for (int l = 0; l < 3; ++l) mi[k][l] = *(const double*)(lds + mo[k][l]);
             const double ybt = *(const double*)(lds + oYBr);
             ZM_STAMP(st3)
-            // The solve is a long chain of short dependent VALU ops; without priority each of them can queue behind a
+            // The solve is a short chain of dependent VALU ops; without priority each of them can queue behind a
             // 64-cycle MFMA of another wave on the shared fp64 pipe (measured: -3..4 % kernel time).
             if constexpr ((X & 2) == 0) __builtin_amdgcn_s_setprio(3);
-            // wave-uniform vote on the scalar unit: "some lane failed the growth check" = ballot(!ok) != 0
-            if (__builtin_amdgcn_ballot_w64(!lu_solve4_nopivot(S, b, x)) != 0ull) {
-                // rare: growth check failed somewhere in the wave -> partial pivoting, IEEE division
+            // X = adj(Suu) [Sux | Suu] on ONE v_mfma_f64_4x4x4_4b: srow = S[g][c] is its B operand (block q = c >> 2) and the cofactor
+            // C[g][c & 3] = adj(Suu)[c & 3][g] its A operand, so lane (g, c) receives X[g][c].  adj(Suu) Suu = det(Suu) I, so
+            // L = X / det, and X[0][N] (lane N) is det(Suu).
+            const double cof = cofactor3(mi);
+            const double xs = __builtin_amdgcn_mfma_f64_4x4x4f64(cof, srow, 0.0, 0, 0, 0);
+            const double det = readlane_f64(xs, N);
+            const double r = fast_rcp(det);
+            double lv = xs * r;  // L_k[g][c]
+            // Guard (wave-uniform): det and 1/det finite, and the Suu columns of X equal det I to |X - det I| <= 2^-45 |det|.  That
+            // residual carries the rounding of the cofactors and of the product (u |adj(S)| |S| per entry), the same error that
+            // reaches the Sux columns: it fires on near-singular Suu (|det| small against the products of its rows), on zero or
+            // NaN det and on overflow; the wave then re-solves with partial pivoting (tools/k1_solve_model.py,
+            // tests/test_k1_solve_model.py).
+            const bool ok = (__builtin_fabs(det) <= 1.79769313486231570815e308) & (__builtin_fabs(r) <= 1.79769313486231570815e308) &
+                            (!cS || __builtin_fabs(__builtin_fma(-eye, det, xs)) <= 0x1p-45 * __builtin_fabs(det));
+            if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) {
+                // rare: near-singular or non-finite Suu somewhere in the wave -> partial pivoting, IEEE division
+#ifdef ZM_K1_LAB
+                if constexpr (((X >> 22) & 1) != 0)
+                    if (lane == 0) atomicAdd(&zm_k1_stamps[6], 1ull);   // lab: count the wave-steps that take this path
+#endif
+                double S[4][4], b[4], x[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) S[i][jj] = exch[i * 16 + N + jj];
+                    b[i] = exch[i * 16 + c];
+                }
                 lu_solve4_fallback(S, b, x);
+                const double x01 = (g & 1) ? x[1] : x[0];
+                const double x23 = (g & 1) ? x[3] : x[2];
+                lv = (g & 2) ? x23 : x01;
             }
             if constexpr (((X >> 21) & 1) != 0) __builtin_amdgcn_wave_barrier();
-            const double x01 = (g & 1) ? x[1] : x[0];
-            const double x23 = (g & 1) ? x[3] : x[2];
-            const double lv = (g & 2) ? x23 : x01;  // L_k[g][c]
             const double ln = -lv;
             if constexpr ((X & 2) == 0) __builtin_amdgcn_s_setprio(0);
             if (vL) {
@@ -295,6 +336,9 @@ __global__ __launch_bounds__(64 * W, WPS) void lqr_backward_dma_f64(const IO* __
                 else *pL = (IO)lv;
             }
             pL -= nm;
+            // L_0 is the last output: V_0 is not needed (the stamped lab build keeps the full step for its per-step averages)
+            if constexpr ((X & 4) == 0)
+                if (j == 0) return;
             ZM_STAMP(st4)
 
             // [Acl ; -R L] = [A ; 0] + [B ; R] (-L)

@@ -117,6 +117,23 @@ __device__ __forceinline__ bool lu_solve4_nopivot(const double (&S)[4][4], const
     return ok;
 }
 
+// det of a 3x3 matrix by expansion along its first row, 9 fp64 VALU (the rounding order tools/k1_solve_model.py restates):
+//   m00 (m11 m22 - m12 m21) - m01 (m10 m22 - m12 m20) + m02 (m10 m21 - m11 m20)
+__device__ __forceinline__ double cofactor3(const double (&m)[3][3]) {
+    const double t0 = __builtin_fma(m[1][1], m[2][2], -(m[1][2] * m[2][1]));
+    const double t1 = __builtin_fma(m[1][0], m[2][2], -(m[1][2] * m[2][0]));
+    const double t2 = __builtin_fma(m[1][0], m[2][1], -(m[1][1] * m[2][0]));
+    return __builtin_fma(m[0][0], t0, __builtin_fma(-m[0][1], t1, m[0][2] * t2));
+}
+
+// v from lane `l`, wave-uniform (two v_readlane_b32 into an SGPR pair)
+__device__ __forceinline__ double readlane_f64(const double v, const int l) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
 // The re-solve after a failed growth check, shared by the sweep kernels: LU with partial pivoting -- unless S holds a NaN.  Then
 // every component of the solution is NaN whichever elimination order runs (a NaN row update f * S[k][j] poisons its whole row even
 // through zeros, a NaN pivot poisons every row below it, and the back substitution multiplies every x_j into the rows above it), so
