@@ -24,8 +24,8 @@
 //     vf_zz <- ensurePositiveDefinite(vf_zz)   (eigenvalue clamp 1e-3, INSIDE the sequential sweep)    (:248)
 //     Q_xx += vf_xx,  Q_uu += vf_uu,  Q_ux += vf_ux                                                    (:196-198)
 // The contraction reads f_xx (n,n,n), f_ux (n,m,n), f_uu (n,m,m) of the step straight from HBM (n terms per tile
-// element), the compact (n+m) x (n+m) matrix goes through LDS into the wave-level Jacobi projection of jacobi16.h and
-// comes back as an accumulator init of G.
+// element); the (n+m) x (n+m) matrix stays on the tile, zero-padded, is PD-projected there by the matrix-sign iteration of
+// ns16.h and becomes an accumulator init of G.
 //
 // MODE 1 = K2 lqr_backward_affine: the same sweep for zopt/lqrUtils.py:207-262 (bilinearAffineLqr), i.e. with
 //     f_x,f_u <- A,B   c_xx,c_ux,c_uu <- Q,H,R   c_x,c_u <- q,r   and the affine-dynamics offset d:
@@ -36,7 +36,6 @@
 // K-step), V^T d a column reduction (2 shuffles) re-laid out through LDS; both are kept apart so that a
 // nonsymmetric V is treated exactly as the reference does.
 #include "dma_ring.h"
-#include "jacobi16.h"
 #include "models.h"
 #include "ns16.h"
 #include "tile16_f64.h"
@@ -72,12 +71,11 @@ struct IlqrAddr {
     const double* pdr0;  // MODE 1: K-step s adds (rowok ? 4 s : 0)
     const double* pz[4]; // MODE 2: element (4r+g, c) of the stacked second-derivative tensor slice i = 0; +i*sz[r]
     int sz[4], stz[4];   // MODE 2: stride over i, stride over the time step
-    int zc[4];           // MODE 2: compact LDS index a*PLD+b of tile element (4r+g, c), or -1
+    int zc[4];           // MODE 2: >= 0 where tile element (4r+g, c) belongs to the (n+m) x (n+m) matrix, -1 on padding
     bool zlive[4];       // MODE 2: tile element (4r+g, c) is a diagonal entry of the live (state, control) index set
     double* pOut;        // L_k[g][c] (c < n) or l_k[g] (c == NP)
     int dF, dC, sF, sC, sCu, scv, sOut, sd;
     bool rowok[KS], vF[KS], vC[KS], vCu, vcv, vOut, vL, cA;
-    bool warm_v = false;   // MODE 2: the Jacobi eigenvector buffer holds the previous step's result
     double vsum = 0.0;     // MODE 0/2, lanes c == NP: sum over the steps of -1/2 l^T Q_uu l  (scalar part of the value function)
     double cu_pad;
 };
@@ -141,24 +139,20 @@ struct SweepLab {};
 __device__ __forceinline__ void ilqr_lds_sync() { wave_lds_sync(); }
 
 // ZIN (MODE 2, the DMA kernel): the caller has contracted vf_zz = sum_i v_x[i] d2f_i/dz2 already (operands in its LDS ring) and
-// passes the tile in `zin` (1), or has PD-projected it as well (2)
-template <int KS, int MODE, bool PREFETCH, int ZIN = 0>
+// passes the tile in `zin`
+template <int KS, int MODE, bool PREFETCH, bool ZIN = false>
 __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], IlqrStepRegs<KS>& d, IlqrAddr<KS>& a,
                                           double* sm, const int g, const int c, const int ob0, const int ob1,
-                                          const int ob2, const int ob3, const int oqa, double* jA, double* jV,
-                                          double* jcs, int* jpq, const int n, const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0},
-                                          SweepLab* lab = nullptr) {
+                                          const int ob2, const int ob3, const int oqa, double* jA, const int n,
+                                          const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0}, SweepLab* lab = nullptr) {
     constexpr int NP = 4 * KS;
     // MODE 2: vf_zz = sum_i v_x[i] * d2f_i/dz2, PD-projected, as extra accumulator init
     d4 pz = zero4();
-    if constexpr (MODE == 2 && ZIN == 2) {
-        pz = zin;                                    // projected by the caller
-    } else if constexpr (MODE == 2 && ZIN == 1) {
+    if constexpr (MODE == 2 && ZIN) {
         d4 zt = zin;
         psd_project_ns<KS + 1, true>(zt, a.zlive, 1e-3, jA, g, c);   // (the ring kernel's contraction is bitwise symmetric)
         pz = zt;
     } else if constexpr (MODE == 2) {
-        const int lane = g * 16 + c;
         double z[4] = {0.0, 0.0, 0.0, 0.0};
         // the loads of 4 slices (16 per lane) are in flight before their FMAs (unrolled, unconditional: slices i >= n
         // re-read slice 0 with weight 0); more in flight would cost the second wave per SIMD its registers
@@ -178,7 +172,6 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
                 for (int r = 0; r < 4; ++r) z[r] = __builtin_fma(vxi, fz[i][r], z[r]);
             }
         }
-#ifndef ZM_DDP_PSD_JACOBI
         // PD projection on the tile itself by matrix-sign iterations on the fp64 MFMA pipe (ns16.h); jA: transpose buffers
         d4 zt;
 #pragma unroll
@@ -188,35 +181,6 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
         }
         psd_project_ns<KS + 1>(zt, a.zlive, 1e-3, jA, g, c);
         pz = zt;
-        (void)lane;
-#else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            a.pz[r] -= a.stz[r];
-            if (a.zc[r] >= 0) jA[a.zc[r]] = z[r];
-        }
-        ilqr_lds_sync();
-        // symmetrise (jnp.linalg.eigh does) -- in place through registers
-        const int k = n + m;
-        double sy[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = lane + 64 * r;
-            const int i = e / k, j = e % k;
-            sy[r] = (e < k * k) ? 0.5 * (jA[i * PLD + j] + jA[j * PLD + i]) : 0.0;
-        }
-        ilqr_lds_sync();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = lane + 64 * r;
-            if (e < k * k) jA[(e / k) * PLD + (e % k)] = sy[r];
-        }
-        ilqr_lds_sync();
-        psd_project_lds(jA, jV, jcs, jpq, k, 1e-3, lane, a.warm_v);
-        a.warm_v = true;   // jV now holds eigenvectors of a neighbouring step's matrix
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pz[r] = (a.zc[r] >= 0) ? jA[a.zc[r]] : 0.0;
-#endif
     }
     // Y = v_xx^T F
     d4 y = zero4();
@@ -350,12 +314,7 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
     if (active && active[traj] == 0) return;  // whole wave leaves: this trajectory keeps its previous policy
     const int g = lane >> 4, c = lane & 15;
     __shared__ double sm[ILQR_LDS_DOUBLES];
-#ifndef ZM_DDP_PSD_JACOBI
-    __shared__ double jA[MODE == 2 ? NS_LDS_DOUBLES : 1], jV[1], jcs[1];
-#else
-    __shared__ double jA[MODE == 2 ? PK * PLD : 1], jV[MODE == 2 ? PK * PLD : 1], jcs[PK];
-#endif
-    __shared__ int jpq[PK];
+    __shared__ double jA[MODE == 2 ? NS_LDS_DOUBLES : 1];
 
     IlqrAddr<KS> a;
     const int nn = n * n, nm = n * m, mm = m * m;
@@ -413,7 +372,7 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
             // compact index: states 0..n-1, controls n..n+m-1
             const int ca = rx ? row : (ru ? n + (row - NP) : -1);
             const int cb = cA ? c : (cB ? n + (c - NP) : -1);
-            a.zc[r] = (ca >= 0 && cb >= 0) ? ca * PLD + cb : -1;
+            a.zc[r] = (ca >= 0 && cb >= 0) ? ca * 17 + cb : -1;   // 17-wide compact index; only its sign is read (a 0/-1 flag changes the generated code)
             a.zlive[r] = (ca >= 0) && (row == c);
             if (Hpk != nullptr) {
                 // packed second derivatives (zm_quadratic_dynamics_pairs_list_f64): element (ca, cb) is pair p = (min, max) of the
@@ -486,7 +445,7 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
         for (int k2 = T - 1; k2 >= 0; --k2) {
             IlqrStepRegs<KS> d;
             ilqr_load_step<KS, MODE>(d, a);
-            ilqr_step<KS, MODE, false>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
+            ilqr_step<KS, MODE, false>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
         }
     } else {
     IlqrStepRegs<KS> d0, d1;
@@ -494,19 +453,19 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
     if (T >= 2) ilqr_load_step<KS, MODE>(d1, a);
     int k = T - 1;
     while (k >= 3) {
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
+        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
+        ilqr_step<KS, MODE, true>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
         k -= 2;
     }
     if (k == 2) {
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
+        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
+        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
+        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
     } else if (k == 1) {
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
+        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
+        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
     } else {
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, jV, jcs, jpq, n, m);
+        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
     }
     }
     // optional: the value function the sweep ends with (riccatiStep_ilqr / _ddp return it: ilqrUtils.py:170, :203)
@@ -534,12 +493,9 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
 // K3-DMA: the iLQR sweep (MODE 0) with its per-step operands staged through an LDS ring by DMA, as K1 does
 // (lqr_backward_dma.hip): no operand prefetch registers, no per-step address arithmetic for loads, no vector-memory
 // latency on the chain.  n in {8, 12}, m = 4, 16-B aligned pointers; every other case runs ilqr_backward_t16_f64.
-// Cache policy of the operand DMA (sc0 = 1, nt = 2, sc1 = 16).  Default policy here: unlike K1 (lqr_backward_dma.hip, where
+// Cache policy of the operand DMA: the default one (aux 0).  Unlike K1 (lqr_backward_dma.hip, where
 // non-temporal loads are worth 10 %), the sweeps measured 7 % SLOWER with nt at 8192 x 100 steps (per-step Hessians 616 -> 660 us,
-// affine 722 -> 754 us, shared Hessians unchanged; gpurun_out/r02_ilqr_nt_ab.txt).  -DZM_ILQR_DMA_AUX=2 builds the nt variant.
-#ifndef ZM_ILQR_DMA_AUX
-#define ZM_ILQR_DMA_AUX 0
-#endif
+// affine 722 -> 754 us, shared Hessians unchanged; profiles/r02_ilqr_nt_ab.txt).
 
 // Slot image of one step (16-B chunks): f_x | f_u | c_x | c_u [| c_xx | c_ux | c_uu unless the Hessians are shared] | zeros.
 namespace zm {
@@ -579,17 +535,13 @@ struct IlqrDmaGeom {
     static_assert(SLOT - OZ >= 16, "slot needs zero padding");
 };
 
-#ifndef ZM_DDP_DMA_WAVES
-#define ZM_DDP_DMA_WAVES 2
-#endif
-#ifndef ZM_ILQR_DMA_WAVES
-#define ZM_ILQR_DMA_WAVES 3
-#endif
 // W: waves per workgroup, wave w of block b works on slot b * W + w (list form only).  The waves share nothing; what W = 4 buys is
 // PLACEMENT when few trajectories are left: the four waves of a workgroup go to the four SIMDs of a CU, whereas single-wave workgroups
 // start doubling up on SIMDs beyond three per CU (768 waves: measured 148 against 119 us per sweep at 808 resp. 758 trajectories).
+// Waves per SIMD the register budget is set for: the projection of the DDP sweep (MODE 2) needs the registers of two
+constexpr int ILQR_DMA_WAVES = 3, DDP_DMA_WAVES = 2;
 template <int N, int M, int D, bool SHARED, int MODE, int NPAIR = 0, int NJP = 0, int NHS = 0, int W = 1>
-__global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_WAVES) void ilqr_backward_dma_f64(
+__global__ __launch_bounds__(64 * W, MODE == 2 ? DDP_DMA_WAVES : ILQR_DMA_WAVES) void ilqr_backward_dma_f64(
     const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
     const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
     const double* __restrict__ c_uu, const double* __restrict__ vf_x, const double* __restrict__ vf_xx,
@@ -601,25 +553,15 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
     constexpr int KS = G::KS, NI = G::NI, SLOT = G::SLOT, NP = N;
     constexpr int nn = N * N, nm = N * M, mm = M * M;
     constexpr int SMO = D * SLOT;
-    // MODE 2 with three waves per SIMD (ZM_DDP_DMA_WAVES = 3) keeps state in LDS while the projection runs: X of the sign iteration
-    // (256 doubles), the value function V, v (6 doubles per lane) and the shared cost Hessian (4 per lane)
-    constexpr bool DIET = (MODE == 2) && (ZM_DDP_DMA_WAVES >= 3);
-    constexpr int XST = DIET ? 256 : 0, VST = DIET ? 64 * 2 * KS : 0, CST = DIET ? 64 * (KS + 1) : 0;
-#ifndef ZM_DDP_LDS_PAD   // occupancy experiments: extra bytes of LDS per wave in MODE 2
-#define ZM_DDP_LDS_PAD 0
-#endif
     constexpr int HDN = NHS ? NPAIR * N : 0;   // dense image of the sparse second derivatives
-    constexpr int PER_WAVE = SMO + ILQR_LDS_DOUBLES * 8 + (MODE == 2 ? NS_LDS_DOUBLES * 8 + ZM_DDP_LDS_PAD : 0) + (XST + VST + CST + HDN) * 8;
+    constexpr int PER_WAVE = SMO + ILQR_LDS_DOUBLES * 8 + (MODE == 2 ? NS_LDS_DOUBLES * 8 : 0) + HDN * 8;
     static_assert(PER_WAVE % 16 == 0, "per-wave LDS slices stay 16-B aligned");
     __shared__ __attribute__((aligned(16))) char lds_all[W * PER_WAVE];
     const int wave = (W == 1) ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     char* const lds = lds_all + wave * PER_WAVE;
     double* sm = (double*)(lds + SMO);
     double* jA = (double*)(lds + SMO + ILQR_LDS_DOUBLES * 8);   // MODE 2: transpose buffers of the sign iteration (ns16.h)
-    double* xst = jA + NS_LDS_DOUBLES;
-    double* vst = xst + XST;
-    double* cst = vst + VST;
-    double* hd = cst + CST;
+    double* hd = jA + NS_LDS_DOUBLES;
     const int lane = threadIdx.x & 63;
     const long slot_ = (long)blockIdx.x * W + wave;
     if (W > 1 && slot_ >= tl.count) return;    // (W > 1: list form; whole waves only, no barrier anywhere in this kernel)
@@ -675,7 +617,7 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
     auto dma = [&](char* slot) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            __builtin_amdgcn_global_load_lds((glb_void_t*)p[i], (lds_void_t*)(slot + i * 1024), 16, 0, ZM_ILQR_DMA_AUX);
+            __builtin_amdgcn_global_load_lds((glb_void_t*)p[i], (lds_void_t*)(slot + i * 1024), 16, 0, 0);
             p[i] -= st[i];
         }
     };
@@ -755,11 +697,6 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
         }
         if (g == 0) sm[80 + c] = cA ? vx[c] : 0.0;
     }
-    if constexpr (DIET) {
-#pragma unroll
-        for (int s = 0; s < KS; ++s) cst[s * 64 + lane] = Csh[s];
-        cst[KS * 64 + lane] = Cush;
-    }
     int hdst0 = 0, hdst1 = 0;   // NHS: dense positions of sparse entries lane, lane + 64
     if constexpr (NHS != 0) {
         for (int e = lane; e < HDN; e += 64) hd[e] = 0.0;
@@ -787,14 +724,10 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
             wait_for_step<NI, D>(j);
             ZM_SWEEP_STAMP(lab, 0);   // waiting for the step's DMA
             IlqrStepRegs<KS> d;
-            if constexpr (!DIET) {
 #pragma unroll
-                for (int s = 0; s < KS; ++s) d.F[s] = *(const double*)(slot + (NJP ? oFp[s] : oF + s * dF));
-                d.cv = *(const double*)(slot + ocv);
-            }
-            if constexpr (DIET) {
-                // (operands are read after the projection)
-            } else if constexpr (SHARED) {
+            for (int s = 0; s < KS; ++s) d.F[s] = *(const double*)(slot + (NJP ? oFp[s] : oF + s * dF));
+            d.cv = *(const double*)(slot + ocv);
+            if constexpr (SHARED) {
 #pragma unroll
                 for (int s = 0; s < KS; ++s) d.C[s] = Csh[s];
                 d.Cu = Cush;
@@ -816,38 +749,7 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
                 if (hdst1 >= 0) hd[hdst1] = h1;
                 ilqr_lds_sync();
             }
-            if constexpr (DIET) {
-                // (see below) the projection first, with as little as possible alive: V, v wait in LDS, the step's operands are
-                // read from the ring afterwards -- the slot is refilled one projection later than otherwise, still a step ahead
-                double vx[N];
-#pragma unroll
-                for (int i = 0; i < N; ++i) vx[i] = sm[80 + i];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double* h = NHS ? (const double*)((const char*)hd + oH[r]) : (const double*)(slot + oH[r]);
-                    double z = 0.0;
-#pragma unroll
-                    for (int i = 0; i < N; ++i) z = __builtin_fma(vx[i], h[i], z);
-                    zin[r] = zok[r] ? z : 0.0;
-                }
-#pragma unroll
-                for (int s = 0; s < KS; ++s) {
-                    vst[s * 64 + lane] = Vxx[s];
-                    vst[(KS + s) * 64 + lane] = vxr[s];
-                }
-                ilqr_lds_sync();
-                psd_project_ns<KS + 1>(zin, a.zlive, 1e-3, jA, g, c, xst);
-                ilqr_lds_sync();
-#pragma unroll
-                for (int s = 0; s < KS; ++s) {
-                    Vxx[s] = vst[s * 64 + lane];
-                    vxr[s] = vst[(KS + s) * 64 + lane];
-                    d.F[s] = *(const double*)(slot + (NJP ? oFp[s] : oF + s * dF));
-                    d.C[s] = cst[s * 64 + lane];
-                }
-                d.cv = *(const double*)(slot + ocv);
-                d.Cu = cst[KS * 64 + lane];
-            } else if constexpr (MODE == 2) {
+            if constexpr (MODE == 2) {
                 // vf_zz[4r+g][c] = sum_i v_x[i] H[pair][i], i ascending (the order of the register kernel's contraction); v_x is
                 // this wave's LDS row sm[80 ..], written by the previous step
                 double vx[N];
@@ -865,12 +767,7 @@ __global__ __launch_bounds__(64 * W, MODE == 2 ? ZM_DDP_DMA_WAVES : ZM_ILQR_DMA_
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // operands are in registers: the slot may be refilled
             if (j - D >= 0) dma(slot);
             ZM_SWEEP_STAMP(lab, 1);   // operand reads (and MODE 2's contraction), DMA issue
-            if constexpr (DIET)
-                ilqr_step<KS, MODE, false, 2>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, nullptr, nullptr, nullptr, N, M, zin);
-            else if constexpr (MODE == 2)
-                ilqr_step<KS, MODE, false, 1>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, nullptr, nullptr, nullptr, N, M, zin, lab);
-            else
-                ilqr_step<KS, MODE, false>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, nullptr, nullptr, nullptr, nullptr, N, M, zero4(), lab);
+            ilqr_step<KS, MODE, false, MODE == 2>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, N, M, zin, lab);
             if (--j < 0) {
 #ifdef ZM_SWEEP_LAB
                 if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1132,9 +1029,6 @@ extern "C" int zm_ddp_backward_pairs_list_f64(const zm_model_t* model, const dou
     if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_list_f64: bad list length");
     if (!model || !f_x || !f_u || !H || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !l || !L)
         return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_list_f64: null pointer");
-#ifdef ZM_DDP_PSD_JACOBI
-    return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_pairs_list_f64: not available in the Jacobi-projection build");
-#endif
     const int n = model->n, m = model->m;
     const int rc = zm_check_sweep_args("zm_ddp_backward_pairs_list_f64", batch, T, n, m);
     if (rc) return rc;

@@ -552,14 +552,11 @@ __device__ __forceinline__ void tile_copy_out(double* __restrict__ op, const dou
 }
 
 constexpr int QP_WAVES = 4;
-#ifndef QP_ROWS
-#define QP_ROWS 32
-#endif
 // Points per chunk = rows of a wave's LDS tile.  64 (every lane a point) leaves one wave per SIMD (37 KB of LDS per wave) and the launch
 // waits on its loads and stores half of its time; with 32 or 16 the idle lanes cost little (the arithmetic is ~25 % of a wave's life at 50
 // points) and two to four times as many waves overlap: expansion at the full batch 133-142 / 128-132 / 122-127 us for 64 / 32 / 16 rows.
 // 32: the wind forms carry twice the arithmetic.
-constexpr int QP_R = QP_ROWS;
+constexpr int QP_R = 32;
 template <bool WIND>
 __global__ __launch_bounds__(64 * QP_WAVES) void expand_quad_points_kernel(const zm_model_t md, const double* __restrict__ xTraj,
                                                                            const double* __restrict__ uTraj,

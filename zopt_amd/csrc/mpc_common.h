@@ -5,9 +5,8 @@
 // Every ZM_MPC_CHK-th ADMM iteration checks the primal-infeasibility certificate and lets the adaptive penalty move (OSQP's
 // `check_termination` / `adaptive_rho_interval`, both tunables of the solver, not of the problem).  8 with moves to the NEAREST
 // tabulated level: measured on BASELINE configs[2] (profiles/r03_mpc_check_interval_ab.txt) 106 -> 60 worst-case iterations.
-#ifndef ZM_MPC_CHK
-#define ZM_MPC_CHK 8
-#endif
+// CHECK_EVERY of the reference ADMM solver under oracle/ replays this schedule and must stay equal to it.
+constexpr int ZM_MPC_CHK = 8;
 
 namespace zm {
 

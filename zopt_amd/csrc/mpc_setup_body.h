@@ -1,6 +1,6 @@
 // Body of the MPC setup kernel (mpc.hip): the Riccati recursion of one problem at one penalty.
 // A function BODY, not a header: #included verbatim inside mpc_setup_kernel and mpc_setup_batched_kernel (mpc.hip), so that the
-// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/mpc_isa_identity.py checks
+// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/isa_identity.py checks
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
     __shared__ double As[SN * SN], Bs[SN * SM], P[SN * SN], PA[SN * SN], PB[SN * SM], Sux[SM * SN], Suu[SM * SM],
         Mi[SM * SM], K[SM * SN], T1[SN * SN], T2[SN * SN];

@@ -1,6 +1,6 @@
 // Body of the lane-per-instance MPC solve kernel (mpc.hip).
 // A function BODY, not a header: #included verbatim inside mpc_solve_kernel and mpc_solve_batched_kernel (mpc.hip), so that the
-// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/mpc_isa_identity.py checks
+// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/isa_identity.py checks
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
     constexpr int W = NS + MC;
     const long inst = (long)blockIdx.x * 64 + threadIdx.x;

@@ -1,6 +1,6 @@
 // Body of the 16-lanes-per-instance MPC solve kernel (mpc_wave.hip).
 // A function BODY, not a header: #included verbatim inside mpc_solve_wave_kernel and mpc_solve_wave_batched_kernel (mpc_wave.hip), so that the
-// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/mpc_isa_identity.py checks
+// kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/isa_identity.py checks
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
     static_assert(NS + MC <= 16, "the stacked index must fit the 16 lanes of a group");
     extern __shared__ __attribute__((aligned(16))) double lds[];

@@ -24,6 +24,7 @@
 
 namespace zm {
 
+constexpr int PK = 16;                    // largest matrix the projection on one tile takes (psd.hip; beyond: psd_tiled.hip)
 constexpr int NS_LD = 17;                 // padded leading dimension of the transpose buffers
 constexpr int NS_LDS_DOUBLES = 2 * 16 * NS_LD;
 
@@ -74,22 +75,11 @@ __device__ __forceinline__ d4 ns_symmetrise(const d4& v, double* T, int& flip, c
 }
 
 // thresholds on F = ||I - Z^2||_F^2 above which one / two further quintics ride along in a booster pair (see below)
-#ifndef NS_RIDER1
-#define NS_RIDER1 0.9
-#endif
-#ifndef NS_RIDER2
-#define NS_RIDER2 1e300
-#endif
+constexpr double NS_RIDER1 = 0.9, NS_RIDER2 = 1e300;
 
 // sign iteration on Z (scaled X) over K row groups; returns |X| = sign(X) X
 template <int K>
-__device__ __forceinline__ d4 ns_sign_times(d4 z, d4& x, const d4& idr, double* T, int& flip, const int g, const int c,
-                                            double* xstash = nullptr) {
-    if (xstash) {   // X leaves the registers for the duration of the iteration
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xstash[r * 64 + g * 16 + c] = x[r];
-        ns_sync();
-    }
+__device__ __forceinline__ d4 ns_sign_times(d4 z, d4& x, const d4& idr, double* T, int& flip, const int g, const int c) {
     constexpr double QA = 3.4445, QB = -4.7750, QC = 2.0315;
     constexpr int MAX_PAIRS = 18, MAX_CUBIC = 14;
     int pairs = 0, cubic = 0;
@@ -147,23 +137,16 @@ __device__ __forceinline__ d4 ns_sign_times(d4 z, d4& x, const d4& idr, double* 
             if (0.5625 * f * f < 1e-18 || cubic >= MAX_CUBIC) break;
         }
     }
-    if (xstash) {
-        ns_sync();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) x[r] = xstash[r * 64 + g * 16 + c];
-    }
     return ns_op<K>(z, x);
 }
 
 // a (D layout: a[r] = A[4r+g][c]) is replaced by its projection.  T: NS_LDS_DOUBLES of LDS private to the wave.
 // KSZ: row groups that can hold live indices; the products run over the row groups that actually do (wave-uniform).
-// xstash: optional 256 doubles of wave-private LDS: X = a - eps I waits there during the iteration instead of in 8 registers (the
-// sweep kernel that wants a third wave per SIMD passes it)
 // SYMIN: the caller guarantees a bitwise symmetric tile (the DDP ring sweep contracts element (i, j) and (j, i) from the same packed row
 // in the same order): the input symmetrisation -- an identity then -- and its LDS round trip are skipped.
 template <int KSZ, bool SYMIN = false>
 __device__ __forceinline__ void psd_project_ns(d4& a, const bool (&live)[4], const double eps, double* T, const int g,
-                                               const int c, double* xstash = nullptr) {
+                                               const int c) {
     int flip = 0;
     d4 x;
     if constexpr (!SYMIN) a = ns_symmetrise(a, T, flip, g, c);        // jnp.linalg.eigh symmetrises its input
@@ -192,10 +175,10 @@ __device__ __forceinline__ void psd_project_ns(d4& a, const bool (&live)[4], con
         for (int r = 0; r < 4; ++r) z[r] = x[r] * inv;
         // nonzero columns all below row group `need`: the higher groups of every iterate stay zero and are skipped
         const int need = (colmask >> 12) ? 4 : (colmask >> 8) ? 3 : (colmask >> 4) ? 2 : 1;
-        if (KSZ >= 4 && need == 4) ax = ns_sign_times<(KSZ >= 4 ? 4 : KSZ)>(z, x, idr, T, flip, g, c, xstash);
-        else if (KSZ >= 3 && need == 3) ax = ns_sign_times<(KSZ >= 3 ? 3 : KSZ)>(z, x, idr, T, flip, g, c, xstash);
-        else if (KSZ >= 2 && need == 2) ax = ns_sign_times<(KSZ >= 2 ? 2 : KSZ)>(z, x, idr, T, flip, g, c, xstash);
-        else ax = ns_sign_times<1>(z, x, idr, T, flip, g, c, xstash);
+        if (KSZ >= 4 && need == 4) ax = ns_sign_times<(KSZ >= 4 ? 4 : KSZ)>(z, x, idr, T, flip, g, c);
+        else if (KSZ >= 3 && need == 3) ax = ns_sign_times<(KSZ >= 3 ? 3 : KSZ)>(z, x, idr, T, flip, g, c);
+        else if (KSZ >= 2 && need == 2) ax = ns_sign_times<(KSZ >= 2 ? 2 : KSZ)>(z, x, idr, T, flip, g, c);
+        else ax = ns_sign_times<1>(z, x, idr, T, flip, g, c);
     }
     d4 p;
 #pragma unroll

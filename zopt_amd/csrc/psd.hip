@@ -1,25 +1,21 @@
-// K5  psd_project -- batched symmetric eigen-decomposition, eigenvalue clamp, reconstruction; fp64, gfx950.
+// K5  psd_project -- batched PD projection of symmetric matrices (the eigenvalue clamp of an eigen-decomposition); fp64, gfx950.
 //
 // Replaces zopt/ilqrUtils.py:217-219 ensurePositiveDefinite(a, eps):  w, v = eigh(a);  (v * max(w, eps)) @ v.T
 // (jnp.linalg.eigh symmetrises its input: (a + a^T)/2) and its users conditionQuadraticCost (:222-234) and
 // conditionValueFunction (:254-257).  The result is a spectral function of the matrix, so it does not depend on
 // the eigenvector signs / ordering an eigensolver happens to return.
 //
-// One wave64 per matrix (k <= 16), matrix and eigenvector accumulator in LDS.  Cyclic two-sided Jacobi with the
-// round-robin parallel ordering: K-1 rounds per sweep, K/2 disjoint rotations per round; the rotations of a round are
-// computed by K/2 lanes, then every lane applies them to its share of the column pairs (A, V) and of the row pairs (A).
-// Sweeps stop when a whole sweep found every |a_pq| <= 2^-52 * sqrt(|a_pp a_qq|) (quadratic convergence: one extra
-// sweep at most), or after 20 sweeps.
-#include "jacobi16.h"
+// One wave64 per matrix (k <= 16): the k x k matrix sits zero-padded in one 16 x 16 MFMA tile and is projected there without an
+// eigen-decomposition, by the matrix-sign iteration of ns16.h (V max(w, eps) V^T = eps I + (X + |X|) / 2 with X = a - eps I).
+// 16 < k <= 64: psd_tiled.hip.
 #include "ns16.h"
 #include "psd_mats.h"
 #include "zm_common.h"
 
 namespace zm {
 
-#ifndef ZM_PSD_JACOBI
-// one wave per matrix: the k x k matrix sits zero-padded in one 16 x 16 MFMA tile (lane (g, c) holds rows 4r+g of column c) and
-// is projected by the matrix-sign iteration of ns16.h -- ~100-200 fp64 MFMAs instead of ~10 Jacobi sweeps through LDS
+// lane (g, c) holds rows 4r+g of column c of the tile; the projection is ~100-200 fp64 MFMAs (the cyclic Jacobi through LDS it
+// replaced took ~10 sweeps and was bound by LDS bandwidth: DESIGN 2.5)
 template <class Mat, int KSZ>
 __device__ __forceinline__ void psd_project_tile(const Mat& M, const long mat, const int k, const double eps, double* T) {
     const int lane = threadIdx.x, g = lane >> 4, c = lane & 15;
@@ -50,25 +46,6 @@ __global__ __launch_bounds__(64) void psd_project_kernel(const Mat M, const int 
     else if (k <= 12) psd_project_tile<Mat, 3>(M, mat, k, eps, T);
     else psd_project_tile<Mat, 4>(M, mat, k, eps, T);
 }
-#else
-template <class Mat>
-__global__ __launch_bounds__(64) void psd_project_kernel(const Mat M, const int k, const double eps, const long count) {
-    __shared__ double As[PK * PLD], Vs[PK * PLD], cs[PK];
-    __shared__ int pq[PK];
-    const int lane = threadIdx.x;
-    const long mat = blockIdx.x;
-    if (mat >= count) return;
-    // load and symmetrise (jnp.linalg.eigh: symmetrize_input=True)
-    for (int e = lane; e < k * k; e += 64) {
-        const int i = e / k, j = e % k;
-        As[i * PLD + j] = 0.5 * (M.load(mat, i, j) + M.load(mat, j, i));
-    }
-    wave_lds_sync();
-    psd_project_lds(As, Vs, cs, pq, k, eps, lane);
-    for (int e = lane; e < k * k; e += 64) M.store(mat, e / k, e % k, As[(e / k) * PLD + (e % k)]);
-}
-
-#endif
 
 // psd_tiled.hip: the same projection on NT x NT tiles for 16 < k <= 64
 int psd_project_tiled_plain(double* A, int64_t count, int k, double eps, hipStream_t st);

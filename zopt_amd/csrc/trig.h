@@ -12,10 +12,6 @@ namespace zm {
 
 __device__ __forceinline__ void zm_sincos(const double x, double* sn, double* cs) {
 #pragma clang fp contract(off)   // every FMA below is explicit: the same bits in whichever kernel this is inlined (see quad_step.h)
-#ifdef ZM_LIBM_SINCOS   // A/B builds: the library everywhere
-    sincos(x, sn, cs);
-    return;
-#endif
     const double k = __builtin_rint(x * 6.36619772367581382433e-01);        // x * 2/pi
     double r = __builtin_fma(-k, 1.57079632679489655800e+00, x);            // fl(pi/2)
     r = __builtin_fma(-k, 6.12323399573676603587e-17, r);                   // pi/2 - fl(pi/2)
