@@ -468,6 +468,31 @@ int zm_mpc_solve_batched_f64(const double* A, const double* B, const double* K, 
                              double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N,
                              int n, int m, void* stream);
 
+/* Reference tracking: the cost of zopt/mpcUtils.py:52-54 about a reference,
+ *     sum_{k<N} (x_k - xr_k)'Q(x_k - xr_k) + (u_k - ur_k)'R(u_k - ur_k)  +  (x_N - xr_N)'Qf(x_N - xr_N),
+ * under the unchanged constraints of :55-58 (the reference regulates to the origin: xr = 0, ur = 0).  A reference only adds a linear
+ * term to the w-update's LQ problem, g_x,k = -(W + W') xr_{k+1} (W = Q, Qf at the last stage), g_u,k = -(R + R') ur_k, constant over
+ * the ADMM iterations: the tables K, Minv of zm_mpc_setup_f64 / zm_mpc_setup_batched_f64, the projection and the infeasibility
+ * certificate are those of zm_mpc_solve_relaxed_f64; the backward stage uses -rho (y - lam) + g_k and the dual tolerance scales with
+ * max(rho |lam|_inf, |g|_inf) (OSQP's ||q|| term).  With xr = 0 and ur = 0 the iterates are those of zm_mpc_solve_relaxed_f64 /
+ * zm_mpc_solve_batched_f64, move for move.  With a non-zero reference the 16-lanes-per-instance kernels also guard the adaptive penalty
+ * against a limit cycle: the third level move in a row that undoes the one before is refused and the penalty then stays fixed.
+ * Affine dynamics offsets x+ = A x + B u + c are NOT covered (they need their own setup tables).
+ *     in : everything zm_mpc_solve_batched_f64 takes, and the weights Q, R, Qf the tables were set up with   [device]
+ *          xRef (batch,N+1,n)  uRef (batch,N,m): the references; either may be NULL (zero).  Row 0 of xRef is not read.   [device]
+ *          shared problem: problem = NULL, rho_p = NULL, the penalty in `rho`, every array without the P axis (P is ignored);
+ *          per-problem data: problem (batch) int32 and rho_p (P) as in zm_mpc_solve_batched_f64 (`rho` is ignored), Q, R, Qf (P,...)
+ *          workspace: 5 * batch * N * (n + m) doubles -- the four blocks of zm_mpc_solve_f64 (the warm start lives there) and
+ *                     g (batch,N,n+m), which the call forms from the references before it launches the solve
+ *     out: as zm_mpc_solve_relaxed_f64.  Same dispatch, ZOPT_AMD_MPC_PATH=lane included. */
+int zm_mpc_solve_tracking_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                              const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                              const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
+                              const double* uRef, double rho, const double* rho_p, const int32_t* problem, int64_t P, double eps_abs,
+                              double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
+                              double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

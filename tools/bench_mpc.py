@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Secondary benchmark (not the driver's bench.py line): BASELINE configs[2] -- lqrMpc on the quadcopter linearised at
 hover (demos/lqrMpc.py:11-32: dt = 0.1, Q = R = I, the demo's bounds), N = 30, `batch` independent instances with
-x0[9:12] ~ U(-10,10)^3 and small velocities / angles.  Reports wall time per batched solve, ADMM iterations and status mix."""
+x0[9:12] ~ U(-10,10)^3 and small velocities / angles.  Reports wall time per batched solve, ADMM iterations and status mix.
+
+--reps R adds a timed leg per tolerance: R cold solves (host clock around a device synchronise, after a warm-up of the same shape), median and
+spread, and the time per ADMM iteration (solve time over the slowest instance's iteration count: a launch ends with its last instance).
+--track times the reference-tracking solve (xRef: every instance follows a position ramp from where it stands, uRef = 0) next to the plain
+one, alternating the two.  --tree DIR imports zopt_amd from another checkout (the plain legs of an older revision, for A/B)."""
 import argparse
 import json
 import os
@@ -20,7 +25,14 @@ def main():
     ap.add_argument("--eps", type=float, nargs="+", default=[1e-2, 1e-4])
     ap.add_argument("--max-iter", type=int, default=100000)
     ap.add_argument("--rh-steps", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=0, help="timed leg: cold solves per tolerance (0: off)")
+    ap.add_argument("--track", action="store_true", help="timed leg: the tracking solve next to the plain one (implies --reps 7)")
+    ap.add_argument("--tree", default=None, help="checkout to import zopt_amd from (default: this one)")
     args = ap.parse_args()
+    if args.tree:
+        sys.path.insert(0, os.path.abspath(args.tree))
+    if args.track and not args.reps:
+        args.reps = 7
     import torch
     from zopt_amd import models, mpcUtils, pytrees
     dt = 0.1
@@ -46,6 +58,38 @@ def main():
                           "iters_mean": float(its.mean()), "iters_max": int(its.max()),
                           "instance_horizon_steps_per_s": args.batch * args.N / t,
                           "admm_sweep_steps_per_s": float(its.sum()) * args.N / t}))
+
+    # timed leg: plain and tracking solves alternated, `reps` cold solves each
+    if args.reps > 0:
+        import zopt_amd
+        legs = {"plain": {}}
+        if args.track:
+            vel = rng.uniform(-0.5, 0.5, (args.batch, 3))              # inside the velocity box (1 m/s)
+            xRef = np.zeros((args.batch, args.N + 1, 12))
+            xRef[:, :, 9:12] = x0[:, None, 9:12] + vel[:, None, :] * (dt * np.arange(args.N + 1))[None, :, None]
+            xRef[:, :, 0:3] = vel[:, None, :]
+            legs["tracking"] = {"xRef": torch.as_tensor(xRef, device="cuda")}
+        for eps in args.eps:
+            kw = dict(eps_abs=eps, eps_rel=eps, max_iter=args.max_iter, warm_start=False)
+            times = {k: [] for k in legs}
+            stats = {}
+            for r in range(args.reps + 1):                              # (the first round warms the shape up and is dropped)
+                for name, ref in legs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    u0, traj, status = prob.solve(tx0, **ref, **kw)
+                    torch.cuda.synchronize()
+                    if r:
+                        times[name].append((time.perf_counter() - t0) * 1e3)
+                    stats[name] = (prob.last_iterations.copy(), float(np.mean(status == "optimal")))
+            for name in legs:
+                ts, (its, ok) = np.sort(times[name]), stats[name]
+                med = float(np.median(ts))
+                print(json.dumps({"timed": name, "tree": os.path.dirname(os.path.dirname(os.path.abspath(zopt_amd.__file__))),
+                                  "workload": f"lqrMpc quadcopter n=12 m=4 N={args.N}, {args.batch} instances, eps={eps:g}",
+                                  "reps": args.reps, "solve_ms_median": med, "solve_ms_min": float(ts[0]), "solve_ms_max": float(ts[-1]),
+                                  "iters_mean": float(its.mean()), "iters_max": int(its.max()), "optimal_frac": ok,
+                                  "ms_per_admm_iteration": med / max(int(its.max()), 1)}))
 
 
     # receding-horizon run (50 MPC steps, demos/lqrMpc.py:40-47: clip, solve, x <- xTraj[1]), warm-started

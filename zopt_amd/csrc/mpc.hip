@@ -92,6 +92,16 @@ __global__ __launch_bounds__(256) void mpc_setup_batched_kernel(const double* __
 // solve: one lane per instance
 // ----------------------------------------------------------------------------------------------------------------
 
+// The hooks of the body (mpc_solve_lane_body.h) for the reference-tracking variant: nothing in the kernels without a reference, so
+// those compile from the tokens they always had.
+#define ZM_TRK_SETUP
+#define ZM_TRK_FIRST
+#define ZM_TRK_PREFETCH(k)
+#define ZM_TRK_PX
+#define ZM_TRK_QU(j)
+#define ZM_TRK_ROTATE
+#define ZM_TRK_ED(ed, dual)
+
 // The shared tables are separate `const __restrict__` kernel arguments so that hipcc can prove them read-only and
 // fetch them with scalar loads (wave-uniform addresses) instead of per-lane vector loads held in hundreds of VGPRs.
 template <int NS, int MC>
@@ -130,6 +140,108 @@ __global__ __launch_bounds__(64) void mpc_solve_batched_kernel(const double* __r
 #include "mpc_solve_lane_body.h"
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// reference tracking (zm_mpc_solve_tracking_f64)
+// ----------------------------------------------------------------------------------------------------------------
+
+// The linear term of  sum_k (x_k - xr_k)' Q (x_k - xr_k) + (u_k - ur_k)' R (u_k - ur_k) + (x_N - xr_N)' Qf (x_N - xr_N)  in the stacked
+// stage layout [x_{k+1} ; u_k] of the solve kernels: one thread per component,
+//     g_x,k = -(W + W') xr_{k+1}   (W = Q for k < N-1, Qf for k = N-1),      g_u,k = -(R + R') ur_k.
+// xr_0 only shifts the cost by a constant and is not read.  prob != NULL: instance b uses the weights of problem prob[b] (already
+// checked against P on the host).  A NULL reference is zero.
+__global__ __launch_bounds__(256) void mpc_track_linear_kernel(const double* __restrict__ Q, const double* __restrict__ R,
+                                                               const double* __restrict__ Qf, const double* __restrict__ xRef,
+                                                               const double* __restrict__ uRef, const int* __restrict__ prob,
+                                                               const long batch, const int N, const int n, const int m,
+                                                               double* __restrict__ g) {
+    const int W = n + m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * N * W) return;
+    const int i = (int)(e % W);
+    const long s = e / W;
+    const int k = (int)(s % N);
+    const long b = s / N;
+    const long p = prob ? prob[b] : 0;
+    double acc = 0.0;
+    if (i < n) {
+        if (xRef) {
+            const double* Wm = (k == N - 1 ? Qf : Q) + p * n * n;
+            const double* xr = xRef + (b * (N + 1) + k + 1) * n;
+            for (int j = 0; j < n; ++j) acc = __builtin_fma(Wm[i * n + j] + Wm[j * n + i], xr[j], acc);
+        }
+    } else if (uRef) {
+        const int r = i - n;
+        const double* Rm = R + p * m * m;
+        const double* ur = uRef + (b * N + k) * m;
+        for (int j = 0; j < m; ++j) acc = __builtin_fma(Rm[r * m + j] + Rm[j * m + r], ur[j], acc);
+    }
+    g[e] = -acc;
+}
+
+// The lane-per-instance body with the linear term: the lane's g_k (instance-major, as the wave kernel reads it: a coverage path) is
+// fetched one stage ahead like (y, lam) and enters the costate and Qu next to -rho (y - lam); the dual tolerance scales with
+// max(rho |lam|_inf, |g|_inf).  PB: per-problem data, the entry block of mpc_solve_batched_kernel.
+#undef ZM_TRK_SETUP
+#undef ZM_TRK_FIRST
+#undef ZM_TRK_PREFETCH
+#undef ZM_TRK_PX
+#undef ZM_TRK_QU
+#undef ZM_TRK_ROTATE
+#undef ZM_TRK_ED
+#define ZM_TRK_SETUP                                                                           \
+    const double* gr = trk.g + ii * ((long)N * W);                                             \
+    double gnorm = 0.0;                                                                        \
+    for (long e = 0; e < (long)N * W; ++e) gnorm = __builtin_fmax(gnorm, __builtin_fabs(gr[e]));
+#define ZM_TRK_FIRST \
+    double gb[W];    \
+    _Pragma("unroll") for (int i = 0; i < W; ++i) gb[i] = gr[(long)(N - 1) * W + i];
+#define ZM_TRK_PREFETCH(k)                                                             \
+    double gq[W];                                                                      \
+    {                                                                                  \
+        const int kp = k > 0 ? k - 1 : 0;                                              \
+        _Pragma("unroll") for (int i = 0; i < W; ++i) gq[i] = gr[(long)kp * W + i];    \
+    }
+#define ZM_TRK_PX _Pragma("unroll") for (int i = 0; i < NS; ++i) p[i] += gb[i];
+#define ZM_TRK_QU(j) +gb[NS + j]
+#define ZM_TRK_ROTATE _Pragma("unroll") for (int i = 0; i < W; ++i) gb[i] = gq[i];
+#define ZM_TRK_ED(ed, dual) \
+    if (gnorm > dual) ed = g.eps_abs + g.eps_rel * gnorm;
+template <int NS, int MC, bool PB>
+__global__ __launch_bounds__(64) void mpc_solve_track_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                             const double* __restrict__ Ktab, const double* __restrict__ Mtab,
+                                                             const double* __restrict__ x_lb, const double* __restrict__ x_ub,
+                                                             const double* __restrict__ u_lb, const double* __restrict__ u_ub,
+                                                             const MpcArgs g_all, const MpcProb pb, const MpcTrack trk) {
+    MpcArgs g = g_all;
+    if constexpr (PB) {
+        const long inst = (long)blockIdx.x * 64 + threadIdx.x;
+        if (inst >= g.batch) return;
+        const long p = pb.prob[inst];
+        A += p * NS * NS;
+        B += p * NS * MC;
+        Ktab += p * g.n_levels * g.N * MC * NS;
+        Mtab += p * g.n_levels * g.N * MC * MC;
+        x_lb += p * NS;
+        x_ub += p * NS;
+        u_lb += p * MC;
+        u_ub += p * MC;
+        g.rho = pb.rho[p];
+    }
+#include "mpc_solve_lane_body.h"
+}
+
+template <int NS, int MC>
+static int launch_mpc_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, hipStream_t st) {
+    const dim3 grid((unsigned)((g.batch + 63) / 64));
+    if (pb)
+        hipLaunchKernelGGL((mpc_solve_track_kernel<NS, MC, true>), grid, dim3(64), 0, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
+                           t.u_ub, g, *pb, trk);
+    else
+        hipLaunchKernelGGL((mpc_solve_track_kernel<NS, MC, false>), grid, dim3(64), 0, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
+                           t.u_ub, g, MpcProb{}, trk);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
 
 template <int NS, int MC>
 static int launch_mpc(const MpcTabs& t, const MpcArgs& g, hipStream_t st) {
@@ -313,4 +425,74 @@ extern "C" int zm_mpc_solve_batched_f64(const double* A, const double* B, const 
     if (n == 2 && m == 1) return zm::launch_mpc_batched<2, 1>(t, g, pb, st);
     if (n == 1 && m == 1) return zm::launch_mpc_batched<1, 1>(t, g, pb, st);
     return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_solve_batched_f64: (n=%d, m=%d) not among the compiled shapes", n, m);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// reference tracking: xRef, uRef -> g (mpc_track_linear_kernel), then the tracking variants of the solve kernels
+// ---------------------------------------------------------------------------------------------------------------------
+
+extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
+                                         const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha,
+                                         const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub,
+                                         const double* x0, const double* xRef, const double* uRef, double rho,
+                                         const double* rho_p, const int32_t* problem, int64_t P, double eps_abs, double eps_rel,
+                                         double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
+                                         double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n,
+                                         int m, void* stream) {
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    if (!(alpha > 0.0 && alpha < 2.0)) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: alpha must lie in (0, 2)");
+    if (!A || !B || !Q || !R || !Qf || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !xTraj || !uTraj ||
+        !status)
+        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: null pointer");
+    if ((problem == nullptr) != (rho_p == nullptr))
+        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: the problem map and the per-problem rho come together");
+    if (batch < 0 || N < 1 || n < 1 || m < 1 || max_iter < 0 || (problem ? P < 1 : !(rho > 0.0)))
+        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: bad size / rho");
+    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
+        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: bad penalty levels");
+    const long W = (long)n + m;
+    const long blocks = ((long)batch * N * W + 255) / 256;
+    if (blocks > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: batch x N x (n + m) too large");
+    hipStream_t st = (hipStream_t)stream;
+    if (problem) {   // as zm_mpc_solve_batched_f64: the index map is checked on the host before anything is launched
+        static thread_local std::vector<int32_t> h;
+        h.resize((size_t)batch);
+        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ZM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int64_t i = 0; i < batch; ++i)
+            if (h[i] < 0 || h[i] >= P)
+                return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: instance %lld maps to problem %d outside [0, %lld)",
+                                     (long long)i, (int)h[i], (long long)P);
+    }
+    // the fifth block of the workspace: g (batch, N, n + m)
+    double* gbuf = workspace + 4L * batch * N * W;
+    hipLaunchKernelGGL(zm::mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
+                       (long)batch, N, n, m, gbuf);
+    ZM_HIP_CHECK(hipGetLastError());
+    zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    zm::MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace,
+                  xTraj, uTraj, (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
+    const zm::MpcProb pbv{(const int*)problem, rho_p};
+    const zm::MpcProb* pb = problem ? &pbv : nullptr;
+    const zm::MpcTrack trk{gbuf};
+    // the dispatch rule of zm_mpc_solve_relaxed_f64
+    static const bool force_lane = [] {
+        const char* e = zm::fallback_env("ZOPT_AMD_MPC_PATH");
+        return e && e[0] == 'l';
+    }();
+    if (!force_lane) {
+        const int rc = zm::mpc_wave_dispatch_track(t, g, pb, trk, n, m, st);
+        if (rc != ZM_EUNSUPPORTED) return rc;
+    }
+    t.K = K + (long)level0 * N * m * n;        // (+ p * n_levels * N * m * n in the kernel)
+    t.Minv = Minv + (long)level0 * N * m * m;
+    if (n == 24 && m == 8) return zm::launch_mpc_track<24, 8>(t, g, pb, trk, st);
+    if (n == 12 && m == 4) return zm::launch_mpc_track<12, 4>(t, g, pb, trk, st);
+    if (n == 8 && m == 4) return zm::launch_mpc_track<8, 4>(t, g, pb, trk, st);
+    if (n == 4 && m == 2) return zm::launch_mpc_track<4, 2>(t, g, pb, trk, st);
+    if (n == 4 && m == 1) return zm::launch_mpc_track<4, 1>(t, g, pb, trk, st);
+    if (n == 2 && m == 2) return zm::launch_mpc_track<2, 2>(t, g, pb, trk, st);
+    if (n == 2 && m == 1) return zm::launch_mpc_track<2, 1>(t, g, pb, trk, st);
+    if (n == 1 && m == 1) return zm::launch_mpc_track<1, 1>(t, g, pb, trk, st);
+    return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_solve_tracking_f64: (n=%d, m=%d) not among the compiled shapes", n, m);
 }

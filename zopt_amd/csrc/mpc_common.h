@@ -38,8 +38,17 @@ struct MpcProb {
     const double* rho;
 };
 
+// reference tracking (zm_mpc_solve_tracking_f64): the linear term of the cost, g (batch, N, n + m) in the stacked stage layout
+// [x_{k+1} ; u_k], formed once per solve by mpc_track_linear_kernel (mpc.hip) and constant over the ADMM iterations.  Its own kernel
+// argument, after MpcArgs / MpcProb: the argument blocks of the kernels without a reference keep their layout.
+struct MpcTrack {
+    const double* g;
+};
+
 // mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.
 int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, int n, int m, hipStream_t st);
 int mpc_wave_dispatch_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st);
+// the tracking variants; pb == nullptr: one problem shared by every instance
+int mpc_wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, int n, int m, hipStream_t st);
 
 }  // namespace zm

@@ -2,6 +2,8 @@
 // A function BODY, not a header: #included verbatim inside mpc_solve_kernel and mpc_solve_batched_kernel (mpc.hip), so that the
 // kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/isa_identity.py checks
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
+// The ZM_TRK_* hooks are the reference-tracking variant (mpc.hip: mpc_solve_track_kernel); they expand to nothing in the kernels
+// without a reference.
     constexpr int W = NS + MC;
     const long inst = (long)blockIdx.x * 64 + threadIdx.x;
     // Lanes beyond the batch leave at once: the sweeps below store unconditionally (no branch per store), so no lane may
@@ -45,6 +47,7 @@
         for (int j = 0; j < MC; ++j) kf[((long)k * MC + j) * bt + ii] = 0.0;
     }
 
+    ZM_TRK_SETUP
     int status = x0_ok ? 0 : ZM_MPC_INFEASIBLE;
     int it = 0;  // this lane's ADMM iterations
     double rp = 0.0, rd = 0.0;
@@ -68,6 +71,7 @@
             yb[i] = y[e];
             lb[i] = lam[e];
         }
+        ZM_TRK_FIRST
 #pragma unroll 1
         for (int k = N - 1; k >= 0; --k) {
             const double* Kk = Ktab + (long)k * MC * NS;
@@ -84,12 +88,14 @@
 #pragma unroll
                 for (int j = 0; j < MC; ++j) kfo[j] = kf[((long)k * MC + j) * bt + ii];
             }
+            ZM_TRK_PREFETCH(k)
 #pragma unroll
             for (int i = 0; i < NS; ++i) p[i] = __builtin_fma(-rho, yb[i] - lb[i], p[i]);
+            ZM_TRK_PX
             double qu[MC];
 #pragma unroll
             for (int j = 0; j < MC; ++j) {
-                double sacc = -rho * (yb[NS + j] - lb[NS + j]);
+                double sacc = -rho * (yb[NS + j] - lb[NS + j]) ZM_TRK_QU(j);
 #pragma unroll
                 for (int i = 0; i < NS; ++i) sacc = __builtin_fma(B[i * MC + j], p[i], sacc);
                 qu[j] = sacc;
@@ -118,6 +124,7 @@
                 yb[i] = yq[i];
                 lb[i] = lq[i];
             }
+            ZM_TRK_ROTATE
         }
         // ---- forward rollout w, projection y, dual update lam, residual norms (and r = w - y, support function on chk)
         double x[NS];
@@ -213,7 +220,8 @@
             rp = nrp;
             rd = rho * nrd;
             const double ep = g.eps_abs + g.eps_rel * __builtin_fmax(nw, ny);
-            const double ed = g.eps_abs + g.eps_rel * rho * nl;
+            double ed = g.eps_abs + g.eps_rel * rho * nl;
+            ZM_TRK_ED(ed, rho * nl)
             near_ok = (rp <= 10.0 * ep) && (rd <= 10.0 * ed);
             if (rp <= ep && rd <= ed) {
                 status = ZM_MPC_OPTIMAL;

@@ -2,6 +2,8 @@
 // A function BODY, not a header: #included verbatim inside mpc_solve_wave_kernel and mpc_solve_wave_batched_kernel (mpc_wave.hip), so that the
 // kernel that existed before the per-problem variant compiles from the very same tokens (same ISA; tools/isa_identity.py checks
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
+// The ZM_TRK_* hooks are the reference-tracking variant (mpc_wave.hip: mpc_solve_wave_track_kernel); they expand to nothing in the
+// kernels without a reference.
     static_assert(NS + MC <= 16, "the stacked index must fit the 16 lanes of a group");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int W = NS + MC;
@@ -71,6 +73,7 @@
     struct Tab {
         double fwd[NS], adj[MC];
         double y, lam, kf;
+        ZM_TRK_TAB
     };
     // Table addresses: a per-lane base (role and penalty level: set at the top of every ADMM iteration) plus stage index x a per-lane
     // stage stride -- one v_mad per table and stage; the elements of a slice sit at compile-time offsets on either side of the role mask.
@@ -103,6 +106,7 @@
         for (int i = 0; i < NS; ++i) t.fwd[i] = Arow[i];
     };
 
+    ZM_TRK_SETUP
     const double alpha = g.alpha, om_alpha = 1.0 - g.alpha;
     int status = x0_in ? 0 : ZM_MPC_INFEASIBLE;
     int it = 0;
@@ -120,8 +124,8 @@
             auto bstage = [&](const int k, const Tab& t) {
                 const double z = -rho * (t.y - t.lam);    // -rho z_x (state lanes), -rho z_u (control lanes)
                 const double kfo = t.kf;
-                const double p = pp + z;                  // costate of x_{k+1} (state lanes)
-                double q = sx ? 0.0 : z;
+                const double p = pp + z ZM_TRK_G(t);      // costate of x_{k+1} (state lanes)
+                double q = sx ? 0.0 : z ZM_TRK_G(t);
                 mv<NS>(ABcol, p, q);                      // A^T p (state lanes);  Qu = -rho z_u + B^T p (control lanes)
                 double r = 0.0;
                 mv<MC, NS>(t.adj, q, r);                  // K^T Qu (state lanes);  kf = Suu^-1 Qu (control lanes)
@@ -132,15 +136,21 @@
             load_tab(N - 1, t0);
             load_tab(N - 2, t1);
             load_tab(N - 3, t2);
+            ZM_TRK_LOAD(N - 1, t0)
+            ZM_TRK_LOAD(N - 2, t1)
+            ZM_TRK_LOAD(N - 3, t2)
             int k = N - 1;
 #pragma unroll 1
             for (; k >= 2; k -= 3) {
                 bstage(k, t0);
                 load_tab(k - 3, t0);
+                ZM_TRK_LOAD(k - 3, t0)
                 bstage(k - 1, t1);
                 load_tab(k - 4, t1);
+                ZM_TRK_LOAD(k - 4, t1)
                 bstage(k - 2, t2);
                 load_tab(k - 5, t2);
+                ZM_TRK_LOAD(k - 5, t2)
             }
             if (k >= 0) bstage(k, t0);
             if (k >= 1) bstage(k - 1, t1);
@@ -208,7 +218,8 @@
             rp = nrp;
             rd = rho * nrd;
             const double ep = g.eps_abs + g.eps_rel * __builtin_fmax(nw, ny);
-            const double ed = g.eps_abs + g.eps_rel * rho * nl;
+            double ed = g.eps_abs + g.eps_rel * rho * nl;
+            ZM_TRK_ED(ed, rho * nl)
             near_ok = (rp <= 10.0 * ep) && (rd <= 10.0 * ed);
             if (rp <= ep && rd <= ed) {
                 status = ZM_MPC_OPTIMAL;
@@ -232,6 +243,7 @@
             if (want == want && want > 0.0) dl = (int)lrint(log(want) / log(g.rho_step));   // the NEAREST tabulated level
             int nl_ = lvl + dl;
             nl_ = nl_ < 0 ? 0 : (nl_ >= g.n_levels ? g.n_levels - 1 : nl_);
+            ZM_TRK_LEVEL(nl_)
             if (nl_ != lvl) {
                 const double rnew = g.rho * pow(g.rho_step, (double)(nl_ - g.level0));
                 const double sc = rho / rnew;

@@ -82,6 +82,15 @@ __device__ __forceinline__ double row_sum(double v) { return row16_sum_from8(v);
 // LDS per group and stage (doubles): y[16] lam[16] r[16] kf[16], one slot per lane
 constexpr int WS_STAGE = 64;
 
+// The hooks of the body (mpc_solve_wave_body.h) for the reference-tracking variant: nothing in the kernels without a reference, so
+// those compile from the tokens they always had.
+#define ZM_TRK_TAB
+#define ZM_TRK_SETUP
+#define ZM_TRK_G(t)
+#define ZM_TRK_LOAD(k, t)
+#define ZM_TRK_ED(ed, dual)
+#define ZM_TRK_LEVEL(nl)
+
 // Lane roles (round 3): the STACKED index [x ; u] on the 16 lanes of a group -- lane i < NS owns state component i, lane NS + j owns
 // control component j (NS + MC <= 16 for every compiled shape).  A mat-vec over the state lanes then serves both blocks of its result in
 // ONE FMA per broadcast, each lane with its own coefficients ([A^T p ; B^T p], [A x ; K x]), and the projection / dual update runs once
@@ -124,6 +133,111 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_batched_kernel(const double
     }
 #include "mpc_solve_wave_body.h"
 }
+// Reference tracking (zm_mpc_solve_tracking_f64): the same body with a second linear term, -rho (y - lam) + g_k, at the top of each
+// backward stage.  g (mpc.hip: mpc_track_linear_kernel) is constant over the iterations and read-only, so it is NOT a fifth LDS slot:
+// the lane's component of stage k is fetched from L2 three stages ahead, together with the table slices of that stage (one more
+// coalesced 128-byte line per group and stage, in flight behind the same ~500 cycles), and only in the backward sweep.  The LDS stage
+// stays WS_STAGE doubles: the horizon cap and the occupancy are those of the kernels without a reference.  The scale of the dual
+// tolerance becomes max(rho |lam|_inf, |g|_inf) (OSQP's ||q|| term); |g|_inf is taken once at entry.  PB: per-problem data, the entry
+// block of mpc_solve_wave_batched_kernel.
+#undef ZM_TRK_TAB
+#undef ZM_TRK_SETUP
+#undef ZM_TRK_G
+#undef ZM_TRK_LOAD
+#undef ZM_TRK_ED
+#undef ZM_TRK_LEVEL
+#define ZM_TRK_TAB double g;
+#define ZM_TRK_SETUP                                                                          \
+    const double* gw = trk.g + inst * ((long)N * W) + iw; /* + k * W */                       \
+    double gnorm = 0.0;                                                                       \
+    for (int k = 0; k < N; ++k) {                                                             \
+        const double gk = gw[(long)k * W];                                                    \
+        if (sw) amax(gnorm, gk);                                                              \
+    }                                                                                         \
+    gnorm = row_max(gnorm);                                                                   \
+    int trk_last = 0, trk_rev = 0; /* the last level move; consecutive reversals of it */     \
+    bool trk_locked = false;                                                                  \
+    auto load_g = [&](int k, Tab& t) {                                                        \
+        k = k < 0 ? 0 : (k >= N ? N - 1 : k);                                                 \
+        t.g = gw[(long)k * W];                                                                \
+    };
+// (added to the costate and to Qu, not to z: the sums without a reference keep their roundings, so a zero reference gives their bits)
+#define ZM_TRK_G(t) +t.g
+#define ZM_TRK_LOAD(k, t) load_g(k, t);
+#define ZM_TRK_ED(ed, dual) \
+    if (gnorm > dual) ed = g.eps_abs + g.eps_rel * gnorm;
+// Cycle guard of the adaptive penalty.  The level rule reads the residual ratio one check (ZM_MPC_CHK iterations) after a move, while
+// the move's transient still dominates it; from a cold start far from a reference outside the box two adjacent levels can each ask
+// for the other at every check, for ever (seen: levels 5 <-> 6, ratio ~5.5 / ~0.34, "user_limit" where a fixed penalty needs 95
+// iterations).  A move that undoes the move of the check before is a reversal; the third reversal in a row is refused and the
+// penalty stays where it is for the rest of the solve (ADMM converges at any fixed penalty).  Anything short of that pattern -- in
+// particular every solve whose level sequence does not ping-pong four times running -- takes the moves of the kernels without a
+// reference, which have no such guard (their code is pinned).  With a zero reference (g = 0) the guard is off: that solve IS the
+// regulator's, move for move, as zm_mpc_solve_tracking_f64 promises.
+constexpr int ZM_TRK_REVERSALS = 3;
+#define ZM_TRK_LEVEL(nl)                                                                  \
+    if (gnorm > 0.0) {                                                                    \
+        const int mv = nl - lvl;                                                          \
+        if (trk_locked) {                                                                 \
+            nl = lvl;                                                                     \
+        } else if (mv != 0 && trk_last != 0 && ((mv > 0) != (trk_last > 0))) {            \
+            if (++trk_rev >= ZM_TRK_REVERSALS) {                                          \
+                trk_locked = true;                                                        \
+                nl = lvl;                                                                 \
+            }                                                                             \
+        } else {                                                                          \
+            trk_rev = 0;                                                                  \
+        }                                                                                 \
+        trk_last = nl - lvl;                                                              \
+    }
+template <int NS, int MC, bool PB>
+__global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                                  const double* __restrict__ Ktab, const double* __restrict__ Mtab,
+                                                                  const double* __restrict__ x_lb, const double* __restrict__ x_ub,
+                                                                  const double* __restrict__ u_lb, const double* __restrict__ u_ub,
+                                                                  const MpcArgs g_all, const MpcProb pb, const MpcTrack trk) {
+    MpcArgs g = g_all;
+    if constexpr (PB) {
+        const long inst_raw = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
+        const long p = pb.prob[inst_raw < g.batch ? inst_raw : g.batch - 1];
+        A += p * NS * NS;
+        B += p * NS * MC;
+        Ktab += p * g.n_levels * g.N * MC * NS;
+        Mtab += p * g.n_levels * g.N * MC * MC;
+        x_lb += p * NS;
+        x_ub += p * NS;
+        u_lb += p * MC;
+        u_ub += p * MC;
+        g.rho = pb.rho[p];
+    }
+#include "mpc_solve_wave_body.h"
+}
+
+template <int NS, int MC, bool PB>
+static int launch_wave_track(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, hipStream_t st) {
+    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
+    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // as launch_wave: the lane-per-instance tracking kernel takes it
+    ZM_HIP_CHECK(hipFuncSetAttribute((const void*)mpc_solve_wave_track_kernel<NS, MC, PB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     150 * 1024));
+    hipLaunchKernelGGL((mpc_solve_wave_track_kernel<NS, MC, PB>), dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B,
+                       t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g, pb, trk);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+template <bool PB>
+static int wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, int n, int m,
+                               hipStream_t st) {
+    if (n == 12 && m == 4) return launch_wave_track<12, 4, PB>(t, g, pb, trk, st);
+    if (n == 8 && m == 4) return launch_wave_track<8, 4, PB>(t, g, pb, trk, st);
+    if (n == 4 && m == 2) return launch_wave_track<4, 2, PB>(t, g, pb, trk, st);
+    if (n == 4 && m == 1) return launch_wave_track<4, 1, PB>(t, g, pb, trk, st);
+    if (n == 2 && m == 2) return launch_wave_track<2, 2, PB>(t, g, pb, trk, st);
+    if (n == 2 && m == 1) return launch_wave_track<2, 1, PB>(t, g, pb, trk, st);
+    if (n == 1 && m == 1) return launch_wave_track<1, 1, PB>(t, g, pb, trk, st);
+    return ZM_EUNSUPPORTED;
+}
+
 template <int NS, int MC, bool PB>
 static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, hipStream_t st) {
     const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
@@ -159,6 +273,10 @@ int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, int n, int m, hipStrea
 
 int mpc_wave_dispatch_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st) {
     return wave_dispatch<true>(t, g, pb, n, m, st);
+}
+
+int mpc_wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, int n, int m, hipStream_t st) {
+    return pb ? wave_dispatch_track<true>(t, g, *pb, trk, n, m, st) : wave_dispatch_track<false>(t, g, MpcProb{}, trk, n, m, st);
 }
 
 }  // namespace zm

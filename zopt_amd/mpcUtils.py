@@ -1,7 +1,8 @@
 """Drop-in for the solve path of ``zopt.mpcUtils`` (class ``lqrMpc``) on MI355X HIP kernels.
 
 Same constructor and ``solve`` signature as the reference (mpcUtils.py:14-26, 61-81).  New: ``x0`` may carry leading
-batch axes -- every initial state is an independent QP instance solved by one GPU lane.  The plotting / animation helpers
+batch axes -- every initial state is an independent QP instance solved by one GPU lane; `solve` takes references to track (keywords
+xRef, uRef).  The plotting / animation helpers
 of the reference module (mpcUtils.py:84-202) are presentation code and not part of this package.
 """
 from __future__ import annotations
@@ -223,6 +224,11 @@ class lqrMpc():
                 horizon step first, the right guess inside the receding-horizon loop of demos/lqrMpc.py:41-48);
                 `solver` may be None or "OSQP" (the build has one solver); eps_dual_inf / verbose / polish are accepted
                 and ignored.
+                Extension (keywords): xRef (..., N+1, n), uRef (..., N, m) -- references to track: the cost becomes
+                sum (x_k - xRef_k)'Q(x_k - xRef_k) + (u_k - uRef_k)'R(u_k - uRef_k) + (x_N - xRef_N)'Qf(x_N - xRef_N) under the same
+                constraints.  Either may be None (zeros); a `Trajectory` may be given as xRef alone.  Row 0 of xRef only shifts the cost
+                by a constant (accepted so that a Trajectory's xTraj passes as is).  Leading axes broadcast against those of x0 (and the
+                problem shape).  In a receding-horizon loop the caller passes the moved reference window at every step.
 
         Returns
         -------
@@ -230,6 +236,7 @@ class lqrMpc():
             traj : Trajectory tuple (xTraj (…, N+1, n), uTraj (…, N, m))
             status : problem status, one of [optimal, optimal_inaccurate, infeasible, user_limit] (a list of them for a batch)
         """
+        xRef, uRef = kwargs.pop("xRef", None), kwargs.pop("uRef", None)
         solver = kwargs.pop("solver", None)
         if solver not in (None, "OSQP"):
             raise ValueError(f"solver {solver!r} is not available in zopt_amd (ADMM only; pass solver='OSQP' or None)")
@@ -258,6 +265,8 @@ class lqrMpc():
             kwargs.pop(k, None)
         if kwargs:
             raise TypeError(f"unknown solver options {sorted(kwargs)}")
+        if xRef is not None or uRef is not None:
+            return self._solve_tracking(x0, xRef, uRef, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift)
         if self.P is not None:
             return self._solve_batched(x0, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift)
         shp = tuple(x0.shape) if hasattr(x0, "shape") else tuple(np.shape(x0))
@@ -353,6 +362,93 @@ class lqrMpc():
         xo = arr.result_like(xT.reshape(lead + (N + 1, n))[..., :self._n_user], x0)
         uo = arr.result_like(uT.reshape(lead + (N, m))[..., :self._m_user], x0)
         status = np.vectorize(_STATUS.get, otypes=[object])(codes)
+        return uo[..., 0, :], Trajectory(xo, uo), status
+
+    def _solve_tracking(self, x0, xRef, uRef, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift):
+        """solve() about a reference (shared or per-problem data): x0, xRef and uRef broadcast to one batch shape, the references are
+        padded with zeros to the compiled shape, and zm_mpc_solve_tracking_f64 forms the linear term and runs the tracking kernels."""
+        if isinstance(xRef, Trajectory):
+            if uRef is not None:
+                raise ValueError("a Trajectory given as xRef carries its own uTraj: pass it alone (uRef=None)")
+            xRef, uRef = xRef.xTraj, xRef.uTraj
+        N, n, m = self.N, self.n, self.m
+        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+        shp = shape_of(x0)
+        if len(shp) < 1 or shp[-1] != self._n_user:
+            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
+        leads = {"x0": (shp, shp[:-1])}
+        for name, X, want in (("xRef", xRef, (N + 1, self._n_user)), ("uRef", uRef, (N, self._m_user))):
+            if X is not None:
+                s = shape_of(X)
+                if len(s) < 2 or s[-2:] != want:
+                    raise ValueError(f"{name} has shape {s}, expected (..., {want[0]}, {want[1]})")
+                leads[name] = (s, s[:-2])
+        try:
+            lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
+        except ValueError:
+            raise ValueError(", ".join(f"{k} of shape {s}" for k, (s, _) in leads.items()) + " do not broadcast against each other"
+                             + ("" if self.P is None else f" and the problem shape {self.P}") + ": inconsistent shapes") from None
+        lead = tuple(int(v) for v in lead)
+        Bn = int(np.prod(lead))
+        arr.require_gpu()
+        if Bn == 0:   # nothing to solve: shaped empty results, nothing launched
+            dev = x0.device if arr.is_torch(x0) and x0.is_cuda else torch.device("cuda")
+            self.last_iterations = np.zeros(lead, dtype=np.int32)
+            self.last_residuals = np.zeros(lead + (2,))
+            xo = arr.result_like(torch.empty(lead + (N + 1, self._n_user), dtype=torch.float64, device=dev), x0)
+            uo = arr.result_like(torch.empty(lead + (N, self._m_user), dtype=torch.float64, device=dev), x0)
+            return uo[..., 0, :], Trajectory(xo, uo), np.empty(lead, dtype=object)
+        if self.P is None:
+            d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
+            dev = x0.device if arr.is_torch(x0) and x0.is_cuda else d["A"].device
+            rho_s, drho, prob, Pn, rho_key = rho, None, None, 0, rho
+        else:
+            d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
+            dev = d["A"].device
+            Pn = int(np.prod(self.P))
+            prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P),
+                                                                        lead)).reshape(-1), device=dev)
+            rho_s, rho_key = 0.0, rho.tobytes()
+
+        def flat(X, tail, width):   # broadcast to the batch, one row per instance, the padded components zero
+            t = arr.to_device(X, torch.float64, dev)
+            t = t.expand(lead + tail).reshape((Bn,) + tail)
+            if width != tail[-1]:
+                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
+            return t.contiguous()
+        dx0 = flat(x0, (self._n_user,), n)
+        dxr = None if xRef is None else flat(xRef, (N + 1, self._n_user), n)
+        dur = None if uRef is None else flat(uRef, (N, self._m_user), m)
+        # (a workspace of its own kind: the fifth block holds the linear term of the cost)
+        key = ("tracking", lead, str(dev), rho_key, adaptive)
+        warm = warm and self._ws is not None and self._ws[0] == key
+        if not warm:
+            self._ws = (key, torch.empty(5 * Bn * N * (n + m), dtype=torch.float64, device=dev))
+        ws = self._ws[1]
+        xT = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
+        uT = torch.empty((Bn, N, m), dtype=torch.float64, device=dev)
+        st = torch.empty(Bn, dtype=torch.int32, device=dev)
+        its = torch.empty(Bn, dtype=torch.int32, device=dev)
+        res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = _lib.lib().zm_mpc_solve_tracking_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["Q"].data_ptr(), d["R"].data_ptr(),
+                                                   d["Qf"].data_ptr(), K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP,
+                                                   alpha, d["x_lb"].data_ptr(), d["x_ub"].data_ptr(), d["u_lb"].data_ptr(),
+                                                   d["u_ub"].data_ptr(), dx0.data_ptr(), ptr(dxr), ptr(dur), rho_s, ptr(drho),
+                                                   ptr(prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter,
+                                                   (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
+                                                   st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m,
+                                                   ctypes.c_void_p(arr.stream_ptr(dx0)))
+        _lib.check(rc, "lqrMpc.solve")
+        self.last_iterations = its.reshape(lead).cpu().numpy()
+        self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
+        codes = st.cpu().numpy().reshape(lead)
+        xo = arr.result_like(xT.reshape(lead + (N + 1, n))[..., :self._n_user], x0)
+        uo = arr.result_like(uT.reshape(lead + (N, m))[..., :self._m_user], x0)
+        if len(lead) == 0:
+            status = _STATUS[int(codes)]
+        else:
+            status = np.vectorize(_STATUS.get, otypes=[object])(codes)
         return uo[..., 0, :], Trajectory(xo, uo), status
 
 
