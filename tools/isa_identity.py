@@ -5,7 +5,8 @@ Compiles the given sources (default mpc.hip and mpc_wave.hip) of both trees to a
 tests/test_dpp_hazards.py; no GPU needed), cuts out every function of the base whose symbol matches the regex (default: the
 mpc_setup_kernel, mpc_solve_kernel, mpc_solve_wave_kernel instantiations) and compares with the same symbol in the working tree
   * its instruction text.  Basic-block labels carry the function's ordinal in the file (.LBB<f>_<b>), which moves when kernels are
-    added before it, so the ordinal is dropped before comparing;
+    added before it, so the ordinal is dropped before comparing; so is the per-file counter in the labels of long branches
+    (.Lpost_getpc<c>), which moves when the order of the functions in the file does;
   * for a kernel, the lines of its descriptor that decide occupancy (RESOURCES below: LDS, scratch, registers).
 A function of the base that the working tree no longer has counts as DIFFERENT.
 
@@ -48,6 +49,7 @@ def functions(asm):
             t = ln.split(";")[0].rstrip()
             t = re.sub(r"\.LBB\d+_", ".LBB_", t)
             t = re.sub(r"\.Ltmp\d+", ".Ltmp", t)
+            t = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", t)
             if t.strip():
                 body.append(t)
     return out

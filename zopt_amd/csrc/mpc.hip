@@ -28,7 +28,6 @@
 #include "mpc_common.h"
 
 #include <cstdlib>
-#include <type_traits>
 #include <vector>
 
 namespace zm {
@@ -126,16 +125,7 @@ __global__ __launch_bounds__(64) void mpc_solve_batched_kernel(const double* __r
     {
         const long inst = (long)blockIdx.x * 64 + threadIdx.x;
         if (inst >= g.batch) return;
-        const long p = pb.prob[inst];
-        A += p * NS * NS;
-        B += p * NS * MC;
-        Ktab += p * g.n_levels * g.N * MC * NS;
-        Mtab += p * g.n_levels * g.N * MC * MC;
-        x_lb += p * NS;
-        x_ub += p * NS;
-        u_lb += p * MC;
-        u_ub += p * MC;
-        g.rho = pb.rho[p];
+        ZM_MPC_ENTER_PROBLEM(inst)
     }
 #include "mpc_solve_lane_body.h"
 }
@@ -216,47 +206,112 @@ __global__ __launch_bounds__(64) void mpc_solve_track_kernel(const double* __res
     if constexpr (PB) {
         const long inst = (long)blockIdx.x * 64 + threadIdx.x;
         if (inst >= g.batch) return;
-        const long p = pb.prob[inst];
-        A += p * NS * NS;
-        B += p * NS * MC;
-        Ktab += p * g.n_levels * g.N * MC * NS;
-        Mtab += p * g.n_levels * g.N * MC * MC;
-        x_lb += p * NS;
-        x_ub += p * NS;
-        u_lb += p * MC;
-        u_ub += p * MC;
-        g.rho = pb.rho[p];
+        ZM_MPC_ENTER_PROBLEM(inst)
     }
 #include "mpc_solve_lane_body.h"
 }
 
-template <int NS, int MC>
-static int launch_mpc_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, hipStream_t st) {
-    const dim3 grid((unsigned)((g.batch + 63) / 64));
-    if (pb)
-        hipLaunchKernelGGL((mpc_solve_track_kernel<NS, MC, true>), grid, dim3(64), 0, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
-                           t.u_ub, g, *pb, trk);
-    else
-        hipLaunchKernelGGL((mpc_solve_track_kernel<NS, MC, false>), grid, dim3(64), 0, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
-                           t.u_ub, g, MpcProb{}, trk);
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
+// ----------------------------------------------------------------------------------------------------------------
+// host side: one shape ladder, one launcher, one routine behind the three solve entry points
+// ----------------------------------------------------------------------------------------------------------------
+
+// f(Int<NS>, Int<MC>) for the compiled shape (n, m); ZM_EUNSUPPORTED for any other
+template <typename F>
+static int for_mpc_shape(int n, int m, F f) {
+    if (n == 24 && m == 8) return f(Int<24>{}, Int<8>{});   // beyond the 16-index tile: lane per instance, registers + scratch
+    if (n == 12 && m == 4) return f(Int<12>{}, Int<4>{});
+    if (n == 8 && m == 4) return f(Int<8>{}, Int<4>{});
+    if (n == 4 && m == 2) return f(Int<4>{}, Int<2>{});
+    if (n == 4 && m == 1) return f(Int<4>{}, Int<1>{});
+    if (n == 2 && m == 2) return f(Int<2>{}, Int<2>{});
+    if (n == 2 && m == 1) return f(Int<2>{}, Int<1>{});
+    if (n == 1 && m == 1) return f(Int<1>{}, Int<1>{});
+    return ZM_EUNSUPPORTED;
 }
 
+// pb != nullptr: per-problem data; trk != nullptr: the tracking variants
 template <int NS, int MC>
-static int launch_mpc(const MpcTabs& t, const MpcArgs& g, hipStream_t st) {
-    hipLaunchKernelGGL((mpc_solve_kernel<NS, MC>), dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, st, t.A, t.B, t.K,
-                       t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g);
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
+static int launch_mpc(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, hipStream_t st) {
+    const auto go = [&](auto kernel, auto... more) -> int {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
+                           t.u_ub, g, more...);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    };
+    if (trk && pb) return go(mpc_solve_track_kernel<NS, MC, true>, *pb, *trk);
+    if (trk) return go(mpc_solve_track_kernel<NS, MC, false>, MpcProb{}, *trk);
+    return pb ? go(mpc_solve_batched_kernel<NS, MC>, *pb) : go(mpc_solve_kernel<NS, MC>);
 }
 
-template <int NS, int MC>
-static int launch_mpc_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, hipStream_t st) {
-    hipLaunchKernelGGL((mpc_solve_batched_kernel<NS, MC>), dim3((unsigned)((g.batch + 63) / 64)), dim3(64), 0, st, t.A, t.B, t.K,
-                       t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g, pb);
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
+// The three solve entry points.  `fn` is the entry point's name, the prefix of its error messages.
+//   zm_mpc_solve_relaxed_f64 : one problem, scalar rho                          (problem, rho_p, Q, R, Qf, xRef, uRef NULL)
+//   zm_mpc_solve_batched_f64 : per_problem -- problem and rho_p are required    (Q, R, Qf, xRef, uRef NULL)
+//   zm_mpc_solve_tracking_f64: tracking -- Q, R, Qf are required, n and m are checked, the linear term is formed first; problem and
+//                              rho_p come together or not at all
+static int mpc_solve(const char* fn, bool per_problem, bool tracking, const double* A, const double* B, const double* Q, const double* R,
+                     const double* Qf, const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha,
+                     const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub, const double* x0,
+                     const double* xRef, const double* uRef, double rho, const double* rho_p, const int32_t* problem, int64_t P,
+                     double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
+                     double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream) {
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    if (!(alpha > 0.0 && alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", fn);
+    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !xTraj || !uTraj || !status ||
+        (tracking && (!Q || !R || !Qf)) || (per_problem && (!rho_p || !problem)))
+        return set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if ((problem == nullptr) != (rho_p == nullptr))
+        return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", fn);
+    if (batch < 0 || N < 1 || max_iter < 0 || (tracking && (n < 1 || m < 1)) || (problem ? P < 1 : !(rho > 0.0)))
+        return set_error(ZM_EINVAL, tracking ? "%s: bad size / rho" : "%s: bad size", fn);
+    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
+        return set_error(ZM_EINVAL, "%s: bad penalty levels", fn);
+    const long W = (long)n + m;
+    const long blocks = ((long)batch * N * W + 255) / 256;   // of mpc_track_linear_kernel
+    if (tracking && blocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
+    hipStream_t st = (hipStream_t)stream;
+    // every instance's problem index must lie in [0, P): the kernels offset every table by it, so it is checked here, on the host,
+    // before anything is launched (one small copy of the index map; the solve's own results come back through a sync anyway)
+    if (problem) {
+        static thread_local std::vector<int32_t> h;
+        h.resize((size_t)batch);
+        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ZM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int64_t i = 0; i < batch; ++i)
+            if (h[i] < 0 || h[i] >= P)
+                return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d outside [0, %lld)", fn, (long long)i, (int)h[i],
+                                 (long long)P);
+    }
+    // tracking: the fifth block of the workspace holds the linear term g (batch, N, n + m)
+    double* gbuf = tracking ? workspace + 4L * batch * N * W : nullptr;
+    if (tracking) {
+        hipLaunchKernelGGL(mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
+                           (long)batch, N, n, m, gbuf);
+        ZM_HIP_CHECK(hipGetLastError());
+    }
+    MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    // with per-problem data g.rho is unused (each instance takes its problem's pb.rho[p]); 1.0 keeps the struct well-formed
+    const MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace,
+                    xTraj, uTraj, (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
+    const MpcProb pbv{(const int*)problem, rho_p};
+    const MpcProb* pb = problem ? &pbv : nullptr;
+    const MpcTrack trkv{gbuf};
+    const MpcTrack* trk = tracking ? &trkv : nullptr;
+    // default: 16 lanes per instance with the iterates in LDS (mpc_wave.hip); ZOPT_AMD_MPC_PATH=lane forces the
+    // lane-per-instance kernel below, which also takes the shapes and the horizons that do not fit LDS.  It runs every problem at its
+    // level0 table (fixed penalty).
+    static const bool force_lane = [] {
+        const char* e = fallback_env("ZOPT_AMD_MPC_PATH");
+        return e && e[0] == 'l';
+    }();
+    if (!force_lane) {
+        const int rc = mpc_wave_dispatch(t, g, pb, trk, n, m, st);
+        if (rc != ZM_EUNSUPPORTED) return rc;
+    }
+    t.K = K + (long)level0 * N * m * n;        // (+ p * n_levels * N * m * n in the kernel)
+    t.Minv = Minv + (long)level0 * N * m * m;
+    const int rc = for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_mpc<ns.value, mc.value>(t, g, pb, trk, st); });
+    if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the compiled shapes", fn, n, m);
+    return rc;
 }
 
 }  // namespace zm
@@ -313,38 +368,9 @@ extern "C" int zm_mpc_solve_relaxed_f64(const double* A, const double* B, const 
                                         double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace,
                                         double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
                                         int64_t batch, int N, int n, int m, void* stream) {
-    if (batch == 0) return ZM_OK;
-    if (!(alpha > 0.0 && alpha < 2.0)) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_relaxed_f64: alpha must lie in (0, 2)");   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !xTraj || !uTraj || !status)
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_f64: null pointer");
-    if (batch < 0 || N < 1 || max_iter < 0 || !(rho > 0.0)) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_f64: bad size");
-    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_adaptive_f64: bad penalty levels");
-    zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    zm::MpcArgs g{x0, rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace, xTraj, uTraj, (int*)status, (int*)iters, resid,
-                  (long)batch, N, n_levels, level0, rho_step, alpha};
-    hipStream_t st = (hipStream_t)stream;
-    // default: 16 lanes per instance with the iterates in LDS (mpc_wave.hip); ZOPT_AMD_MPC_PATH=lane forces the
-    // lane-per-instance kernel below, which also takes the horizons that do not fit LDS (fixed penalty: level0 only)
-    static const bool force_lane = [] {
-        const char* e = zm::fallback_env("ZOPT_AMD_MPC_PATH");
-        return e && e[0] == 'l';
-    }();
-    if (!force_lane) {
-        const int rc = zm::mpc_wave_dispatch(t, g, n, m, st);
-        if (rc != ZM_EUNSUPPORTED) return rc;
-    }
-    t.K = K + (long)level0 * N * m * n;
-    t.Minv = Minv + (long)level0 * N * m * m;
-    if (n == 24 && m == 8) return zm::launch_mpc<24, 8>(t, g, st);   // beyond the 16-index tile: lane per instance, registers + scratch
-    if (n == 12 && m == 4) return zm::launch_mpc<12, 4>(t, g, st);
-    if (n == 8 && m == 4) return zm::launch_mpc<8, 4>(t, g, st);
-    if (n == 4 && m == 2) return zm::launch_mpc<4, 2>(t, g, st);
-    if (n == 4 && m == 1) return zm::launch_mpc<4, 1>(t, g, st);
-    if (n == 2 && m == 2) return zm::launch_mpc<2, 2>(t, g, st);
-    if (n == 2 && m == 1) return zm::launch_mpc<2, 1>(t, g, st);
-    if (n == 1 && m == 1) return zm::launch_mpc<1, 1>(t, g, st);
-    return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_solve_f64: (n=%d, m=%d) not among the compiled shapes", n, m);
+    return zm::mpc_solve("zm_mpc_solve_relaxed_f64", false, false, A, B, nullptr, nullptr, nullptr, K, Minv, n_levels, level0, rho_step,
+                         alpha, x_lb, x_ub, u_lb, u_ub, x0, nullptr, nullptr, rho, nullptr, nullptr, 0, eps_abs, eps_rel, eps_prim_inf,
+                         max_iter, warm_start, workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -378,59 +404,12 @@ extern "C" int zm_mpc_solve_batched_f64(const double* A, const double* B, const 
                                         int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj,
                                         int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
                                         void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!(alpha > 0.0 && alpha < 2.0)) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_batched_f64: alpha must lie in (0, 2)");
-    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !rho || !problem || !workspace || !xTraj || !uTraj ||
-        !status)
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_batched_f64: null pointer");
-    if (batch < 0 || P < 1 || N < 1 || max_iter < 0) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_batched_f64: bad size");
-    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_batched_f64: bad penalty levels");
-    hipStream_t st = (hipStream_t)stream;
-    // every instance's problem index must lie in [0, P): the kernels offset every table by it, so it is checked here, on the host,
-    // before anything is launched (one small copy of the index map; the solve's own results come back through a sync anyway)
-    {
-        static thread_local std::vector<int32_t> h;
-        h.resize((size_t)batch);
-        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ZM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int64_t i = 0; i < batch; ++i)
-            if (h[i] < 0 || h[i] >= P)
-                return zm::set_error(ZM_EINVAL, "zm_mpc_solve_batched_f64: instance %lld maps to problem %d outside [0, %lld)",
-                                     (long long)i, (int)h[i], (long long)P);
-    }
-    zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    // g.rho is unused by the batched kernels (each instance takes its problem's pb.rho[p]); 1.0 keeps the struct well-formed
-    zm::MpcArgs g{x0, 1.0, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace, xTraj, uTraj,
-                  (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
-    const zm::MpcProb pb{(const int*)problem, rho};
-    // the dispatch rule of zm_mpc_solve_relaxed_f64: 16 lanes per instance unless ZOPT_AMD_MPC_PATH=lane or the shape / horizon does
-    // not fit it; the lane-per-instance kernel runs every problem at its level0 table (fixed penalty)
-    static const bool force_lane = [] {
-        const char* e = zm::fallback_env("ZOPT_AMD_MPC_PATH");
-        return e && e[0] == 'l';
-    }();
-    if (!force_lane) {
-        const int rc = zm::mpc_wave_dispatch_batched(t, g, pb, n, m, st);
-        if (rc != ZM_EUNSUPPORTED) return rc;
-    }
-    t.K = K + (long)level0 * N * m * n;        // + p * n_levels * N * m * n in the kernel
-    t.Minv = Minv + (long)level0 * N * m * m;
-    if (n == 24 && m == 8) return zm::launch_mpc_batched<24, 8>(t, g, pb, st);
-    if (n == 12 && m == 4) return zm::launch_mpc_batched<12, 4>(t, g, pb, st);
-    if (n == 8 && m == 4) return zm::launch_mpc_batched<8, 4>(t, g, pb, st);
-    if (n == 4 && m == 2) return zm::launch_mpc_batched<4, 2>(t, g, pb, st);
-    if (n == 4 && m == 1) return zm::launch_mpc_batched<4, 1>(t, g, pb, st);
-    if (n == 2 && m == 2) return zm::launch_mpc_batched<2, 2>(t, g, pb, st);
-    if (n == 2 && m == 1) return zm::launch_mpc_batched<2, 1>(t, g, pb, st);
-    if (n == 1 && m == 1) return zm::launch_mpc_batched<1, 1>(t, g, pb, st);
-    return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_solve_batched_f64: (n=%d, m=%d) not among the compiled shapes", n, m);
+    return zm::mpc_solve("zm_mpc_solve_batched_f64", true, false, A, B, nullptr, nullptr, nullptr, K, Minv, n_levels, level0, rho_step,
+                         alpha, x_lb, x_ub, u_lb, u_ub, x0, nullptr, nullptr, 0.0, rho, problem, P, eps_abs, eps_rel, eps_prim_inf,
+                         max_iter, warm_start, workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
 // reference tracking: xRef, uRef -> g (mpc_track_linear_kernel), then the tracking variants of the solve kernels
-// ---------------------------------------------------------------------------------------------------------------------
-
 extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
                                          const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha,
                                          const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub,
@@ -439,60 +418,7 @@ extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const
                                          double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
                                          double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n,
                                          int m, void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!(alpha > 0.0 && alpha < 2.0)) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: alpha must lie in (0, 2)");
-    if (!A || !B || !Q || !R || !Qf || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !xTraj || !uTraj ||
-        !status)
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: null pointer");
-    if ((problem == nullptr) != (rho_p == nullptr))
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: the problem map and the per-problem rho come together");
-    if (batch < 0 || N < 1 || n < 1 || m < 1 || max_iter < 0 || (problem ? P < 1 : !(rho > 0.0)))
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: bad size / rho");
-    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
-        return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: bad penalty levels");
-    const long W = (long)n + m;
-    const long blocks = ((long)batch * N * W + 255) / 256;
-    if (blocks > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: batch x N x (n + m) too large");
-    hipStream_t st = (hipStream_t)stream;
-    if (problem) {   // as zm_mpc_solve_batched_f64: the index map is checked on the host before anything is launched
-        static thread_local std::vector<int32_t> h;
-        h.resize((size_t)batch);
-        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ZM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int64_t i = 0; i < batch; ++i)
-            if (h[i] < 0 || h[i] >= P)
-                return zm::set_error(ZM_EINVAL, "zm_mpc_solve_tracking_f64: instance %lld maps to problem %d outside [0, %lld)",
-                                     (long long)i, (int)h[i], (long long)P);
-    }
-    // the fifth block of the workspace: g (batch, N, n + m)
-    double* gbuf = workspace + 4L * batch * N * W;
-    hipLaunchKernelGGL(zm::mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
-                       (long)batch, N, n, m, gbuf);
-    ZM_HIP_CHECK(hipGetLastError());
-    zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    zm::MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace,
-                  xTraj, uTraj, (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
-    const zm::MpcProb pbv{(const int*)problem, rho_p};
-    const zm::MpcProb* pb = problem ? &pbv : nullptr;
-    const zm::MpcTrack trk{gbuf};
-    // the dispatch rule of zm_mpc_solve_relaxed_f64
-    static const bool force_lane = [] {
-        const char* e = zm::fallback_env("ZOPT_AMD_MPC_PATH");
-        return e && e[0] == 'l';
-    }();
-    if (!force_lane) {
-        const int rc = zm::mpc_wave_dispatch_track(t, g, pb, trk, n, m, st);
-        if (rc != ZM_EUNSUPPORTED) return rc;
-    }
-    t.K = K + (long)level0 * N * m * n;        // (+ p * n_levels * N * m * n in the kernel)
-    t.Minv = Minv + (long)level0 * N * m * m;
-    if (n == 24 && m == 8) return zm::launch_mpc_track<24, 8>(t, g, pb, trk, st);
-    if (n == 12 && m == 4) return zm::launch_mpc_track<12, 4>(t, g, pb, trk, st);
-    if (n == 8 && m == 4) return zm::launch_mpc_track<8, 4>(t, g, pb, trk, st);
-    if (n == 4 && m == 2) return zm::launch_mpc_track<4, 2>(t, g, pb, trk, st);
-    if (n == 4 && m == 1) return zm::launch_mpc_track<4, 1>(t, g, pb, trk, st);
-    if (n == 2 && m == 2) return zm::launch_mpc_track<2, 2>(t, g, pb, trk, st);
-    if (n == 2 && m == 1) return zm::launch_mpc_track<2, 1>(t, g, pb, trk, st);
-    if (n == 1 && m == 1) return zm::launch_mpc_track<1, 1>(t, g, pb, trk, st);
-    return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_solve_tracking_f64: (n=%d, m=%d) not among the compiled shapes", n, m);
+    return zm::mpc_solve("zm_mpc_solve_tracking_f64", false, true, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb,
+                         x_ub, u_lb, u_ub, x0, xRef, uRef, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start,
+                         workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
 }

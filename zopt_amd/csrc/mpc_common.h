@@ -2,6 +2,8 @@
 #pragma once
 #include "zm_common.h"
 
+#include <type_traits>
+
 // Every ZM_MPC_CHK-th ADMM iteration checks the primal-infeasibility certificate and lets the adaptive penalty move (OSQP's
 // `check_termination` / `adaptive_rho_interval`, both tunables of the solver, not of the problem).  8 with moves to the NEAREST
 // tabulated level: measured on BASELINE configs[2] (profiles/r03_mpc_check_interval_ab.txt) 106 -> 60 worst-case iterations.
@@ -45,10 +47,27 @@ struct MpcTrack {
     const double* g;
 };
 
-// mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.
-int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, int n, int m, hipStream_t st);
-int mpc_wave_dispatch_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st);
-// the tracking variants; pb == nullptr: one problem shared by every instance
-int mpc_wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, int n, int m, hipStream_t st);
+// Entry block of the per-problem kernels: instance `inst` reads its problem index, offsets A, B, the bounds and the tables by it and takes
+// the problem's penalty.  A macro, not a function: the kernels' `__restrict__` parameters do not survive being passed by reference
+// (other code, more scratch).  Expands inside a kernel with the parameters of mpc_solve_batched_kernel and a local MpcArgs g.
+#define ZM_MPC_ENTER_PROBLEM(inst)              \
+    const long p = pb.prob[inst];               \
+    A += p * NS * NS;                           \
+    B += p * NS * MC;                           \
+    Ktab += p * g.n_levels * g.N * MC * NS;     \
+    Mtab += p * g.n_levels * g.N * MC * MC;     \
+    x_lb += p * NS;                             \
+    x_ub += p * NS;                             \
+    u_lb += p * MC;                             \
+    u_ub += p * MC;                             \
+    g.rho = pb.rho[p];
+
+// the (n, m) of a compiled kernel as a value: what for_mpc_shape() (one per file: the files compile different sets) hands to its callback
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.  pb: per-problem data,
+// trk: reference tracking; either may be nullptr.
+int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st);
 
 }  // namespace zm

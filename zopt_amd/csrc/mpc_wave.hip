@@ -29,9 +29,6 @@ __device__ __forceinline__ double dpp_src(double v) {
     asm("s_nop 1" : "+v"(v));
     return v;
 }
-// a1 += sum_l c1[l] v_l,  a2 += sum_l c2[l] v_l   over the first NL lanes of the row.  The sums run as PS interleaved partial
-// chains (term l goes to chain l % PS): a single chain of 12 dependent FMAs is the longest dependency of a stage, and the
-// solve is the latency of 60 such stages per ADMM iteration.
 // acc += sum_l c[l] v_(OFF + l): the vector's components sit in lanes OFF .. OFF + NL - 1 of the row.  The sums run as PS interleaved
 // partial chains (term l goes to chain l % PS; chain 0 starts from acc): a single chain of 12 dependent FMAs would be the longest
 // dependency of a stage.
@@ -120,16 +117,7 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_batched_kernel(const double
     MpcArgs g = g_all;
     {
         const long inst_raw = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
-        const long p = pb.prob[inst_raw < g.batch ? inst_raw : g.batch - 1];
-        A += p * NS * NS;
-        B += p * NS * MC;
-        Ktab += p * g.n_levels * g.N * MC * NS;
-        Mtab += p * g.n_levels * g.N * MC * MC;
-        x_lb += p * NS;
-        x_ub += p * NS;
-        u_lb += p * MC;
-        u_ub += p * MC;
-        g.rho = pb.rho[p];
+        ZM_MPC_ENTER_PROBLEM(inst_raw < g.batch ? inst_raw : g.batch - 1)
     }
 #include "mpc_solve_wave_body.h"
 }
@@ -199,84 +187,44 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
     MpcArgs g = g_all;
     if constexpr (PB) {
         const long inst_raw = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
-        const long p = pb.prob[inst_raw < g.batch ? inst_raw : g.batch - 1];
-        A += p * NS * NS;
-        B += p * NS * MC;
-        Ktab += p * g.n_levels * g.N * MC * NS;
-        Mtab += p * g.n_levels * g.N * MC * MC;
-        x_lb += p * NS;
-        x_ub += p * NS;
-        u_lb += p * MC;
-        u_ub += p * MC;
-        g.rho = pb.rho[p];
+        ZM_MPC_ENTER_PROBLEM(inst_raw < g.batch ? inst_raw : g.batch - 1)
     }
 #include "mpc_solve_wave_body.h"
 }
 
-template <int NS, int MC, bool PB>
-static int launch_wave_track(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, hipStream_t st) {
-    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
-    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // as launch_wave: the lane-per-instance tracking kernel takes it
-    ZM_HIP_CHECK(hipFuncSetAttribute((const void*)mpc_solve_wave_track_kernel<NS, MC, PB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     150 * 1024));
-    hipLaunchKernelGGL((mpc_solve_wave_track_kernel<NS, MC, PB>), dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B,
-                       t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g, pb, trk);
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
-}
-
-template <bool PB>
-static int wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, int n, int m,
-                               hipStream_t st) {
-    if (n == 12 && m == 4) return launch_wave_track<12, 4, PB>(t, g, pb, trk, st);
-    if (n == 8 && m == 4) return launch_wave_track<8, 4, PB>(t, g, pb, trk, st);
-    if (n == 4 && m == 2) return launch_wave_track<4, 2, PB>(t, g, pb, trk, st);
-    if (n == 4 && m == 1) return launch_wave_track<4, 1, PB>(t, g, pb, trk, st);
-    if (n == 2 && m == 2) return launch_wave_track<2, 2, PB>(t, g, pb, trk, st);
-    if (n == 2 && m == 1) return launch_wave_track<2, 1, PB>(t, g, pb, trk, st);
-    if (n == 1 && m == 1) return launch_wave_track<1, 1, PB>(t, g, pb, trk, st);
+// f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16; ZM_EUNSUPPORTED for any other
+template <typename F>
+static int for_mpc_shape(int n, int m, F f) {
+    if (n == 12 && m == 4) return f(Int<12>{}, Int<4>{});
+    if (n == 8 && m == 4) return f(Int<8>{}, Int<4>{});
+    if (n == 4 && m == 2) return f(Int<4>{}, Int<2>{});
+    if (n == 4 && m == 1) return f(Int<4>{}, Int<1>{});
+    if (n == 2 && m == 2) return f(Int<2>{}, Int<2>{});
+    if (n == 2 && m == 1) return f(Int<2>{}, Int<1>{});
+    if (n == 1 && m == 1) return f(Int<1>{}, Int<1>{});
     return ZM_EUNSUPPORTED;
 }
 
-template <int NS, int MC, bool PB>
-static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, hipStream_t st) {
+// pb != nullptr: per-problem data; trk != nullptr: the tracking variants
+template <int NS, int MC>
+static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, hipStream_t st) {
     const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
     if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // horizon too long for LDS: the lane-per-instance kernel takes it
-    const void* fn = PB ? (const void*)mpc_solve_wave_batched_kernel<NS, MC> : (const void*)mpc_solve_wave_kernel<NS, MC>;
-    // per launch (cheap): the attribute is per device, and several devices may be driven from one process
-    ZM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    if constexpr (PB)
-        hipLaunchKernelGGL((mpc_solve_wave_batched_kernel<NS, MC>), dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B,
-                           t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g, pb);
-    else
-        hipLaunchKernelGGL((mpc_solve_wave_kernel<NS, MC>), dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K,
-                           t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub, g);
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
+    const auto go = [&](auto kernel, auto... more) -> int {
+        // per launch (cheap): the attribute is per device, and several devices may be driven from one process
+        ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
+                           t.u_ub, g, more...);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    };
+    if (trk && pb) return go(mpc_solve_wave_track_kernel<NS, MC, true>, *pb, *trk);
+    if (trk) return go(mpc_solve_wave_track_kernel<NS, MC, false>, MpcProb{}, *trk);
+    return pb ? go(mpc_solve_wave_batched_kernel<NS, MC>, *pb) : go(mpc_solve_wave_kernel<NS, MC>);
 }
 
-template <bool PB>
-static int wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st) {
-    if (n == 12 && m == 4) return launch_wave<12, 4, PB>(t, g, pb, st);
-    if (n == 8 && m == 4) return launch_wave<8, 4, PB>(t, g, pb, st);
-    if (n == 4 && m == 2) return launch_wave<4, 2, PB>(t, g, pb, st);
-    if (n == 4 && m == 1) return launch_wave<4, 1, PB>(t, g, pb, st);
-    if (n == 2 && m == 2) return launch_wave<2, 2, PB>(t, g, pb, st);
-    if (n == 2 && m == 1) return launch_wave<2, 1, PB>(t, g, pb, st);
-    if (n == 1 && m == 1) return launch_wave<1, 1, PB>(t, g, pb, st);
-    return ZM_EUNSUPPORTED;
-}
-
-int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, int n, int m, hipStream_t st) {
-    return wave_dispatch<false>(t, g, MpcProb{}, n, m, st);
-}
-
-int mpc_wave_dispatch_batched(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, int n, int m, hipStream_t st) {
-    return wave_dispatch<true>(t, g, pb, n, m, st);
-}
-
-int mpc_wave_dispatch_track(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack& trk, int n, int m, hipStream_t st) {
-    return pb ? wave_dispatch_track<true>(t, g, *pb, trk, n, m, st) : wave_dispatch_track<false>(t, g, MpcProb{}, trk, n, m, st);
+int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
+    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave<ns.value, mc.value>(t, g, pb, trk, st); });
 }
 
 }  // namespace zm

@@ -49,118 +49,36 @@ class lqrMpc():
         """
         if Qf is None:
             Qf = Q
-        if _has_leading_axes(A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub):
-            self._init_batched(A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf)
-            return
-        self.P = None
-        f64 = lambda X: np.ascontiguousarray(np.asarray(X, dtype=np.float64))
-        self.A, self.B, self.Q, self.R, self.Qf = f64(A), f64(B), f64(Q), f64(R), f64(Qf)
-        self.n, self.m = self.B.shape
+        batched = _has_leading_axes(A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub)
+        data = {k: _host_f64(X) for k, X in zip(_ARRAYS, (A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub))}
         self.N = int(N)
-        self.x_lb, self.x_ub, self.u_lb, self.u_ub = f64(x_lb), f64(x_ub), f64(u_lb), f64(u_ub)
-        if self.A.shape != (self.n, self.n) or self.Q.shape != (self.n, self.n) or self.R.shape != (self.m, self.m) \
-                or self.x_lb.shape != (self.n,) or self.u_lb.shape != (self.m,) or self.N < 1:
-            raise ValueError("inconsistent lqrMpc problem shapes")
-        # cvxpy refuses the reference's problem (DCPError at solve time) unless every quad_form weight is positive semidefinite; here the
-        # ADMM's Hessians 2Q + rho I would hide a slightly indefinite weight and return the stationary point of a non-convex problem
-        for name, W in (("Q", self.Q), ("R", self.R), ("Qf", self.Qf)):
-            w = np.linalg.eigvalsh(0.5 * (W + W.T))
-            if w[0] < -1e-10 * max(1.0, abs(w[-1])):
-                raise ValueError(f"lqrMpc: {name} is not positive semidefinite (smallest eigenvalue {w[0]:.3g}): the problem is not "
-                                 f"convex (cvxpy raises DCPError for the reference's quad_form)")
+        n, m, P = _problem_shape(data, self.N, batched)
+        # one problem: P is None, rho a float -- solve() then runs the shared-problem kernels (scalar table loads)
+        self.P = P if batched else None
+        _check_psd(data, P)
         self._dev = None
         self._tables = {}
-        self._ws = None   # ((batch, device, rho), ADMM workspace) of the last solve: warm start
-        # one penalty for every instance: the geometric mean of the cost curvatures keeps both blocks of the
-        # w-update Hessian (2Q + rho I, 2R + rho I) comparably conditioned
-        self.rho = float(np.sqrt(max(np.trace(2 * self.Q) / self.n, 1e-12) * max(np.trace(2 * self.R) / self.m, 1e-12)))
+        self._ws = None   # (key, ADMM workspace) of the last solve: warm start
+        rho = _penalty(data["Q"], data["R"], P)
+        self.rho = rho if batched else float(rho)
         # The solve kernels are compiled for a few (n, m); any other n <= 24, m <= 8 is embedded in the next one: the extra
         # states follow x+ = 0 from x = 0 with unit weight and no bound, the extra controls act on nothing and cost u^2 --
         # they stay exactly zero and are sliced off the results.
-        self._n_user, self._m_user = self.n, self.m
-        fit = [(ns, mc) for (ns, mc) in self._COMPILED if ns >= self.n and mc >= self.m]
+        self._n_user, self._m_user = n, m
+        fit = [(ns, mc) for (ns, mc) in self._COMPILED if ns >= n and mc >= m]
         if not fit:
-            raise ValueError(f"lqrMpc: (n={self.n}, m={self.m}) outside the compiled kernels (n <= 24, m <= 8)")
-        ns, mc = min(fit, key=lambda t: (t[0] * t[1], t[0]))
-        if (ns, mc) != (self.n, self.m):
-            n0, m0 = self.n, self.m
-            pad2 = lambda X, r, c, d: np.block([[X, np.zeros((X.shape[0], c - X.shape[1]))],
-                                                [np.zeros((r - X.shape[0], X.shape[1])), d * np.eye(r - X.shape[0], c - X.shape[1])]])
-            self.A = pad2(self.A, ns, ns, 0.0)
-            self.B = pad2(self.B, ns, mc, 0.0)
-            self.Q, self.Qf = pad2(self.Q, ns, ns, 1.0), pad2(self.Qf, ns, ns, 1.0)
-            self.R = pad2(self.R, mc, mc, 1.0)
-            inf = np.inf
-            self.x_lb = np.concatenate([self.x_lb, np.full(ns - n0, -inf)])
-            self.x_ub = np.concatenate([self.x_ub, np.full(ns - n0, inf)])
-            self.u_lb = np.concatenate([self.u_lb, np.full(mc - m0, -inf)])
-            self.u_ub = np.concatenate([self.u_ub, np.full(mc - m0, inf)])
-            self.n, self.m = ns, mc
+            raise ValueError(f"lqrMpc: (n={n}, m={m}) outside the compiled kernels (n <= 24, m <= 8)")
+        self.n, self.m = min(fit, key=lambda t: (t[0] * t[1], t[0]))
+        if batched or (self.n, self.m) != (n, m):   # (per-problem data is also materialised to P here)
+            data = _embed(data, P, self.n, self.m)
+        for k, X in data.items():
+            setattr(self, k, X)
 
     # (24, 8): beyond the 16-index tile of the 16-lanes-per-instance kernel -- the lane-per-instance kernel with a fixed penalty (no
     # tabulated levels): a coverage path, an order of magnitude slower per instance than the (12, 4) kernels
     _COMPILED = ((24, 8), (12, 4), (8, 4), (4, 2), (4, 1), (2, 2), (2, 1), (1, 1))
 
     N_LEVELS, RHO_STEP = 7, 5.0      # adaptive penalty: rho * 5^(l - 3), l = 0..6  (OSQP changes rho only by factors >= 5)
-
-    def _init_batched(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf):
-        """Per-problem data: the checks, penalty and embedding of the single-problem constructor, applied problem by problem."""
-        A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub = (_host_f64(X) for X in (A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub))
-        if B.ndim < 2:
-            raise ValueError("inconsistent lqrMpc problem shapes")
-        n, m = B.shape[-2:]
-        self.N = int(N)
-        mats = {"A": (A, (n, n)), "B": (B, (n, m)), "Q": (Q, (n, n)), "R": (R, (m, m)), "Qf": (Qf, (n, n)),
-                "x_lb": (x_lb, (n,)), "x_ub": (x_ub, (n,)), "u_lb": (u_lb, (m,)), "u_ub": (u_ub, (m,))}
-        if self.N < 1 or any(X.ndim < len(t) or X.shape[X.ndim - len(t):] != t for X, t in mats.values()):
-            raise ValueError("inconsistent lqrMpc problem shapes")
-        try:
-            P = np.broadcast_shapes(*(X.shape[:X.ndim - len(t)] for X, t in mats.values()))
-        except ValueError:
-            raise ValueError("inconsistent lqrMpc problem shapes: the leading (problem) axes do not broadcast: "
-                             + ", ".join(f"{k} {X.shape}" for k, (X, _) in mats.items())) from None
-        self.P = tuple(int(d) for d in P)
-        # PSD check per problem (see the single-problem constructor); the first offending problem is named by its index in P
-        for name, W in (("Q", Q), ("R", R), ("Qf", Qf)):
-            w = np.linalg.eigvalsh(0.5 * (W + np.swapaxes(W, -1, -2)))
-            bad = np.broadcast_to(w[..., 0] < -1e-10 * np.maximum(1.0, np.abs(w[..., -1])), self.P)
-            if bad.any():
-                i = tuple(int(v) for v in np.argwhere(bad)[0])
-                lo = float(np.broadcast_to(w[..., 0], self.P)[i])
-                raise ValueError(f"lqrMpc: {name}[{', '.join(map(str, i))}] is not positive semidefinite (smallest eigenvalue {lo:.3g}): "
-                                 f"the problem is not convex (cvxpy raises DCPError for the reference's quad_form)")
-        self._dev = None
-        self._tables = {}
-        self._ws = None
-        # the single-problem penalty, problem by problem: the same operations in the same order (a trace is the pairwise sum of the
-        # contiguous diagonal, as np.trace's), so rho[i] is bit for bit lqrMpc(A[i], B[i], ...).rho
-        tq = np.ascontiguousarray(np.diagonal(2 * Q, axis1=-2, axis2=-1)).sum(axis=-1) / n
-        tr = np.ascontiguousarray(np.diagonal(2 * R, axis1=-2, axis2=-1)).sum(axis=-1) / m
-        self.rho = np.sqrt(np.broadcast_to(np.maximum(tq, 1e-12) * np.maximum(tr, 1e-12), self.P)).astype(np.float64)
-        self._n_user, self._m_user = n, m
-        fit = [(ns, mc) for (ns, mc) in self._COMPILED if ns >= n and mc >= m]
-        if not fit:
-            raise ValueError(f"lqrMpc: (n={n}, m={m}) outside the compiled kernels (n <= 24, m <= 8)")
-        ns, mc = min(fit, key=lambda t: (t[0] * t[1], t[0]))
-        # every array materialised to P, embedded as the single-problem constructor embeds it (pad2: zero / unit padding blocks)
-        inf = np.inf
-
-        def emb(X, r, c, d):
-            out = np.zeros(self.P + (r, c))
-            out[..., :X.shape[-2], :X.shape[-1]] = X
-            for i in range(min(r - X.shape[-2], c - X.shape[-1])):
-                out[..., X.shape[-2] + i, X.shape[-1] + i] = d
-            return out
-
-        def embv(v, k, fill):
-            out = np.full(self.P + (k,), fill)
-            out[..., :v.shape[-1]] = v
-            return out
-        self.A, self.B = emb(A, ns, ns, 0.0), emb(B, ns, mc, 0.0)
-        self.Q, self.Qf, self.R = emb(Q, ns, ns, 1.0), emb(Qf, ns, ns, 1.0), emb(R, mc, mc, 1.0)
-        self.x_lb, self.x_ub = embv(x_lb, ns, -inf), embv(x_ub, ns, inf)
-        self.u_lb, self.u_ub = embv(u_lb, mc, -inf), embv(u_ub, mc, inf)
-        self.n, self.m = ns, mc
 
     def _device_problem_batched(self, rho, adaptive):
         """Device copies of the per-problem data and their tables: ONE setup launch for every (problem, penalty level)."""
@@ -265,113 +183,14 @@ class lqrMpc():
             kwargs.pop(k, None)
         if kwargs:
             raise TypeError(f"unknown solver options {sorted(kwargs)}")
-        if xRef is not None or uRef is not None:
-            return self._solve_tracking(x0, xRef, uRef, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift)
-        if self.P is not None:
-            return self._solve_batched(x0, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift)
-        shp = tuple(x0.shape) if hasattr(x0, "shape") else tuple(np.shape(x0))
-        if len(shp) < 1 or shp[-1] != self._n_user:
-            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
-        lead = shp[:-1]
-        d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
-        dx0 = arr.to_device(x0, torch.float64).reshape(-1, self._n_user)
-        if self.n != self._n_user:
-            dx0 = torch.nn.functional.pad(dx0, (0, self.n - self._n_user))
-        dx0 = dx0.contiguous()
-        Bn = dx0.shape[0]
-        dev = dx0.device
-        N, n, m = self.N, self.n, self.m
-        key = (Bn, str(dev), rho, adaptive)
-        warm = warm and self._ws is not None and self._ws[0] == key
-        if not warm:
-            self._ws = (key, torch.empty(4 * Bn * N * (n + m), dtype=torch.float64, device=dev))
-        ws = self._ws[1]
-        xT = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
-        uT = torch.empty((Bn, N, m), dtype=torch.float64, device=dev)
-        st = torch.empty(Bn, dtype=torch.int32, device=dev)
-        its = torch.empty(Bn, dtype=torch.int32, device=dev)
-        res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
-        rc = _lib.lib().zm_mpc_solve_relaxed_f64(d["A"].data_ptr(), d["B"].data_ptr(), K.data_ptr(), Mi.data_ptr(), n_levels,
-                                                  level0, self.RHO_STEP, alpha, d["x_lb"].data_ptr(), d["x_ub"].data_ptr(),
-                                                  d["u_lb"].data_ptr(), d["u_ub"].data_ptr(), dx0.data_ptr(), rho, eps_abs,
-                                                  eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0,
-                                                  ws.data_ptr(), xT.data_ptr(), uT.data_ptr(), st.data_ptr(), its.data_ptr(),
-                                                  res.data_ptr(), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
-        _lib.check(rc, "lqrMpc.solve")
-        self.last_iterations = its.reshape(lead).cpu().numpy()
-        self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
-        codes = st.cpu().numpy().reshape(lead)
-        xo = arr.result_like(xT.reshape(lead + (N + 1, n))[..., :self._n_user], x0)
-        uo = arr.result_like(uT.reshape(lead + (N, m))[..., :self._m_user], x0)
-        if len(lead) == 0:
-            status = _STATUS[int(codes)]
-        else:
-            status = np.vectorize(_STATUS.get, otypes=[object])(codes)
-        return uo[..., 0, :], Trajectory(xo, uo), status
-
-    def _solve_batched(self, x0, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift):
-        """solve() with per-problem data: x0 (..., n) broadcasts against P, every instance reads its problem's tables through an
-        int32 instance -> problem map (one launch for all of them)."""
-        shp = tuple(x0.shape) if hasattr(x0, "shape") else tuple(np.shape(x0))
-        if len(shp) < 1 or shp[-1] != self._n_user:
-            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
-        try:
-            lead = tuple(int(v) for v in np.broadcast_shapes(shp[:-1], self.P))
-        except ValueError:
-            raise ValueError(f"x0 of shape {shp} does not broadcast against the problem shape {self.P}: inconsistent shapes") from None
-        N, n, m = self.N, self.n, self.m
-        Pn, Bn = int(np.prod(self.P)), int(np.prod(lead))
-        arr.require_gpu()
-        if Bn == 0:   # no problems or no initial states: shaped empty results, nothing launched
-            dev = x0.device if arr.is_torch(x0) and x0.is_cuda else torch.device("cuda")
-            self.last_iterations = np.zeros(lead, dtype=np.int32)
-            self.last_residuals = np.zeros(lead + (2,))
-            xo = arr.result_like(torch.empty(lead + (N + 1, self._n_user), dtype=torch.float64, device=dev), x0)
-            uo = arr.result_like(torch.empty(lead + (N, self._m_user), dtype=torch.float64, device=dev), x0)
-            return uo[..., 0, :], Trajectory(xo, uo), np.empty(lead, dtype=object)
-        d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
-        dev = d["A"].device
-        dx0 = arr.to_device(x0, torch.float64, dev)
-        dx0 = dx0.expand(lead + (self._n_user,)).reshape(-1, self._n_user)
-        if n != self._n_user:
-            dx0 = torch.nn.functional.pad(dx0, (0, n - self._n_user))
-        dx0 = dx0.contiguous()
-        prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
-                               device=dev)
-        key = (lead, str(dev), rho.tobytes(), adaptive)
-        warm = warm and self._ws is not None and self._ws[0] == key
-        if not warm:
-            self._ws = (key, torch.empty(4 * Bn * N * (n + m), dtype=torch.float64, device=dev))
-        ws = self._ws[1]
-        xT = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
-        uT = torch.empty((Bn, N, m), dtype=torch.float64, device=dev)
-        st = torch.empty(Bn, dtype=torch.int32, device=dev)
-        its = torch.empty(Bn, dtype=torch.int32, device=dev)
-        res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
-        rc = _lib.lib().zm_mpc_solve_batched_f64(d["A"].data_ptr(), d["B"].data_ptr(), K.data_ptr(), Mi.data_ptr(), n_levels, level0,
-                                                  self.RHO_STEP, alpha, d["x_lb"].data_ptr(), d["x_ub"].data_ptr(),
-                                                  d["u_lb"].data_ptr(), d["u_ub"].data_ptr(), dx0.data_ptr(), drho.data_ptr(),
-                                                  prob.data_ptr(), Pn, eps_abs, eps_rel, eps_pinf, max_iter,
-                                                  (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
-                                                  st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m,
-                                                  ctypes.c_void_p(arr.stream_ptr(dx0)))
-        _lib.check(rc, "lqrMpc.solve")
-        self.last_iterations = its.reshape(lead).cpu().numpy()
-        self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
-        codes = st.cpu().numpy().reshape(lead)
-        xo = arr.result_like(xT.reshape(lead + (N + 1, n))[..., :self._n_user], x0)
-        uo = arr.result_like(uT.reshape(lead + (N, m))[..., :self._m_user], x0)
-        status = np.vectorize(_STATUS.get, otypes=[object])(codes)
-        return uo[..., 0, :], Trajectory(xo, uo), status
-
-    def _solve_tracking(self, x0, xRef, uRef, rho, eps_abs, eps_rel, max_iter, adaptive, eps_pinf, alpha, warm, shift):
-        """solve() about a reference (shared or per-problem data): x0, xRef and uRef broadcast to one batch shape, the references are
-        padded with zeros to the compiled shape, and zm_mpc_solve_tracking_f64 forms the linear term and runs the tracking kernels."""
         if isinstance(xRef, Trajectory):
             if uRef is not None:
                 raise ValueError("a Trajectory given as xRef carries its own uTraj: pass it alone (uRef=None)")
             xRef, uRef = xRef.xTraj, xRef.uTraj
+        tracking = xRef is not None or uRef is not None
         N, n, m = self.N, self.n, self.m
+
+        # 1. shapes: x0 and the references broadcast (with the problem shape) to the batch shape `lead`
         shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
         shp = shape_of(x0)
         if len(shp) < 1 or shp[-1] != self._n_user:
@@ -386,66 +205,89 @@ class lqrMpc():
         try:
             lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
         except ValueError:
-            raise ValueError(", ".join(f"{k} of shape {s}" for k, (s, _) in leads.items()) + " do not broadcast against each other"
-                             + ("" if self.P is None else f" and the problem shape {self.P}") + ": inconsistent shapes") from None
+            who = ", ".join(f"{k} of shape {s}" for k, (s, _) in leads.items())
+            if tracking:
+                who += " do not broadcast against each other" + ("" if self.P is None else f" and the problem shape {self.P}")
+            else:   # (x0 alone: only a problem shape can be in its way)
+                who += f" does not broadcast against the problem shape {self.P}"
+            raise ValueError(who + ": inconsistent shapes") from None
         lead = tuple(int(v) for v in lead)
         Bn = int(np.prod(lead))
         arr.require_gpu()
-        if Bn == 0:   # nothing to solve: shaped empty results, nothing launched
+
+        # 2. nothing to solve: shaped empty results, nothing launched.  (Not for a plain solve: that one goes on, drops the warm start
+        # and lets the C side return at batch == 0, as it always has.)
+        if Bn == 0 and (tracking or self.P is not None):
             dev = x0.device if arr.is_torch(x0) and x0.is_cuda else torch.device("cuda")
             self.last_iterations = np.zeros(lead, dtype=np.int32)
             self.last_residuals = np.zeros(lead + (2,))
             xo = arr.result_like(torch.empty(lead + (N + 1, self._n_user), dtype=torch.float64, device=dev), x0)
             uo = arr.result_like(torch.empty(lead + (N, self._m_user), dtype=torch.float64, device=dev), x0)
             return uo[..., 0, :], Trajectory(xo, uo), np.empty(lead, dtype=object)
+
+        # 3. the problem on the device and its tables
         if self.P is None:
             d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
-            dev = x0.device if arr.is_torch(x0) and x0.is_cuda else d["A"].device
-            rho_s, drho, prob, Pn, rho_key = rho, None, None, 0, rho
+            drho, Pn, rho_key = None, 0, rho
         else:
             d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
-            dev = d["A"].device
-            Pn = int(np.prod(self.P))
-            prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P),
-                                                                        lead)).reshape(-1), device=dev)
-            rho_s, rho_key = 0.0, rho.tobytes()
+            Pn, rho_key = int(np.prod(self.P)), rho.tobytes()
 
-        def flat(X, tail, width):   # broadcast to the batch, one row per instance, the padded components zero
+        # 4. one row per instance, the padded components zero.  A plain solve runs where x0 is (host data: on the current device), the
+        # others where the problem's tables are -- unless a single problem tracks from an x0 that is on a device already.
+        def flat(X, tail, width, dev):
             t = arr.to_device(X, torch.float64, dev)
             t = t.expand(lead + tail).reshape((Bn,) + tail)
             if width != tail[-1]:
                 t = torch.nn.functional.pad(t, (0, width - tail[-1]))
             return t.contiguous()
-        dx0 = flat(x0, (self._n_user,), n)
-        dxr = None if xRef is None else flat(xRef, (N + 1, self._n_user), n)
-        dur = None if uRef is None else flat(uRef, (N, self._m_user), m)
-        # (a workspace of its own kind: the fifth block holds the linear term of the cost)
-        key = ("tracking", lead, str(dev), rho_key, adaptive)
+        dx0 = flat(x0, (self._n_user,), n, d["A"].device if tracking or self.P is not None else None)
+        dev = dx0.device if self.P is None else d["A"].device
+        dxr = None if xRef is None else flat(xRef, (N + 1, self._n_user), n, dev)
+        dur = None if uRef is None else flat(uRef, (N, self._m_user), m, dev)
+        prob = None   # instance -> problem
+        if self.P is not None:
+            prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
+                                   device=dev)
+
+        # 5. workspace (y, lam, kf, rv; tracking: a fifth block for the linear term of the cost) and the warm start from it.  A plain solve
+        # is keyed on the number of instances, the others on the batch shape, tracking as a kind of its own.
+        key = (("tracking", lead) if tracking else lead if self.P is not None else Bn, str(dev), rho_key, adaptive)
         warm = warm and self._ws is not None and self._ws[0] == key
         if not warm:
-            self._ws = (key, torch.empty(5 * Bn * N * (n + m), dtype=torch.float64, device=dev))
+            self._ws = (key, torch.empty((5 if tracking else 4) * Bn * N * (n + m), dtype=torch.float64, device=dev))
         ws = self._ws[1]
+
+        # 6. outputs
         xT = torch.empty((Bn, N + 1, n), dtype=torch.float64, device=dev)
         uT = torch.empty((Bn, N, m), dtype=torch.float64, device=dev)
         st = torch.empty(Bn, dtype=torch.int32, device=dev)
         its = torch.empty(Bn, dtype=torch.int32, device=dev)
         res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
+
+        # 7. the C call: the plain and the per-problem kernels, or the tracking variants of either (other kernels, slower per iteration)
+        p = lambda k: d[k].data_ptr()
         ptr = lambda t: None if t is None else t.data_ptr()
-        rc = _lib.lib().zm_mpc_solve_tracking_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["Q"].data_ptr(), d["R"].data_ptr(),
-                                                   d["Qf"].data_ptr(), K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP,
-                                                   alpha, d["x_lb"].data_ptr(), d["x_ub"].data_ptr(), d["u_lb"].data_ptr(),
-                                                   d["u_ub"].data_ptr(), dx0.data_ptr(), ptr(dxr), ptr(dur), rho_s, ptr(drho),
-                                                   ptr(prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter,
-                                                   (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
-                                                   st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m,
-                                                   ctypes.c_void_p(arr.stream_ptr(dx0)))
+        common = (K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP, alpha, p("x_lb"), p("x_ub"), p("u_lb"), p("u_ub"),
+                  dx0.data_ptr())
+        out = (eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
+               st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+        if tracking:
+            rc = _lib.lib().zm_mpc_solve_tracking_f64(p("A"), p("B"), p("Q"), p("R"), p("Qf"), *common, ptr(dxr), ptr(dur),
+                                                       rho if self.P is None else 0.0, ptr(drho), ptr(prob), Pn, *out)
+        elif self.P is not None:
+            rc = _lib.lib().zm_mpc_solve_batched_f64(p("A"), p("B"), *common, drho.data_ptr(), prob.data_ptr(), Pn, *out)
+        else:
+            rc = _lib.lib().zm_mpc_solve_relaxed_f64(p("A"), p("B"), *common, rho, *out)
         _lib.check(rc, "lqrMpc.solve")
+
+        # 8. results
         self.last_iterations = its.reshape(lead).cpu().numpy()
         self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
         codes = st.cpu().numpy().reshape(lead)
         xo = arr.result_like(xT.reshape(lead + (N + 1, n))[..., :self._n_user], x0)
         uo = arr.result_like(uT.reshape(lead + (N, m))[..., :self._m_user], x0)
-        if len(lead) == 0:
+        if len(lead) == 0:   # (one problem only: a problem shape has at least one axis)
             status = _STATUS[int(codes)]
         else:
             status = np.vectorize(_STATUS.get, otypes=[object])(codes)
@@ -463,3 +305,67 @@ def _has_leading_axes(A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub):
     """True if any problem array carries axes in front of its single-problem shape (matrices 2-D, bounds 1-D)"""
     nd = lambda X: len(X.shape) if hasattr(X, "shape") else np.ndim(X)
     return any(nd(X) > 2 for X in (A, B, Q, R, Qf)) or any(nd(v) > 1 for v in (x_lb, x_ub, u_lb, u_ub))
+
+
+_ARRAYS = ("A", "B", "Q", "R", "Qf", "x_lb", "x_ub", "u_lb", "u_ub")
+
+
+def _problem_shape(data, N, batched):
+    """(n, m, P) of the constructor's arrays: P is the broadcast of their leading axes, () for one problem."""
+    if data["B"].ndim < 2:
+        raise ValueError("inconsistent lqrMpc problem shapes")
+    n, m = data["B"].shape[-2:]
+    tails = {"A": (n, n), "B": (n, m), "Q": (n, n), "R": (m, m), "Qf": (n, n), "x_lb": (n,), "x_ub": (n,), "u_lb": (m,), "u_ub": (m,)}
+    if not batched:   # the single-problem constructor never looked at the other three
+        tails = {k: tails[k] for k in ("A", "B", "Q", "R", "x_lb", "u_lb")}
+    if N < 1 or any(data[k].ndim < len(t) or data[k].shape[data[k].ndim - len(t):] != t for k, t in tails.items()):
+        raise ValueError("inconsistent lqrMpc problem shapes")
+    try:
+        P = np.broadcast_shapes(*(data[k].shape[:data[k].ndim - len(t)] for k, t in tails.items()))
+    except ValueError:
+        raise ValueError("inconsistent lqrMpc problem shapes: the leading (problem) axes do not broadcast: "
+                         + ", ".join(f"{k} {data[k].shape}" for k in tails)) from None
+    return n, m, tuple(int(v) for v in P)
+
+
+def _check_psd(data, P):
+    """cvxpy refuses the reference's problem (DCPError at solve time) unless every quad_form weight is positive semidefinite; here the
+    ADMM's Hessians 2Q + rho I would hide a slightly indefinite weight and return the stationary point of a non-convex problem.  The
+    first offending problem is named by its index in P."""
+    for name in ("Q", "R", "Qf"):
+        W = data[name]
+        w = np.linalg.eigvalsh(0.5 * (W + np.swapaxes(W, -1, -2)))
+        bad = np.broadcast_to(w[..., 0] < -1e-10 * np.maximum(1.0, np.abs(w[..., -1])), P)
+        if bad.any():
+            i = tuple(int(v) for v in np.argwhere(bad)[0])
+            lo = float(np.broadcast_to(w[..., 0], P)[i])
+            which = f"[{', '.join(map(str, i))}]" if i else ""
+            raise ValueError(f"lqrMpc: {name}{which} is not positive semidefinite (smallest eigenvalue {lo:.3g}): "
+                             f"the problem is not convex (cvxpy raises DCPError for the reference's quad_form)")
+
+
+def _penalty(Q, R, P):
+    """One penalty per problem, shape P: the geometric mean of the cost curvatures keeps both blocks of the w-update Hessian
+    (2Q + rho I, 2R + rho I) comparably conditioned.  A trace is the pairwise sum of the contiguous diagonal, as np.trace's."""
+    tq = np.ascontiguousarray(np.diagonal(2 * Q, axis1=-2, axis2=-1)).sum(axis=-1) / Q.shape[-1]
+    tr = np.ascontiguousarray(np.diagonal(2 * R, axis1=-2, axis2=-1)).sum(axis=-1) / R.shape[-1]
+    return np.sqrt(np.broadcast_to(np.maximum(tq, 1e-12) * np.maximum(tr, 1e-12), P)).astype(np.float64)
+
+
+def _embed(data, P, ns, mc):
+    """Every array materialised to P and embedded in the compiled shape (ns, mc): zero blocks next to the matrices, the weights' new
+    diagonal 1, A's and B's 0, the new components unbounded."""
+    def mat(X, r, c, d):
+        out = np.zeros(P + (r, c))
+        out[..., :X.shape[-2], :X.shape[-1]] = X
+        for i in range(min(r - X.shape[-2], c - X.shape[-1])):
+            out[..., X.shape[-2] + i, X.shape[-1] + i] = d
+        return out
+
+    def vec(v, k, fill):
+        out = np.full(P + (k,), fill)
+        out[..., :v.shape[-1]] = v
+        return out
+    shape = {"A": (ns, ns, 0.0), "B": (ns, mc, 0.0), "Q": (ns, ns, 1.0), "R": (mc, mc, 1.0), "Qf": (ns, ns, 1.0)}
+    bound = {"x_lb": (ns, -np.inf), "x_ub": (ns, np.inf), "u_lb": (mc, -np.inf), "u_ub": (mc, np.inf)}
+    return {k: mat(X, *shape[k]) if k in shape else vec(X, *bound[k]) for k, X in data.items()}
