@@ -8,9 +8,13 @@ that solver is not part of the reference tree and not installed here, and the re
                             mpcUtils.py:48-59 (dynamics, bounds, and the reduced-gradient / complementarity
                             condition in the condensed variables);
   * `solve_reference`    -- an independent high-accuracy solve (condensed QP, SciPy trust-constr) for small problems;
-  * `admm`               -- a NumPy restatement of the build's own ADMM (zopt_amd/csrc/mpc.hip) for iterate-level checks.
+  * `admm`               -- a NumPy restatement of the build's own ADMM (zopt_amd/csrc/mpc.hip) for iterate-level checks;
+  * `admm_levels`        -- the restatement of the WHOLE solve (zopt_amd/csrc/mpc_solve_wave_body.h): adaptive penalty levels, warm and
+                            shifted starts, the linear term and the cycle guard of the tracking kernels, the stored state.
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 import numpy as np
 import scipy.optimize as spo
@@ -180,3 +184,164 @@ def admm(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, e
                 status = "infeasible"
                 break
     return x, u, status, it
+
+
+def admm_levels(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, eps_rel=1e-5, max_iter=10000, eps_prim_inf=1e-4,
+                alpha=1.6, n_levels=7, rho_step=5.0, g=None, warm=None, shift=False, guard=True):
+    """NumPy restatement of ONE instance of zopt_amd/csrc/mpc_solve_wave_body.h (and, with n_levels=1, of mpc_solve_lane_body.h), in its
+    order: backward sweep with z = -rho (y - lam) + g, rollout, relaxed iterate / clip / dual step / norms, termination test, then at
+    every CHECK_EVERY-th iteration of an instance that goes on: the level rule (cycle guard first when g != 0), then the primal
+    infeasibility certificate on the dual step of that iteration.
+
+    rho is the penalty of level `n_levels // 2`; level l runs rho * rho_step ** (l - n_levels // 2).  n_levels = 1: fixed penalty.
+    g = (gx (N, n), gu (N, m)): the linear term of a tracking cost (tests/mpc_tracking_ref.py: linear_term), None = 0.
+    warm = (y (N, n + m), lam (N, n + m), level): the state a previous solve returned (the kernels keep it only after "optimal");
+    shift: stage k starts from stage k + 1 of it, the last stage from itself.  guard=False switches the cycle guard off (tests only).
+
+    The guard as the kernel spells it (mpc_wave.hip: ZM_TRK_LEVEL): a wanted move opposite in sign to the decision of the check before
+    is a reversal; the third reversal in a row is refused and the level locked for the rest of the solve; any other decision (a
+    decision not to move included, which also clears the remembered move) resets the count.
+
+    No level move is taken at iteration max_iter: no iteration follows it, and the returned (x, u) is the rollout of the last iterate
+    at the penalty that iterate was computed with.
+
+    Returns a namespace: x (N+1, n), u (N, m), status, iters, rp, rd (of the last iteration), y, lam (N, n+m: [x_{k+1} ; u_k]), level,
+    rho_final, moves [(iteration, from, to)], locked, and the decision margins of the run: level_margin = min over the level decisions
+    of the distance of log(want) / log(rho_step) from the nearest half-integer, stop_margin = min over the iterations of
+    |max(rp / ep, rd / ed) - 1|, near_margin = |max(rp / ep, rd / ed) / 10 - 1| of the last iteration (the test at the cap)."""
+    n, m = B.shape
+    level0 = n_levels // 2
+    rho0 = float(rho)
+    tabs = {}
+
+    def tables(l):   # K_k, Suu_k^-1 at the level's penalty (mpc_setup_body.h)
+        if l not in tabs:
+            r_ = rho0 * rho_step ** (l - level0)
+            Hx, Hu = 2 * Q + r_ * np.eye(n), 2 * R + r_ * np.eye(m)
+            P = 2 * Qf + r_ * np.eye(n)
+            K, Mi = [None] * N, [None] * N
+            for k in range(N - 1, -1, -1):
+                Suu = Hu + B.T @ P @ B
+                Sux = B.T @ P @ A
+                Mi[k] = np.linalg.inv(Suu)
+                K[k] = Mi[k] @ Sux
+                P = Hx + A.T @ P @ A - Sux.T @ K[k]
+            tabs[l] = (r_, K, Mi)
+        return tabs[l]
+
+    lvl = level0
+    yx, yu, lx, lu = np.zeros((N, n)), np.zeros((N, m)), np.zeros((N, n)), np.zeros((N, m))
+    if warm is not None:
+        wy, wl, wlvl = warm
+        if n_levels > 1 and 0 <= int(wlvl) < n_levels:
+            lvl = int(wlvl)
+        ks = [k + 1 if (shift and k + 1 < N) else k for k in range(N)]
+        wy, wl = np.asarray(wy, dtype=np.float64)[ks], np.asarray(wl, dtype=np.float64)[ks]
+        yx, yu, lx, lu = wy[:, :n].copy(), wy[:, n:].copy(), wl[:, :n].copy(), wl[:, n:].copy()
+    if g is None:
+        gx, gu = np.zeros((N, n)), np.zeros((N, m))
+    else:
+        gx, gu = np.asarray(g[0], dtype=np.float64), np.asarray(g[1], dtype=np.float64)
+    gn = max(np.max(np.abs(gx)), np.max(np.abs(gu)))
+    rho_l, K, Mi = tables(lvl)
+    kf = np.zeros((N, m))
+
+    def roll(K, kf):
+        xs, us = [np.asarray(x0, dtype=np.float64)], []
+        for k in range(N):
+            us.append(-K[k] @ xs[-1] - kf[k])
+            xs.append(A @ xs[-1] + B @ us[-1])
+        return np.stack(xs), np.stack(us)
+
+    out = SimpleNamespace(moves=[], locked=False, level_margin=np.inf, stop_margin=np.inf, near_margin=np.inf, rp=0.0, rd=0.0)
+    status, it, near_ok = None, 0, False
+    x, u = roll(K, kf)
+    if np.any(x0 < x_lb) or np.any(x0 > x_ub):
+        status = "infeasible"
+    last, rev = 0, 0
+    while status is None and it < max_iter:
+        it += 1
+        chk = (it % CHECK_EVERY) == 0
+        zx, zu = -rho_l * (yx - lx) + gx, -rho_l * (yu - lu) + gu
+        p = zx[N - 1]
+        for k in range(N - 1, -1, -1):
+            qu = zu[k] + B.T @ p
+            kf[k] = Mi[k] @ qu
+            p = (zx[k - 1] if k >= 1 else 0.0) + A.T @ p - K[k].T @ qu
+        x, u = roll(K, kf)
+        xh, uh = alpha * x[1:] + (1.0 - alpha) * yx, alpha * u + (1.0 - alpha) * yu
+        yxn = np.clip(xh + lx, x_lb, x_ub)
+        yun = np.clip(uh + lu, u_lb, u_ub)
+        rp = max(np.max(np.abs(x[1:] - yxn)), np.max(np.abs(u - yun)))
+        rx, ru = xh - yxn, uh - yun
+        nrd = max(np.max(np.abs(yxn - yx)), np.max(np.abs(yun - yu)))
+        rd = rho_l * nrd
+        lx, lu = lx + rx, lu + ru
+        yx, yu = yxn, yun
+        nwy = max(np.max(np.abs(x[1:])), np.max(np.abs(u)), np.max(np.abs(yx)), np.max(np.abs(yu)))
+        nl = max(np.max(np.abs(lx)), np.max(np.abs(lu)))
+        ep = eps_abs + eps_rel * nwy
+        ed = eps_abs + eps_rel * rho_l * nl
+        if gn > rho_l * nl:
+            ed = eps_abs + eps_rel * gn
+        out.rp, out.rd = rp, rd
+        near_ok = bool(rp <= 10.0 * ep and rd <= 10.0 * ed)
+        if rp == rp:
+            worst = max(rp / ep, rd / ed)
+            out.stop_margin = min(out.stop_margin, abs(worst - 1.0))
+            out.near_margin = abs(worst / 10.0 - 1.0)
+        if rp <= ep and rd <= ed:
+            status = "optimal"
+            break
+        if not (rp == rp):
+            break                      # NaN iterates: the limit status
+        if not chk:
+            continue
+        if n_levels > 1 and it < max_iter:
+            tiny = 1e-300
+            rpn = rp / max(nwy, tiny)
+            rdn = rd / max(rho_l * nl, tiny)
+            want = np.sqrt(rpn / max(rdn, tiny))
+            dl = 0
+            if want == want and want > 0.0:
+                t = np.log(want) / np.log(rho_step)
+                dl = int(np.rint(t))
+                out.level_margin = min(out.level_margin, abs(abs(t - np.floor(t)) - 0.5))
+            new = min(max(lvl + dl, 0), n_levels - 1)
+            if gn > 0.0 and guard:
+                mv = new - lvl
+                if out.locked:
+                    new = lvl
+                elif mv != 0 and last != 0 and ((mv > 0) != (last > 0)):
+                    rev += 1
+                    if rev >= 3:
+                        out.locked = True
+                        new = lvl
+                else:
+                    rev = 0
+                last = new - lvl
+            if new != lvl:
+                out.moves.append((it, lvl, new))
+                r_new, K, Mi = tables(new)
+                sc = rho_l / r_new
+                lx, lu = lx * sc, lu * sc
+                rho_l, lvl = r_new, new
+        # OSQP-style primal infeasibility certificate on the dual step of this iteration
+        s = rx[N - 1].copy()
+        gmax = 0.0
+        for k in range(N - 1, -1, -1):
+            gmax = max(gmax, np.max(np.abs(ru[k] + B.T @ s)))
+            s = (rx[k - 1] if k >= 1 else 0.0) + A.T @ s
+        sup = 0.0
+        for r_, lo_, hi_ in ((rx, x_lb, x_ub), (ru, u_lb, u_ub)):
+            lo_b, hi_b = np.broadcast_to(lo_, r_.shape), np.broadcast_to(hi_, r_.shape)
+            pos, neg = r_ > 0, r_ < 0
+            sup += np.sum(r_[pos] * hi_b[pos]) + np.sum(r_[neg] * lo_b[neg])
+        dn = max(np.max(np.abs(rx)), np.max(np.abs(ru)))
+        if gmax <= eps_prim_inf * dn and (s @ x0 - sup) > eps_prim_inf * dn:
+            status = "infeasible"
+    if status is None:
+        status = "optimal_inaccurate" if near_ok else "user_limit"
+    out.x, out.u, out.status, out.iters = x, u, status, it
+    out.y, out.lam, out.level, out.rho_final = np.hstack([yx, yu]), np.hstack([lx, lu]), lvl, rho_l
+    return out

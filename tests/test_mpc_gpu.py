@@ -2,7 +2,9 @@
 
 The reference's arithmetic here is OSQP's (not in the reference tree, not installed): numeric parity is UNPINNED.  The tests
 therefore use (i) the reference's own test problem with its hand-derived optimum, (ii) solver-independent KKT certificates,
-(iii) an independent SciPy solve of the condensed QP, (iv) iterate-level agreement with the NumPy restatement of the ADMM."""
+(iii) an independent SciPy solve of the condensed QP, (iv) iterate-level agreement with the NumPy restatement of the ADMM: here at a
+fixed penalty from a cold start; with the adaptive penalty, warm and shifted starts, the tracking guard and on the lane kernel in
+tests/test_mpc_iterates_gpu.py (restatement: oracle/mpc_oracle.py admm_levels, pinned by tests/test_mpc_levels_oracle.py)."""
 import numpy as np
 import pytest
 
@@ -59,9 +61,8 @@ def test_constrained_small_problems_against_independent_solve(mpc, n, m, N):
     x0 = rng.uniform(-1.0, 1.0, (nb, n))
     u0, traj, status = prob.solve(x0, eps_abs=eps, eps_rel=eps, max_iter=30000)
     n_active = n_ref = 0
+    assert np.all(status == "optimal")
     for b in range(nb):
-        if status[b] != "optimal":
-            continue
         x, u = traj.xTraj[b], traj.uTraj[b]
         kkt = mo.kkt_residuals(A, B, Q, R, Qf, N, -x_ub, x_ub, -u_ub, u_ub, x0[b], x, u, act_tol=1e-4)
         assert kkt["dyn"] <= 1e-12 and kkt["bound"] <= 1e-4 and kkt["stat"] <= 1e-3
@@ -318,12 +319,10 @@ def test_shapes_between_the_compiled_kernels(mpc, n, m):
     x0 = 0.5 * rng.standard_normal((5, n))
     u0, traj, status = prob.solve(x0, eps_abs=1e-7, eps_rel=1e-7, max_iter=100000)
     assert u0.shape == (5, m) and traj.xTraj.shape == (5, N + 1, n) and traj.uTraj.shape == (5, N, m)
+    assert np.all(status == "optimal")
     for b in range(5):
-        if status[b] != "optimal":
-            continue
         kkt = mo.kkt_residuals(A, B, Q, R, Qf, N, -x_ub, x_ub, -u_ub, u_ub, x0[b], traj.xTraj[b], traj.uTraj[b], act_tol=1e-5)
         assert kkt["dyn"] <= 1e-12 and kkt["bound"] <= 1e-5 and kkt["stat"] <= 1e-4
-    assert np.sum(status == "optimal") >= 3
-    b = int(np.where(status == "optimal")[0][0])
+    b = 0
     xr, ur, fr = mo.solve_reference(A, B, Q, R, Qf, N, -x_ub, x_ub, -u_ub, u_ub, x0[b])
     assert np.max(np.abs(traj.uTraj[b] - ur)) <= 2e-4

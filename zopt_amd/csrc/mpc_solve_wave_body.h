@@ -233,8 +233,9 @@
         // ---- adaptive penalty (OSQP adaptive_rho): rho <- rho sqrt(normalised primal / normalised dual residual), taken in
         //      whole steps of the tabulated levels: to the level nearest the wanted penalty on the log scale (so a move happens
         //      when the penalty is off by at least sqrt(rho_step)); the scaled dual lam = mu / rho is rescaled so that the
-        //      unscaled multiplier mu is unchanged
-        if (g.n_levels > 1 && chk && !done) {
+        //      unscaled multiplier mu is unchanged.  Not at the last iteration the cap allows: no iteration follows it, and the final
+        //      rollout below pairs the kf of the last iterate with the level's K_k, so a move there returned a trajectory that is no iterate
+        if (g.n_levels > 1 && chk && !done && gi + 1 < g.max_iter) {
             const double tiny = 1e-300;
             const double rpn = rp / __builtin_fmax(__builtin_fmax(nw, ny), tiny);
             const double rdn = rd / __builtin_fmax(rho * nl, tiny);
