@@ -493,6 +493,36 @@ int zm_mpc_solve_tracking_f64(const double* A, const double* B, const double* Q,
                               double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
                               void* stream);
 
+/* The receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) as ONE call: `steps` solves of every instance in a row, each
+ * from the state the previous one led to,
+ *     x <- clip(x, x_lb + clip_tol, x_ub - clip_tol);  states[s] = x;  solve from x (step 0 cold, later steps with `warm_start`);
+ *     inputs[s] = uTraj_s[0];  x <- xTraj_s[1] + disturbance[s];                        states[steps] = clip(x, ...)
+ * -- exactly what a loop of zm_mpc_solve_relaxed_f64 / zm_mpc_solve_batched_f64 / zm_mpc_solve_tracking_f64 calls computes (one entry
+ * point for the three forms: problem, rho_p, Q, R, Qf, xRef, uRef, disturbance may be NULL with the meanings they have there), whatever
+ * the status of a step: a step that does not end "optimal" still leaves a rollout, and the step after it starts cold.
+ * Regulator runs (xRef = uRef = NULL) at the shapes and horizons of the 16-lanes-per-instance kernels are ONE launch: the step loop runs
+ * inside the kernel, and a wave goes on to its next step as soon as its own four instances are through (the gain over a launch per step
+ * is per wave, not per instance).  Tracking runs, (n, m) = (24, 8), horizons beyond LDS and ZOPT_AMD_MPC_PATH=lane take a host loop that
+ * enqueues the launches of a single solve and a small advance kernel per step.  Neither synchronises or copies anything to the host,
+ * apart from the one check of the problem map that zm_mpc_solve_batched_f64 documents.
+ *     in : the arguments of zm_mpc_solve_tracking_f64 with the same meanings; x0 (batch,n)   [device]
+ *          xRef (batch,xref_rows,n) with xref_rows = steps + N, uRef (batch,uref_rows,m) with uref_rows = steps + N - 1: step s tracks
+ *          rows s .. s + N of xRef and s .. s + N - 1 of uRef; either may be NULL (its row count is then ignored)   [device]
+ *          warm_start: 0 / 1 / 2 (shifted) for the steps after the first;  clip_tol >= 0, or negative for no clip
+ *          disturbance (steps,batch,n) or NULL   [device]
+ *          workspace: (tracking ? 5 : 4) * batch * N * (n + m) doubles, plus batch * ((N + 1) * n + N * m) doubles when xPred is NULL
+ *                     (the rollout every step overwrites)   [device]
+ *     out: STEP-MAJOR.  states (steps+1,batch,n)  inputs (steps,batch,m)  status, iters (steps,batch) int32   [device]
+ *          xPred (steps,batch,N+1,n)  uPred (steps,batch,N,m): the rollout of every step; both NULL to skip   [device] */
+int zm_mpc_closed_loop_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                           const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                           const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
+                           const double* uRef, int xref_rows, int uref_rows, double rho, const double* rho_p, const int32_t* problem,
+                           int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, int steps,
+                           double clip_tol, const double* disturbance, double* workspace, double* states, double* inputs,
+                           int32_t* status, int32_t* iters, double* xPred, double* uPred, int64_t batch, int N, int n, int m,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Receding-horizon MPC about a moving reference: 64 quadcopters (the linearisation and bounds of the reference's demos/lqrMpc.py) each
 follow a position ramp; at every step the caller moves the reference window, the solve starts from the shifted iterates of the previous
-one, and the vehicle takes the first planned step ("assume perfect tracking", demos/lqrMpc.py:47)."""
+one, and the vehicle takes the first planned step ("assume perfect tracking", demos/lqrMpc.py:47).  First the loop written out by hand
+over `solve`, then the same run as one call, `simulate`, which takes the whole reference (steps + N rows) and moves the window itself."""
 import os
 import sys
 
@@ -31,13 +32,31 @@ def window(step):
     return xRef
 
 
+opts = dict(eps_abs=1e-2, eps_rel=1e-2, max_iter=4000)
+
+# by hand: a launch and its round trips per step
 x = np.zeros((Bn, 12))
+xs = []
 for i in range(steps):
     x = np.clip(x, -x_ub + 1e-6, x_ub - 1e-6)
     xRef = window(i)
-    u, traj, status = prob.solve(x, xRef=xRef, eps_abs=1e-2, eps_rel=1e-2, max_iter=4000, warm_start="shift" if i else False)
+    xs.append(x)
+    u, traj, status = prob.solve(x, xRef=xRef, warm_start="shift" if i else False, **opts)
     err = np.linalg.norm(x[:, 9:12] - xRef[:, 0, 9:12], axis=1)
     if i % 10 == 0 or i == steps - 1:
         print(f"step {i:2d}: position error mean {err.mean():.3f} max {err.max():.3f} m, {int(prob.last_iterations.max())} ADMM iterations, "
               f"{int(np.sum(status == 'optimal'))}/{Bn} optimal")
     x = traj.xTraj[:, 1]
+xs.append(np.clip(x, -x_ub + 1e-6, x_ub - 1e-6))
+
+# the same run as one call on the device: the reference of the whole run, row s + k = row k of step s's window
+t = dt * np.arange(steps + N)
+xRefAll = np.zeros((Bn, steps + N, 12))
+xRefAll[:, :, 9:12] = p0[:, None, :] + vel[:, None, :] * t[None, :, None]
+xRefAll[:, :, 0:3] = vel[:, None, :]
+run = mpcUtils.lqrMpc(A, B, np.eye(12), np.eye(4), N, -x_ub, x_ub, -u_ub, u_ub).simulate(
+    np.zeros((Bn, 12)), steps, xRef=xRefAll, clip_tol=1e-6, warm_start="shift", **opts)
+err = np.linalg.norm(run.xTraj[:, -1, 9:12] - xRefAll[:, steps, 9:12], axis=1)
+print(f"simulate: {steps} steps in one call, final position error mean {err.mean():.3f} max {err.max():.3f} m, "
+      f"{int(np.sum(run.status == 'optimal'))}/{run.status.size} solves optimal, up to {int(run.iterations.max())} ADMM iterations; "
+      f"largest difference from the hand-written loop's states {np.max(np.abs(run.xTraj - np.stack(xs, axis=1))):.1e}")

@@ -86,6 +86,13 @@ SYMBOLS = {
                                   [_c_dp] * 7 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] + [ctypes.c_double] * 3 +
                                   [ctypes.c_int] * 2 + [_c_dp] * 6 +
                                   [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub, x0, xRef, uRef, xref_rows, uref_rows, rho,
+    #  rho_p (P) | NULL, problem (batch) | NULL, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start, steps, clip_tol, disturbance, ws,
+    #  states, inputs, status, iters, xPred, uPred, batch, N, n, m, stream)
+    "zm_mpc_closed_loop_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                               [_c_dp] * 7 + [ctypes.c_int] * 2 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] +
+                               [ctypes.c_double] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] + [_c_dp] * 8 +
+                               [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "zm_mpc_solve_warm_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_double] * 4 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                               [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, active, shared_hessian, l, L, batch, T, n, m, stream)

@@ -212,6 +212,73 @@ __global__ __launch_bounds__(64) void mpc_solve_track_kernel(const double* __res
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// closed-loop run (zm_mpc_closed_loop_f64): the kernels of the host loop
+// ----------------------------------------------------------------------------------------------------------------
+
+// mpc_track_linear_kernel for a WINDOW of longer references: instance b keeps xrows rows of xRef and urows rows of uRef, and the solve of
+// step `row0` tracks rows row0 .. row0 + N of xRef and row0 .. row0 + N - 1 of uRef.  The same sums in the same order, so a window gives
+// the bits mpc_track_linear_kernel gives for the same rows handed to it as an (N + 1)- / N-row reference.
+__global__ __launch_bounds__(256) void mpc_track_linear_window_kernel(const double* __restrict__ Q, const double* __restrict__ R,
+                                                                      const double* __restrict__ Qf, const double* __restrict__ xRef,
+                                                                      const double* __restrict__ uRef, const int* __restrict__ prob,
+                                                                      const long batch, const int N, const int n, const int m,
+                                                                      const long xrows, const long urows, const long row0,
+                                                                      double* __restrict__ g) {
+    const int W = n + m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * N * W) return;
+    const int i = (int)(e % W);
+    const long s = e / W;
+    const int k = (int)(s % N);
+    const long b = s / N;
+    const long p = prob ? prob[b] : 0;
+    double acc = 0.0;
+    if (i < n) {
+        if (xRef) {
+            const double* Wm = (k == N - 1 ? Qf : Q) + p * n * n;
+            const double* xr = xRef + (b * xrows + row0 + k + 1) * n;
+            for (int j = 0; j < n; ++j) acc = __builtin_fma(Wm[i * n + j] + Wm[j * n + i], xr[j], acc);
+        }
+    } else if (uRef) {
+        const int r = i - n;
+        const double* Rm = R + p * m * m;
+        const double* ur = uRef + (b * urows + row0 + k) * m;
+        for (int j = 0; j < m; ++j) acc = __builtin_fma(Rm[r * m + j] + Rm[j * m + r], ur[j], acc);
+    }
+    g[e] = -acc;
+}
+
+// Between two solves of the host loop, one thread per (instance, component of [x ; u]):
+//     state component i :  dst[b][i] = clip(src[b * src_stride + i] + dist[b][i])   into [x_lb + clip_tol, x_ub - clip_tol] of b's problem
+//     control component j: udst[b][j] = usrc[b * usrc_stride + j]
+// With src = row 1 of a step's rollout this is the successor state and the input applied; with src = x0 (dist, usrc NULL) the first state.
+// dist NULL: nothing is added; clip_tol < 0: no clip; usrc NULL: the control threads do nothing.
+__global__ __launch_bounds__(256) void mpc_advance_kernel(const double* src, const long src_stride, const double* dist, const double* x_lb,
+                                                          const double* x_ub, const int* prob, const double clip_tol, double* dst,
+                                                          const double* usrc, const long usrc_stride, double* udst, const long batch,
+                                                          const int n, const int m) {
+    const int W = n + m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * W) return;
+    const int i = (int)(e % W);
+    const long b = e / W;
+    if (i < n) {
+        double v = src[b * src_stride + i];
+        if (dist) v += dist[b * n + i];
+        if (clip_tol >= 0.0) {   // min(max(v, lo), hi): np.clip's order, a NaN passes through
+            const long p = prob ? prob[b] : 0;
+            const double lo = x_lb[p * n + i] + clip_tol, hi = x_ub[p * n + i] - clip_tol;
+            v = v < lo ? lo : v;
+            v = v > hi ? hi : v;
+        }
+        dst[b * n + i] = v;
+    } else if (usrc) {
+        const int j = i - n;
+        udst[b * m + j] = usrc[b * usrc_stride + j];
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // host side: one shape ladder, one launcher, one routine behind the three solve entry points
 // ----------------------------------------------------------------------------------------------------------------
 
@@ -243,6 +310,66 @@ static int launch_mpc(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, con
     return pb ? go(mpc_solve_batched_kernel<NS, MC>, *pb) : go(mpc_solve_kernel<NS, MC>);
 }
 
+// The argument checks of the solve entry points and of zm_mpc_closed_loop_f64, all before any launch.  `fn` is the entry point's name,
+// the prefix of its error messages; `outputs` is false if one of the entry point's own output pointers is NULL.
+static int mpc_check_args(const char* fn, bool per_problem, bool tracking, bool outputs, const double* A, const double* B, const double* Q,
+                          const double* R, const double* Qf, const double* K, const double* Minv, int n_levels, int level0, double rho_step,
+                          double alpha, const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub, const double* x0,
+                          double rho, const double* rho_p, const int32_t* problem, int64_t P, int max_iter, const double* workspace,
+                          int64_t batch, int N, int n, int m) {
+    if (!(alpha > 0.0 && alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", fn);
+    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !outputs ||
+        (tracking && (!Q || !R || !Qf)) || (per_problem && (!rho_p || !problem)))
+        return set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if ((problem == nullptr) != (rho_p == nullptr))
+        return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", fn);
+    if (batch < 0 || N < 1 || max_iter < 0 || (tracking && (n < 1 || m < 1)) || (problem ? P < 1 : !(rho > 0.0)))
+        return set_error(ZM_EINVAL, tracking ? "%s: bad size / rho" : "%s: bad size", fn);
+    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
+        return set_error(ZM_EINVAL, "%s: bad penalty levels", fn);
+    const long blocks = ((long)batch * N * ((long)n + m) + 255) / 256;   // of mpc_track_linear_kernel
+    if (tracking && blocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
+    return ZM_OK;
+}
+
+// every instance's problem index must lie in [0, P): the kernels offset every table by it, so it is checked here, on the host,
+// before anything is launched (one small copy of the index map; the solve's own results come back through a sync anyway)
+static int mpc_check_map(const char* fn, const int32_t* problem, int64_t P, int64_t batch, hipStream_t st) {
+    if (!problem) return ZM_OK;
+    static thread_local std::vector<int32_t> h;
+    h.resize((size_t)batch);
+    ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ZM_HIP_CHECK(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < batch; ++i)
+        if (h[i] < 0 || h[i] >= P)
+            return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d outside [0, %lld)", fn, (long long)i, (int)h[i], (long long)P);
+    return ZM_OK;
+}
+
+// ZOPT_AMD_MPC_PATH=lane forces the lane-per-instance kernels (read once per process)
+static bool mpc_force_lane() {
+    static const bool force_lane = [] {
+        const char* e = fallback_env("ZOPT_AMD_MPC_PATH");
+        return e && e[0] == 'l';
+    }();
+    return force_lane;
+}
+
+// One solve launch.  Default: 16 lanes per instance with the iterates in LDS (mpc_wave.hip); ZOPT_AMD_MPC_PATH=lane forces the
+// lane-per-instance kernel below, which also takes the shapes and the horizons that do not fit LDS.  It runs every problem at its
+// level0 table (fixed penalty).  `t` holds the whole tables (every level).
+static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
+    if (!mpc_force_lane()) {
+        const int rc = mpc_wave_dispatch(t, g, pb, trk, n, m, st);
+        if (rc != ZM_EUNSUPPORTED) return rc;
+    }
+    t.K += (long)g.level0 * g.N * m * n;        // (+ p * n_levels * N * m * n in the kernel)
+    t.Minv += (long)g.level0 * g.N * m * m;
+    const int rc = for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_mpc<ns.value, mc.value>(t, g, pb, trk, st); });
+    if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the compiled shapes", fn, n, m);
+    return rc;
+}
+
 // The three solve entry points.  `fn` is the entry point's name, the prefix of its error messages.
 //   zm_mpc_solve_relaxed_f64 : one problem, scalar rho                          (problem, rho_p, Q, R, Qf, xRef, uRef NULL)
 //   zm_mpc_solve_batched_f64 : per_problem -- problem and rho_p are required    (Q, R, Qf, xRef, uRef NULL)
@@ -255,62 +382,102 @@ static int mpc_solve(const char* fn, bool per_problem, bool tracking, const doub
                      double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
                      double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream) {
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!(alpha > 0.0 && alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", fn);
-    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !xTraj || !uTraj || !status ||
-        (tracking && (!Q || !R || !Qf)) || (per_problem && (!rho_p || !problem)))
-        return set_error(ZM_EINVAL, "%s: null pointer", fn);
-    if ((problem == nullptr) != (rho_p == nullptr))
-        return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", fn);
-    if (batch < 0 || N < 1 || max_iter < 0 || (tracking && (n < 1 || m < 1)) || (problem ? P < 1 : !(rho > 0.0)))
-        return set_error(ZM_EINVAL, tracking ? "%s: bad size / rho" : "%s: bad size", fn);
-    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
-        return set_error(ZM_EINVAL, "%s: bad penalty levels", fn);
+    int rc = mpc_check_args(fn, per_problem, tracking, xTraj && uTraj && status, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha,
+                            x_lb, x_ub, u_lb, u_ub, x0, rho, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
+    if (rc != ZM_OK) return rc;
     const long W = (long)n + m;
-    const long blocks = ((long)batch * N * W + 255) / 256;   // of mpc_track_linear_kernel
-    if (tracking && blocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
     hipStream_t st = (hipStream_t)stream;
-    // every instance's problem index must lie in [0, P): the kernels offset every table by it, so it is checked here, on the host,
-    // before anything is launched (one small copy of the index map; the solve's own results come back through a sync anyway)
-    if (problem) {
-        static thread_local std::vector<int32_t> h;
-        h.resize((size_t)batch);
-        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ZM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int64_t i = 0; i < batch; ++i)
-            if (h[i] < 0 || h[i] >= P)
-                return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d outside [0, %lld)", fn, (long long)i, (int)h[i],
-                                 (long long)P);
-    }
+    rc = mpc_check_map(fn, problem, P, batch, st);
+    if (rc != ZM_OK) return rc;
     // tracking: the fifth block of the workspace holds the linear term g (batch, N, n + m)
     double* gbuf = tracking ? workspace + 4L * batch * N * W : nullptr;
     if (tracking) {
+        const long blocks = ((long)batch * N * W + 255) / 256;
         hipLaunchKernelGGL(mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
                            (long)batch, N, n, m, gbuf);
         ZM_HIP_CHECK(hipGetLastError());
     }
-    MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
     // with per-problem data g.rho is unused (each instance takes its problem's pb.rho[p]); 1.0 keeps the struct well-formed
     const MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace,
                     xTraj, uTraj, (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
     const MpcProb pbv{(const int*)problem, rho_p};
-    const MpcProb* pb = problem ? &pbv : nullptr;
     const MpcTrack trkv{gbuf};
-    const MpcTrack* trk = tracking ? &trkv : nullptr;
-    // default: 16 lanes per instance with the iterates in LDS (mpc_wave.hip); ZOPT_AMD_MPC_PATH=lane forces the
-    // lane-per-instance kernel below, which also takes the shapes and the horizons that do not fit LDS.  It runs every problem at its
-    // level0 table (fixed penalty).
-    static const bool force_lane = [] {
-        const char* e = fallback_env("ZOPT_AMD_MPC_PATH");
-        return e && e[0] == 'l';
-    }();
-    if (!force_lane) {
-        const int rc = mpc_wave_dispatch(t, g, pb, trk, n, m, st);
+    return mpc_enqueue(fn, t, g, problem ? &pbv : nullptr, tracking ? &trkv : nullptr, n, m, st);
+}
+
+// zm_mpc_closed_loop_f64: `steps` receding-horizon solves of every instance, nothing but launches on `st` after the argument checks.
+//   (a) regulator runs at the shapes and horizons of the 16-lanes-per-instance kernels: ONE launch, the step loop inside the kernel
+//       (mpc_wave.hip: mpc_closed_loop_wave_kernel);
+//   (b) everything else -- tracking, (24, 8), horizons beyond LDS, ZOPT_AMD_MPC_PATH=lane: a loop that enqueues, per step, the launches
+//       of a single solve and mpc_advance_kernel, with no host synchronisation in between.
+static int mpc_closed_loop(const char* fn, const double* A, const double* B, const double* Q, const double* R, const double* Qf,
+                           const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                           const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
+                           const double* uRef, int xref_rows, int uref_rows, double rho, const double* rho_p, const int32_t* problem,
+                           int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, int steps,
+                           double clip_tol, const double* disturbance, double* workspace, double* states, double* inputs, int32_t* status,
+                           int32_t* iters, double* xPred, double* uPred, int64_t batch, int N, int n, int m, void* stream) {
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    const bool tracking = xRef || uRef;
+    int rc = mpc_check_args(fn, false, tracking, states && inputs && status && iters, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step,
+                            alpha, x_lb, x_ub, u_lb, u_ub, x0, rho, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
+    if (rc != ZM_OK) return rc;
+    if (steps < 1) return set_error(ZM_EINVAL, "%s: steps must be at least 1", fn);
+    if (n < 1 || m < 1) return set_error(ZM_EINVAL, "%s: bad size", fn);
+    if ((xPred == nullptr) != (uPred == nullptr)) return set_error(ZM_EINVAL, "%s: the two prediction arrays come together", fn);
+    if ((xRef && xref_rows != steps + N) || (uRef && uref_rows != steps + N - 1))
+        return set_error(ZM_EINVAL, "%s: a reference needs steps + N rows of xRef and steps + N - 1 rows of uRef", fn);
+    const long W = (long)n + m;
+    const long ablocks = ((long)batch * W + 255) / 256;           // of mpc_advance_kernel
+    const long gblocks = ((long)batch * N * W + 255) / 256;       // of mpc_track_linear_window_kernel
+    if (ablocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x (n + m) too large", fn);
+    hipStream_t st = (hipStream_t)stream;
+    rc = mpc_check_map(fn, problem, P, batch, st);
+    if (rc != ZM_OK) return rc;
+
+    // workspace: the blocks of a solve (the fifth: the linear term of a tracking step), then -- unless the predictions are kept -- the
+    // rollout every step overwrites
+    double* gbuf = tracking ? workspace + 4L * batch * N * W : nullptr;
+    double* scratch = workspace + (tracking ? 5L : 4L) * batch * N * W;
+    const long xsz = (long)batch * (N + 1) * n, usz = (long)batch * N * m;
+    const MpcLoop lp{steps, warm_start == 2 ? 2 : (warm_start ? 1 : 0), clip_tol, x0, disturbance, states, inputs, (int*)status, (int*)iters,
+                     xPred ? xPred : scratch, uPred ? uPred : scratch + xsz, xPred ? xsz : 0, uPred ? usz : 0};
+    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    const MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, 0, workspace, lp.xPred, lp.uPred, lp.status, lp.iters,
+                    nullptr, (long)batch, N, n_levels, level0, rho_step, alpha};
+    const MpcProb pbv{(const int*)problem, rho_p};
+    const MpcProb* pb = problem ? &pbv : nullptr;
+    if (!tracking && !mpc_force_lane()) {
+        rc = mpc_wave_closed_loop_dispatch(t, g, pb, lp, n, m, st);
         if (rc != ZM_EUNSUPPORTED) return rc;
     }
-    t.K = K + (long)level0 * N * m * n;        // (+ p * n_levels * N * m * n in the kernel)
-    t.Minv = Minv + (long)level0 * N * m * m;
-    const int rc = for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_mpc<ns.value, mc.value>(t, g, pb, trk, st); });
-    if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the compiled shapes", fn, n, m);
+    const MpcTrack trkv{gbuf};
+    const auto advance = [&](const double* src, long src_stride, const double* dist, double* dst, const double* usrc, double* udst) -> int {
+        hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, x_lb, x_ub,
+                           (const int*)problem, clip_tol, dst, usrc, (long)N * m, udst, (long)batch, n, m);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    };
+    rc = advance(x0, n, nullptr, states, nullptr, nullptr);
+    for (int s = 0; s < steps && rc == ZM_OK; ++s) {
+        if (tracking) {
+            hipLaunchKernelGGL(mpc_track_linear_window_kernel, dim3((unsigned)gblocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef,
+                               (const int*)problem, (long)batch, N, n, m, (long)xref_rows, (long)uref_rows, (long)s, gbuf);
+            ZM_HIP_CHECK(hipGetLastError());
+        }
+        MpcArgs gs = g;
+        gs.x0 = states + (long)s * batch * n;
+        gs.xTraj = lp.xPred + s * lp.xpred_step;
+        gs.uTraj = lp.uPred + s * lp.upred_step;
+        gs.status = lp.status + (long)s * batch;
+        gs.iters = lp.iters + (long)s * batch;
+        gs.warm = s ? lp.warm : 0;
+        rc = mpc_enqueue(fn, t, gs, pb, tracking ? &trkv : nullptr, n, m, st);
+        if (rc != ZM_OK) break;
+        rc = advance(gs.xTraj + n, (long)(N + 1) * n, disturbance ? disturbance + (long)s * batch * n : nullptr,
+                     states + (long)(s + 1) * batch * n, gs.uTraj, inputs + (long)s * batch * m);
+    }
     return rc;
 }
 
@@ -421,4 +588,19 @@ extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const
     return zm::mpc_solve("zm_mpc_solve_tracking_f64", false, true, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb,
                          x_ub, u_lb, u_ub, x0, xRef, uRef, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start,
                          workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
+}
+
+// the receding-horizon loop as one call: see mpc_closed_loop
+extern "C" int zm_mpc_closed_loop_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                                      const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                                      const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
+                                      const double* uRef, int xref_rows, int uref_rows, double rho, const double* rho_p,
+                                      const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter,
+                                      int warm_start, int steps, double clip_tol, const double* disturbance, double* workspace,
+                                      double* states, double* inputs, int32_t* status, int32_t* iters, double* xPred, double* uPred,
+                                      int64_t batch, int N, int n, int m, void* stream) {
+    return zm::mpc_closed_loop("zm_mpc_closed_loop_f64", A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub,
+                               x0, xRef, uRef, xref_rows, uref_rows, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter,
+                               warm_start, steps, clip_tol, disturbance, workspace, states, inputs, status, iters, xPred, uPred, batch, N,
+                               n, m, stream);
 }

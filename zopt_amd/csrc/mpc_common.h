@@ -47,6 +47,21 @@ struct MpcTrack {
     const double* g;
 };
 
+// closed-loop run (zm_mpc_closed_loop_f64): `steps` receding-horizon solves in a row, step-major arrays -- step s of an array is one
+// batch-sized slab further on, so a step's solve sees the layouts of a single solve through offset pointers.
+struct MpcLoop {
+    int steps;
+    int warm;                 // MpcArgs::warm of the steps after the first (the first is always a cold start)
+    double clip_tol;          // every state is clipped into [x_lb + clip_tol, x_ub - clip_tol] before it is solved from; < 0: no clip
+    const double* x0;         // (batch, n)         the initial states
+    const double* dist;       // (steps, batch, n)  added to the successor state; may be nullptr
+    double* states;           // (steps + 1, batch, n)
+    double* inputs;           // (steps, batch, m)
+    int *status, *iters;      // (steps, batch)
+    double *xPred, *uPred;    // the rollout of every step, (batch, N + 1, n) / (batch, N, m) each ...
+    long xpred_step, upred_step;   // ... this many doubles apart: one rollout when predictions are kept, 0 when every step reuses one scratch
+};
+
 // Entry block of the per-problem kernels: instance `inst` reads its problem index, offsets A, B, the bounds and the tables by it and takes
 // the problem's penalty.  A macro, not a function: the kernels' `__restrict__` parameters do not survive being passed by reference
 // (other code, more scratch).  Expands inside a kernel with the parameters of mpc_solve_batched_kernel and a local MpcArgs g.
@@ -69,5 +84,8 @@ using Int = std::integral_constant<int, V>;
 // mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.  pb: per-problem data,
 // trk: reference tracking; either may be nullptr.
 int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st);
+// mpc_wave.hip: the whole closed-loop run of a regulator as ONE launch of the same kernels with the step loop inside.  `g` carries the
+// options and the workspace of every step (its x0, outputs and warm are set per step from `lp`).  ZM_EUNSUPPORTED as above.
+int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, int n, int m, hipStream_t st);
 
 }  // namespace zm

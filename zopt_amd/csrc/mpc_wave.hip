@@ -121,6 +121,75 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_batched_kernel(const double
     }
 #include "mpc_solve_wave_body.h"
 }
+// Closed-loop run (zm_mpc_closed_loop_f64): the receding-horizon loop of demos/lqrMpc.py:40-47 INSIDE the kernel, around the same body --
+// per step s: the state (already clipped into the box) is solved from, the group's state lanes form x_{s+1} = clip(xTraj_s[1] + w_s) and
+// store it, the control lanes store u_s = uTraj_s[0]; the body sees a local MpcArgs whose x0, outputs and warm point at step s.  One
+// launch for the whole run: no launch, allocation or host round trip per step, and a wave whose four instances finish a step early goes on
+// to the next one at once instead of waiting for the slowest instance of the batch (the step loop is wave-uniform: the gain is per wave,
+// not per instance).
+// Across a step boundary the body reads what the previous step wrote to global memory: the warm-start blocks and the state (each lane
+// its own words) and the `ok` flag / level (lane 0 of the group writes, all 16 lanes read; an idle group reads the last instance's, which
+// another group of the same wave writes).  Every reader sits in the same single-wave workgroup, so a workgroup-scope release / acquire
+// fence between the steps orders them (a wait for the outstanding stores, no cache maintenance); none of these words is reached through a
+// `const __restrict__` parameter.  Idle groups of the last block shadow the last instance and store nothing here either; they keep
+// looping with their wave.  PB: per-problem data, the entry block of mpc_solve_wave_batched_kernel.
+template <int NS, int MC, bool PB>
+__global__ __launch_bounds__(64) void mpc_closed_loop_wave_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                                  const double* __restrict__ Ktab, const double* __restrict__ Mtab,
+                                                                  const double* __restrict__ x_lb, const double* __restrict__ x_ub,
+                                                                  const double* __restrict__ u_lb, const double* __restrict__ u_ub,
+                                                                  const MpcArgs g_all, const MpcProb pb, const MpcLoop lp) {
+    MpcArgs g_run = g_all;
+    const long o_batch = g_all.batch;
+    const int o_li = threadIdx.x & 15;
+    const long o_raw = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
+    const bool o_live = o_raw < o_batch;
+    const long o_inst = o_live ? o_raw : o_batch - 1;
+    if constexpr (PB) {
+        MpcArgs& g = g_run;
+        ZM_MPC_ENTER_PROBLEM(o_inst)
+    }
+    const bool o_sx = o_li < NS, o_su = (o_li >= NS) && (o_li < NS + MC);
+    const int o_ix = o_sx ? o_li : 0, o_iu = o_su ? o_li - NS : 0;
+    const bool o_clip = lp.clip_tol >= 0.0;
+    const double c_lo = x_lb[o_ix] + lp.clip_tol, c_hi = x_ub[o_ix] - lp.clip_tol;
+    const auto into_box = [&](double v) {   // min(max(v, lo), hi): np.clip's order, a NaN passes through
+        if (o_clip) {
+            v = v < c_lo ? c_lo : v;
+            v = v > c_hi ? c_hi : v;
+        }
+        return v;
+    };
+    const long slab_x = o_batch * NS, slab_u = o_batch * MC;
+    if (o_live && o_sx) lp.states[o_inst * NS + o_ix] = into_box(lp.x0[o_inst * NS + o_ix]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll 1
+    for (int s = 0; s < lp.steps; ++s) {
+        MpcArgs g = g_run;
+        g.x0 = lp.states + s * slab_x;
+        g.xTraj = lp.xPred + s * lp.xpred_step;
+        g.uTraj = lp.uPred + s * lp.upred_step;
+        g.status = lp.status + s * o_batch;
+        g.iters = lp.iters + s * o_batch;
+        g.resid = nullptr;
+        g.warm = s ? lp.warm : 0;
+        {
+#include "mpc_solve_wave_body.h"
+        }
+        if (o_live) {
+            if (o_sx) {
+                double xn = g.xTraj[(o_inst * (g.N + 1) + 1) * NS + o_ix];
+                if (lp.dist) xn += lp.dist[s * slab_x + o_inst * NS + o_ix];
+                lp.states[(s + 1) * slab_x + o_inst * NS + o_ix] = into_box(xn);
+            }
+            if (o_su) lp.inputs[s * slab_u + o_inst * MC + o_iu] = g.uTraj[(o_inst * g.N) * MC + o_iu];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
 // Reference tracking (zm_mpc_solve_tracking_f64): the same body with a second linear term, -rho (y - lam) + g_k, at the top of each
 // backward stage.  g (mpc.hip: mpc_track_linear_kernel) is constant over the iterations and read-only, so it is NOT a fifth LDS slot:
 // the lane's component of stage k is fetched from L2 three stages ahead, together with the table slices of that stage (one more
@@ -225,6 +294,25 @@ static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, co
 
 int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
     return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave<ns.value, mc.value>(t, g, pb, trk, st); });
+}
+
+// the closed-loop kernel: grid and LDS of launch_wave
+template <int NS, int MC>
+static int launch_wave_closed_loop(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, hipStream_t st) {
+    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
+    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // horizon too long for LDS: the host loop over the lane-per-instance kernel takes it
+    const auto go = [&](auto kernel, const MpcProb& pbv) -> int {
+        ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
+                           t.u_ub, g, pbv, lp);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    };
+    return pb ? go(mpc_closed_loop_wave_kernel<NS, MC, true>, *pb) : go(mpc_closed_loop_wave_kernel<NS, MC, false>, MpcProb{});
+}
+
+int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, int n, int m, hipStream_t st) {
+    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave_closed_loop<ns.value, mc.value>(t, g, pb, lp, st); });
 }
 
 }  // namespace zm

@@ -2,11 +2,13 @@
 
 Same constructor and ``solve`` signature as the reference (mpcUtils.py:14-26, 61-81).  New: ``x0`` may carry leading
 batch axes -- every initial state is an independent QP instance solved by one GPU lane; `solve` takes references to track (keywords
-xRef, uRef).  The plotting / animation helpers
+xRef, uRef); `simulate` runs the whole receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) on the device in one call.
+The plotting / animation helpers
 of the reference module (mpcUtils.py:84-202) are presentation code and not part of this package.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
@@ -24,6 +26,10 @@ except Exception:  # pragma: no cover
 # both residuals within 10x their tolerances.  "unbounded" cannot arise for this QP (Q, Qf >= 0, R > 0); an instance that is neither
 # solved nor certified infeasible at the limit is "user_limit" (cvxpy's name for OSQP's "maximum iterations reached").
 _STATUS = {1: "optimal", 2: "infeasible", 3: "user_limit", 4: "optimal_inaccurate"}
+
+# what `lqrMpc.simulate` returns: the closed-loop states (..., S+1, n) and inputs (..., S, m), the status strings and ADMM iteration counts
+# of every step (..., S), and -- on request -- the rollout every step planned, a Trajectory of (..., S, N+1, n) / (..., S, N, m)
+MpcClosedLoop = collections.namedtuple("MpcClosedLoop", ("xTraj", "uTraj", "status", "iterations", "predictions"))
 
 
 class lqrMpc():
@@ -126,6 +132,39 @@ class lqrMpc():
             self._tables[key] = (K, Mi, nl, l0)
         return self._dev, self._tables[key]
 
+    def _solver_options(self, kwargs, warm_default):
+        """The solver options of `solve` (and `simulate`) taken out of `kwargs`, which must be empty afterwards:
+        (eps_abs, eps_rel, max_iter, rho, adaptive_rho, eps_prim_inf, alpha, warm, shift)."""
+        solver = kwargs.pop("solver", None)
+        if solver not in (None, "OSQP"):
+            raise ValueError(f"solver {solver!r} is not available in zopt_amd (ADMM only; pass solver='OSQP' or None)")
+        eps_abs = float(kwargs.pop("eps_abs", 1e-5))
+        eps_rel = float(kwargs.pop("eps_rel", 1e-5))
+        max_iter = int(kwargs.pop("max_iter", 10000))
+        rho = kwargs.pop("rho", self.rho)
+        if self.P is None:
+            rho = float(rho)
+        else:   # a scalar or an array that broadcasts to the problem shape
+            try:
+                rho = np.array(np.broadcast_to(_host_f64(rho), self.P))   # (a writable copy: torch refuses read-only views)
+            except ValueError:
+                raise ValueError(f"rho of shape {np.shape(rho)} does not broadcast to the problem shape {self.P}") from None
+            if not np.all(rho > 0.0):
+                raise ValueError("rho must be positive")
+        adaptive = bool(kwargs.pop("adaptive_rho", True))        # OSQP / cvxpy default
+        eps_pinf = float(kwargs.pop("eps_prim_inf", 1e-4))
+        alpha = float(kwargs.pop("alpha", 1.6))
+        if not (0.0 < alpha < 2.0):
+            raise ValueError("alpha must lie in (0, 2)")
+        warm = kwargs.pop("warm_start", kwargs.pop("warm_starting", warm_default))
+        shift = isinstance(warm, str) and warm == "shift"     # extension: previous iterates advanced by one horizon step
+        warm = bool(warm)
+        for k in ("eps_dual_inf", "verbose", "polish", "polishing"):
+            kwargs.pop(k, None)
+        if kwargs:
+            raise TypeError(f"unknown solver options {sorted(kwargs)}")
+        return eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift
+
     def solve(self, x0, **kwargs):
         """
         Solve the MPC step at state x0 (reference mpcUtils.py:61-81)
@@ -155,34 +194,7 @@ class lqrMpc():
             status : problem status, one of [optimal, optimal_inaccurate, infeasible, user_limit] (a list of them for a batch)
         """
         xRef, uRef = kwargs.pop("xRef", None), kwargs.pop("uRef", None)
-        solver = kwargs.pop("solver", None)
-        if solver not in (None, "OSQP"):
-            raise ValueError(f"solver {solver!r} is not available in zopt_amd (ADMM only; pass solver='OSQP' or None)")
-        eps_abs = float(kwargs.pop("eps_abs", 1e-5))
-        eps_rel = float(kwargs.pop("eps_rel", 1e-5))
-        max_iter = int(kwargs.pop("max_iter", 10000))
-        rho = kwargs.pop("rho", self.rho)
-        if self.P is None:
-            rho = float(rho)
-        else:   # a scalar or an array that broadcasts to the problem shape
-            try:
-                rho = np.array(np.broadcast_to(_host_f64(rho), self.P))   # (a writable copy: torch refuses read-only views)
-            except ValueError:
-                raise ValueError(f"rho of shape {np.shape(rho)} does not broadcast to the problem shape {self.P}") from None
-            if not np.all(rho > 0.0):
-                raise ValueError("rho must be positive")
-        adaptive = bool(kwargs.pop("adaptive_rho", True))        # OSQP / cvxpy default
-        eps_pinf = float(kwargs.pop("eps_prim_inf", 1e-4))
-        alpha = float(kwargs.pop("alpha", 1.6))
-        if not (0.0 < alpha < 2.0):
-            raise ValueError("alpha must lie in (0, 2)")
-        warm = kwargs.pop("warm_start", kwargs.pop("warm_starting", True))
-        shift = isinstance(warm, str) and warm == "shift"     # extension: previous iterates advanced by one horizon step
-        warm = bool(warm)
-        for k in ("eps_dual_inf", "verbose", "polish", "polishing"):
-            kwargs.pop(k, None)
-        if kwargs:
-            raise TypeError(f"unknown solver options {sorted(kwargs)}")
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(kwargs, True)
         if isinstance(xRef, Trajectory):
             if uRef is not None:
                 raise ValueError("a Trajectory given as xRef carries its own uTraj: pass it alone (uRef=None)")
@@ -292,6 +304,135 @@ class lqrMpc():
         else:
             status = np.vectorize(_STATUS.get, otypes=[object])(codes)
         return uo[..., 0, :], Trajectory(xo, uo), status
+
+    def simulate(self, x0, steps, disturbance=None, clip_tol=1e-6, return_predictions=False, xRef=None, uRef=None, **solver_opts):
+        """
+        The receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) as one call, entirely on the device:
+
+            x = x0
+            for s in range(steps):
+                if clip_tol is not None: x = clip(x, x_lb + clip_tol, x_ub - clip_tol)
+                xTraj[s] = x
+                u, traj, status[s] = self.solve(x, warm_start=(False if s == 0 else W), window s of the references, **solver_opts)
+                uTraj[s] = u;  iterations[s] = self.last_iterations
+                x = traj.xTraj[1] + (disturbance[s] if disturbance is not None else 0)
+            xTraj[steps] = clip(x, ...) if clip_tol is not None else x
+
+        with the results that loop gives, whatever the status of a step (a step that is not "optimal" still leaves a rollout, and the step
+        after it starts cold).  A regulator run is one launch of a kernel that has the step loop inside (a wave goes on to its next step
+        as soon as its own four instances are through); tracking runs, (n, m) beyond the 16-lane kernels and horizons beyond LDS are a
+        queue of launches without a host round trip.  `simulate` has its own workspace: a `solve` after it (warm start, `last_iterations`,
+        `last_residuals`) behaves as if it had not happened.
+
+        Arguments
+        ---------
+            x0 : initial state (..., n)
+            steps : number S of MPC steps, >= 1
+            disturbance : (..., S, n), added to the successor state of every step; None: none
+            clip_tol : the demo's 1e-6; None: the state is not clipped
+            return_predictions : keep the rollout of every step
+            xRef (..., S + N, n), uRef (..., S + N - 1, m) : references to track; step s tracks rows s : s+N+1 of xRef and s : s+N of
+                uRef.  Either may be None (a Trajectory is not accepted: the two lengths differ from a Trajectory's).
+            **solver_opts : the options of `solve`; warm_start (default "shift") applies to the steps after the first, which is always
+                a cold start.
+            Leading axes of x0, disturbance, xRef, uRef broadcast against each other and the problem shape.
+
+        Returns
+        -------
+            MpcClosedLoop(xTraj (..., S+1, n), uTraj (..., S, m), status (..., S) strings, iterations (..., S) int32,
+                          predictions: None or Trajectory((..., S, N+1, n), (..., S, N, m)))
+        """
+        S = int(steps)
+        if S < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if clip_tol is not None and not (float(clip_tol) >= 0.0):
+            raise ValueError(f"clip_tol must be non-negative (or None for no clip), got {clip_tol}")
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(solver_opts, "shift")
+        if isinstance(xRef, Trajectory) or isinstance(uRef, Trajectory):
+            raise ValueError("simulate takes xRef (..., steps + N, n) and uRef (..., steps + N - 1, m) as arrays, not a Trajectory")
+        tracking = xRef is not None or uRef is not None
+        N, n, m = self.N, self.n, self.m
+
+        # 1. shapes
+        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+        shp = shape_of(x0)
+        if len(shp) < 1 or shp[-1] != self._n_user:
+            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
+        leads = {"x0": (shp, shp[:-1])}
+        for name, X, want in (("disturbance", disturbance, (S, self._n_user)), ("xRef", xRef, (S + N, self._n_user)),
+                              ("uRef", uRef, (S + N - 1, self._m_user))):
+            if X is not None:
+                sh = shape_of(X)
+                if len(sh) < 2 or sh[-2:] != want:
+                    raise ValueError(f"{name} has shape {sh}, expected (..., {want[0]}, {want[1]}) for steps = {S}, N = {N}")
+                leads[name] = (sh, sh[:-2])
+        try:
+            lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
+        except ValueError:
+            who = ", ".join(f"{k} of shape {sh}" for k, (sh, _) in leads.items())
+            raise ValueError(who + " do not broadcast against each other"
+                             + ("" if self.P is None else f" and the problem shape {self.P}") + ": inconsistent shapes") from None
+        lead = tuple(int(v) for v in lead)
+        Bn = int(np.prod(lead))
+        arr.require_gpu()
+
+        # 2. the problem on the device and its tables (shared with `solve`: they depend on the problem and the penalty only)
+        if self.P is None:
+            d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
+            drho, Pn = None, 0
+        else:
+            d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
+            Pn = int(np.prod(self.P))
+
+        # 3. one row per instance, the padded components zero; device placement as in `solve`
+        def flat(X, tail, width, dev):
+            t = arr.to_device(X, torch.float64, dev)
+            t = t.expand(lead + tail).reshape((Bn,) + tail)
+            if width != tail[-1]:
+                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
+            return t.contiguous()
+        dx0 = flat(x0, (self._n_user,), n, d["A"].device if tracking or self.P is not None else None)
+        dev = dx0.device if self.P is None else d["A"].device
+        dxr = None if xRef is None else flat(xRef, (S + N, self._n_user), n, dev)
+        dur = None if uRef is None else flat(uRef, (S + N - 1, self._m_user), m, dev)
+        dw = None if disturbance is None else flat(disturbance, (S, self._n_user), n, dev).transpose(0, 1).contiguous()   # step-major
+        prob = None   # instance -> problem
+        if self.P is not None:
+            prob = torch.as_tensor(np.array(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
+                                   device=dev)
+
+        # 4. outputs (step-major on the device) and the run's own workspace
+        f64 = dict(dtype=torch.float64, device=dev)
+        xs = torch.empty((S + 1, Bn, n), **f64)
+        us = torch.empty((S, Bn, m), **f64)
+        st = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+        its = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+        xp = torch.empty((S, Bn, N + 1, n), **f64) if return_predictions else None
+        up = torch.empty((S, Bn, N, m), **f64) if return_predictions else None
+        ws = torch.empty((5 if tracking else 4) * Bn * N * (n + m) + (0 if return_predictions else Bn * ((N + 1) * n + N * m)), **f64)
+
+        # 5. the C call
+        if Bn > 0:
+            p = lambda k: d[k].data_ptr()
+            ptr = lambda t: None if t is None else t.data_ptr()
+            rc = _lib.lib().zm_mpc_closed_loop_f64(
+                p("A"), p("B"), p("Q"), p("R"), p("Qf"), K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP, alpha, p("x_lb"),
+                p("x_ub"), p("u_lb"), p("u_ub"), dx0.data_ptr(), ptr(dxr), ptr(dur), S + N, S + N - 1, rho if self.P is None else 0.0,
+                ptr(drho), ptr(prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, S,
+                -1.0 if clip_tol is None else float(clip_tol), ptr(dw), ws.data_ptr(), xs.data_ptr(), us.data_ptr(), st.data_ptr(),
+                its.data_ptr(), ptr(xp), ptr(up), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+            _lib.check(rc, "lqrMpc.simulate")
+
+        # 6. results: batch-leading views of the step-major arrays
+        view = lambda t, tail, width: arr.result_like(t.transpose(0, 1).reshape(lead + tail)[..., :width], x0)
+        codes = st.transpose(0, 1).reshape(lead + (S,)).cpu().numpy()
+        status = np.vectorize(_STATUS.get, otypes=[object])(codes) if Bn > 0 else np.empty(lead + (S,), dtype=object)
+        pred = None
+        if return_predictions:
+            pred = Trajectory(view(xp, (S, N + 1, n), self._n_user), view(up, (S, N, m), self._m_user))
+        return MpcClosedLoop(view(xs, (S + 1, n), self._n_user), view(us, (S, m), self._m_user), status,
+                             view(its, (S,), None), pred)
+
 
 
 def _host_f64(X):
