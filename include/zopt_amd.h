@@ -523,6 +523,39 @@ int zm_mpc_closed_loop_f64(const double* A, const double* B, const double* Q, co
                            int32_t* status, int32_t* iters, double* xPred, double* uPred, int64_t batch, int N, int n, int m,
                            void* stream);
 
+/* Stage-varying dynamics (extension; what linearising a model about a TRAJECTORY gives): the QP of zopt/mpcUtils.py:48-59 with
+ *     x_{k+1} = A_k x_k + B_k u_k + c_k,   k = 0 .. N-1,
+ * per problem, under the cost, bounds, ADMM, termination and status codes of zm_mpc_solve_tracking_f64 in its per-problem form.
+ * zm_mpc_setup_ltv_f64: the Riccati recursion of zm_mpc_setup_batched_f64 with the stage's own A_k, B_k (constant A_k, B_k give its
+ *     tables bit for bit), one workgroup per (problem, level), one launch.  It also emits D_k = P_{k+1} c_k, the offset's share of the
+ *     costate (P_{k+1}: the value matrix the recursion holds on entering stage k, P_N = 2 Qf + rho I), and ABt, the columns of
+ *     [A_k | B_k] as contiguous rows, which the backward sweep of the solve reads per lane.
+ *     in : A (P,N,n,n)  B (P,N,n,m)  c (P,N,n) or NULL (zero)  Q (P,n,n)  R (P,m,m)  Qf (P,n,n)  rho (P,L)   [device]
+ *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m)  D (P,L,N,n)  ABt (P,N,n+m,n): row i < n is column i of A_k, row n + j column j of B_k [device]
+ *     n <= 12 and m <= 4 (ZM_EUNSUPPORTED beyond: there is no lane-per-instance kernel for stage-varying dynamics).
+ * zm_mpc_solve_ltv_f64: instance i solves problem problem[i] in [0, P).  The backward stage is p = p' + z_x + g_x + D_k,
+ *     Qu = z_u + g_u + B_k' p, kf = Suu_k^-1 Qu, p' = A_k' p - K_k' Qu; the forward stage u = -K_k x - kf, x+ = A_k x + B_k u + c_k; the
+ *     free response of the infeasibility certificate carries the offsets.  The dual tolerance scales with max(rho |lam|_inf, |g|_inf) (c
+ *     sits in the constraints, not in the cost); the cycle guard of the adaptive penalty is on when g != 0 or the problem's c != 0.
+ *     With constant A_k, B_k and c = 0 the iterates are those of zm_mpc_solve_tracking_f64 on the same data, move for move.
+ *     in : the arguments of zm_mpc_solve_tracking_f64 in its per-problem form (rho_p and problem are required), with A, B per stage
+ *          as above, and c (P,N,n) (a zero array where zm_mpc_setup_ltv_f64 was given NULL), D and ABt from that call   [device]
+ *          xRef, uRef: either may be NULL (zero).  workspace: 5 * batch * N * (n + m) doubles, as zm_mpc_solve_tracking_f64.
+ *     out: as zm_mpc_solve_tracking_f64.
+ *     16 lanes per instance only: ZM_EUNSUPPORTED for (n, m) outside the compiled shapes with n + m <= 16 and for horizons whose
+ *     iterates do not fit LDS (4 * N * 64 * 8 B > 150 KiB, i.e. N > 75); ZOPT_AMD_MPC_PATH does not apply.  Reads the index map back
+ *     to the host to check it, like zm_mpc_solve_batched_f64. */
+int zm_mpc_setup_ltv_f64(const double* A, const double* B, const double* c, const double* Q, const double* R, const double* Qf,
+                         const double* rho, int64_t P, int L, int N, int n, int m, double* K, double* Minv, double* D, double* ABt,
+                         void* stream);
+int zm_mpc_solve_ltv_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Q, const double* R,
+                         const double* Qf, const double* K, const double* Minv, const double* D, int n_levels, int level0,
+                         double rho_step, double alpha, const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub,
+                         const double* x0, const double* xRef, const double* uRef, const double* rho_p, const int32_t* problem,
+                         int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace,
+                         double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,135 @@
+"""GPU tests of mpcUtils.ltvMpc: stage-varying dynamics x+ = A_k x + B_k u + c_k through the ADMM kernels (zm_mpc_setup_ltv_f64,
+zm_mpc_solve_ltv_f64).  Every case is held to the NumPy restatement of the whole solve (tests/mpc_ltv_ref.py: admm_levels_ltv) by the
+suite's rule: same status, iteration count, final level and `ok` flag; x, u, y, lam and the residuals to 1e-9 max(1, |reference|).
+tests/test_mpc_ltv.py checks, without a GPU, that these inputs stay clear of every rounding-sensitive decision."""
+import numpy as np
+import pytest
+
+from tests import mpc_ltv_ref as lr
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def mpc():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from zopt_amd import mpcUtils
+    return mpcUtils
+
+
+def _hold(mpc, name, prob=None, **kw):
+    c, ref = lr.build(name), lr.reference(name)
+    got = lr.run_steps(prob or lr.make_problem(mpc, c), c, ref, **kw)
+    worst = lr.compare(name, ref, got)
+    print(f"{name}: largest deviation {worst:.2e} of its bound")
+    return got
+
+
+@pytest.mark.parametrize("name", lr.GROUPS["shapes"])
+def test_every_compiled_shape(mpc, name):
+    """one shared problem, batch 7 (two waves, an idle group, instance 3 outside its box); every lane-role mask, N = 1 and 2 against the
+    three-stage prefetch"""
+    got = _hold(mpc, name)
+    assert got[0]["status"][3] == "infeasible" and got[0]["iters"][3] == 0
+
+
+@pytest.mark.parametrize("name", lr.GROUPS["embedded"])
+def test_embedded_shapes(mpc, name):
+    got = _hold(mpc, name)
+    c = lr.build(name)
+    assert got[0]["x"].shape[-1] == c.inst[0][0].shape[-1] and got[0]["u"].shape[-1] == c.inst[0][1].shape[-1]
+
+
+@pytest.mark.parametrize("name", lr.GROUPS["per_problem"])
+def test_per_problem_data(mpc, name):
+    """P = (5,): distinct A_k, B_k, c_k, weights and bounds"""
+    _hold(mpc, name)
+
+
+def test_chain_of_solves_and_update(mpc):
+    """(12, 4, 10): cold -> warm -> "shift", then update() with re-perturbed dynamics and a warm solve; the reference is fed its own
+    previous state and the new data.  update() keeps the workspace (the solve after it starts warm) and rebuilds the tables."""
+    c = lr.build("chain")
+    prob = lr.make_problem(mpc, c)
+    seen = []
+
+    def update(**kw):
+        seen.append((prob._ws, len(prob._tables)))
+        prob.update(**kw)
+        assert prob._ws is seen[-1][0] and prob._tables == {}
+    _hold(mpc, "chain", prob=prob, update=update)
+    assert len(seen) == 1 and seen[0][1] == 1 and len(prob._tables) == 1
+
+
+def test_update_takes_device_tensors(mpc):
+    """update() with device tensors gives what it gives with their NumPy copies"""
+    import torch
+    c, ref = lr.build("chain"), lr.reference("chain")
+    prob = lr.make_problem(mpc, c)
+    dev = lambda **kw: prob.update(**{k: torch.as_tensor(v, device="cuda") for k, v in kw.items()})
+    lr.compare("chain (device update)", ref, lr.run_steps(prob, c, ref, update=dev))
+
+
+@pytest.mark.parametrize("name", lr.GROUPS["tracking"])
+def test_tracking(mpc, name):
+    """references that leave the box, on top of stage-varying dynamics with offsets"""
+    _hold(mpc, name, prob=_quad_problem(mpc, lr.build(name)) if name == "trackquad" else None)
+
+
+@pytest.mark.parametrize("n,m,N", [(4, 2, 6), (12, 4, 7)])
+def test_constant_dynamics_are_lqrMpc(mpc, n, m, N):
+    """the anchor: constant A_k, B_k and c = 0 against lqrMpc with the same per-problem data -- same status, iterations and level,
+    trajectories to 1e-9"""
+    from tests import mpc_iterates_cases as ic
+    from tests.test_mpc_batched import _family
+    A, B, Q, R, xl, xu, ul, uu = _family((5,), n, m, seed=10 * n + m)
+    x0 = 0.5 * xu * np.random.default_rng(3).uniform(-1, 1, (5, n))
+    kw = dict(eps_abs=1e-6, eps_rel=1e-6, max_iter=3000)
+    lti = mpc.lqrMpc(A, B, Q, R, N, xl, xu, ul, uu)
+    _, t0, s0 = lti.solve(x0, **kw)
+    it0, lv0 = lti.last_iterations.copy(), ic.read_state(lti, 5, N)[2]
+    ltv = mpc.ltvMpc(np.repeat(A[:, None], N, axis=1), np.repeat(B[:, None], N, axis=1), Q, R, N, xl, xu, ul, uu)
+    _, t1, s1 = ltv.solve(x0, **kw)
+    assert list(s1) == list(s0) and "optimal" in set(s0)
+    assert np.array_equal(ltv.last_iterations, it0) and np.array_equal(ic.read_state(ltv, 5, N)[2], lv0)
+    scale = 1e-9 * max(1.0, np.max(np.abs(t0.xTraj)), np.max(np.abs(t0.uTraj)))
+    assert np.max(np.abs(t1.xTraj - t0.xTraj)) <= scale and np.max(np.abs(t1.uTraj - t0.uTraj)) <= scale
+
+
+def test_infeasible_through_the_offset(mpc):
+    """c_k = (1.5, 0) pushes x_1 out of the box whatever u does: the certificate, whose free response carries the offsets, says so at a
+    check; the same problem with c = 0 is solved"""
+    got = _hold(mpc, "infeasible")
+    assert list(got[0]["status"]) == ["infeasible", "optimal"] and got[0]["iters"][0] % 8 == 0
+
+
+def _quad_problem(mpc, c):
+    """the case's problem as a user builds it: the device expansion of the registered model about the case's trajectories"""
+    from zopt_amd import models, pytrees
+    xT, uT = c.traj
+    dyn = pytrees.AffineDynamics.from_trajectory(models.QuadcopterEuler(lr.QUAD_DT), pytrees.Trajectory(xT, uT))
+    Q, R, Qf, xl, xu, ul, uu = c.inst[0][3:]
+    return mpc.ltvMpc.fromExpansion(dyn, pytrees.Trajectory(xT, uT), Q, R, xl, xu, ul, uu, Qf=Qf)
+
+
+def test_quadcopter_about_trajectories(mpc):
+    """fromExpansion of AffineDynamics.from_trajectory(models.QuadcopterEuler(dt), traj): N = 30, 5 instances about 5 distinct
+    non-equilibrium trajectories, the cost about trim.  Held to the reference (whose data is the oracle's expansion of the same model);
+    the plan satisfies x+ = A_k x + B_k u + c_k to 1e-10 and the bounds to the primal tolerance of the solve."""
+    c = lr.build("quad")
+    prob = _quad_problem(mpc, c)
+    assert prob.N == 30 and prob.P == (5,)
+    for b, (A, B, ck, *_) in enumerate(c.inst):   # the device expansion is the oracle's
+        assert np.max(np.abs(prob.A[b] - A)) <= 1e-12 and np.max(np.abs(prob.B[b] - B)) <= 1e-12 and np.max(np.abs(prob.c[b] - ck)) <= 1e-11
+    got = _hold(mpc, "quad", prob=prob)[0]
+    x, u = got["x"], got["u"]
+    assert set(got["status"]) == {"optimal"}
+    dyn = np.einsum("bkij,bkj->bki", prob.A, x[:, :-1]) + np.einsum("bkij,bkj->bki", prob.B, u) + prob.c
+    assert np.max(np.abs(x[:, 1:] - dyn)) <= 1e-10
+    eps = c.steps[0]["kw"]["eps_abs"]
+    tol = eps + eps * max(np.max(np.abs(x)), np.max(np.abs(u))) + 1e-9
+    xl, xu, ul, uu = c.inst[0][6:]
+    assert np.max(np.maximum(x - xu, 0)) <= tol and np.max(np.maximum(xl - x, 0)) <= tol
+    assert np.max(np.maximum(u - uu, 0)) <= tol and np.max(np.maximum(ul - u, 0)) <= tol

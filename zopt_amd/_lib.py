@@ -93,6 +93,15 @@ SYMBOLS = {
                                [_c_dp] * 7 + [ctypes.c_int] * 2 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] +
                                [ctypes.c_double] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] + [_c_dp] * 8 +
                                [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (A (P,N,n,n), B (P,N,n,m), c (P,N,n) | NULL, Q, R, Qf, rho (P,L), P, L, N, n, m, K, Minv, D, ABt, stream)
+    "zm_mpc_setup_ltv_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
+                             [_c_dp] * 4 + [ctypes.c_void_p]),
+    # (A, B, c, ABt, Q, R, Qf, K, Minv, D, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub, x0, xRef | NULL, uRef | NULL,
+    #  rho_p (P), problem (batch), P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start, ws, xTraj, uTraj, status, iters, resid, batch,
+    #  N, n, m, stream)
+    "zm_mpc_solve_ltv_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                             [_c_dp] * 9 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
+                             [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "zm_mpc_solve_warm_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_double] * 4 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                               [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, active, shared_hessian, l, L, batch, T, n, m, stream)

@@ -87,6 +87,99 @@ __global__ __launch_bounds__(256) void mpc_setup_batched_kernel(const double* __
 #include "mpc_setup_body.h"
 }
 
+// Stage-varying dynamics (zm_mpc_setup_ltv_f64): the recursion of mpc_setup_body.h with the stage's own A_k, B_k, reloaded into LDS at
+// the top of every stage; workgroup b = p * L + l as in mpc_setup_batched_kernel.  The same products in the same order (the body is
+// restated here, not included: its A and B are loaded once, before its stage loop), so constant A_k, B_k give that kernel's tables bit
+// for bit.  Two more outputs: D_k = P_{k+1} c_k (P,L,N,n), formed from the value matrix before the stage updates it -- the offset's share
+// of the costate in the solve's backward sweep -- and, by the workgroup of level 0 alone (it does not depend on the penalty), ABt
+// (P,N,n+m,n): row i < n is column i of A_k, row n + j column j of B_k, the contiguous form the lanes of mpc_solve_wave_ltv_kernel read
+// their column of [A_k | B_k] in.  c may be nullptr (D = 0).
+template <int SN, int SM>
+__global__ __launch_bounds__(256) void mpc_setup_ltv_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                            const double* __restrict__ c, const double* __restrict__ Q,
+                                                            const double* __restrict__ R, const double* __restrict__ Qf,
+                                                            const double* __restrict__ rho_tab, const int L, const int N, const int n,
+                                                            const int m, double* __restrict__ Kout, double* __restrict__ Minvout,
+                                                            double* __restrict__ Dout, double* __restrict__ ABt) {
+    const long b = blockIdx.x, p = b / L;
+    const bool pack = (b % L) == 0;
+    A += p * N * n * n;
+    B += p * N * n * m;
+    if (c) c += p * N * n;
+    Q += p * n * n;
+    R += p * m * m;
+    Qf += p * n * n;
+    Kout += b * N * m * n;
+    Minvout += b * N * m * m;
+    Dout += b * N * n;
+    ABt += p * N * (n + m) * n;
+    const double rho = rho_tab[b];
+    __shared__ double As[SN * SN], Bs[SN * SM], P[SN * SN], PA[SN * SN], PB[SN * SM], Sux[SM * SN], Suu[SM * SM], Mi[SM * SM], K[SM * SN],
+        T1[SN * SN], T2[SN * SN];
+    const int t = threadIdx.x;
+    for (int e = t; e < n * n; e += blockDim.x) P[e] = 2.0 * Qf[e] + ((e / n == e % n) ? rho : 0.0);  // P_N = 2 Qf + rho I
+    __syncthreads();
+    for (int k = N - 1; k >= 0; --k) {
+        // (As, Bs of the stage above were last read before the barrier that ends it; P holds P_{k+1})
+        for (int e = t; e < n * n; e += blockDim.x) As[e] = A[(long)k * n * n + e];
+        for (int e = t; e < n * m; e += blockDim.x) Bs[e] = B[(long)k * n * m + e];
+        if (t < n) {
+            double s = 0.0;
+            if (c)
+                for (int j = 0; j < n; ++j) s = __builtin_fma(P[t * n + j], c[(long)k * n + j], s);
+            Dout[(long)k * n + t] = s;
+        }
+        __syncthreads();
+        if (pack)
+            for (int e = t; e < (n + m) * n; e += blockDim.x) {
+                const int i = e / n, l = e % n;
+                ABt[(long)k * (n + m) * n + e] = i < n ? As[l * n + i] : Bs[l * m + (i - n)];
+            }
+        mm_nn(PA, P, As, n, n, n);
+        mm_nn(PB, P, Bs, n, n, m);
+        mm_tn(Sux, Bs, PA, n, m, n);  // B_k^T P A_k
+        mm_tn(Suu, Bs, PB, n, m, m);  // B_k^T P B_k
+        if (t < m * m) Suu[t] += 2.0 * R[t] + ((t / m == t % m) ? rho : 0.0);
+        __syncthreads();
+        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= 4), as in mpc_setup_body.h
+            double a[SM][2 * SM];
+            for (int i = 0; i < m; ++i)
+                for (int j = 0; j < m; ++j) {
+                    a[i][j] = Suu[i * m + j];
+                    a[i][m + j] = (i == j) ? 1.0 : 0.0;
+                }
+            for (int cc = 0; cc < m; ++cc) {
+                int pv = cc;
+                for (int i = cc + 1; i < m; ++i)
+                    if (__builtin_fabs(a[i][cc]) > __builtin_fabs(a[pv][cc])) pv = i;
+                for (int j = 0; j < 2 * m; ++j) {
+                    const double tmp = a[cc][j];
+                    a[cc][j] = a[pv][j];
+                    a[pv][j] = tmp;
+                }
+                const double inv = 1.0 / a[cc][cc];
+                for (int j = 0; j < 2 * m; ++j) a[cc][j] *= inv;
+                for (int i = 0; i < m; ++i)
+                    if (i != cc) {
+                        const double f = a[i][cc];
+                        for (int j = 0; j < 2 * m; ++j) a[i][j] = __builtin_fma(-f, a[cc][j], a[i][j]);
+                    }
+            }
+            for (int i = 0; i < m; ++i)
+                for (int j = 0; j < m; ++j) Mi[i * m + j] = a[i][m + j];
+        }
+        __syncthreads();
+        mm_nn(K, Mi, Sux, m, m, n);     // K_k = Suu^-1 B_k^T P A_k
+        mm_tn(T1, As, PA, n, n, n);     // A_k^T P A_k
+        mm_tn(T2, Sux, K, m, n, n);     // Sux^T K
+        for (int e = t; e < n * n; e += blockDim.x)
+            P[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+        for (int e = t; e < m * n; e += blockDim.x) Kout[(long)k * m * n + e] = K[e];
+        for (int e = t; e < m * m; e += blockDim.x) Minvout[(long)k * m * m + e] = Mi[e];
+        __syncthreads();
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // solve: one lane per instance
 // ----------------------------------------------------------------------------------------------------------------
@@ -588,6 +681,60 @@ extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const
     return zm::mpc_solve("zm_mpc_solve_tracking_f64", false, true, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb,
                          x_ub, u_lb, u_ub, x0, xRef, uRef, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start,
                          workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stage-varying dynamics: x+ = A_k x + B_k u + c_k per problem (16 lanes per instance only)
+// ---------------------------------------------------------------------------------------------------------------------
+
+extern "C" int zm_mpc_setup_ltv_f64(const double* A, const double* B, const double* c, const double* Q, const double* R, const double* Qf,
+                                    const double* rho, int64_t P, int L, int N, int n, int m, double* K, double* Minv, double* D,
+                                    double* ABt, void* stream) {
+    if (P == 0) return ZM_OK;   /* no problems: nothing to do (pointers of empty arrays may be NULL) */
+    if (!A || !B || !Q || !R || !Qf || !rho || !K || !Minv || !D || !ABt) return zm::set_error(ZM_EINVAL, "zm_mpc_setup_ltv_f64: null pointer");
+    if (P < 0 || L < 1 || N < 1 || n < 1 || m < 1 || P * L > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "zm_mpc_setup_ltv_f64: bad size");
+    if (n > zm::SN || m > zm::SM)
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_mpc_setup_ltv_f64: (n=%d, m=%d) not covered (n <= 12, m <= 4)", n, m);
+    hipLaunchKernelGGL((zm::mpc_setup_ltv_kernel<zm::SN, zm::SM>), dim3((unsigned)(P * L)), dim3(256), 0, (hipStream_t)stream, A, B, c, Q, R,
+                       Qf, rho, L, N, n, m, K, Minv, D, ABt);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_mpc_solve_ltv_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Q, const double* R,
+                                    const double* Qf, const double* K, const double* Minv, const double* D, int n_levels, int level0,
+                                    double rho_step, double alpha, const double* x_lb, const double* x_ub, const double* u_lb,
+                                    const double* u_ub, const double* x0, const double* xRef, const double* uRef, const double* rho_p,
+                                    const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter,
+                                    int warm_start, double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters,
+                                    double* resid, int64_t batch, int N, int n, int m, void* stream) {
+    const char* fn = "zm_mpc_solve_ltv_f64";
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    int rc = zm::mpc_check_args(fn, true, true, xTraj && uTraj && status && c && D && ABt, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step,
+                                alpha, x_lb, x_ub, u_lb, u_ub, x0, 0.0, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
+    if (rc != ZM_OK) return rc;
+    // the one kernel there is: refuse what it does not take before anything is launched
+    if (zm::for_mpc_shape(n, m, [](auto ns, auto mc) { return ns.value + mc.value <= 16 ? ZM_OK : ZM_EUNSUPPORTED; }) != ZM_OK)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
+    if ((size_t)4 * N * 64 * sizeof(double) > 150 * 1024)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: N=%d beyond the horizons whose iterates fit LDS (N <= 75)", fn, N);
+    hipStream_t st = (hipStream_t)stream;
+    rc = zm::mpc_check_map(fn, problem, P, batch, st);
+    if (rc != ZM_OK) return rc;
+    const long W = (long)n + m;
+    // the fifth block of the workspace holds the linear term g (batch, N, n + m): a zero block without a reference
+    double* gbuf = workspace + 4L * batch * N * W;
+    const long blocks = ((long)batch * N * W + 255) / 256;
+    hipLaunchKernelGGL(zm::mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
+                       (long)batch, N, n, m, gbuf);
+    ZM_HIP_CHECK(hipGetLastError());
+    const zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    const zm::MpcArgs g{x0, 1.0, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace, xTraj, uTraj,
+                        (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
+    rc = zm::mpc_wave_ltv_dispatch(t, g, zm::MpcProb{(const int*)problem, rho_p}, zm::MpcTrack{gbuf}, zm::MpcLtv{c, D, ABt}, n, m, st);
+    if (rc == ZM_EUNSUPPORTED)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
+    return rc;
 }
 
 // the receding-horizon loop as one call: see mpc_closed_loop

@@ -47,6 +47,12 @@ struct MpcTrack {
     const double* g;
 };
 
+// stage-varying dynamics (zm_mpc_solve_ltv_f64): with A (P,N,n,n) and B (P,N,n,m) in MpcTabs, the offsets c (P,N,n), their share of the costate D (P,n_levels,N,n) and ABt (P,N,n+m,n), the columns of [A_k | B_k] as contiguous rows, the last two
+// written by mpc_setup_ltv_kernel (mpc.hip)
+struct MpcLtv {
+    const double *c, *D, *ABt;
+};
+
 // closed-loop run (zm_mpc_closed_loop_f64): `steps` receding-horizon solves in a row, step-major arrays -- step s of an array is one
 // batch-sized slab further on, so a step's solve sees the layouts of a single solve through offset pointers.
 struct MpcLoop {
@@ -87,5 +93,9 @@ int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, con
 // mpc_wave.hip: the whole closed-loop run of a regulator as ONE launch of the same kernels with the step loop inside.  `g` carries the
 // options and the workspace of every step (its x0, outputs and warm are set per step from `lp`).  ZM_EUNSUPPORTED as above.
 int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, int n, int m, hipStream_t st);
+// mpc_wave.hip: stage-varying dynamics, always per-problem and with a linear term (mpc_solve_wave_ltv.h).  ZM_EUNSUPPORTED as above; there
+// is no other kernel to take what does not fit.
+int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
+                          hipStream_t st);
 
 }  // namespace zm

@@ -261,6 +261,9 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
 #include "mpc_solve_wave_body.h"
 }
 
+// stage-varying dynamics (zm_mpc_solve_ltv_f64): mpc_solve_wave_ltv_kernel, in this translation unit with the kernels it borrows from
+#include "mpc_solve_wave_ltv.h"
+
 // f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16; ZM_EUNSUPPORTED for any other
 template <typename F>
 static int for_mpc_shape(int n, int m, F f) {
@@ -294,6 +297,24 @@ static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, co
 
 int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
     return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave<ns.value, mc.value>(t, g, pb, trk, st); });
+}
+
+// the stage-varying kernel: grid and LDS of launch_wave; nothing else takes a horizon that does not fit
+template <int NS, int MC>
+static int launch_wave_ltv(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, hipStream_t st) {
+    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
+    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;
+    const auto kernel = mpc_solve_wave_ltv_kernel<NS, MC>;
+    ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub,
+                       g, pb, trk, lv);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
+                          hipStream_t st) {
+    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave_ltv<ns.value, mc.value>(t, g, pb, trk, lv, st); });
 }
 
 // the closed-loop kernel: grid and LDS of launch_wave

@@ -3,6 +3,7 @@
 Same constructor and ``solve`` signature as the reference (mpcUtils.py:14-26, 61-81).  New: ``x0`` may carry leading
 batch axes -- every initial state is an independent QP instance solved by one GPU lane; `solve` takes references to track (keywords
 xRef, uRef); `simulate` runs the whole receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) on the device in one call.
+`ltvMpc` (extension) is the same QP with stage-varying dynamics x+ = A_k x + B_k u + c_k, a linearisation about a trajectory.
 The plotting / animation helpers
 of the reference module (mpcUtils.py:84-202) are presentation code and not part of this package.
 """
@@ -84,6 +85,8 @@ class lqrMpc():
     # tabulated levels): a coverage path, an order of magnitude slower per instance than the (12, 4) kernels
     _COMPILED = ((24, 8), (12, 4), (8, 4), (4, 2), (4, 1), (2, 2), (2, 1), (1, 1))
 
+    _LTV = False                     # ltvMpc (below) shares `solve` and overrides this
+
     N_LEVELS, RHO_STEP = 7, 5.0      # adaptive penalty: rho * 5^(l - 3), l = 0..6  (OSQP changes rho only by factors >= 5)
 
     def _device_problem_batched(self, rho, adaptive):
@@ -146,7 +149,7 @@ class lqrMpc():
             rho = float(rho)
         else:   # a scalar or an array that broadcasts to the problem shape
             try:
-                rho = np.array(np.broadcast_to(_host_f64(rho), self.P))   # (a writable copy: torch refuses read-only views)
+                rho = np.array(np.broadcast_to(_host_f64(rho).reshape(np.shape(rho)), self.P))   # (a writable copy; 0-d stays 0-d)
             except ValueError:
                 raise ValueError(f"rho of shape {np.shape(rho)} does not broadcast to the problem shape {self.P}") from None
             if not np.all(rho > 0.0):
@@ -200,6 +203,7 @@ class lqrMpc():
                 raise ValueError("a Trajectory given as xRef carries its own uTraj: pass it alone (uRef=None)")
             xRef, uRef = xRef.xTraj, xRef.uTraj
         tracking = xRef is not None or uRef is not None
+        linear = tracking or self._LTV   # the workspace has a fifth block for the linear term of the cost
         N, n, m = self.N, self.n, self.m
 
         # 1. shapes: x0 and the references broadcast (with the problem shape) to the batch shape `lead`
@@ -242,7 +246,8 @@ class lqrMpc():
             d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
             drho, Pn, rho_key = None, 0, rho
         else:
-            d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
+            d, tabs = self._device_problem_batched(rho, adaptive)
+            K, Mi, n_levels, level0, drho = tabs[:5]
             Pn, rho_key = int(np.prod(self.P)), rho.tobytes()
 
         # 4. one row per instance, the padded components zero.  A plain solve runs where x0 is (host data: on the current device), the
@@ -264,10 +269,10 @@ class lqrMpc():
 
         # 5. workspace (y, lam, kf, rv; tracking: a fifth block for the linear term of the cost) and the warm start from it.  A plain solve
         # is keyed on the number of instances, the others on the batch shape, tracking as a kind of its own.
-        key = (("tracking", lead) if tracking else lead if self.P is not None else Bn, str(dev), rho_key, adaptive)
+        key = (("tracking", lead) if linear else lead if self.P is not None else Bn, str(dev), rho_key, adaptive)
         warm = warm and self._ws is not None and self._ws[0] == key
         if not warm:
-            self._ws = (key, torch.empty((5 if tracking else 4) * Bn * N * (n + m), dtype=torch.float64, device=dev))
+            self._ws = (key, torch.empty((5 if linear else 4) * Bn * N * (n + m), dtype=torch.float64, device=dev))
         ws = self._ws[1]
 
         # 6. outputs
@@ -284,7 +289,11 @@ class lqrMpc():
                   dx0.data_ptr())
         out = (eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
                st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
-        if tracking:
+        if self._LTV:   # (ltvMpc: stage-varying dynamics, always per-problem, a reference or none)
+            D, ABt = tabs[6:8]
+            rc = _lib.lib().zm_mpc_solve_ltv_f64(p("A"), p("B"), p("c"), ABt.data_ptr(), p("Q"), p("R"), p("Qf"), K.data_ptr(), Mi.data_ptr(),
+                                                  D.data_ptr(), *common[2:], ptr(dxr), ptr(dur), drho.data_ptr(), prob.data_ptr(), Pn, *out)
+        elif tracking:
             rc = _lib.lib().zm_mpc_solve_tracking_f64(p("A"), p("B"), p("Q"), p("R"), p("Qf"), *common, ptr(dxr), ptr(dur),
                                                        rho if self.P is None else 0.0, ptr(drho), ptr(prob), Pn, *out)
         elif self.P is not None:
@@ -432,6 +441,166 @@ class lqrMpc():
             pred = Trajectory(view(xp, (S, N + 1, n), self._n_user), view(up, (S, N, m), self._m_user))
         return MpcClosedLoop(view(xs, (S + 1, n), self._n_user), view(us, (S, m), self._m_user), status,
                              view(its, (S,), None), pred)
+
+
+class ltvMpc(lqrMpc):
+    """Box-constrained MPC with stage-varying affine dynamics (extension),
+
+        x_{k+1} = A_k x_k + B_k u_k + c_k,   k = 0 .. N-1,
+
+    under lqrMpc's cost, bounds and ADMM: the QP that linearising a model about a TRAJECTORY gives (real-time-iteration nonlinear MPC,
+    gain-scheduled horizons, periodic systems).  `solve` is lqrMpc's, with its options, return values, status strings, warm and shifted
+    starts and tracking keywords; the kernels read their dynamics per stage and carry the offset (zm_mpc_setup_ltv_f64,
+    zm_mpc_solve_ltv_f64).  Only the 16-lanes-per-instance kernels exist for this form: n <= 12, m <= 4 (smaller shapes are embedded per
+    stage, as lqrMpc embeds them) and horizons whose iterates fit LDS, N <= 75; ZOPT_AMD_MPC_PATH does not apply.
+    """
+
+    _LTV = True
+    _COMPILED = tuple(s for s in lqrMpc._COMPILED if s[0] + s[1] <= 16)
+    N_MAX = 75   # 4 instances x N stages x 64 doubles of LDS <= 150 KiB
+
+    def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None):
+        """
+        Arguments
+        ---------
+            A : (..., N, n, n)   B : (..., N, n, m)   c : (..., N, n) or None (zeros) -- the dynamics of every stage
+            Q, R, Qf, x_lb, x_ub, u_lb, u_ub, N : as lqrMpc takes them, leading axes included
+        The leading axes broadcast to the problem shape `P`; () is one problem.  Nothing here touches a GPU.
+        """
+        if Qf is None:
+            Qf = Q
+        self.N = int(N)
+        data = {k: _host_f64(X) for k, X in zip(_ARRAYS, (A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub))}
+        data["c"] = None if c is None else _host_f64(c)
+        n, m, P = _ltv_problem_shape(data, self.N)
+        self.P = P
+        _check_psd(data, P)
+        if n > 12 or m > 4:
+            raise ValueError(f"ltvMpc: (n={n}, m={m}) outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")
+        if self.N > self.N_MAX:
+            raise ValueError(f"ltvMpc: N={self.N} beyond the horizons whose iterates fit LDS (N <= {self.N_MAX})")
+        self._dev = None
+        self._tables = {}
+        self._ws = None
+        self.rho = _penalty(data["Q"], data["R"], P)
+        self._n_user, self._m_user = n, m
+        self.n, self.m = min(((ns, mc) for (ns, mc) in self._COMPILED if ns >= n and mc >= m), key=lambda t: (t[0] * t[1], t[0]))
+        # per stage what _embed does per problem: A_k, B_k padded with zero blocks, c_k with zeros, the extra weights 1, no extra bound
+        stage = _embed({k: data[k] for k in ("A", "B")}, P + (self.N,), self.n, self.m)
+        fixed = _embed({k: data[k] for k in _ARRAYS[2:]}, P, self.n, self.m)
+        cs = np.zeros(P + (self.N, self.n))
+        if data["c"] is not None:
+            cs[..., :n] = data["c"]
+        for k, X in {**stage, **fixed, "c": cs}.items():
+            setattr(self, k, X)
+
+    @classmethod
+    def fromExpansion(cls, dyn, traj, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None):
+        """The problem of an `AffineDynamics` (f, f_x, f_u) expanded about `traj` (AffineDynamics.from_trajectory(model, traj)): in absolute
+        coordinates x+ ~ f + f_x (x - xbar_k) + f_u (u - ubar_k), i.e. A_k = f_x, B_k = f_u, c_k = f - f_x xbar_k - f_u ubar_k.  N is the
+        number of stages of the expansion; bounds and references are in absolute coordinates."""
+        f, f_x, f_u = (_host_f64(X) for X in tuple.__iter__(dyn))
+        xbar, ubar = _host_f64(tuple.__getitem__(traj, 0))[..., :-1, :], _host_f64(tuple.__getitem__(traj, 1))
+        c = f - np.einsum("...ij,...j->...i", f_x, xbar) - np.einsum("...ij,...j->...i", f_u, ubar)
+        return cls(f_x, f_u, Q, R, f.shape[-2], x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=c)
+
+    def update(self, A=None, B=None, c=None):
+        """New dynamics data of the same shapes (the next linearisation of a real-time-iteration loop).  NumPy arrays or torch tensors; a
+        device tensor is copied device to device, without a host copy (the attributes A, B, c then keep the data they had).  The tables
+        are rebuilt by one setup launch before the next solve; the warm-start workspace survives."""
+        n, m, N = self._n_user, self._m_user, self.N
+        new = {}
+        for name, X, tail in (("A", A, (N, n, n)), ("B", B, (N, n, m)), ("c", c, (N, n))):
+            if X is None:
+                continue
+            shp = tuple(X.shape) if hasattr(X, "shape") else np.shape(X)
+            ok = len(shp) >= len(tail) and shp[len(shp) - len(tail):] == tail
+            if ok:
+                try:
+                    ok = np.broadcast_shapes(shp[:len(shp) - len(tail)], self.P) == self.P
+                except ValueError:
+                    ok = False
+            if not ok:
+                raise ValueError(f"ltvMpc.update: {name} has shape {shp}, expected {('...',) + tail} with leading axes that broadcast "
+                                 f"to the problem shape {self.P} (N = {N})")
+            new[name] = (X, tail)
+        if not new:
+            return
+        arr.require_gpu()
+        d = self._device_data()
+        Pn = int(np.prod(self.P))
+        for name, (X, tail) in new.items():
+            t = arr.to_device(X, torch.float64, d["A"].device).expand(self.P + tail).reshape((Pn,) + tail)
+            d[name][(slice(None), slice(None)) + tuple(slice(0, w) for w in tail[1:])].copy_(t)   # (the padded part stays as it is)
+            if not (arr.is_torch(X) and X.is_cuda):
+                getattr(self, name)[(Ellipsis,) + tuple(slice(0, w) for w in tail[1:])] = _host_f64(X)
+        self._tables = {}
+
+    def simulate(self, *args, **kwargs):
+        raise NotImplementedError("ltvMpc.simulate: a moving window needs new tables at every step; loop over update() and solve()")
+
+    def _device_problem(self, rho, adaptive):   # (a single problem is the per-problem form with P = ())
+        raise NotImplementedError
+
+    def _device_data(self):
+        if self._dev is None:
+            Pn = int(np.prod(self.P))
+            self._dev = {k: arr.to_device(getattr(self, k).reshape((Pn,) + getattr(self, k).shape[len(self.P):]), torch.float64)
+                         for k in _ARRAYS + ("c",)}
+        return self._dev
+
+    def _device_problem_batched(self, rho, adaptive):
+        """Device copies of the data and the tables of every (problem, penalty level): ONE setup launch.  The tuple lqrMpc keeps, then
+        D (P, L, N, n) and ABt (P, N, n + m, n)."""
+        arr.require_gpu()
+        d = self._device_data()
+        key = (rho.tobytes(), bool(adaptive))
+        if key not in self._tables:
+            Pn = int(np.prod(self.P))
+            nl = self.N_LEVELS if adaptive else 1
+            l0 = nl // 2
+            dev = d["A"].device
+            fac = np.array([self.RHO_STEP ** (l - l0) for l in range(nl)])
+            rtab = arr.to_device(rho.reshape(Pn, 1) * fac[None, :], torch.float64, dev)
+            E = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+            K, Mi, D = E(Pn, nl, self.N, self.m, self.n), E(Pn, nl, self.N, self.m, self.m), E(Pn, nl, self.N, self.n)
+            ABt = E(Pn, self.N, self.n + self.m, self.n)
+            rc = _lib.lib().zm_mpc_setup_ltv_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["c"].data_ptr(), d["Q"].data_ptr(),
+                                                 d["R"].data_ptr(), d["Qf"].data_ptr(), rtab.data_ptr(), Pn, nl, self.N, self.n, self.m,
+                                                 K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(),
+                                                 ctypes.c_void_p(arr.stream_ptr(K)))
+            _lib.check(rc, "ltvMpc setup")
+            self._tables[key] = (K, Mi, nl, l0, arr.to_device(rho.reshape(Pn), torch.float64, dev), rtab, D, ABt)
+        return d, self._tables[key]
+
+
+def _ltv_problem_shape(data, N):
+    """(n, m, P) of ltvMpc's arrays: A (..., N, n, n), B (..., N, n, m), c (..., N, n) | None, the rest as lqrMpc's."""
+    if data["B"].ndim < 3:
+        raise ValueError("ltvMpc: B must have shape (..., N, n, m)")
+    n, m = data["B"].shape[-2:]
+    if N < 1:
+        raise ValueError(f"ltvMpc: N = {N}, expected at least one stage")
+    tails = {"A": (N, n, n), "B": (N, n, m), "c": (N, n), "Q": (n, n), "R": (m, m), "Qf": (n, n), "x_lb": (n,), "x_ub": (n,),
+             "u_lb": (m,), "u_ub": (m,)}
+    lead = {}
+    for k, t in tails.items():
+        X = data[k]
+        if X is None:
+            continue
+        staged = k in ("A", "B", "c")   # (the stage axis is checked on its own: its message names N)
+        if X.ndim < len(t) or X.shape[X.ndim - len(t) + staged:] != t[staged:]:
+            raise ValueError(f"inconsistent ltvMpc problem shapes: {k} has shape {X.shape}, expected (..., {', '.join(map(str, t))})")
+        if staged and X.shape[X.ndim - len(t)] != N:
+            raise ValueError(f"inconsistent ltvMpc problem shapes: {k} of shape {X.shape} has {X.shape[X.ndim - len(t)]} stages, "
+                             f"expected N = {N}")
+        lead[k] = X.shape[:X.ndim - len(t)]
+    try:
+        P = np.broadcast_shapes(*lead.values())
+    except ValueError:
+        raise ValueError("inconsistent ltvMpc problem shapes: the leading (problem) axes do not broadcast: "
+                         + ", ".join(f"{k} {data[k].shape}" for k in lead)) from None
+    return n, m, tuple(int(v) for v in P)
 
 
 
