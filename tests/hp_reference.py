@@ -1,4 +1,5 @@
-"""High-precision references for the Riccati tests: the finite-horizon recursion in long double and a Newton-refined DARE solution.
+"""High-precision references for the Riccati tests: the finite-horizon recursion in long double and Newton-refined DARE / CARE
+solutions (`care_refined` is `dare_refined`'s continuous-time counterpart: Newton-Kleinman steps on SciPy's solve_continuous_are).
 
 The fp64 oracle (oracle/zopt_oracle.py) carries its own rounding error, which on hard inputs is of the same order as a kernel's.
 These references sit well below both, so a test can tell the kernel's error from the oracle's:
@@ -88,3 +89,52 @@ def dare_refined(A, B, Q, R, rtol=1e-17, max_newton=4):
     L, Acl, Res = dare_gain_residual(A, B, Q, R, P)
     rho_cl = float(np.max(np.abs(np.linalg.eigvals(Acl.astype(np.float64)))))
     return L, P, rho_cl, np.max(np.abs(Res)) / np.max(np.abs(P))
+
+
+def care_gain_residual(A, B, Q, R, P):
+    """Long double: the gain K = R^-1 B^T P of a value matrix P, the closed loop A - B K and the CARE residual
+    A^T P + P A - K^T R K + Q.  The quadratic term is formed through K: under cheap control (R = r I, r -> 0) B^T P is O(sqrt r) and
+    K^T R K is O(1), whereas P (B R^-1 B^T) P multiplies by G ~ 1/r first and cancels eight digits in fp64."""
+    A, B, Q, R, P = (np.asarray(x, dtype=LD) for x in (A, B, Q, R, P))
+    K = solve_ld(R, _T(B) @ P)
+    Acl = A - B @ K
+    Res = _T(A) @ P + P @ A - (_T(K) @ R) @ K + Q
+    return K, Acl, Res
+
+
+def care_refined(A, B, Q, R, rtol=1e-17, max_newton=6):
+    """Stabilising CARE solution of ONE design to long-double accuracy: SciPy's solve_continuous_are, then Newton-Kleinman steps
+    P <- P + E with Acl^T E + E Acl = -Res(P) (fp64 Lyapunov solve of the long-double residual) until max|E| <= rtol * max|P|
+    (at most `max_newton`).
+
+    Returns (K, P, abscissa_cl, res): the gain and value (long double), the closed loop's spectral abscissa max Re eig(A - B K) and
+    the final residual max|Res| / max|P| (long double arithmetic)."""
+    A, B, Q, R = (np.asarray(x, dtype=np.float64) for x in (A, B, Q, R))
+    P = spl.solve_continuous_are(A, B, Q, R).astype(LD)
+    P = (P + _T(P)) / 2
+    for _ in range(max_newton):
+        _, Acl, Res = care_gain_residual(A, B, Q, R, P)
+        Res = (Res + _T(Res)) / 2
+        E = spl.solve_continuous_lyapunov(Acl.astype(np.float64).T, -Res.astype(np.float64))
+        P = P + ((E + E.T) / 2).astype(LD)
+        if np.max(np.abs(E)) <= rtol * float(np.max(np.abs(P))):
+            break
+    K, Acl, Res = care_gain_residual(A, B, Q, R, P)
+    abscissa_cl = float(np.max(np.linalg.eigvals(Acl.astype(np.float64)).real))
+    return K, P, abscissa_cl, np.max(np.abs(Res)) / np.max(np.abs(P))
+
+
+def care_scipy_error(A, B, Q, R, K_ref, P_ref):
+    """SciPy's own error on ONE design against the refined solution, in P and in K = solve(R, B^T P), each relative to max|ref|: the
+    yardstick the hard-spectrum CARE tests scale their bound by (K needs its own: under cheap control it amplifies P's error)."""
+    A, B, Q, R = (np.asarray(x, dtype=np.float64) for x in (A, B, Q, R))
+    P = spl.solve_continuous_are(A, B, Q, R)
+    K = np.linalg.solve(R, B.T @ P)
+    Pr, Kr = np.asarray(P_ref, dtype=np.float64), np.asarray(K_ref, dtype=np.float64)
+    return float(np.max(np.abs(P - Pr)) / np.max(np.abs(Pr))), float(np.max(np.abs(K - Kr)) / np.max(np.abs(Kr)))
+
+
+def care_bounds(scipy_err_P, scipy_err_K, floor=1e-10, factor=100.0):
+    """(bound on P, bound on K), relative to max|ref|, from `care_scipy_error`'s pair: max(floor, factor * SciPy's own error).
+    Reference side only; the CPU pins and the GPU test both take their bound from here."""
+    return max(floor, factor * scipy_err_P), max(floor, factor * scipy_err_K)

@@ -168,3 +168,170 @@ HARD_DARE = {
 def hard_dare(name: str, n: int, m: int, batch: int = 2):
     """The seeded batch of HARD_DARE[name] at (n, m) that both the CPU property tests and the GPU tests use."""
     return HARD_DARE[name](batch, n, m, seed=1000 + 97 * n + m)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Hard-spectrum designs for the continuous-time Riccati equation (care.hip): the counterparts of HARD_DARE.  Each returns
+# (A, B, Q, R) with a leading batch axis and ONE hard feature (tests/test_hp_reference.py asserts it); none has Hamiltonian
+# eigenvalues on the imaginary axis, so the stabilising solution exists and is unique.
+def _abscissa_block(rng, k, alpha):
+    """A random k x k block G / sqrt(k), shifted so that its spectral abscissa max Re(eig) is alpha."""
+    G = rng.standard_normal((k, k)) / np.sqrt(k)
+    return G + (alpha - np.max(np.linalg.eigvals(G).real)) * np.eye(k)
+
+
+def care_slow_unreachable(batch: int, n: int, m: int, seed: int = 0, lam: float = -1e-3):
+    """A stable random block (abscissa -0.5) on states 0..n-2 plus a mode lam on state n-1 that B does not reach; Q = R = I.  The
+    mode stays in the closed loop and its value entry -1 / (2 lam) = 500 dominates P.  lam > 0: no stabilising solution."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = np.zeros((batch, n, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _abscissa_block(rng, n - 1, -0.5)
+        A[i, n - 1, n - 1] = lam
+        B[i, :n - 1] = rng.standard_normal((n - 1, m))
+    return A, B, np.tile(np.eye(n), (batch, 1, 1)), np.tile(np.eye(m), (batch, 1, 1))
+
+
+def care_weakly_detectable(batch: int, n: int, m: int, seed: int = 0, lam: float = 1e-3, q: float = 1e-6):
+    """An unstable mode lam on state n-1, reached by B, weighted by only q in Q: the optimal loop mirrors it to about -lam, so the
+    Hamiltonian has eigenvalues ~1e-3 from the imaginary axis."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = rng.standard_normal((batch, n, m))
+    Q = np.zeros((batch, n, n))
+    R = np.empty((batch, m, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _abscissa_block(rng, n - 1, -0.5)
+        A[i, n - 1, n - 1] = lam
+        Q[i, :n - 1, :n - 1] = _spd(rng, n - 1)
+        Q[i, n - 1, n - 1] = q
+        R[i] = _spd(rng, m)
+    return A, B, Q, R
+
+
+def care_marginally_stabilisable(batch: int, n: int, m: int, seed: int = 0, lam: float = 0.02, b: float = 1e-2):
+    """An unstable mode lam on state n-1 that only input 0 reaches, through B[n-1, 0] = b: stabilising it costs ~ 2 lam / b^2, so its
+    value entry and the gain's column n-1 are large."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = np.empty((batch, n, m))
+    Q = np.empty((batch, n, n))
+    R = np.empty((batch, m, m))
+    for i in range(batch):
+        A[i, :n - 1, :n - 1] = _abscissa_block(rng, n - 1, -0.5)
+        A[i, n - 1, n - 1] = lam
+        B[i, :n - 1] = rng.standard_normal((n - 1, m))
+        B[i, n - 1] = 0.0
+        B[i, n - 1, 0] = b
+        Q[i] = _spd(rng, n)
+        R[i] = _spd(rng, m)
+    return A, B, Q, R
+
+
+def _care_random(batch, n, m, seed, alpha):
+    rng = np.random.default_rng(seed)
+    A = np.stack([_abscissa_block(rng, n, alpha) for _ in range(batch)])
+    B = rng.standard_normal((batch, n, m))
+    Q = np.stack([_spd(rng, n) for _ in range(batch)])
+    R = np.stack([_spd(rng, m) for _ in range(batch)])
+    return A, B, Q, R
+
+
+def care_cheap_control(batch: int, n: int, m: int, seed: int = 0, r: float = 1e-8):
+    """R = r I on an unstable random system (abscissa +0.2): G = B R^-1 B^T ~ 1/r, B^T P = O(sqrt r), K = O(1 / sqrt r)."""
+    A, B, Q, _ = _care_random(batch, n, m, seed, 0.2)
+    return A, B, Q, np.tile(r * np.eye(m), (batch, 1, 1))
+
+
+def care_expensive_control(batch: int, n: int, m: int, seed: int = 0):
+    """R = 1e8 I on an unstable random system (abscissa +0.05): the gain is tiny, the unstable modes are only just mirrored."""
+    A, B, Q, _ = _care_random(batch, n, m, seed, 0.05)
+    return A, B, Q, np.tile(1e8 * np.eye(m), (batch, 1, 1))
+
+
+def care_badly_scaled(batch: int, n: int, m: int, seed: int = 0):
+    """A random system (abscissa +0.05) in coordinates x' = D x, D = diag(logspace(-2, 2, n)): D A D^-1, D B, D^-T Q D^-1, R.  The
+    solution is P' = D^-1 P D^-1, K' = K D^-1: entries over eight decades."""
+    A, B, Q, R = _care_random(batch, n, m, seed, 0.05)
+    d = np.logspace(-2, 2, n)
+    return A * d[:, None] / d[None, :], B * d[:, None], Q / (d[:, None] * d[None, :]), R        # (d_i d_j: Q stays exactly symmetric)
+
+
+def care_stiff(batch: int, n: int, m: int, seed: int = 0):
+    """A symmetric A with eigenvalues -logspace(-3, 3, n) in a random orthogonal basis plus a 1e-3 perturbation: time scales over six
+    decades, so the Cayley shift gamma ~ |A| maps the slow modes to 1 - O(1e-6) and the doubling iteration needs ~20 steps."""
+    rng = np.random.default_rng(seed)
+    A = np.empty((batch, n, n))
+    for i in range(batch):
+        U, _ = np.linalg.qr(rng.standard_normal((n, n)))
+        lam = -np.logspace(-3, 3, n) if n > 1 else np.array([-1.0])
+        A[i] = (U * lam) @ U.T + 1e-3 * rng.standard_normal((n, n))
+    B = rng.standard_normal((batch, n, m))
+    Q = np.stack([_spd(rng, n) for _ in range(batch)])
+    R = np.stack([_spd(rng, m) for _ in range(batch)])
+    return A, B, Q, R
+
+
+def care_integrator_chains(batch: int, n: int, m: int, seed: int = 0):
+    """Nilpotent integrator chains of length 4 (the last one shorter when 4 does not divide n), one input per chain at its end, the
+    couplings drawn from [0.5, 1.5]: every open-loop eigenvalue is 0 and defective.  Inputs beyond the chains are unused (zero
+    columns of B).  More chains than inputs is refused: the single-input 16-chain has |P| ~ 1e35 and no usable reference."""
+    chains = -(-n // 4)
+    if m < chains:
+        raise ValueError(f"integrator_chains needs m >= ceil(n / 4) = {chains} inputs, got {m}")
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    B = np.zeros((batch, n, m))
+    for i in range(batch):
+        for c in range(chains):
+            lo, hi = 4 * c, min(4 * c + 4, n)
+            for j in range(lo, hi - 1):
+                A[i, j, j + 1] = rng.uniform(0.5, 1.5)
+            B[i, hi - 1, c] = rng.uniform(0.5, 1.5)
+    Q = np.stack([_spd(rng, n) for _ in range(batch)])
+    R = np.stack([_spd(rng, m) for _ in range(batch)])
+    return A, B, Q, R
+
+
+def care_light_oscillators(batch: int, n: int, m: int, seed: int = 0, damping: float = 1e-4, q: float = 1e-4):
+    """2 x 2 rotation blocks [[-d, w], [-w, -d]], d = 1e-4, w in [0.5, 3] (a last state -d when n is odd), Q = q * SPD: the
+    Hamiltonian's eigenvalues sit ~1e-2 |w| from the imaginary axis."""
+    rng = np.random.default_rng(seed)
+    A = np.zeros((batch, n, n))
+    for i in range(batch):
+        for j in range(0, n - 1, 2):
+            w = rng.uniform(0.5, 3.0)
+            A[i, j:j + 2, j:j + 2] = [[-damping, w], [-w, -damping]]
+        if n % 2:
+            A[i, n - 1, n - 1] = -damping
+    B = rng.standard_normal((batch, n, m))
+    Q = q * np.stack([_spd(rng, n) for _ in range(batch)])
+    R = np.stack([_spd(rng, m) for _ in range(batch)])
+    return A, B, Q, R
+
+
+def _cheap(r):
+    return lambda batch, n, m, seed=0: care_cheap_control(batch, n, m, seed=seed, r=r)
+
+
+# name -> generator (batch, n, m, seed) of the continuous-time hard-spectrum families above
+HARD_CARE = {
+    "slow_unreachable": care_slow_unreachable,
+    "weakly_detectable": care_weakly_detectable,
+    "marginally_stabilisable": care_marginally_stabilisable,
+    "cheap_control_1e-2": _cheap(1e-2),
+    "cheap_control_1e-4": _cheap(1e-4),
+    "cheap_control_1e-6": _cheap(1e-6),
+    "cheap_control_1e-8": _cheap(1e-8),
+    "expensive_control": care_expensive_control,
+    "badly_scaled": care_badly_scaled,
+    "stiff": care_stiff,
+    "integrator_chains": care_integrator_chains,
+    "light_oscillators": care_light_oscillators,
+}
+
+
+def hard_care(name: str, n: int, m: int, batch: int = 2):
+    """The seeded batch of HARD_CARE[name] at (n, m) that both the CPU property tests and the GPU tests use."""
+    return HARD_CARE[name](batch, n, m, seed=2000 + 97 * n + m)

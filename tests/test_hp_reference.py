@@ -171,3 +171,110 @@ def test_refined_dare_against_40_digit_newton():
     scale = np.max(np.abs(P_mp))
     assert abs(rho - 0.999) <= 1e-12
     assert np.max(np.abs(P - P_mp)) <= 1e-16 * scale
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Continuous time: care_refined and the HARD_CARE generators, at the shapes of tests/test_care_hard_gpu.py
+CARE_SHAPES = [(12, 4), (8, 2), (16, 16), (5, 3), (3, 7), (16, 1)]
+CARE_CASES = [(name, n, m) for name in sorted(problems.HARD_CARE) for n, m in CARE_SHAPES
+              if not (name == "integrator_chains" and (n, m) == (16, 1))]
+
+
+@functools.lru_cache(maxsize=None)
+def _care_refined(name, n, m):
+    A, B, Q, R = problems.hard_care(name, n, m)
+    return (A, B, Q, R), [hp.care_refined(A[i], B[i], Q[i], R[i]) for i in range(A.shape[0])]
+
+
+def test_care_known_answer():
+    """A = B = Q = R = I2: P = K = (1 + sqrt 2) I, closed loop -sqrt 2 I."""
+    I = np.eye(2)
+    K, P, absc, res = hp.care_refined(I, I, I, I)
+    ref = (1 + np.sqrt(np.longdouble(2))) * np.eye(2, dtype=np.longdouble)
+    assert P.dtype == np.longdouble and np.max(np.abs(P - ref)) <= 1e-18 and np.max(np.abs(K - ref)) <= 1e-18
+    assert res <= 1e-18 and abs(absc + np.sqrt(2)) <= 1e-12
+
+
+def test_care_residual_goes_through_the_gain():
+    """cheap control: the residual formed as P G P cancels at the 1e-8 level in fp64, the one formed through K does not"""
+    A, B, Q, R = (x[0] for x in problems.hard_care("cheap_control_1e-8", 8, 2))
+    _, P, _, res = hp.care_refined(A, B, Q, R)
+    Pf = P.astype(np.float64)
+    G = B @ np.linalg.solve(R, B.T)
+    naive = np.max(np.abs(A.T @ Pf + Pf @ A - Pf @ G @ Pf + Q)) / np.max(np.abs(Pf))
+    assert res <= 1e-13 and naive >= 1e-11
+
+
+@pytest.mark.parametrize("name,n,m", CARE_CASES)
+def test_care_refined_residual_on_hard_problems(name, n, m):
+    """Newton-Kleinman refinement brings every design's CARE residual (long double) at least 1000 x below the bound the GPU test
+    applies to that design, max(1e-10, 100 x SciPy's own error); SciPy's error is recorded per design (run with -s)."""
+    (A, B, Q, R), refs = _care_refined(name, n, m)
+    for i, (K, P, absc, res) in enumerate(refs):
+        eP, eK = hp.care_scipy_error(A[i], B[i], Q[i], R[i], K, P)
+        bP, bK = hp.care_bounds(eP, eK)
+        print(f"{name} ({n},{m}) design {i}: residual {float(res):.1e}  SciPy's error P {eP:.1e} K {eK:.1e}  bound P {bP:.1e} K {bK:.1e}")
+        assert bP == max(1e-10, 100 * eP) and bK == max(1e-10, 100 * eK)
+        assert res * 1000 <= min(bP, bK), (i, float(res))
+        assert res <= (1e-13 if name.startswith("cheap_control") else 1e-16), (i, float(res))
+        assert np.all(np.isfinite(K.astype(np.float64))) and absc < 0.0
+        assert np.max(np.abs(P - np.swapaxes(P, -1, -2))) <= 1e-17 * np.max(np.abs(P))
+
+
+@pytest.mark.parametrize("name,n,m", CARE_CASES)
+def test_care_generator_has_its_hard_feature(name, n, m):
+    (A, B, Q, R), refs = _care_refined(name, n, m)
+    assert A.shape == (2, n, n) and B.shape == (2, n, m) and Q.shape == (2, n, n) and R.shape == (2, m, m)
+    assert not np.array_equal(A[0], A[1]) or not np.array_equal(B[0], B[1])
+    for i, (K, P, absc, _) in enumerate(refs):
+        a, b, q, r = A[i], B[i], Q[i], R[i]
+        Kf, Pf = K.astype(np.float64), P.astype(np.float64)
+        assert np.all(np.linalg.eigvalsh(r) > 0) and np.all(np.linalg.eigvalsh((q + q.T) / 2) >= -1e-12 * np.max(np.abs(q)))
+        assert np.array_equal(q, q.T) and np.array_equal(r, r.T)
+        ham = np.block([[a, -b @ np.linalg.solve(r, b.T)], [-q, -a.T]])
+        if name == "badly_scaled":     # judge the Hamiltonian in the balanced coordinates: its eigenvalues are the same
+            dd = np.concatenate([np.logspace(-2, 2, n), 1 / np.logspace(-2, 2, n)])
+            ham = ham / dd[:, None] * dd[None, :]
+        assert np.min(np.abs(np.linalg.eigvals(ham).real)) >= 5e-4                # nothing on the imaginary axis
+        assert absc < 0 and np.all(np.linalg.eigvalsh((Pf + Pf.T) / 2) >= -1e-12 * np.max(np.abs(Pf)))
+        open_loop = np.max(np.linalg.eigvals(a).real)
+        top = np.argmax(np.abs(Pf))
+        if name == "slow_unreachable":
+            assert np.all(b[n - 1] == 0) and np.all(a[n - 1, :n - 1] == 0) and a[n - 1, n - 1] == -1e-3
+            assert abs(absc + 1e-3) <= 1e-12                                       # the unreachable slow mode IS the closed loop's
+            assert top == (n - 1) * n + (n - 1) and abs(Pf[n - 1, n - 1] - 500.0) <= 5.0
+        elif name == "weakly_detectable":
+            assert a[n - 1, n - 1] == 1e-3 and abs(open_loop - 1e-3) <= 1e-12 and q[n - 1, n - 1] == 1e-6
+            assert -5e-3 <= absc < 0                                               # only just mirrored
+        elif name == "marginally_stabilisable":
+            assert abs(open_loop - 0.02) <= 1e-12 and np.count_nonzero(b[n - 1]) == 1 and b[n - 1, 0] == 1e-2
+            assert top == (n - 1) * n + (n - 1) and Pf[n - 1, n - 1] >= 500.0 and -0.03 <= absc
+            assert np.argmax(np.max(np.abs(Kf), axis=0)) == n - 1                  # the gain's column n-1 is the large one
+        elif name.startswith("cheap_control"):
+            rr_ = float(name.split("_")[-1])
+            assert np.array_equal(r, rr_ * np.eye(m)) and abs(open_loop - 0.2) <= 1e-12
+            assert np.max(np.abs(Kf)) >= 0.5 / np.sqrt(rr_)                        # K = O(1 / sqrt r)
+            assert np.max(np.abs(b.T @ Pf)) <= 20 * np.sqrt(rr_) * max(1.0, np.max(np.abs(Pf)))       # B^T P = O(sqrt r)
+        elif name == "expensive_control":
+            assert np.array_equal(r, 1e8 * np.eye(m)) and abs(open_loop - 0.05) <= 1e-12
+            # unstable modes only mirrored, not damped further
+            assert absc >= -0.051 and np.max(np.abs(Kf)) <= 1e-1 and np.max(np.abs(Pf)) >= 1e5
+        elif name == "badly_scaled":
+            d = np.abs(np.diag(Pf))
+            assert abs(open_loop - 0.05) <= 1e-9 and d.max() / d.min() >= 1e6      # value entries over many decades
+        elif name == "stiff":
+            ev = np.abs(np.linalg.eigvals(a))
+            assert np.max(np.abs(a - a.T)) <= 2e-2 and ev.max() / ev.min() >= (1e5 if n > 3 else 1e4)
+        elif name == "integrator_chains":
+            assert np.all(np.linalg.matrix_power(a, 4) == 0) and np.any(np.linalg.matrix_power(a, min(3, n - 1)) != 0)
+            assert np.count_nonzero(b) == -(-n // 4)                               # one input per chain
+        elif name == "light_oscillators":
+            assert abs(open_loop + 1e-4) <= 1e-12 and np.max(np.abs(q)) <= 1e-3
+            assert absc >= -0.05 and np.max(np.abs(Pf)) <= 0.1
+
+
+def test_integrator_chains_refuse_more_chains_than_inputs():
+    with pytest.raises(ValueError):
+        problems.hard_care("integrator_chains", 16, 1)
+    with pytest.raises(ValueError):
+        problems.hard_care("integrator_chains", 9, 2)

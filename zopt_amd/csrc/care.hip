@@ -260,6 +260,118 @@ __global__ __launch_bounds__(64) void care_sda_kernel(const double* __restrict__
     wsync();
     wput(sT1, p, g, c);
     wsync();
+    // Newton-Kleinman polish.  The doubling iteration forms G = B R^-1 B^T and inverts I + G H: under cheap control (R = r I,
+    // G ~ 1/r) that costs up to eight digits of P.  One Newton step from the doubled P restores them, because its residual
+    // A^T P + P A - K^T R K + Q goes through K = R^-1 B^T P (B^T P is O(sqrt r), K^T R K is O(1)) and never through G:
+    //   Acl = A - B K;   Acl^T X + X Acl = -Res;   P <- P + X
+    // The Lyapunov equation is solved by the squared Smith iteration on the Cayley transform Ad = (Acl + g I)(Acl - g I)^-1,
+    // g = 1.25 |Acl|_inf:  X = sum_k (Ad^T)^k X0 Ad^k,  X0 = 2 g (Acl - g I)^-T Res (Acl - g I)^-1.
+    // A second step is taken only when the first moved P by more than kPolishRepeat max|P|; a step that does not converge or
+    // is not finite is dropped, so the doubled P is never made worse.  `info` keeps the doubling count.
+    constexpr int kPolishSteps = 2, kSmithMaxSquarings = 60;
+    constexpr double kSmithTol = 1e-16;      // the Smith sum has converged: its last increment relative to max|X|
+    constexpr double kPolishRepeat = 1e-12;  // a Newton step that moved P by more than this (relative) is followed by another
+    if (status == 0) {                       // the original A and B (the doubling loop overwrote their tiles); a step keeps them
+        wload(sA, A + inst * n * n, n, n, g, c);
+        wload(sG, B + inst * n * m, n, m, g, c);
+    }
+    for (int step = 0; step < kPolishSteps && status == 0; ++step) {
+        wload(sM, R + inst * m * m, m, m, g, c);           // R: its tile is reused below for Acl - g I
+        double kk[4] = {0.0, 0.0, 0.0, 0.0};
+        wmm_acc<false, false>(kk, sRB, sT1, n, g, c);
+        wput(sT2, kk, g, c);                               // sT2 = K
+        wsync();
+        double rk[4] = {0.0, 0.0, 0.0, 0.0}, bk[4] = {0.0, 0.0, 0.0, 0.0}, ktrk[4] = {0.0, 0.0, 0.0, 0.0}, acl[4], res[4];
+        wmm_acc<false, false>(rk, sM, sT2, m, g, c);
+        wmm_acc<false, false>(bk, sG, sT2, m, g, c);
+        wput(sT3, rk, g, c);                               // sT3 = R K
+        wget(acl, sA, g, c);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = 4 * r + g;
+            acl[r] -= bk[r];
+            res[r] = (i < n && c < n) ? Q[inst * n * n + i * n + c] : 0.0;
+        }
+        wput(sH, acl, g, c);                               // sH = Acl
+        wsync();
+        wmm_acc<true, false>(res, sA, sT1, n, g, c);       // + A^T P
+        wmm_acc<false, false>(res, sT1, sA, n, g, c);      // + P A
+        wmm_acc<true, false>(ktrk, sT2, sT3, m, g, c);     // K^T (R K)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) res[r] -= ktrk[r];
+        double rs2 = 0.0;
+        if (g == 0 && c < n)
+            for (int j = 0; j < n; ++j) rs2 += fabs(sH[c * WLD + j]);
+        double gc = 1.25 * wave_max(rs2);
+        if (!(gc > 0.0)) gc = 1.0;
+        wsync();
+        wput(sT3, res, g, c);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acl[r] -= gc * id[r];
+        wput(sM, acl, g, c);                               // sM = Acl - g I
+        wput(sT2, id, g, c);
+        wsync();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) res[r] = 0.5 * (sT3[(4 * r + g) * WLD + c] + sT3[c * WLD + (4 * r + g)]);
+        wsync();
+        wput(sT3, res, g, c);                              // sT3 = (Res + Res^T) / 2
+        wsync();
+        if (!wsolve(sM, sT2, nullptr, n, g, c)) break;     // sT2 = Mi = (Acl - g I)^-1
+        double ad[4], x[4] = {0.0, 0.0, 0.0, 0.0}, t[4] = {0.0, 0.0, 0.0, 0.0};
+        wmm_acc<true, false>(t, sT2, sT3, n, g, c);        // Mi^T Res
+        wput(sM, t, g, c);
+        wsync();
+        wmm_acc<false, false>(x, sM, sT2, n, g, c);        // (Mi^T Res) Mi
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            x[r] *= 2.0 * gc;
+            ad[r] = id[r] + 2.0 * gc * sT2[(4 * r + g) * WLD + c];   // (Acl + g I) Mi = I + 2 g Mi
+        }
+        wsync();
+        wput(sT3, x, g, c);                                // sT3 = X
+        wput(sH, ad, g, c);                                // sH = Ad
+        wsync();
+        bool smith = false;
+        for (int sq = 0; sq < kSmithMaxSquarings && !smith; ++sq) {        // X <- X + Ad^T X Ad;  Ad <- Ad^2
+            double u[4] = {0.0, 0.0, 0.0, 0.0}, inc[4] = {0.0, 0.0, 0.0, 0.0}, ad2[4] = {0.0, 0.0, 0.0, 0.0};
+            wmm_acc<true, false>(u, sH, sT3, n, g, c);
+            wmm_acc<false, false>(ad2, sH, sH, n, g, c);
+            wput(sM, u, g, c);
+            wsync();
+            wmm_acc<false, false>(inc, sM, sH, n, g, c);
+            double di = 0.0, sx = 0.0, bad = 0.0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                x[r] += inc[r];
+                di = fmax(di, fabs(inc[r]));
+                sx = fmax(sx, fabs(x[r]));
+                if (!(fabs(x[r]) < 1e300) || !(fabs(ad2[r]) < 1e300)) bad = 1.0;
+            }
+            di = wave_max(di);
+            sx = wave_max(sx);
+            bad = wave_max(bad);
+            wsync();
+            wput(sT3, x, g, c);
+            wput(sH, ad2, g, c);
+            wsync();
+            if (bad > 0.0) break;
+            smith = di <= kSmithTol * sx;
+        }
+        if (!smith) break;
+        double dx = 0.0, ps = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double xs = 0.5 * (sT3[(4 * r + g) * WLD + c] + sT3[c * WLD + (4 * r + g)]);
+            p[r] += xs;
+            dx = fmax(dx, fabs(xs));
+            ps = fmax(ps, fabs(p[r]));
+        }
+        dx = wave_max(dx);
+        ps = wave_max(ps);
+        wput(sT1, p, g, c);
+        wsync();
+        if (!(dx > kPolishRepeat * ps)) break;
+    }
     double k_[4] = {0.0, 0.0, 0.0, 0.0};
     wmm_acc<false, false>(k_, sRB, sT1, n, g, c);
 #pragma unroll
