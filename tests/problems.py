@@ -335,3 +335,307 @@ HARD_CARE = {
 def hard_care(name: str, n: int, m: int, batch: int = 2):
     """The seeded batch of HARD_CARE[name] at (n, m) that both the CPU property tests and the GPU tests use."""
     return HARD_CARE[name](batch, n, m, seed=2000 + 97 * n + m)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Hard quadratic models for the iLQR / affine-LQR / DDP backward sweeps (ilqr_backward.hip, sweep_tiled_f64.hip): each generator
+# (batch, T, n, m, seed) -> (dyn, cost, Vf) starts from `random_ilqr_model` and gives it ONE hard feature
+# (tests/test_hp_reference.py asserts that it has it).
+def _sT(X):
+    return np.swapaxes(X, -1, -2)
+
+
+def _antisym(rng, shape, scale):
+    N = rng.standard_normal(shape)
+    return scale * (N - _sT(N))
+
+
+def sweep_unstable(batch, T, n, m, seed=0, growth=1.3):
+    """Every step's f_x is a random matrix scaled to the spectral radius `growth` > 1: the value grows along the sweep."""
+    (f, f_x, f_u), cost, Vf = random_ilqr_model(batch, T, n, m, seed)
+    rho = np.max(np.abs(np.linalg.eigvals(f_x)), axis=-1)
+    return (f, f_x * (growth / rho)[..., None, None], f_u), cost, Vf
+
+
+def sweep_cheap_control(batch, T, n, m, seed=0, r=None):
+    """c_uu scaled by r = 1e-8 (c_ux and c_u by sqrt r, so the stacked Hessian stays positive definite): Q_uu is dominated by
+    f_u^T v_xx f_u and Q_xx - L^T Q_uu L cancels what the controls reach.  With more controls than states f_u^T v_xx f_u is singular and
+    cond(Q_uu) ~ 1 / r: r = 1e-4 there keeps the problem well posed in fp64."""
+    r = (1e-8 if m <= n else 1e-4) if r is None else r
+    dyn, (c, c_x, c_u, c_xx, c_ux, c_uu), Vf = random_ilqr_model(batch, T, n, m, seed)
+    return dyn, (c, c_x, c_u * np.sqrt(r), c_xx, c_ux * np.sqrt(r), c_uu * r), Vf
+
+
+def sweep_expensive_control(batch, T, n, m, seed=0, r=1e8):
+    """c_uu scaled by 1e8: tiny gains."""
+    dyn, (c, c_x, c_u, c_xx, c_ux, c_uu), Vf = random_ilqr_model(batch, T, n, m, seed)
+    return dyn, (c, c_x, c_u, c_xx, c_ux, c_uu * r), Vf
+
+
+def sweep_illcond_quu(batch, T, n, m, seed=0, r=None):
+    """f_u of rank one (an outer product) and c_uu scaled by r = 1e-4 (1e-3 beyond m = 6): f_u^T v_xx f_u has rank one, so cond(Q_uu)
+    ~ |f_u|^2 |v_xx| / r ~ 1e6..1e7 -- as ill conditioned as the fp64 oracle itself resolves to 1e-9 (m = 1: a rank-one f_u has full
+    rank, only the small c_uu remains)."""
+    r = (1e-4 if m <= 6 else 1e-3) if r is None else r
+    (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), Vf = random_ilqr_model(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 1)
+    f_u = rng.standard_normal((batch, T, n, 1)) * rng.standard_normal((batch, T, 1, m))
+    return (f, f_x, f_u), (c, c_x, c_u * np.sqrt(r), c_xx, c_ux * np.sqrt(r), c_uu * r), Vf
+
+
+def sweep_pivoting(batch, T, n, m, seed=0, scale=1e4):
+    """c_uu + scale * (diag(c_uu) P), P a cyclic column shift, at every step: nonsymmetric, with entries ~scale off the diagonal
+    and O(10) on it, so the elimination without row exchanges meets multipliers in the hundreds -- far above the kernels' limit of
+    4 -- loses that many digits and must be abandoned, while Q_uu itself is well conditioned (m = 1: no permutation exists, the
+    family is the plain one with a large c_uu)."""
+    dyn, (c, c_x, c_u, c_xx, c_ux, c_uu), Vf = random_ilqr_model(batch, T, n, m, seed)
+    dg = c_uu * np.eye(m)
+    return dyn, (c, c_x, c_u, c_xx, c_ux, c_uu + scale * np.roll(dg, 1, axis=-1)), Vf
+
+
+def sweep_scaling(n):
+    """The diagonal of `sweep_badly_scaled`'s coordinate change x' = D x."""
+    return np.logspace(-2, 2, n)
+
+
+def sweep_badly_scaled(batch, T, n, m, seed=0):
+    """The plain model in coordinates x' = D x, D = diag(logspace(-2, 2, n)), every operand transformed consistently: D f_x D^-1,
+    D f_u, D^-1 c_x, D^-1 c_xx D^-1, c_ux D^-1, D^-1 v_x, D^-1 v_xx D^-1.  The policy is l' = l, L' = L D^-1: columns over four
+    decades (c_xx and v_xx, scaled on both sides, over eight)."""
+    (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = random_ilqr_model(batch, T, n, m, seed)
+    d = sweep_scaling(n)
+    return ((f * d, f_x * d[:, None] / d[None, :], f_u * d[:, None]),
+            (c, c_x / d, c_u, c_xx / (d[:, None] * d[None, :]), c_ux / d[None, :], c_uu),
+            (v, v_x / d, v_xx / (d[:, None] * d[None, :])))
+
+
+def sweep_nonsymmetric(batch, T, n, m, seed=0):
+    """O(1) antisymmetric parts in c_xx, c_uu and v_xx: the reference's formulas do not symmetrise, so the kernels may not either."""
+    dyn, (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = random_ilqr_model(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 2)
+    return (dyn, (c, c_x, c_u, c_xx + _antisym(rng, c_xx.shape, 0.5), c_ux, c_uu + _antisym(rng, c_uu.shape, 0.5)),
+            (v, v_x, v_xx + _antisym(rng, v_xx.shape, 0.5)))
+
+
+def sweep_zero_gradient(batch, T, n, m, seed=0):
+    """c_x = c_u = v_x = 0: l must be exactly 0 at every step."""
+    dyn, (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = random_ilqr_model(batch, T, n, m, seed)
+    return dyn, (c, 0 * c_x, 0 * c_u, c_xx, c_ux, c_uu), (v, 0 * v_x, v_xx)
+
+
+# name -> generator (batch, T, n, m, seed); "plain" is the yardstick family the bounds' floor comes from, not a hard one
+HARD_SWEEP = {
+    "unstable": sweep_unstable,
+    "cheap_control": sweep_cheap_control,
+    "expensive_control": sweep_expensive_control,
+    "illcond_quu": sweep_illcond_quu,
+    "pivoting": sweep_pivoting,
+    "badly_scaled": sweep_badly_scaled,
+    "nonsymmetric": sweep_nonsymmetric,
+    "zero_gradient": sweep_zero_gradient,
+}
+
+
+# The long horizon of every shape the GPU tests run, and the (family, shape) pairs that need a shorter one for the fp64 oracle's own error
+# to stay below 1e-9 (tests/test_hp_reference.py asserts it): the value of `unstable` grows along directions one step cannot reach,
+# that of `nonsymmetric` grows through its antisymmetric part.
+SWEEP_T = {(12, 4): 100, (8, 4): 100, (5, 3): 40, (1, 1): 40, (11, 1): 40, (3, 4): 40, (16, 4): 12, (20, 6): 8, (33, 9): 5, (48, 16): 4}
+SWEEP_T_SHORTER = {("unstable", 12, 4): 60, ("unstable", 8, 4): 60, ("nonsymmetric", 12, 4): 20, ("nonsymmetric", 8, 4): 20}
+
+
+def sweep_horizon(name: str, n: int, m: int):
+    return SWEEP_T_SHORTER.get((name, n, m), SWEEP_T[(n, m)])
+
+
+def hard_sweep(name: str, n: int, m: int, T: int, batch: int = 2, shared: bool = False):
+    """The seeded batch of HARD_SWEEP[name] (or of the plain family, name "plain") at (n, m, T) that the CPU property tests and the
+    GPU tests both use; shared: with `share_hessians`."""
+    gen = random_ilqr_model if name == "plain" else HARD_SWEEP[name]
+    out = gen(batch, T, n, m, 3000 + 97 * n + 13 * m + T)
+    return share_hessians(*out) if shared else out
+
+
+def hard_affine(name: str, n: int, m: int, T: int, batch: int = 2):
+    """The `bilinearAffineLqr` operands (A, B, d, Q, R, H, q, r, q0) of `hard_sweep(name, ...)`: A = f_x, B = f_u, Q = c_xx, R = c_uu,
+    H = c_ux, q = c_x, r = c_u, q0 = c and a non-zero offset d (in `badly_scaled`'s coordinates where that is the family).  The
+    recursion starts from Q[T-1], q[T-1]; the model's terminal value is not used."""
+    (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), _ = hard_sweep(name, n, m, T, batch)
+    d = 0.5 * np.random.default_rng(4000 + 97 * n + 13 * m + T).standard_normal((batch, T, n))
+    if name == "badly_scaled":
+        d = d * sweep_scaling(n)
+    return f_x, f_u, d, c_xx, c_uu, c_ux, c_x, c_u, c
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Spectra that stress the PD projection V max(w, eps) V^T (ns16.h, psd_tiled.hip), shared by the stand-alone projection tests.
+ADVERSARIAL_SPECTRA = ("scaled_normal", "half_at_eps", "sixteen_decades", "rank_one", "dominant_pair", "hugging_eps", "zero_rows",
+                       "all_pd")
+
+
+def adversarial_spectrum(kind, k: int, rng):
+    """Eigenvalues (k,) of kind ADVERSARIAL_SPECTRA[kind] (or its name), drawn from `rng`, for the clamp eps = 1e-3: many decades of
+    magnitude, eigenvalues hugging eps from both sides, rank one, a dominant pair, everything already PD.  "zero_rows" is a plain
+    wide spectrum; its caller zeroes rows and columns of the assembled matrix."""
+    kind = ADVERSARIAL_SPECTRA.index(kind) if isinstance(kind, str) else kind
+    if kind == 0:
+        return rng.standard_normal(k) * 10 ** rng.uniform(-3, 3)
+    if kind == 1:
+        return np.concatenate([rng.standard_normal(k // 2), 1e-3 + rng.standard_normal(k - k // 2) * 1e-9])
+    if kind == 2:
+        return 10.0 ** rng.uniform(-14, 2, k) * rng.choice([-1, 1], k)
+    if kind == 3:
+        lam = np.zeros(k)
+        lam[0] = rng.standard_normal()
+        return lam
+    if kind == 4:
+        lam = rng.standard_normal(k)
+        lam[:2] = 1e3
+        return lam
+    if kind == 5:
+        return 1e-3 + 10.0 ** rng.uniform(-16, -2, k) * rng.choice([-1, 1], k)
+    if kind == 6:
+        return rng.standard_normal(k) * 10 ** rng.uniform(0, 2)
+    return 10.0 ** rng.uniform(-2, 4, k)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Second-derivative families for the DDP sweep: (f_xx, f_ux, f_uu) stacked on a plain or an unstable model such that the matrix the
+# sweep projects, vf_zz = sum_i v_x[i] d2f_i, has a planted spectrum at the terminal step: the terminal v_x is the unit vector of
+# state I0, the slice I0 of every step holds a matrix with a planted spectrum (tests.hp_reference.psd_from_spectrum_ld), the other
+# slices are small.  Earlier steps project whatever the sweep makes of it; hp_reference.ddp_backward_hp reports that spectrum.
+DDP_I0 = 1
+DDP_EPS = 1e-3
+
+
+def ddp_spectrum(name: str, k: int, rng):
+    """The planted eigenvalues (k,) of the DDP family `name`."""
+    if name == "strongly_indefinite":
+        return rng.uniform(10, 100, k) * rng.choice([-1, 1], k)
+    if name == "hugging_eps":
+        return DDP_EPS + 10.0 ** rng.uniform(-9, -3, k) * rng.choice([-1, 1], k)
+    if name == "wide_decades":
+        return 10.0 ** rng.uniform(-10, 2, k) * rng.choice([-1, 1], k)
+    if name == "half_at_eps":
+        lam = rng.standard_normal(k)
+        lam[k // 2:] = DDP_EPS + 1e-8 * rng.uniform(1, 3, k - k // 2) * rng.choice([-1, 1], k - k // 2)
+        return lam
+    if name == "rank_one":
+        lam = np.zeros(k)
+        lam[0] = rng.uniform(0.5, 2) * rng.choice([-1, 1])
+        return lam
+    if name == "all_pd":
+        return DDP_EPS + 10.0 ** rng.uniform(-2, 1, k)
+    raise KeyError(name)
+
+
+def _ddp_planted(name, other, model=random_ilqr_model):
+    def gen(batch, T, n, m, seed=0):
+        from tests import hp_reference as hp
+        (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = model(batch, T, n, m, seed)
+        rng = np.random.default_rng(seed + 5)
+        k = n + m
+        Z = other * rng.standard_normal((batch, T, n, k, k))
+        Z = Z + _sT(Z)
+        planted = np.empty((batch, T, k))
+        for b in range(batch):
+            for t in range(T):
+                planted[b, t] = ddp_spectrum(name, k, rng)
+                Z[b, t, DDP_I0 % n] = hp.psd_from_spectrum_ld(k, planted[b, t], int(rng.integers(1 << 31)), DDP_EPS)[0]
+        v_x = np.zeros((batch, n))
+        v_x[:, DDP_I0 % n] = 1.0
+        f_xx, f_ux, f_uu = (np.ascontiguousarray(X) for X in (Z[..., :n, :n], Z[..., n:, :n], Z[..., n:, n:]))
+        return (f, f_x, f_u, f_xx, f_ux, f_uu), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx), planted[:, T - 1]
+    return gen
+
+
+def _ddp_control_affine(rows):
+    def gen(batch, T, n, m, seed=0):
+        """f_ux = f_uu = 0 exactly and f_xx non-zero only among the first `rows` states (a model that is affine in its controls and
+        in its other states): exactly zero rows / columns in vf_zz, and the projection's row-group dispatch."""
+        dyn, cost, Vf = random_ilqr_model(batch, T, n, m, seed)
+        rng = np.random.default_rng(seed + 5)
+        r = min(rows, n)
+        f_xx = np.zeros((batch, T, n, n, n))
+        blk = 0.2 * rng.standard_normal((batch, T, n, r, r))
+        f_xx[..., :r, :r] = blk + _sT(blk)
+        return dyn + (f_xx, np.zeros((batch, T, n, m, n)), np.zeros((batch, T, n, m, m))), cost, Vf, None
+    return gen
+
+
+def ddp_vanishing(batch, T, n, m, seed=0):
+    """v_x = 0 at the terminal step and c_x = 0, so vf_zz = 0 exactly on the last step (the projection has nothing to iterate on);
+    c_u ~ 1e-12 makes v_x, and with it vf_zz, ~1e-12 on the steps before: a - eps I is -eps I to twelve digits."""
+    (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = random_ilqr_model(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 5)
+    sym = lambda X: X + _sT(X)      # noqa: E731
+    second = (sym(0.2 * rng.standard_normal((batch, T, n, n, n))), 0.2 * rng.standard_normal((batch, T, n, m, n)),
+              sym(0.2 * rng.standard_normal((batch, T, n, m, m))))
+    return (f, f_x, f_u) + second, (c, 0 * c_x, 1e-12 * c_u, c_xx, c_ux, c_uu), (v, 0 * v_x, v_xx), None
+
+
+def ddp_plain(batch, T, n, m, seed=0):
+    """The yardstick family of the DDP bounds: `random_ilqr_model` with 0.2 randn second derivatives (the existing parity tests')."""
+    dyn, cost, Vf = random_ilqr_model(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 5)
+    sym = lambda X: 0.5 * (X + _sT(X))      # noqa: E731
+    return (dyn + (0.2 * sym(rng.standard_normal((batch, T, n, n, n))), 0.2 * rng.standard_normal((batch, T, n, m, n)),
+                   0.2 * sym(rng.standard_normal((batch, T, n, m, m)))), cost, Vf, None)
+
+
+# name -> generator (batch, T, n, m, seed) -> (dyn with second derivatives, cost, Vf, planted terminal spectrum (batch, n + m) or None)
+HARD_DDP = {
+    "strongly_indefinite": _ddp_planted("strongly_indefinite", 1e-2, model=lambda *a: sweep_unstable(*a, growth=1.1)),
+    "hugging_eps": _ddp_planted("hugging_eps", 1e-6),
+    "half_at_eps": _ddp_planted("half_at_eps", 1e-12),
+    "wide_decades": _ddp_planted("wide_decades", 1e-3),
+    "rank_one": _ddp_planted("rank_one", 1e-3),
+    "control_affine_4": _ddp_control_affine(4),
+    "control_affine_8": _ddp_control_affine(8),
+    "control_affine_9": _ddp_control_affine(9),
+    "vanishing": ddp_vanishing,
+    "all_pd": _ddp_planted("all_pd", 0.0),
+}
+
+
+def share_hessians(dyn, cost, Vf):
+    """The same model with ONE cost Hessian for every trajectory and step (c_xx[0, 0] etc., and v_xx[0]): the time-invariant quadratic
+    cost the sweeps take as single matrices (`shared_hessian = 1`)."""
+    c, c_x, c_u, c_xx, c_ux, c_uu = cost
+    v, v_x, v_xx = Vf
+    bc = lambda X, lead: np.broadcast_to(X[(0,) * lead], X.shape).copy()      # noqa: E731
+    return dyn, (c, c_x, c_u, bc(c_xx, 2), bc(c_ux, 2), bc(c_uu, 2)), (v, v_x, bc(v_xx, 1))
+
+
+# the 28 variable pairs (a <= b, all among the first 9 states) in which the registered quadcopter model has a second derivative
+# (zm_model_hessian_pairs; tests/test_sweeps_hard_gpu.py checks this copy against the library's)
+QUAD_HESSIAN_PAIRS = [(0, 0), (1, 1), (2, 2), (2, 4), (1, 5), (0, 5), (2, 3), (1, 3), (0, 4), (6, 6), (6, 7), (7, 7), (6, 8), (7, 8), (8, 8),
+                      (0, 6), (0, 7), (0, 8), (1, 6), (1, 7), (1, 8), (2, 6), (2, 7), (2, 8), (4, 6), (4, 7), (5, 6), (5, 7)]
+
+
+def ddp_packed_pairs(batch, T, n, m, seed=0):
+    """`control_affine_9` at the quadcopter's shape with f_xx restricted to the model's 28 declared pairs and shared cost Hessians: the
+    numbers the packed-pairs sweep (zm_ddp_backward_pairs_list_f64, LDS-ring form) takes as H[b, t, p, i] = f_xx[b, t, i, a_p, b_p]."""
+    assert (n, m) == (12, 4)
+    dyn, cost, Vf, _ = _ddp_control_affine(9)(batch, T, n, m, seed)
+    keep = np.zeros((n, n))
+    for a, b in QUAD_HESSIAN_PAIRS:
+        keep[a, b] = keep[b, a] = 1.0
+    (f, f_x, f_u), cost, Vf = share_hessians(dyn[:3], cost, Vf)
+    return (f, f_x, f_u, dyn[3] * keep, dyn[4], dyn[5]), cost, Vf, None
+
+
+def hard_ddp(name: str, n: int, m: int, T: int, batch: int = 2):
+    """The seeded batch of HARD_DDP[name] (or of `ddp_plain`, name "plain"; of `ddp_packed_pairs`, name "packed_pairs") at (n, m, T) that the CPU property tests and the GPU
+    tests both use."""
+    gen = {"plain": ddp_plain, "packed_pairs": ddp_packed_pairs}.get(name) or HARD_DDP[name]
+    return gen(batch, T, n, m, 5000 + 97 * n + 13 * m + T)
+
+
+# The (n, m) the hard-family GPU tests run on each path (T from `sweep_horizon`; the DDP horizons stay short: every step costs the
+# reference a long-double eigensolve).
+ILQR_ONE_TILE_SHAPES = [(12, 4), (8, 4), (5, 3), (1, 1), (11, 1), (3, 4)]
+ILQR_TILED_SHAPES = [(16, 4), (20, 6), (33, 9), (48, 16)]
+AFFINE_SHAPES = [(12, 4), (8, 4), (5, 3), (20, 6), (48, 16)]
+DDP_SHAPES = {(12, 4): 8, (5, 3): 6, (2, 2): 5, (16, 4): 4, (20, 6): 3}      # (n, m) -> T
+RING_HORIZONS = [1, 2, 3, 4, 7]                                               # around the DMA ring's depth, on `unstable`
+PSD_SIZES = [2, 7, 16, 17, 32, 33, 48, 49, 64]

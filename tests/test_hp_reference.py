@@ -1,6 +1,7 @@
 """CPU tests of the high-precision references (tests/hp_reference.py) and of the hard-spectrum generators (tests/problems.py).
 
-The GPU tests of the DARE and of the tiled finite-horizon sweep judge the kernels against these references; here the references are
+The GPU tests of the DARE, the CARE, the tiled finite-horizon sweep, the iLQR / affine / DDP backward sweeps and the PD projection judge
+the kernels against these references; here the references are
 pinned by a known answer, by their own residuals, by the fp64 oracle on easy inputs and by an independent 40-digit computation, and
 every generator is shown to have the hard feature it claims, so that the GPU tests cannot drift into easy problems."""
 import functools
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import zopt_oracle as zo
+from tests import hard_cases as hc
 from tests import hp_reference as hp
 from tests import problems
 
@@ -278,3 +280,214 @@ def test_integrator_chains_refuse_more_chains_than_inputs():
         problems.hard_care("integrator_chains", 16, 1)
     with pytest.raises(ValueError):
         problems.hard_care("integrator_chains", 9, 2)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Backward sweeps and PD projection: the long-double references, HARD_SWEEP / HARD_DDP and the adversarial spectra, at the shapes and
+# horizons of tests/test_sweeps_hard_gpu.py and tests/test_psd_hard_gpu.py
+ORACLE_LIMIT = 1e-9        # a case whose fp64 oracle is further than this from the reference teaches nothing about a kernel
+SWEEP_CASES = [(name, n, m) for name in sorted(problems.HARD_SWEEP) for n, m in problems.ILQR_ONE_TILE_SHAPES + problems.ILQR_TILED_SHAPES]
+DDP_CASES = [(name, n, m) for name in sorted(problems.HARD_DDP) for n, m in problems.DDP_SHAPES]
+
+
+@pytest.mark.parametrize("n,m,T", [(12, 4, 100), (5, 3, 40), (20, 6, 8)])
+def test_sweep_references_match_their_oracles_on_the_plain_family(n, m, T):
+    """ilqr_backward_ld, affine_lqr_ld and ddp_backward_hp (with eigh_ld inside) against zo.backwardPass_ilqr, zo.bilinearAffineLqr and
+    zo.backwardPass_ddp on the plain family: 1e-13 in the tests' metric."""
+    for case in (hc.ilqr_case("plain", n, m, T), hc.affine_case("plain", n, m, T), hc.ddp_case("plain", n, m, min(T, 6))):
+        assert case["ref"]["L"].dtype == np.longdouble and case["ref"]["L"].shape[-2:] == (m, n)
+        assert case["e_l"] <= 1e-13 and case["e_L"] <= 1e-13
+
+
+def test_sweep_references_keep_the_reference_formulas():
+    """One step by hand: v_x' = Q_x - L^T (Q_uu l), v_xx' = Q_xx - (L^T Q_uu) L with a NONSYMMETRIC v_xx, c_xx, c_uu used as they
+    stand (no Joseph form, no symmetrisation), against zo.riccatiStep_ilqr."""
+    dyn, cost, Vf = problems.hard_sweep("nonsymmetric", 5, 3, 1)
+    ref = hp.ilqr_backward_ld(dyn, cost, Vf)
+    for b in range(2):
+        V, pol = zo.riccatiStep_ilqr(tuple(x[b, 0] for x in dyn), tuple(x[b, 0] for x in cost), tuple(x[b] for x in Vf))
+        assert np.max(np.abs(V.v_xx - V.v_xx.T)) > 0.1                                         # really nonsymmetric
+        assert np.max(np.abs(ref["v_xx"][b, 0] - V.v_xx)) <= 1e-13 * np.max(np.abs(V.v_xx))
+        assert np.max(np.abs(ref["v_x"][b, 0] - V.v_x)) <= 1e-13 * np.max(np.abs(V.v_x))
+        assert np.max(np.abs(ref["L"][b, 0] - pol.L)) <= 1e-13 * np.max(np.abs(pol.L))
+
+
+@pytest.mark.parametrize("k", [1, 2, 7, 16, 33, 64])
+def test_eigh_ld_recovers_a_planted_spectrum(k):
+    """eigh_ld on U diag(w) U^T (long double, unrounded): the planted eigenvalues to 1e-17 of the largest, orthonormal vectors, and
+    the decomposition reassembles the matrix; psd_project_ld of the fp64-rounded matrix is the planted projection to fp64 rounding."""
+    rng = np.random.default_rng(k)
+    w = rng.standard_normal(k) * 10.0 ** rng.uniform(-3, 3, k)
+    a64, P, U = hp.psd_from_spectrum_ld(k, w, seed=k + 1)
+    assert a64.dtype == np.float64 and P.dtype == np.longdouble and np.array_equal(a64, a64.T)
+    assert np.max(np.abs(U.T @ U - np.eye(k))) <= 1e-17
+    a = (U * w.astype(np.longdouble)) @ U.T
+    wl, V = hp.eigh_ld(np.stack([a, a.T]))
+    scale = np.max(np.abs(w))
+    assert np.max(np.abs(wl[0] - np.sort(w))) <= 1e-17 * scale and np.array_equal(wl[0], wl[1])
+    assert np.max(np.abs(V[0].T @ V[0] - np.eye(k))) <= 1e-17
+    assert np.max(np.abs((V[0] * wl[0]) @ V[0].T - (a + a.T) / 2)) <= 1e-17 * scale
+    assert np.max(np.abs(hp.psd_project_ld(a64) - P)) <= 1e-15 * max(scale, 1e-3)
+    assert np.max(np.abs(hp.psd_project_ld(a64).astype(np.float64) - zo.ensurePositiveDefinite(a64))) <= 1e-12 * max(scale, 1e-3)
+
+
+def test_eigh_ld_against_mpmath():
+    """eigh_ld against mpmath.eigsy at 40 digits on three 16 x 16 matrices: dense random, a wide planted spectrum, a repeated
+    eigenvalue."""
+    mp = pytest.importorskip("mpmath")
+    mp.mp.dps = 40
+    rng = np.random.default_rng(3)
+    M = rng.standard_normal((16, 16))
+    wide = hp.psd_from_spectrum_ld(16, 10.0 ** rng.uniform(-10, 2, 16) * rng.choice([-1, 1], 16), 4)[0]
+    rep = hp.psd_from_spectrum_ld(16, np.repeat([2.0, -1.0, 1e-3, 0.0], 4), 5)[0]
+    for a in (M + M.T, wide, rep):
+        w_mp = mp.eigsy(mp.matrix([[mp.mpf(float(x)) for x in row] for row in a]), eigvals_only=True)
+        w_mp = np.sort(np.array([np.longdouble(mp.nstr(x, 30)) for x in w_mp]))
+        w, _ = hp.eigh_ld(a)
+        assert np.max(np.abs(w - w_mp)) <= 1e-17 * np.max(np.abs(w_mp))
+
+
+def _max_multiplier(M):
+    """the largest multiplier of Gaussian elimination WITHOUT row exchanges on M (fp64)"""
+    M = np.array(M, dtype=np.float64)
+    worst = 0.0
+    for j in range(M.shape[0] - 1):
+        f = M[j + 1:, j] / M[j, j]
+        worst = max(worst, float(np.max(np.abs(f))))
+        M[j + 1:] -= f[:, None] * M[j]
+    return worst
+
+
+@pytest.mark.parametrize("name,n,m", SWEEP_CASES)
+def test_sweep_family_has_its_feature_and_is_well_posed(name, n, m):
+    """Every HARD_SWEEP generator has the feature it names at every shape the GPU tests run, and on every such case (iLQR; affine where
+    the shape is an affine one; shared Hessians at (12, 4)) the fp64 oracle is within 1e-9 of the long-double reference."""
+    T = problems.sweep_horizon(name, n, m)
+    case, plain = hc.ilqr_case(name, n, m, T), hc.ilqr_case("plain", n, m, T)
+    (f, f_x, f_u), (c, c_x, c_u, c_xx, c_ux, c_uu), (v, v_x, v_xx) = case["args"]
+    ref = case["ref"]
+    print(f"{name} ({n},{m},{T}): oracle l {case['e_l']:.1e} L {case['e_L']:.1e}  cond(Q_uu) <= {ref['cond_quu'].max():.1e}")
+    assert f_u.shape == (2, T, n, m) and not np.array_equal(f_x[0], f_x[1])
+    assert max(case["e_l"], case["e_L"]) <= ORACLE_LIMIT and max(plain["e_l"], plain["e_L"]) <= 1e-13
+    if (n, m) in problems.AFFINE_SHAPES:
+        a = hc.affine_case(name, n, m, T)
+        assert max(a["e_l"], a["e_L"]) <= ORACLE_LIMIT and np.all(a["args"][2] != 0)
+    if (n, m) == (12, 4):
+        s = hc.ilqr_case(name, n, m, T, shared=True)
+        assert max(s["e_l"], s["e_L"]) <= ORACLE_LIMIT and np.array_equal(s["args"][1][3][1, 3], s["args"][1][3][0, 0])
+    Lf = ref["L"].astype(np.float64)
+    V_next = np.concatenate([ref["v_xx"][:, 1:], np.asarray(v_xx, dtype=np.longdouble)[:, None]], axis=1).astype(np.float64)
+    fvf = np.swapaxes(f_u, -1, -2) @ V_next @ f_u                              # f_u^T v_xx f_u of every step
+    if name == "unstable":
+        assert np.all(np.abs(np.max(np.abs(np.linalg.eigvals(f_x)), axis=-1) - 1.3) <= 1e-9)
+        if n > m and T >= 20:      # the value grows beyond the plain family's where one step cannot reach every direction
+            assert np.max(np.abs(ref["v_xx"])) >= 2 * np.max(np.abs(plain["ref"]["v_xx"]))
+    elif name == "cheap_control":
+        assert np.max(np.abs(c_uu)) <= (1e-7 if m <= n else 1e-3)
+        assert np.median(np.max(np.abs(fvf), axis=(-1, -2)) / np.max(np.abs(c_uu), axis=(-1, -2))) >= (1e6 if m <= n else 1e2)
+    elif name == "expensive_control":
+        assert np.min(np.abs(np.diagonal(c_uu, axis1=-1, axis2=-2))) >= 1e8 and np.max(np.abs(Lf)) <= 1e-6
+    elif name == "illcond_quu":
+        assert np.all(np.linalg.matrix_rank(f_u) == 1)
+        if m > 1:
+            assert 1e5 <= ref["cond_quu"].max() <= 1e8 and ref["cond_quu"].min() >= 1e3
+    elif name == "pivoting":
+        Quu = c_uu + fvf
+        assert np.max(np.abs(c_uu - np.swapaxes(c_uu, -1, -2))) >= (1e3 if m > 1 else 0.0)
+        if m > 1:      # every step's elimination without row exchanges exceeds the kernels' multiplier limit of 4 by far
+            assert min(_max_multiplier(Quu[b, k]) for b in range(2) for k in range(T)) >= 50.0
+            assert ref["cond_quu"].max() <= 10.0                                             # ... while Q_uu is well conditioned
+    elif name == "badly_scaled":
+        d = problems.sweep_scaling(n)
+        assert np.max(np.abs(Lf * d - plain["ref"]["L"].astype(np.float64))) <= 1e-9 * np.max(np.abs(Lf * d))      # the plain policy, rescaled
+        if n > 1:
+            col = np.max(np.abs(Lf), axis=(0, 1, 2))
+            assert d.max() / d.min() == pytest.approx(1e4) and col.max() / col.min() >= 1e3
+    elif name == "nonsymmetric":
+        for X in (c_xx, v_xx) + ((c_uu,) if m > 1 else ()):
+            if X.shape[-1] > 1:
+                assert np.max(np.abs(X - np.swapaxes(X, -1, -2))) >= 0.5
+    elif name == "zero_gradient":
+        assert not c_x.any() and not c_u.any() and not v_x.any() and not ref["l"].any() and np.max(np.abs(Lf)) > 0.01
+
+
+def test_ring_horizon_cases_are_well_posed():
+    for n in (12, 8):
+        for T in problems.RING_HORIZONS:
+            case = hc.ilqr_case("unstable", n, 4, T)
+            assert max(case["e_l"], case["e_L"]) <= ORACLE_LIMIT
+
+
+@pytest.mark.parametrize("name,n,m", DDP_CASES + [("packed_pairs", 12, 4)])
+def test_ddp_family_has_its_feature_and_is_well_posed(name, n, m):
+    """Every HARD_DDP generator has the feature it names -- the planted spectrum is what the terminal step projects, the zero rows are
+    exactly zero -- and the fp64 oracle (eigh) is within 1e-9 of the long-double sweep on every case the GPU tests run."""
+    T = problems.DDP_SHAPES[(n, m)]
+    case = hc.ddp_case(name, n, m, T)
+    (f, f_x, f_u, f_xx, f_ux, f_uu), cost, (v, v_x, v_xx) = case["args"]
+    ref, planted = case["ref"], case["planted"]
+    k, eps = n + m, problems.DDP_EPS
+    print(f"{name} ({n},{m},{T}): oracle l {case['e_l']:.1e} L {case['e_L']:.1e}  sensitivity l {case['s_l']:.1e} L {case['s_L']:.1e}  "
+          f"smallest |eig(vf_zz - eps I)| / |.|_F {np.min(np.abs(ref['spectrum'])):.1e}")
+    assert max(case["e_l"], case["e_L"]) <= ORACLE_LIMIT
+    assert np.array_equal(f_xx, np.swapaxes(f_xx, -1, -2)) and np.array_equal(f_uu, np.swapaxes(f_uu, -1, -2))
+    term = np.einsum("bi,bijk->bjk", v_x, np.block([[f_xx[:, -1], np.swapaxes(f_ux[:, -1], -1, -2)], [f_ux[:, -1], f_uu[:, -1]]]))
+    w_term = hp.eigh_ld(term)[0].astype(np.float64)                             # what the terminal step projects
+    fro = np.sqrt(np.sum((w_term - eps) ** 2, axis=-1, keepdims=True))
+    assert np.max(np.abs(ref["spectrum"][:, -1] - (w_term - eps) / np.where(fro > 0, fro, 1))) <= 1e-12
+    if planted is not None:
+        assert np.max(np.abs(w_term - np.sort(planted, axis=-1))) <= 1e-15 * max(1.0, np.max(np.abs(planted)))
+    if name == "strongly_indefinite":
+        assert np.all(np.abs(planted) >= 10) and np.all(np.abs(planted) <= 100) and np.any(planted < 0) and np.any(planted > 0)
+        assert np.all(np.abs(np.max(np.abs(np.linalg.eigvals(f_x)), axis=-1) - 1.1) <= 1e-9)
+    elif name == "hugging_eps":
+        gap = np.abs(planted - eps)
+        assert gap.min() >= 1e-9 * (1 - 1e-6) and gap.max() <= 1e-3 and np.any(planted < eps) and np.any(planted > eps)
+    elif name == "half_at_eps":      # eigenvalues of vf_zz - eps I ~1e-8 of its norm next to O(1) ones: beyond a shortened sign iteration
+        gap = np.abs(planted[:, k // 2:] - eps)
+        assert gap.min() >= 1e-8 * (1 - 1e-6) and gap.max() <= 3e-8 and np.max(np.abs(planted[:, :k // 2])) >= 0.3
+        small = np.sort(np.abs(ref["spectrum"][:, -1]), axis=-1)[:, :k - k // 2]
+        assert small.min() >= 1e-9 and small.max() <= 2e-7
+    elif name == "wide_decades":
+        mag = np.abs(planted)
+        assert mag.min() >= 1e-10 and mag.max() <= 1e2 and mag.max() / mag.min() >= (1e6 if k > 4 else 1e2) and np.any(planted < 0)
+    elif name == "rank_one":
+        assert np.all(np.count_nonzero(planted, axis=-1) == 1)
+    elif name == "all_pd":
+        assert planted.min() > eps and np.array_equal(np.sort(v_x, axis=-1)[:, -1], np.ones(2))
+    elif name.startswith("control_affine") or name == "packed_pairs":
+        r = min(9 if name == "packed_pairs" else int(name.split("_")[-1]), n)
+        assert not f_ux.any() and not f_uu.any() and not f_xx[..., r:, :].any() and not f_xx[..., :, r:].any()
+        assert np.all(np.any(f_xx[..., :r, :r] != 0, axis=(-1, -2)))
+        if name == "packed_pairs":
+            keep = np.zeros((n, n), dtype=bool)
+            for a, b in problems.QUAD_HESSIAN_PAIRS:
+                keep[a, b] = keep[b, a] = True
+            assert len(set(problems.QUAD_HESSIAN_PAIRS)) == 28 and not f_xx[..., ~keep].any() and np.all(f_xx[0, 0, 0][keep] != 0)
+            assert np.array_equal(cost[3][1, 2], cost[3][0, 0])                     # shared cost Hessians
+    elif name == "vanishing":
+        assert not v_x.any() and not cost[1].any() and not term.any()              # vf_zz = 0 exactly on the last step
+        vf = np.abs(ref["v_x"].astype(np.float64))
+        assert 0 < vf.max() <= 1e-10                                                # ... and ~1e-12 on the steps before
+        assert np.all(np.abs(ref["spectrum"][:, :-1] + 1 / np.sqrt(k)) <= 1e-6)    # a - eps I is -eps I to many digits
+
+
+@pytest.mark.parametrize("kind", range(len(problems.ADVERSARIAL_SPECTRA)))
+def test_adversarial_spectra_have_their_feature(kind):
+    eps = 1e-3
+    for k in problems.PSD_SIZES:
+        w = problems.adversarial_spectrum(kind, k, np.random.default_rng(kind + k))
+        name = problems.ADVERSARIAL_SPECTRA[kind]
+        assert w.shape == (k,) and np.array_equal(w, problems.adversarial_spectrum(name, k, np.random.default_rng(kind + k)))
+        if name == "half_at_eps":
+            assert np.all(np.abs(w[k // 2:] - eps) <= 1e-8)
+        elif name == "sixteen_decades":
+            assert np.abs(w).max() / np.abs(w).min() >= (1e6 if k > 2 else 1.0) and np.abs(w).min() >= 1e-14
+        elif name == "rank_one":
+            assert np.count_nonzero(w) == 1
+        elif name == "dominant_pair":
+            assert np.all(w[:2] == 1e3) and np.all(np.abs(w[2:]) <= 10)
+        elif name == "hugging_eps":
+            assert np.all(np.abs(w - eps) <= 1e-2) and np.all(np.abs(w - eps) >= 1e-16)
+        elif name == "all_pd":
+            assert w.min() >= 1e-2 > eps

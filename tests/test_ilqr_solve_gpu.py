@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import zopt_oracle as zo
+from tests import problems
 
 pytestmark = pytest.mark.gpu
 
@@ -245,24 +246,7 @@ def test_ensurePositiveDefinite_adversarial_spectra(mods, kind):
     for t in range(24):
         k = int(rng.integers(2, 17))
         Q, _ = np.linalg.qr(rng.standard_normal((k, k)))
-        if kind == 0:
-            lam = rng.standard_normal(k) * 10 ** rng.uniform(-3, 3)
-        elif kind == 1:
-            lam = np.concatenate([rng.standard_normal(k // 2), 1e-3 + rng.standard_normal(k - k // 2) * 1e-9])
-        elif kind == 2:
-            lam = 10.0 ** rng.uniform(-14, 2, k) * rng.choice([-1, 1], k)
-        elif kind == 3:
-            lam = np.zeros(k)
-            lam[0] = rng.standard_normal()
-        elif kind == 4:
-            lam = rng.standard_normal(k)
-            lam[:2] = 1e3
-        elif kind == 5:
-            lam = 1e-3 + 10.0 ** rng.uniform(-16, -2, k) * rng.choice([-1, 1], k)
-        elif kind == 6:      # exactly zero rows / columns around a dense block
-            lam = rng.standard_normal(k) * 10 ** rng.uniform(0, 2)
-        else:                # already positive definite, wide range
-            lam = 10.0 ** rng.uniform(-2, 4, k)
+        lam = problems.adversarial_spectrum(kind, k, rng)      # kind 6: exactly zero rows / columns around a dense block, below
         a = (Q * lam) @ Q.T
         a = 0.5 * (a + a.T)
         if kind == 6:

@@ -11,6 +11,9 @@
 // finish.  One reduction (F) and one LDS transpose (the symmetrisation) per group / per two cubic steps: they cost a wave about as much
 // as two of the products, which is why the steps come in groups.  An eigenvalue of X below ~1e-12 |X|_F is not resolved
 // within the iteration caps; it then contributes an error of at most its own size.
+// (A measurement recorded in DESIGN 3.1, not an assertion of the suite: on 96 planted `hugging_eps` spectra with eigenvalues of X down
+// to 1e-16 |X|_F, against an exact reference, the error of such a matrix was <= 2 % of its largest unresolved eigenvalue and
+// <= 1e-15 |X|_F.  tests/test_psd_hard_gpu.py holds the same spectra to 2e-11 relative and to a smallest eigenvalue >= eps (1 - 1e-6).)
 // Measured against eigh on 900 adversarial spectra (tools/ns_psd_model.py): <= 4e-12 relative, 3e-15 on dense random matrices.
 //
 // The tile algebra gives X^T Y for free (tile16_f64.h); Z is symmetric, so X^T Y = X Y -- but rounding makes Z' = Z^T W slightly
