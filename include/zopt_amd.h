@@ -556,6 +556,61 @@ int zm_mpc_solve_ltv_f64(const double* A, const double* B, const double* c, cons
                          double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
                          void* stream);
 
+/* Real-time-iteration nonlinear MPC (extension): zm_mpc_solve_ltv_f64 on the linearisation of a REGISTERED MODEL about a plan, every
+ * instance its own problem (P = batch, problem[i] = i).  Shapes: the model's (n_user, m_user) embedded in a compiled (ns, mc) of the
+ * 16-lanes-per-instance kernels, as zopt_amd/mpcUtils.py embeds them; models: ZM_MODEL_QUADCOPTER (12, 4) and ZM_MODEL_QUADCOPTER_RB
+ * (8, 4) with dt > 0, ZM_MODEL_LINEAR with n <= 12, m <= 4.
+ * zm_model_step_f64: xNext[b] = f(x[b], u[b]), one step of the model's step function per instance.
+ *     Replaces: calling the reference's dynamics callable (zopt/quadcopter.py:116-144 under demos/iterativeLqr.py:35's Euler step) per
+ *     instance; it is the plant of zm_mpc_rti_f64 as a call of its own (the same kernel).
+ *     in : x (batch,n)  u (batch,m)   out: xNext (batch,n)   [device]
+ * zm_mpc_relinearize_f64: the expansion of zm_linearize_dynamics_f64 (the same device functions) about stage k of instance b's plan,
+ *     written as the problem data of zm_mpc_setup_ltv_f64 / zm_mpc_solve_ltv_f64:
+ *         A[b][k] <- f_x,  B[b][k] <- f_u  (the leading n_user x n_user / n_user x m_user blocks; padding is left as it is),
+ *         c[b][k] <- f - f_x xbar_k - f_u ubar_k  (the first n_user components), each component ONE FMA chain in this order:
+ *         s = f_i;  s = fma(-f_x[i][j], xbar_k[j], s), j = 0 .. n_user-1;  then  s = fma(-f_u[i][j], ubar_k[j], s), j = 0 .. m_user-1.
+ *     Replaces: AffineDynamics.from_trajectory (zopt/pytrees.py:147-153) followed by the host-side c_k of ltvMpc.fromExpansion and the
+ *     copies of ltvMpc.update (zopt_amd/mpcUtils.py).
+ *     in : xPlan (batch,N+1,n_user)  uPlan (batch,N,m_user), absolute coordinates   [device]
+ *     out: A (batch,N,ns,ns)  B (batch,N,ns,mc)  c (batch,N,ns)   [device]
+ * zm_mpc_rti_f64: `steps` real-time iterations of every instance as ONE call,
+ *         x <- clip(x0);  states[0] = x
+ *         per step s:  zm_mpc_relinearize_f64 about the plan;  zm_mpc_setup_ltv_f64;  zm_mpc_solve_ltv_f64 from states[s], tracking rows
+ *                      s .. s + N of xRef and s .. s + N - 1 of uRef (step 0 cold, later steps with `warm_start`);  inputs[s] = uTraj_s[0];
+ *                      states[s + 1] = clip(f_plant(states[s], inputs[s]) + disturbance[s]);
+ *                      plan <- rows 1 .. N of xTraj_s and 1 .. N - 1 of uTraj_s, the last row repeated (its head is the PREDICTED successor)
+ *     -- exactly what that loop of calls computes, whatever the status of a step: a step that does not end "optimal" still leaves a
+ *     rollout, and the step after it starts cold.  The plant step is the model's step function (zm_model_step_f64), not an expansion.
+ *     Replaces: the Python loop of tools/examples/mpc_ltv.py (real-time iteration with zopt's pytrees.AffineDynamics.from_trajectory,
+ *     zopt/pytrees.py:147-153, around an MPC solve, zopt/mpcUtils.py:61-81, as demos/lqrMpc.py:40-47 loops around it).
+ *     After the argument checks and one read-back of `problem` (it must be the identity) the call only enqueues on `stream`: per step the
+ *     expansion, the table setup, the linear term of the window, the solve, the plant step and the plan shift; nothing is synchronised or
+ *     copied to the host inside the loop.
+ *     in : model; plant: the model the state is advanced with, of the same (n, m) (NULL: `model`)
+ *          xPlan (batch,N+1,n_user)  uPlan (batch,N,m_user): the first expansion point; on return the plan after the last step's shift
+ *          A, B, c as zm_mpc_relinearize_f64 writes them (their padding must hold what zm_mpc_solve_ltv_f64 expects: zero); on return
+ *          the last step's linearisation.  Q (batch,ns,ns)  R (batch,mc,mc)  Qf (batch,ns,ns)  bounds (batch,ns) / (batch,mc)
+ *          rho_tab (batch,n_levels): the penalty of each (problem, level), as zm_mpc_setup_ltv_f64 takes it;  rho_p (batch): level0's
+ *          K, Minv, D, ABt: the tables of zm_mpc_setup_ltv_f64 (P = batch), written at every step; on return those of the last step
+ *          x0 (batch,ns);  xRef (batch,xref_rows,ns), uRef (batch,uref_rows,mc) with xref_rows = steps + N, uref_rows = steps + N - 1,
+ *          either may be NULL;  disturbance (steps,batch,ns) or NULL;  clip_tol >= 0, or negative for no clip;  warm_start 0 / 1 / 2
+ *          workspace: 5 * batch * N * (ns + mc) doubles (on return the warm-start state of the last step), plus
+ *                     batch * ((N + 1) * ns + N * mc) doubles when xPred is NULL   [device]
+ *     out: STEP-MAJOR, as zm_mpc_closed_loop_f64: states (steps+1,batch,ns)  inputs (steps,batch,mc)  status, iters (steps,batch) int32
+ *          resid (batch,2) or NULL: the residuals of the last step;  xPred (steps,batch,N+1,ns)  uPred (steps,batch,N,mc) or both NULL
+ *     ZM_EUNSUPPORTED, before any launch, for (ns, mc) and N outside zm_mpc_solve_ltv_f64's. */
+int zm_model_step_f64(const zm_model_t* model, const double* x, const double* u, double* xNext, int64_t batch, void* stream);
+int zm_mpc_relinearize_f64(const zm_model_t* model, const double* xPlan, const double* uPlan, double* A, double* B, double* c,
+                           int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream);
+int zm_mpc_rti_f64(const zm_model_t* model, const zm_model_t* plant, double* xPlan, double* uPlan, double* A, double* B, double* c,
+                   const double* Q, const double* R, const double* Qf, const double* rho_tab, double* K, double* Minv, double* D,
+                   double* ABt, int n_levels, int level0, double rho_step, double alpha, const double* x_lb, const double* x_ub,
+                   const double* u_lb, const double* u_ub, const double* x0, const double* xRef, const double* uRef, int xref_rows,
+                   int uref_rows, const double* rho_p, const int32_t* problem, double eps_abs, double eps_rel, double eps_prim_inf,
+                   int max_iter, int warm_start, int steps, double clip_tol, const double* disturbance, double* workspace,
+                   double* states, double* inputs, int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred,
+                   int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,17 @@ SYMBOLS = {
     "zm_mpc_solve_ltv_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
                              [_c_dp] * 9 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                              [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, x, u, xNext, batch, stream)
+    "zm_model_step_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
+    # (model*, xPlan, uPlan, A, B, c, batch, N, n_user, m_user, ns, mc, stream)
+    "zm_mpc_relinearize_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    # (model*, plant* | NULL, xPlan, uPlan, A, B, c, Q, R, Qf, rho_tab, K, Minv, D, ABt, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb,
+    #  u_ub, x0, xRef | NULL, uRef | NULL, xref_rows, uref_rows, rho_p, problem, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start, steps,
+    #  clip_tol, disturbance | NULL, ws, states, inputs, status, iters, resid | NULL, xPred | NULL, uPred | NULL, batch, N, n_user, m_user,
+    #  ns, mc, stream)
+    "zm_mpc_rti_f64": (ctypes.c_int, [_c_dp] * 15 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] + [_c_dp] * 7 +
+                       [ctypes.c_int] * 2 + [_c_dp] * 2 + [ctypes.c_double] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] + [_c_dp] * 9 +
+                       [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "zm_mpc_solve_warm_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_double] * 4 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                               [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, active, shared_hessian, l, L, batch, T, n, m, stream)

@@ -1048,3 +1048,110 @@ extern "C" int zm_model_nonlinear_mask(const zm_model_t* model, uint32_t* mask) 
     *mask = zm::model_nonlinear_mask(md);
     return ZM_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// real-time-iteration MPC (zm_mpc_relinearize_f64, zm_mpc_rti_f64): the expansion written as the LTV solver's problem data
+// ---------------------------------------------------------------------------------------------------------------------
+namespace zm {
+
+// linearize_dynamics_kernel's expansion (the same device functions: the quadcopter's closed forms, dual numbers for the rest; 16 lanes per
+// point, lane j owns column j of [f_x | f_u]) about stage k of instance b's plan, written as that instance's stage-varying dynamics:
+//     A[b][k] (ns, ns) <- f_x,  B[b][k] (ns, mc) <- f_u  in their leading n x n / n x m blocks (the padding of an embedded shape is not
+//     touched),  c[b][k] (ns) <- f - f_x xbar_k - f_u ubar_k  in its first n components.
+// c_i is ONE FMA chain by lane i, from the tile the group has just written:  s = f_i;  s = fma(-f_x[i][j], xbar[j], s) for j = 0 .. n-1;
+// then s = fma(-f_u[i][j], ubar[j], s) for j = 0 .. m-1.
+template <bool QUAD, bool WIND>
+__global__ __launch_bounds__(64 * LIN_WAVES) void mpc_rti_relinearize_kernel(const zm_model_t md, const double* __restrict__ xPlan,
+                                                                             const double* __restrict__ uPlan, double* __restrict__ A,
+                                                                             double* __restrict__ B, double* __restrict__ c,
+                                                                             const long batch, const int N, const int ns, const int mc) {
+    constexpr int TF = MAXN * (MAXN + MAXM);                   // f sits behind the [f_x | f_u] image
+    __shared__ double tile[4 * LIN_WAVES][TF + MAXN];
+    const int lane = threadIdx.x;
+    const int j = lane & 15;
+    const int q = lane >> 4;
+    const long gi = (long)blockIdx.x * (4 * LIN_WAVES) + q;    // b * N + k
+    if (gi >= batch * N) return;
+    const long b = gi / N;
+    const int k = (int)(gi - b * N);
+    const int n = QUAD ? 12 : md.n, m = QUAD ? 4 : md.m;
+    double xv[MAXN], uv[MAXM];
+    {
+        const double* xk = xPlan + (b * (N + 1) + k) * n;
+        const double* uk = uPlan + gi * m;
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) xv[i] = (i < n) ? xk[i] : 0.0;
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i) uv[i] = (i < m) ? uk[i] : 0.0;
+    }
+    double col[MAXN];
+    if constexpr (QUAD) {
+        const QuadAtoms a = quad_atoms(md, xv, uv);
+        double o[12];
+        quad_jac_column<WIND>(j, a, o);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) col[i] = __builtin_fma(md.dt, o[i], (i == j) ? 1.0 : 0.0);
+        if (j == 0) {
+            double xd[12];
+            quad_inertial_dynamics<double>(xv, uv, md.wind_ned, xd);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) tile[q][TF + i] = xv[i] + md.dt * xd[i];
+        }
+    } else {
+        Dual x[MAXN], u[MAXM], xn[MAXN];
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) x[i] = Dual{xv[i], (i == j) ? 1.0 : 0.0};
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i) u[i] = Dual{uv[i], (n + i == j) ? 1.0 : 0.0};
+        model_step<Dual>(md, x, u, xn);
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) col[i] = xn[i].d;
+        if (j == 0) {
+#pragma unroll
+            for (int i = 0; i < MAXN; ++i)
+                if (i < n) tile[q][TF + i] = xn[i].v;
+        }
+    }
+    if (j < n + m) {
+        double* t = tile[q] + ((j < n) ? j : n * n + (j - n));
+        const int st = (j < n) ? n : m;
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i)
+            if (i < n) t[i * st] = col[i];
+    }
+    wave_lds_sync();
+    double* oa = A + gi * ns * ns;
+    double* ob = B + gi * ns * mc;
+    for (int e = j; e < n * n; e += 16) oa[(e / n) * ns + e % n] = tile[q][e];
+    for (int e = j; e < n * m; e += 16) ob[(e / m) * mc + e % m] = tile[q][n * n + e];
+    if (j < n) {
+        double s = tile[q][TF + j];
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i)
+            if (i < n) s = __builtin_fma(-tile[q][j * n + i], xv[i], s);
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i)
+            if (i < m) s = __builtin_fma(-tile[q][n * n + j * m + i], uv[i], s);
+        c[gi * ns + j] = s;
+    }
+}
+
+int check_model(const zm_model_t* model, zm_model_t& md, const char* who) { return zm_check_model(model, md, who); }
+
+// `md` has passed check_model and mpc_rti_check_model (mpc.hip); sizes are the caller's to check
+int mpc_relinearize_enqueue(const zm_model_t& md, const double* xPlan, const double* uPlan, double* A, double* B, double* c, long batch,
+                            int N, int ns, int mc, hipStream_t st) {
+    constexpr int GPB = 4 * LIN_WAVES;
+    const dim3 grid((unsigned)((batch * N + GPB - 1) / GPB)), block(64 * LIN_WAVES);
+    const bool windy = md.wind_ned[0] != 0.0 || md.wind_ned[1] != 0.0 || md.wind_ned[2] != 0.0;
+    if (md.kind == ZM_MODEL_QUADCOPTER && windy)
+        hipLaunchKernelGGL((mpc_rti_relinearize_kernel<true, true>), grid, block, 0, st, md, xPlan, uPlan, A, B, c, batch, N, ns, mc);
+    else if (md.kind == ZM_MODEL_QUADCOPTER)
+        hipLaunchKernelGGL((mpc_rti_relinearize_kernel<true, false>), grid, block, 0, st, md, xPlan, uPlan, A, B, c, batch, N, ns, mc);
+    else
+        hipLaunchKernelGGL((mpc_rti_relinearize_kernel<false, false>), grid, block, 0, st, md, xPlan, uPlan, A, B, c, batch, N, ns, mc);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+}  // namespace zm

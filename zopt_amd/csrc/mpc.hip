@@ -26,6 +26,7 @@
 // subspace from the box.  The certificate is sound but can need thousands of iterations; an infeasible instance that
 // is not certified within max_iter reports "user_limit".
 #include "mpc_common.h"
+#include "models.h"
 
 #include <cstdlib>
 #include <vector>
@@ -372,6 +373,72 @@ __global__ __launch_bounds__(256) void mpc_advance_kernel(const double* src, con
 }
 
 // ----------------------------------------------------------------------------------------------------------------
+// real-time-iteration run (zm_mpc_rti_f64): the kernels between two solves (the expansion is linearize.hip's)
+// ----------------------------------------------------------------------------------------------------------------
+
+// The plant, one lane per instance: one step of the registered model from x[b] (first md.n of x_stride) under u[b] (first md.m of
+// u_stride) by models.h's model_step -- the step function, not an expansion -- then mpc_advance_kernel's state rule with every instance
+// its own problem:   dst[b][i] = clip(x+_i + dist[b][i])  into [x_lb[b][i] + clip_tol, x_ub[b][i] - clip_tol],  i < md.n.
+// dist NULL: nothing is added; clip_tol < 0: no clip (the bounds are not read).  Components md.n .. dst_stride of dst (the padding of an
+// embedded shape) are set to zero.  udst != NULL: udst[b] (mcw) = the first mcw components of u[b], the input applied.
+// zm_model_step_f64 is this kernel with dist = NULL, clip_tol < 0, udst = NULL.
+__global__ __launch_bounds__(64) void mpc_rti_plant_kernel(const zm_model_t md, const double* __restrict__ x, const long x_stride,
+                                                           const double* __restrict__ u, const long u_stride,
+                                                           const double* __restrict__ dist, const double* __restrict__ x_lb,
+                                                           const double* __restrict__ x_ub, const double clip_tol,
+                                                           double* __restrict__ dst, const int dst_stride, double* __restrict__ udst,
+                                                           const int mcw, const long batch) {
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    const int n = md.n, m = md.m;
+    double xv[MAXN], uv[MAXM], xn[MAXN];
+#pragma unroll
+    for (int i = 0; i < MAXN; ++i) xv[i] = (i < n) ? x[b * x_stride + i] : 0.0;
+#pragma unroll
+    for (int i = 0; i < MAXM; ++i) uv[i] = (i < m) ? u[b * u_stride + i] : 0.0;
+    model_step<double>(md, xv, uv, xn);
+#pragma unroll
+    for (int i = 0; i < MAXN; ++i) {
+        if (i < n) {
+            double v = xn[i];
+            if (dist) v += dist[b * dst_stride + i];
+            if (clip_tol >= 0.0) {   // min(max(v, lo), hi): np.clip's order, a NaN passes through
+                const double lo = x_lb[b * dst_stride + i] + clip_tol, hi = x_ub[b * dst_stride + i] - clip_tol;
+                v = v < lo ? lo : v;
+                v = v > hi ? hi : v;
+            }
+            dst[b * dst_stride + i] = v;
+        }
+    }
+    for (int i = n; i < dst_stride; ++i) dst[b * dst_stride + i] = 0.0;
+    if (udst)
+        for (int j = 0; j < mcw; ++j) udst[b * mcw + j] = u[b * u_stride + j];
+}
+
+// The next expansion point, one thread per component: the step's rollout moved on by one stage, its last row repeated,
+//     xPlan[b][k] (n) <- xTraj[b][min(k + 1, N)] (first n of ns),  k = 0 .. N;     uPlan[b][k] (m) <- uTraj[b][min(k + 1, N - 1)] (first m of mc).
+// The head of the plan is the PREDICTED successor, not the measured one.
+__global__ __launch_bounds__(256) void mpc_rti_shift_kernel(const double* __restrict__ xTraj, const double* __restrict__ uTraj,
+                                                            double* __restrict__ xPlan, double* __restrict__ uPlan, const long batch,
+                                                            const int N, const int n, const int m, const int ns, const int mc) {
+    const long xper = (long)(N + 1) * n, per = xper + (long)N * m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * per) return;
+    const long b = e / per;
+    long r = e - b * per;
+    if (r < xper) {
+        const int k = (int)(r / n), i = (int)(r % n);
+        const int src = k + 1 < N ? k + 1 : N;
+        xPlan[b * xper + r] = xTraj[(b * (N + 1) + src) * ns + i];
+    } else {
+        r -= xper;
+        const int k = (int)(r / m), j = (int)(r % m);
+        const int src = k + 1 < N - 1 ? k + 1 : N - 1;
+        uPlan[b * (long)N * m + r] = uTraj[(b * N + src) * mc + j];
+    }
+}
+
+// ----------------------------------------------------------------------------------------------------------------
 // host side: one shape ladder, one launcher, one routine behind the three solve entry points
 // ----------------------------------------------------------------------------------------------------------------
 
@@ -574,6 +641,125 @@ static int mpc_closed_loop(const char* fn, const double* A, const double* B, con
     return rc;
 }
 
+// The models of the real-time-iteration entry points: a registered model of exactly (n, m); the quadcopters as a discrete step (dt > 0)
+static int mpc_rti_check_model(const char* fn, const char* what, const zm_model_t* model, zm_model_t& md, int n, int m) {
+    const int rc = check_model(model, md, fn);
+    if (rc != ZM_OK) return rc;
+    if (md.n != n || md.m != m)
+        return set_error(ZM_EINVAL, "%s: the %s has (n=%d, m=%d), the problem (n=%d, m=%d)", fn, what, md.n, md.m, n, m);
+    if (md.kind != ZM_MODEL_LINEAR && !(md.dt > 0.0)) return set_error(ZM_EINVAL, "%s: the %s needs a step dt > 0", fn, what);
+    return ZM_OK;
+}
+
+// the shapes and horizons of the one kernel for stage-varying dynamics (mpc_wave.hip: mpc_wave_ltv_dispatch), refused before any launch
+static int mpc_ltv_check_shape(const char* fn, int N, int n, int m) {
+    if (for_mpc_shape(n, m, [](auto ns, auto mc) { return ns.value + mc.value <= 16 ? ZM_OK : ZM_EUNSUPPORTED; }) != ZM_OK)
+        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
+    if ((size_t)4 * N * 64 * sizeof(double) > 150 * 1024)
+        return set_error(ZM_EUNSUPPORTED, "%s: N=%d beyond the horizons whose iterates fit LDS (N <= 75)", fn, N);
+    return ZM_OK;
+}
+
+static int mpc_relinearize(const char* fn, const zm_model_t* model, const double* xPlan, const double* uPlan, double* A, double* B,
+                           double* c, int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream) {
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    if (!xPlan || !uPlan || !A || !B || !c) return set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if (batch < 0 || N < 1 || n_user < 1 || m_user < 1 || ns < n_user || mc < m_user) return set_error(ZM_EINVAL, "%s: bad size", fn);
+    if (ns > SN || mc > SM) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (n <= 12, m <= 4)", fn, ns, mc);
+    if (((long)batch * N + 15) / 16 > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N too large", fn);
+    zm_model_t md;
+    const int rc = mpc_rti_check_model(fn, "model", model, md, n_user, m_user);
+    if (rc != ZM_OK) return rc;
+    return mpc_relinearize_enqueue(md, xPlan, uPlan, A, B, c, (long)batch, N, ns, mc, (hipStream_t)stream);
+}
+
+// zm_mpc_rti_f64: `steps` real-time iterations of every instance, nothing but launches on `st` after the argument checks and the one
+// read-back of the problem map -- mpc_closed_loop's form (b) with the expansion and the table setup inside the loop:
+//     relinearise about the plan -> mpc_setup_ltv_kernel -> mpc_track_linear_window_kernel -> the LTV solve -> plant step, plan shift
+static int mpc_rti(const char* fn, const zm_model_t* model, const zm_model_t* plant, double* xPlan, double* uPlan, double* A, double* B,
+                   double* c, const double* Q, const double* R, const double* Qf, const double* rho_tab, double* K, double* Minv, double* D,
+                   double* ABt, int n_levels, int level0, double rho_step, double alpha, const double* x_lb, const double* x_ub,
+                   const double* u_lb, const double* u_ub, const double* x0, const double* xRef, const double* uRef, int xref_rows,
+                   int uref_rows, const double* rho_p, const int32_t* problem, double eps_abs, double eps_rel, double eps_prim_inf,
+                   int max_iter, int warm_start, int steps, double clip_tol, const double* disturbance, double* workspace, double* states,
+                   double* inputs, int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred, int64_t batch, int N,
+                   int n_user, int m_user, int n, int m, void* stream) {
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    int rc = mpc_check_args(fn, true, true, states && inputs && status && iters && xPlan && uPlan && c && D && ABt && rho_tab, A, B, Q, R,
+                            Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub, x0, 0.0, rho_p, problem, batch,
+                            max_iter, workspace, batch, N, n, m);
+    if (rc != ZM_OK) return rc;
+    if (steps < 1) return set_error(ZM_EINVAL, "%s: steps must be at least 1", fn);
+    if (n_user < 1 || m_user < 1 || n_user > n || m_user > m) return set_error(ZM_EINVAL, "%s: bad size", fn);
+    if ((xPred == nullptr) != (uPred == nullptr)) return set_error(ZM_EINVAL, "%s: the two prediction arrays come together", fn);
+    if ((xRef && xref_rows != steps + N) || (uRef && uref_rows != steps + N - 1))
+        return set_error(ZM_EINVAL, "%s: a reference needs steps + N rows of xRef and steps + N - 1 rows of uRef", fn);
+    if ((rc = mpc_ltv_check_shape(fn, N, n, m)) != ZM_OK) return rc;
+    zm_model_t md, pl;
+    if ((rc = mpc_rti_check_model(fn, "model", model, md, n_user, m_user)) != ZM_OK) return rc;
+    if ((rc = mpc_rti_check_model(fn, "plant", plant ? plant : model, pl, n_user, m_user)) != ZM_OK) return rc;
+    const long W = (long)n + m;
+    const long ablocks = ((long)batch * W + 255) / 256;                                         // of mpc_advance_kernel
+    const long gblocks = ((long)batch * N * W + 255) / 256;                                     // of mpc_track_linear_window_kernel
+    const long sblocks = ((long)batch * ((long)(N + 1) * n_user + (long)N * m_user) + 255) / 256;   // of mpc_rti_shift_kernel
+    if (gblocks > 0x7fffffffL || sblocks > 0x7fffffffL || (long)batch * n_levels > 0x7fffffffL)
+        return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
+    hipStream_t st = (hipStream_t)stream;
+    {   // every instance is its own problem: the map must be the identity (one small copy, as mpc_check_map's)
+        static thread_local std::vector<int32_t> h;
+        h.resize((size_t)batch);
+        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ZM_HIP_CHECK(hipStreamSynchronize(st));
+        for (int64_t i = 0; i < batch; ++i)
+            if (h[i] != (int32_t)i)
+                return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d; every instance is its own problem here", fn, (long long)i,
+                                 (int)h[i]);
+    }
+
+    // workspace: the five blocks of a tracking solve, then -- unless the predictions are kept -- the rollout every step overwrites
+    double* gbuf = workspace + 4L * batch * N * W;
+    double* scratch = workspace + 5L * batch * N * W;
+    const long xsz = (long)batch * (N + 1) * n, usz = (long)batch * N * m;
+    const long xstep = xPred ? xsz : 0, ustep = uPred ? usz : 0;
+    double* xroll = xPred ? xPred : scratch;
+    double* uroll = uPred ? uPred : scratch + xsz;
+    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
+    const MpcArgs g{x0, 1.0, eps_abs, eps_rel, eps_prim_inf, max_iter, 0, workspace, xroll, uroll, (int*)status, (int*)iters, resid, (long)batch,
+                    N, n_levels, level0, rho_step, alpha};
+    const MpcProb pb{(const int*)problem, rho_p};
+    const int warm = warm_start == 2 ? 2 : (warm_start ? 1 : 0);
+    hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, x0, (long)n, (const double*)nullptr, x_lb, x_ub,
+                       (const int*)problem, clip_tol, states, (const double*)nullptr, 0L, (double*)nullptr, (long)batch, n, m);
+    ZM_HIP_CHECK(hipGetLastError());
+    for (int s = 0; s < steps; ++s) {
+        if ((rc = mpc_relinearize_enqueue(md, xPlan, uPlan, A, B, c, (long)batch, N, n, m, st)) != ZM_OK) return rc;
+        hipLaunchKernelGGL((mpc_setup_ltv_kernel<SN, SM>), dim3((unsigned)(batch * n_levels)), dim3(256), 0, st, A, B, c, Q, R, Qf, rho_tab,
+                           n_levels, N, n, m, K, Minv, D, ABt);
+        ZM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(mpc_track_linear_window_kernel, dim3((unsigned)gblocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
+                           (long)batch, N, n, m, (long)xref_rows, (long)uref_rows, (long)s, gbuf);
+        ZM_HIP_CHECK(hipGetLastError());
+        MpcArgs gs = g;
+        gs.x0 = states + (long)s * batch * n;
+        gs.xTraj = xroll + s * xstep;
+        gs.uTraj = uroll + s * ustep;
+        gs.status = g.status + (long)s * batch;
+        gs.iters = g.iters + (long)s * batch;
+        gs.warm = s ? warm : 0;
+        rc = mpc_wave_ltv_dispatch(t, gs, pb, MpcTrack{gbuf}, MpcLtv{c, D, ABt}, n, m, st);
+        if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
+        if (rc != ZM_OK) return rc;
+        hipLaunchKernelGGL(mpc_rti_plant_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, pl, gs.x0, (long)n, gs.uTraj,
+                           (long)N * m, disturbance ? disturbance + (long)s * batch * n : nullptr, x_lb, x_ub, clip_tol,
+                           states + (long)(s + 1) * batch * n, n, inputs + (long)s * batch * m, m, (long)batch);
+        ZM_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(mpc_rti_shift_kernel, dim3((unsigned)sblocks), dim3(256), 0, st, gs.xTraj, gs.uTraj, xPlan, uPlan, (long)batch, N,
+                           n_user, m_user, n, m);
+        ZM_HIP_CHECK(hipGetLastError());
+    }
+    return ZM_OK;
+}
+
 }  // namespace zm
 
 extern "C" int zm_mpc_setup_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
@@ -750,4 +936,43 @@ extern "C" int zm_mpc_closed_loop_f64(const double* A, const double* B, const do
                                x0, xRef, uRef, xref_rows, uref_rows, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter,
                                warm_start, steps, clip_tol, disturbance, workspace, states, inputs, status, iters, xPred, uPred, batch, N,
                                n, m, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// real-time-iteration nonlinear MPC: a registered model expanded about a plan, per instance, at every step
+// ---------------------------------------------------------------------------------------------------------------------
+
+extern "C" int zm_model_step_f64(const zm_model_t* model, const double* x, const double* u, double* xNext, int64_t batch, void* stream) {
+    const char* fn = "zm_model_step_f64";
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    zm_model_t md;
+    const int rc = zm::check_model(model, md, fn);
+    if (rc != ZM_OK) return rc;
+    if (!x || !u || !xNext) return zm::set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if (batch < 0 || (batch + 63) / 64 > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "%s: bad size", fn);
+    hipLaunchKernelGGL(zm::mpc_rti_plant_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, md, x, (long)md.n, u,
+                       (long)md.m, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, -1.0, xNext, md.n,
+                       (double*)nullptr, 0, (long)batch);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_mpc_relinearize_f64(const zm_model_t* model, const double* xPlan, const double* uPlan, double* A, double* B, double* c,
+                                      int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream) {
+    return zm::mpc_relinearize("zm_mpc_relinearize_f64", model, xPlan, uPlan, A, B, c, batch, N, n_user, m_user, ns, mc, stream);
+}
+
+extern "C" int zm_mpc_rti_f64(const zm_model_t* model, const zm_model_t* plant, double* xPlan, double* uPlan, double* A, double* B, double* c,
+                              const double* Q, const double* R, const double* Qf, const double* rho_tab, double* K, double* Minv,
+                              double* D, double* ABt, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                              const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
+                              const double* uRef, int xref_rows, int uref_rows, const double* rho_p, const int32_t* problem,
+                              double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, int steps,
+                              double clip_tol, const double* disturbance, double* workspace, double* states, double* inputs,
+                              int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred, int64_t batch, int N,
+                              int n_user, int m_user, int ns, int mc, void* stream) {
+    return zm::mpc_rti("zm_mpc_rti_f64", model, plant, xPlan, uPlan, A, B, c, Q, R, Qf, rho_tab, K, Minv, D, ABt, n_levels, level0, rho_step,
+                       alpha, x_lb, x_ub, u_lb, u_ub, x0, xRef, uRef, xref_rows, uref_rows, rho_p, problem, eps_abs, eps_rel, eps_prim_inf,
+                       max_iter, warm_start, steps, clip_tol, disturbance, workspace, states, inputs, status, iters, resid, xPred, uPred,
+                       batch, N, n_user, m_user, ns, mc, stream);
 }

@@ -98,4 +98,11 @@ int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcP
 int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
                           hipStream_t st);
 
+// linearize.hip (where the model expansions live): the argument check of the entry points that take a registered model, and the launch
+// of mpc_rti_relinearize_kernel -- the expansion of `md` about every stage of the plans xPlan (batch,N+1,n), uPlan (batch,N,m), written
+// into A (batch,N,ns,ns), B (batch,N,ns,mc), c (batch,N,ns) (n = md.n <= ns, m = md.m <= mc).
+int check_model(const zm_model_t* model, zm_model_t& md, const char* who);
+int mpc_relinearize_enqueue(const zm_model_t& md, const double* xPlan, const double* uPlan, double* A, double* B, double* c, long batch,
+                            int N, int ns, int mc, hipStream_t st);
+
 }  // namespace zm

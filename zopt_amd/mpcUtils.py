@@ -537,7 +537,8 @@ class ltvMpc(lqrMpc):
         self._tables = {}
 
     def simulate(self, *args, **kwargs):
-        raise NotImplementedError("ltvMpc.simulate: a moving window needs new tables at every step; loop over update() and solve()")
+        raise NotImplementedError("ltvMpc.simulate: a moving window needs new tables at every step; loop over update() and solve(), or -- "
+                                  "for a registered model linearised about the moving plan -- call realTimeIteration()")
 
     def _device_problem(self, rho, adaptive):   # (a single problem is the per-problem form with P = ())
         raise NotImplementedError
@@ -549,6 +550,20 @@ class ltvMpc(lqrMpc):
                          for k in _ARRAYS + ("c",)}
         return self._dev
 
+    def _empty_tables(self, rho, adaptive):
+        """The tuple `_device_problem_batched` keeps, its tables allocated and not yet written."""
+        d = self._device_data()
+        Pn = int(np.prod(self.P))
+        nl = self.N_LEVELS if adaptive else 1
+        l0 = nl // 2
+        dev = d["A"].device
+        fac = np.array([self.RHO_STEP ** (l - l0) for l in range(nl)])
+        rtab = arr.to_device(rho.reshape(Pn, 1) * fac[None, :], torch.float64, dev)
+        E = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        K, Mi, D = E(Pn, nl, self.N, self.m, self.n), E(Pn, nl, self.N, self.m, self.m), E(Pn, nl, self.N, self.n)
+        ABt = E(Pn, self.N, self.n + self.m, self.n)
+        return (K, Mi, nl, l0, arr.to_device(rho.reshape(Pn), torch.float64, dev), rtab, D, ABt)
+
     def _device_problem_batched(self, rho, adaptive):
         """Device copies of the data and the tables of every (problem, penalty level): ONE setup launch.  The tuple lqrMpc keeps, then
         D (P, L, N, n) and ABt (P, N, n + m, n)."""
@@ -556,22 +571,273 @@ class ltvMpc(lqrMpc):
         d = self._device_data()
         key = (rho.tobytes(), bool(adaptive))
         if key not in self._tables:
-            Pn = int(np.prod(self.P))
-            nl = self.N_LEVELS if adaptive else 1
-            l0 = nl // 2
-            dev = d["A"].device
-            fac = np.array([self.RHO_STEP ** (l - l0) for l in range(nl)])
-            rtab = arr.to_device(rho.reshape(Pn, 1) * fac[None, :], torch.float64, dev)
-            E = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-            K, Mi, D = E(Pn, nl, self.N, self.m, self.n), E(Pn, nl, self.N, self.m, self.m), E(Pn, nl, self.N, self.n)
-            ABt = E(Pn, self.N, self.n + self.m, self.n)
+            tabs = self._empty_tables(rho, adaptive)
+            K, Mi, nl, _, _, rtab, D, ABt = tabs
             rc = _lib.lib().zm_mpc_setup_ltv_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["c"].data_ptr(), d["Q"].data_ptr(),
-                                                 d["R"].data_ptr(), d["Qf"].data_ptr(), rtab.data_ptr(), Pn, nl, self.N, self.n, self.m,
-                                                 K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(),
+                                                 d["R"].data_ptr(), d["Qf"].data_ptr(), rtab.data_ptr(), int(np.prod(self.P)), nl, self.N,
+                                                 self.n, self.m, K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(),
                                                  ctypes.c_void_p(arr.stream_ptr(K)))
             _lib.check(rc, "ltvMpc setup")
-            self._tables[key] = (K, Mi, nl, l0, arr.to_device(rho.reshape(Pn), torch.float64, dev), rtab, D, ABt)
+            self._tables[key] = tabs
         return d, self._tables[key]
+
+    # ---- real-time iteration: a registered model linearised about the moving plan --------------------------------------------------
+
+    @classmethod
+    def fromModel(cls, model, plan, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None):
+        """The problem of a registered model (models.QuadcopterEuler, models.QuadcopterRigidBody with dt > 0, models.LinearModel; n <= 12,
+        m <= 4) linearised about `plan`, a Trajectory (xTraj (..., N+1, n), uTraj (..., N, m)) in absolute coordinates: what
+        `fromExpansion(AffineDynamics.from_trajectory(model, plan), plan, ...)` builds, with c_k formed on the device as `relinearize` forms
+        it.  N is the plan's stage count and the plan's leading axes the problem shape (every trajectory is its own problem).  The
+        expansion runs on the device once and is copied to the host for the constructor, which is host-only."""
+        n, m = _model_shape("ltvMpc.fromModel", model)
+        xs, us, lead = _plan_shapes("ltvMpc.fromModel", plan, None, n, m)
+        N = us[-2]
+        arr.require_gpu()
+        Bn = int(np.prod(lead))
+        xP = arr.to_device(tuple.__getitem__(plan, 0), torch.float64).expand(lead + (N + 1, n)).reshape(Bn, N + 1, n).contiguous()
+        uP = arr.to_device(tuple.__getitem__(plan, 1), torch.float64, xP.device).expand(lead + (N, m)).reshape(Bn, N, m).contiguous()
+        Z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=xP.device)
+        A, B, c = Z(Bn, N, n, n), Z(Bn, N, n, m), Z(Bn, N, n)
+        cs = model.c_struct()
+        rc = _lib.lib().zm_mpc_relinearize_f64(ctypes.addressof(cs), xP.data_ptr(), uP.data_ptr(), A.data_ptr(), B.data_ptr(), c.data_ptr(),
+                                               Bn, N, n, m, n, m, ctypes.c_void_p(arr.stream_ptr(xP)))
+        _lib.check(rc, "ltvMpc.fromModel")
+        host = lambda t, tail: t.cpu().numpy().reshape(lead + tail)
+        return cls(host(A, (N, n, n)), host(B, (N, n, m)), Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=host(c, (N, n)))
+
+    def relinearize(self, model, plan):
+        """The next linearisation of a real-time-iteration loop, on the device: `model` expanded about `plan` (a Trajectory, xTraj
+        (..., N+1, n), uTraj (..., N, m) in absolute coordinates, leading axes that broadcast to the problem shape) straight into the
+        problem's device arrays -- A_k = f_x, B_k = f_u, c_k = f - f_x xbar_k - f_u ubar_k (zm_mpc_relinearize_f64) -- the device-side
+        equivalent of `update(A=f_x, B=f_u, c=c)` with device tensors: the host attributes A, B, c keep the data they had, the tables are
+        rebuilt before the next solve, the warm-start workspace survives.  NumPy arrays or torch tensors; contiguous device tensors of
+        the problem's shape are read in place."""
+        n, m, N = self._n_user, self._m_user, self.N
+        _model_shape("ltvMpc.relinearize", model, (n, m))
+        _plan_shapes("ltvMpc.relinearize", plan, N, n, m, self.P)
+        arr.require_gpu()
+        d = self._device_data()
+        Pn = int(np.prod(self.P))
+        dev = d["A"].device
+        xP = arr.to_device(tuple.__getitem__(plan, 0), torch.float64, dev).expand(self.P + (N + 1, n)).reshape(Pn, N + 1, n).contiguous()
+        uP = arr.to_device(tuple.__getitem__(plan, 1), torch.float64, dev).expand(self.P + (N, m)).reshape(Pn, N, m).contiguous()
+        cs = model.c_struct()
+        rc = _lib.lib().zm_mpc_relinearize_f64(ctypes.addressof(cs), xP.data_ptr(), uP.data_ptr(), d["A"].data_ptr(), d["B"].data_ptr(),
+                                               d["c"].data_ptr(), Pn, N, n, m, self.n, self.m, ctypes.c_void_p(arr.stream_ptr(xP)))
+        _lib.check(rc, "ltvMpc.relinearize")
+        self._tables = {}
+
+    def realTimeIteration(self, model, x0, steps, plan=None, plant=None, disturbance=None, clip_tol=1e-6, return_predictions=False,
+                          xRef=None, uRef=None, **solver_opts):
+        """
+        Real-time-iteration nonlinear MPC as one call, entirely on the device (zm_mpc_rti_f64): linearise `model` about the shifted
+        previous plan, solve the stage-varying QP from the shifted iterates, apply the first input through the nonlinear `plant`, repeat.
+        It replaces this loop of public calls, and gives its results bit for bit:
+
+            plan given;  x = x0
+            for s in range(steps):
+                if clip_tol is not None: x = clip(x, x_lb + clip_tol, x_ub - clip_tol)
+                xTraj[s] = x
+                self.relinearize(model, plan)
+                u, traj, status[s] = self.solve(x, window s of xRef / uRef, warm_start=(False if s == 0 else W), **solver_opts)
+                uTraj[s] = u;  iterations[s] = self.last_iterations
+                x = modelStep(plant, x, u) + (disturbance[s] if disturbance is not None else 0)
+                plan = Trajectory(rows 1.. of traj.xTraj with the last repeated, rows 1.. of traj.uTraj with the last repeated)
+            xTraj[steps] = clip(x, ...) if clip_tol is not None else x
+
+        whatever the status of a step (a step that is not "optimal" still leaves a rollout, and the step after it starts cold).  The head
+        of the shifted plan is the PREDICTED successor, not the measured one.  The object is left as that loop leaves it: its device
+        dynamics are the last linearisation, its tables, warm-start workspace, `last_iterations` and `last_residuals` those of the last
+        step; the host attributes A, B, c are untouched (as `update` with device tensors leaves them).
+
+        Arguments
+        ---------
+            model : the registered model that is linearised, of the problem's (n, m)
+            x0 : initial states, (..., n) with leading axes that broadcast to the problem shape: every instance is its own problem
+            steps : number S of MPC steps, >= 1
+            plan : the first expansion point, a Trajectory (xTraj (..., N+1, n), uTraj (..., N, m)) in absolute coordinates (it is not
+                modified); None: the clipped x0 at every stage, with the first N rows of uRef as inputs (zeros without uRef)
+            plant : the model the state is advanced with, of the same (n, m) (e.g. the quadcopter with wind); None: `model`
+            disturbance (..., S, n), clip_tol, return_predictions, xRef (..., S + N, n), uRef (..., S + N - 1, m), **solver_opts :
+                as `lqrMpc.simulate` takes them
+
+        Returns
+        -------
+            MpcClosedLoop, as `lqrMpc.simulate` returns it
+        """
+        S = int(steps)
+        if S < 1:
+            raise ValueError(f"steps must be at least 1, got {steps}")
+        if clip_tol is not None and not (float(clip_tol) >= 0.0):
+            raise ValueError(f"clip_tol must be non-negative (or None for no clip), got {clip_tol}")
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(solver_opts, "shift")
+        if isinstance(xRef, Trajectory) or isinstance(uRef, Trajectory):
+            raise ValueError("realTimeIteration takes xRef (..., steps + N, n) and uRef (..., steps + N - 1, m) as arrays, not a Trajectory")
+        N, n, m, nu, mu = self.N, self.n, self.m, self._n_user, self._m_user
+        _model_shape("ltvMpc.realTimeIteration", model, (nu, mu))
+        if plant is not None:
+            _model_shape("ltvMpc.realTimeIteration", plant, (nu, mu), "plant")
+
+        # 1. shapes: everything broadcasts to the problem shape (every instance is its own problem)
+        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+        shp = shape_of(x0)
+        if len(shp) < 1 or shp[-1] != nu:
+            raise ValueError(f"x0 has shape {shp}, expected (..., {nu})")
+        leads = {"x0": (shp, shp[:-1])}
+        for name, X, want in (("disturbance", disturbance, (S, nu)), ("xRef", xRef, (S + N, nu)), ("uRef", uRef, (S + N - 1, mu))):
+            if X is not None:
+                sh = shape_of(X)
+                if len(sh) < 2 or sh[-2:] != want:
+                    raise ValueError(f"{name} has shape {sh}, expected (..., {want[0]}, {want[1]}) for steps = {S}, N = {N}")
+                leads[name] = (sh, sh[:-2])
+        if plan is not None:
+            xs, us, pl = _plan_shapes("ltvMpc.realTimeIteration", plan, N, nu, mu)
+            leads["plan.xTraj"], leads["plan.uTraj"] = (xs, pl), (us, pl)
+        try:
+            ok = np.broadcast_shapes(*(l for _, l in leads.values()), self.P) == self.P
+        except ValueError:
+            ok = False
+        if not ok:
+            who = ", ".join(f"{k} of shape {sh}" for k, (sh, _) in leads.items())
+            raise ValueError(who + f" do not broadcast to the problem shape {self.P} (every instance is its own problem): inconsistent shapes")
+        lead = self.P
+        Bn = int(np.prod(lead))
+        arr.require_gpu()
+
+        # 2. the problem on the device; the tables of every step are written by the call (those of the last step stay, as a solve's do)
+        d = self._device_data()
+        dev = d["A"].device
+        tabs = self._empty_tables(rho, adaptive)
+        K, Mi, n_levels, level0, drho, rtab, D, ABt = tabs
+
+        # 3. one row per instance, the padded components zero
+        def flat(X, tail, width):
+            t = arr.to_device(X, torch.float64, dev)
+            t = t.expand(lead + tail).reshape((Bn,) + tail)
+            if width != tail[-1]:
+                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
+            return t.contiguous()
+        dx0 = flat(x0, (nu,), n)
+        dxr = None if xRef is None else flat(xRef, (S + N, nu), n)
+        dur = None if uRef is None else flat(uRef, (S + N - 1, mu), m)
+        dw = None if disturbance is None else flat(disturbance, (S, nu), n).transpose(0, 1).contiguous()   # step-major
+        if plan is not None:   # (copies: the call moves its plan on)
+            xP = flat(tuple.__getitem__(plan, 0), (N + 1, nu), nu).clone()
+            uP = flat(tuple.__getitem__(plan, 1), (N, mu), mu).clone()
+        else:
+            xh = dx0[:, :nu]
+            if clip_tol is not None:
+                xh = torch.minimum(torch.maximum(xh, d["x_lb"][:, :nu] + float(clip_tol)), d["x_ub"][:, :nu] - float(clip_tol))
+            xP = xh[:, None, :].expand(Bn, N + 1, nu).contiguous()
+            uP = torch.zeros((Bn, N, mu), dtype=torch.float64, device=dev) if dur is None else dur[:, :N, :mu].contiguous()
+        prob = torch.arange(Bn, dtype=torch.int32, device=dev)
+
+        # 4. outputs (step-major on the device); the workspace is the object's: step 0 starts cold, a later `solve` may start warm from it
+        f64 = dict(dtype=torch.float64, device=dev)
+        xs = torch.empty((S + 1, Bn, n), **f64)
+        us = torch.empty((S, Bn, m), **f64)
+        st = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+        its = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+        res = torch.empty((Bn, 2), **f64)
+        xp = torch.empty((S, Bn, N + 1, n), **f64) if return_predictions else None
+        up = torch.empty((S, Bn, N, m), **f64) if return_predictions else None
+        ws = torch.empty(5 * Bn * N * (n + m) + (0 if return_predictions else Bn * ((N + 1) * n + N * m)), **f64)
+        self._ws = ((("tracking", lead), str(dev), rho.tobytes(), adaptive), ws)
+        self._tables = {(rho.tobytes(), bool(adaptive)): tabs}
+
+        # 5. the C call
+        if Bn > 0:
+            p = lambda k: d[k].data_ptr()
+            ptr = lambda t: None if t is None else t.data_ptr()
+            cs = model.c_struct()
+            cp = None if plant is None else plant.c_struct()
+            rc = _lib.lib().zm_mpc_rti_f64(
+                ctypes.addressof(cs), None if cp is None else ctypes.addressof(cp), xP.data_ptr(), uP.data_ptr(), p("A"), p("B"), p("c"),
+                p("Q"), p("R"), p("Qf"), rtab.data_ptr(), K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(), n_levels, level0,
+                self.RHO_STEP, alpha, p("x_lb"), p("x_ub"), p("u_lb"), p("u_ub"), dx0.data_ptr(), ptr(dxr), ptr(dur), S + N, S + N - 1,
+                drho.data_ptr(), prob.data_ptr(), eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, S,
+                -1.0 if clip_tol is None else float(clip_tol), ptr(dw), ws.data_ptr(), xs.data_ptr(), us.data_ptr(), st.data_ptr(),
+                its.data_ptr(), res.data_ptr(), ptr(xp), ptr(up), Bn, N, nu, mu, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+            _lib.check(rc, "ltvMpc.realTimeIteration")
+
+        # 6. results: batch-leading views of the step-major arrays; the object's record of its last solve
+        self.last_iterations = its[S - 1].reshape(lead).cpu().numpy()
+        self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
+        view = lambda t, tail, width: arr.result_like(t.transpose(0, 1).reshape(lead + tail)[..., :width], x0)
+        codes = st.transpose(0, 1).reshape(lead + (S,)).cpu().numpy()
+        status = np.vectorize(_STATUS.get, otypes=[object])(codes) if Bn > 0 else np.empty(lead + (S,), dtype=object)
+        pred = None
+        if return_predictions:
+            pred = Trajectory(view(xp, (S, N + 1, n), nu), view(up, (S, N, m), mu))
+        return MpcClosedLoop(view(xs, (S + 1, n), nu), view(us, (S, m), mu), status, view(its, (S,), None), pred)
+
+
+def modelStep(model, x, u):
+    """x+ = f(x, u): one step of a registered model (models.QuadcopterEuler, models.QuadcopterRigidBody, models.LinearModel; n <= 12,
+    m <= 4) by its step function on the device (zm_model_step_f64) -- the plant of `ltvMpc.realTimeIteration` as a call of its own.
+    x (..., n), u (..., m) with leading axes that broadcast against each other; NumPy in, NumPy out, device tensors in, device tensors out."""
+    n, m = _model_shape("modelStep", model)
+    shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+    sx, su = shape_of(x), shape_of(u)
+    if len(sx) < 1 or sx[-1] != n or len(su) < 1 or su[-1] != m:
+        raise ValueError(f"modelStep: x has shape {sx}, u has shape {su}, expected (..., {n}) and (..., {m})")
+    try:
+        lead = tuple(int(v) for v in np.broadcast_shapes(sx[:-1], su[:-1]))
+    except ValueError:
+        raise ValueError(f"modelStep: x of shape {sx}, u of shape {su} do not broadcast against each other: inconsistent shapes") from None
+    arr.require_gpu()
+    Bn = int(np.prod(lead))
+    dx = arr.to_device(x, torch.float64)
+    du = arr.to_device(u, torch.float64, dx.device)
+    dx = dx.expand(lead + (n,)).reshape(Bn, n).contiguous()
+    du = du.expand(lead + (m,)).reshape(Bn, m).contiguous()
+    out = torch.empty((Bn, n), dtype=torch.float64, device=dx.device)
+    cs = model.c_struct()
+    rc = _lib.lib().zm_model_step_f64(ctypes.addressof(cs), dx.data_ptr(), du.data_ptr(), out.data_ptr(), Bn,
+                                      ctypes.c_void_p(arr.stream_ptr(dx)))
+    _lib.check(rc, "modelStep")
+    return arr.result_like(out.reshape(lead + (n,)), x)
+
+
+def _model_shape(who, model, want=None, what="model"):
+    """(n, m) of a registered model handle; ValueError outside the kernels' (12, 4), for a quadcopter without a step, or if it is not `want`"""
+    n, m = getattr(model, "n", None), getattr(model, "m", None)
+    if not callable(getattr(model, "c_struct", None)) or n is None or m is None:
+        raise ValueError(f"{who}: the {what} must be a registered model (zopt_amd.models), got {type(model).__name__}")
+    n, m = int(n), int(m)
+    if n < 1 or m < 1 or n > 12 or m > 4:
+        raise ValueError(f"{who}: the {what} has (n={n}, m={m}), outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")
+    if hasattr(model, "dt") and not (model.dt > 0.0):
+        raise ValueError(f"{who}: the {what} needs a step dt > 0 (dt = {model.dt} is its continuous derivative)")
+    if want is not None and (n, m) != tuple(want):
+        raise ValueError(f"{who}: the {what} has (n={n}, m={m}), the problem (n={want[0]}, m={want[1]})")
+    return n, m
+
+
+def _plan_shapes(who, plan, N, n, m, P=None):
+    """(shape of xTraj, shape of uTraj, their common leading axes) of a plan (xTraj (..., N+1, n), uTraj (..., N, m)); N None: the plan's
+    own stage count; P: the leading axes must broadcast to it"""
+    try:
+        xT, uT = tuple.__getitem__(plan, 0), tuple.__getitem__(plan, 1)
+    except Exception:
+        raise ValueError(f"{who}: plan must be a Trajectory (xTraj, uTraj), got {type(plan).__name__}") from None
+    shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+    xs, us = shape_of(xT), shape_of(uT)
+    stages = us[-2] if (N is None and len(us) >= 2) else N
+    ok = len(xs) >= 2 and len(us) >= 2 and stages is not None and stages >= 1 and xs[-2:] == (stages + 1, n) and us[-2:] == (stages, m)
+    lead = None
+    if ok:
+        try:
+            lead = tuple(int(v) for v in np.broadcast_shapes(xs[:-2], us[:-2]))
+            ok = P is None or np.broadcast_shapes(lead, P) == P
+        except ValueError:
+            ok = False
+    if not ok:
+        want = "N" if stages is None else str(stages)
+        raise ValueError(f"{who}: plan has xTraj of shape {xs} and uTraj of shape {us}, expected (..., {want} + 1, {n}) and (..., {want}, {m})"
+                         + ("" if P is None else f" with leading axes that broadcast to the problem shape {P}"))
+    return xs, us, lead
 
 
 def _ltv_problem_shape(data, N):
