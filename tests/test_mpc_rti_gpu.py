@@ -347,6 +347,31 @@ def test_abi_refusals(gpu):
     assert lib.zm_model_step_f64(md, d, d, None, 1, None) == EINVAL and lib.zm_model_step_f64(md, None, None, None, 0, None) == 0
 
 
+def test_abi_refusals_behind_the_map_read_back(gpu):
+    """The refusals that need a device, with the full message: the entries copy the instance -> problem map to the host before they
+    launch anything, so the map is real device memory and every other pointer a dummy (tests/test_mpc_refusals.py: the argument sets,
+    batch 4, N = 3, shape (2, 1); its rows end before the copy).  Nothing is launched."""
+    from tests.test_mpc_refusals import BAT, CL, D, LTV, RTI, TRK, _args
+    lib = gpu.lib.lib()
+    EINVAL, EUNSUP = gpu.lib.ZM_EINVAL, gpu.lib.ZM_EUNSUPPORTED
+    dmap = lambda *v: gpu.torch.tensor(v, dtype=gpu.torch.int32, device="cuda")
+    past, swapped, fine = dmap(0, 1, 2, 1), dmap(0, 1, 3, 2), dmap(0, 1, 1, 0)
+    for entry, over, rc, msg in (
+            (BAT, dict(problem=past), EINVAL, "instance 2 maps to problem 2 outside [0, 2)"),
+            (BAT, dict(problem=dmap(0, -1, 2, 1)), EINVAL, "instance 1 maps to problem -1 outside [0, 2)"),
+            (TRK, dict(problem=past, rho_p=D, P=2), EINVAL, "instance 2 maps to problem 2 outside [0, 2)"),
+            (LTV, dict(problem=past, P=2), EINVAL, "instance 2 maps to problem 2 outside [0, 2)"),
+            (CL, dict(problem=past, rho_p=D, P=2), EINVAL, "instance 2 maps to problem 2 outside [0, 2)"),
+            (RTI, dict(problem=swapped), EINVAL, "instance 2 maps to problem 3; every instance is its own problem here"),
+            # (the shape is looked up after the map is read, the horizon of zm_mpc_solve_ltv_f64 before)
+            (BAT, dict(problem=fine, n=3, m=3), EUNSUP, "(n=3, m=3) not among the compiled shapes"),
+            (BAT, dict(problem=past, n=3, m=3), EINVAL, "instance 2 maps to problem 2 outside [0, 2)"),
+            (LTV, dict(problem=past, P=2, N=76), EUNSUP, "N=76 beyond the horizons whose iterates fit LDS (N <= 75)")):
+        args = _args(entry, {k: v.data_ptr() if hasattr(v, "data_ptr") else v for k, v in over.items()})
+        assert getattr(lib, entry)(*args) == rc, (entry, over)
+        assert lib.zm_last_error().decode() == f"{entry}: {msg}"
+
+
 # 5. streams -----------------------------------------------------------------------------------------------------------------------------
 def test_a_side_stream_gives_the_same_bits(gpu):
     torch = gpu.torch

@@ -439,22 +439,36 @@ __global__ __launch_bounds__(256) void mpc_rti_shift_kernel(const double* __rest
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-// host side: one shape ladder, one launcher, one routine behind the three solve entry points
+// host side: every solve and run entry point (relaxed, batched, tracking, ltv; closed loop, rti) fills one call record by name; the
+// checks, the kernels' argument blocks, the workspace layout and the per-step offsets are each written once and read from it
 // ----------------------------------------------------------------------------------------------------------------
 
-// f(Int<NS>, Int<MC>) for the compiled shape (n, m); ZM_EUNSUPPORTED for any other
-template <typename F>
-static int for_mpc_shape(int n, int m, F f) {
-    if (n == 24 && m == 8) return f(Int<24>{}, Int<8>{});   // beyond the 16-index tile: lane per instance, registers + scratch
-    if (n == 12 && m == 4) return f(Int<12>{}, Int<4>{});
-    if (n == 8 && m == 4) return f(Int<8>{}, Int<4>{});
-    if (n == 4 && m == 2) return f(Int<4>{}, Int<2>{});
-    if (n == 4 && m == 1) return f(Int<4>{}, Int<1>{});
-    if (n == 2 && m == 2) return f(Int<2>{}, Int<2>{});
-    if (n == 2 && m == 1) return f(Int<2>{}, Int<1>{});
-    if (n == 1 && m == 1) return f(Int<1>{}, Int<1>{});
-    return ZM_EUNSUPPORTED;
-}
+// What an MPC entry point receives.  Host only: no kernel takes it.  An entry fills the fields it has and leaves the rest zero.
+struct MpcCall {
+    const char* fn;                                                    // the entry point's name, the prefix of its error messages
+    const double *A, *B, *c, *Q, *R, *Qf, *x_lb, *x_ub, *u_lb, *u_ub;  // the problem(s)
+    const double *K, *Minv, *D, *ABt, *rho_tab;                        // the tables of every penalty level
+    int n_levels, level0;
+    double rho_step, alpha, rho;                                       // rho: the shared problem's penalty ...
+    const double* rho_p;                                               // ... per-problem data: one per problem, with the map
+    const int32_t* problem;                                            // instance -> problem in [0, P)
+    int64_t P;
+    const double *x0, *xRef, *uRef;
+    int xref_rows, uref_rows;                                          // rows per instance of a run's references
+    double eps_abs, eps_rel, eps_prim_inf;
+    int max_iter, warm_start;
+    int steps;                                                         // a run: its steps, MpcLoop's clip_tol and disturbance
+    double clip_tol;
+    const double* disturbance;
+    double* workspace;
+    double *xTraj, *uTraj, *resid;                                     // outputs of a solve (resid also of zm_mpc_rti_f64) ...
+    double *states, *inputs, *xPred, *uPred;                           // ... of a run
+    int32_t *status, *iters;
+    int64_t batch;
+    int N, n, m;                                                       // (n, m): the compiled shape the data is laid out in
+    int n_user, m_user;                                                // zm_mpc_rti_f64: the model's own (n, m) inside it
+    void* stream;
+};
 
 // pb != nullptr: per-problem data; trk != nullptr: the tracking variants
 template <int NS, int MC>
@@ -470,39 +484,118 @@ static int launch_mpc(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, con
     return pb ? go(mpc_solve_batched_kernel<NS, MC>, *pb) : go(mpc_solve_kernel<NS, MC>);
 }
 
-// The argument checks of the solve entry points and of zm_mpc_closed_loop_f64, all before any launch.  `fn` is the entry point's name,
-// the prefix of its error messages; `outputs` is false if one of the entry point's own output pointers is NULL.
-static int mpc_check_args(const char* fn, bool per_problem, bool tracking, bool outputs, const double* A, const double* B, const double* Q,
-                          const double* R, const double* Qf, const double* K, const double* Minv, int n_levels, int level0, double rho_step,
-                          double alpha, const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub, const double* x0,
-                          double rho, const double* rho_p, const int32_t* problem, int64_t P, int max_iter, const double* workspace,
-                          int64_t batch, int N, int n, int m) {
-    if (!(alpha > 0.0 && alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", fn);
-    if (!A || !B || !K || !Minv || !x_lb || !x_ub || !u_lb || !u_ub || !x0 || !workspace || !outputs ||
-        (tracking && (!Q || !R || !Qf)) || (per_problem && (!rho_p || !problem)))
-        return set_error(ZM_EINVAL, "%s: null pointer", fn);
-    if ((problem == nullptr) != (rho_p == nullptr))
-        return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", fn);
-    if (batch < 0 || N < 1 || max_iter < 0 || (tracking && (n < 1 || m < 1)) || (problem ? P < 1 : !(rho > 0.0)))
-        return set_error(ZM_EINVAL, tracking ? "%s: bad size / rho" : "%s: bad size", fn);
-    if (n_levels < 1 || level0 < 0 || level0 >= n_levels || (n_levels > 1 && !(rho_step > 1.0)))
-        return set_error(ZM_EINVAL, "%s: bad penalty levels", fn);
-    const long blocks = ((long)batch * N * ((long)n + m) + 255) / 256;   // of mpc_track_linear_kernel
-    if (tracking && blocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
+static long blocks256(long threads) { return (threads + 255) / 256; }
+
+// The argument checks every solve and run entry point shares, all before any launch.  The flags are the entry's decisions:
+// per_problem -- the map and rho_p are required; tracking -- Q, R, Qf are required and n, m are checked; outputs -- false if one of the
+// entry's own output pointers is NULL.
+static int mpc_check_args(const MpcCall& a, bool per_problem, bool tracking, bool outputs) {
+    if (!(a.alpha > 0.0 && a.alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", a.fn);
+    if (!a.A || !a.B || !a.K || !a.Minv || !a.x_lb || !a.x_ub || !a.u_lb || !a.u_ub || !a.x0 || !a.workspace || !outputs ||
+        (tracking && (!a.Q || !a.R || !a.Qf)) || (per_problem && (!a.rho_p || !a.problem)))
+        return set_error(ZM_EINVAL, "%s: null pointer", a.fn);
+    if ((a.problem == nullptr) != (a.rho_p == nullptr))
+        return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", a.fn);
+    if (a.batch < 0 || a.N < 1 || a.max_iter < 0 || (tracking && (a.n < 1 || a.m < 1)) || (a.problem ? a.P < 1 : !(a.rho > 0.0)))
+        return set_error(ZM_EINVAL, tracking ? "%s: bad size / rho" : "%s: bad size", a.fn);
+    if (a.n_levels < 1 || a.level0 < 0 || a.level0 >= a.n_levels || (a.n_levels > 1 && !(a.rho_step > 1.0)))
+        return set_error(ZM_EINVAL, "%s: bad penalty levels", a.fn);
+    if (tracking && blocks256((long)a.batch * a.N * ((long)a.n + a.m)) > 0x7fffffffL)   // of mpc_track_linear_kernel
+        return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", a.fn);
     return ZM_OK;
 }
 
-// every instance's problem index must lie in [0, P): the kernels offset every table by it, so it is checked here, on the host,
-// before anything is launched (one small copy of the index map; the solve's own results come back through a sync anyway)
-static int mpc_check_map(const char* fn, const int32_t* problem, int64_t P, int64_t batch, hipStream_t st) {
-    if (!problem) return ZM_OK;
+// The checks of a run (zm_mpc_closed_loop_f64, zm_mpc_rti_f64) that follow mpc_check_args.  `sizes_ok` is the entry's own test of its
+// sizes, refused after `steps` and before the prediction arrays.
+static int mpc_check_run(const MpcCall& a, bool sizes_ok) {
+    if (a.steps < 1) return set_error(ZM_EINVAL, "%s: steps must be at least 1", a.fn);
+    if (!sizes_ok) return set_error(ZM_EINVAL, "%s: bad size", a.fn);
+    if ((a.xPred == nullptr) != (a.uPred == nullptr)) return set_error(ZM_EINVAL, "%s: the two prediction arrays come together", a.fn);
+    if ((a.xRef && a.xref_rows != a.steps + a.N) || (a.uRef && a.uref_rows != a.steps + a.N - 1))
+        return set_error(ZM_EINVAL, "%s: a reference needs steps + N rows of xRef and steps + N - 1 rows of uRef", a.fn);
+    return ZM_OK;
+}
+
+// The problem map is read back and checked on the host before anything is launched (one small copy; the results come back through a
+// sync anyway): the kernels offset every table by it.  Every index must lie in [0, P) -- or, `identity`, be the instance's own.
+static int mpc_check_map(const MpcCall& a, bool identity, hipStream_t st) {
+    if (!a.problem) return ZM_OK;
     static thread_local std::vector<int32_t> h;
-    h.resize((size_t)batch);
-    ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    h.resize((size_t)a.batch);
+    ZM_HIP_CHECK(hipMemcpyAsync(h.data(), a.problem, (size_t)a.batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     ZM_HIP_CHECK(hipStreamSynchronize(st));
-    for (int64_t i = 0; i < batch; ++i)
-        if (h[i] < 0 || h[i] >= P)
-            return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d outside [0, %lld)", fn, (long long)i, (int)h[i], (long long)P);
+    for (int64_t i = 0; i < a.batch; ++i) {
+        if (identity && h[i] != (int32_t)i)
+            return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d; every instance is its own problem here", a.fn, (long long)i,
+                             (int)h[i]);
+        if (!identity && (h[i] < 0 || h[i] >= a.P))
+            return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d outside [0, %lld)", a.fn, (long long)i, (int)h[i],
+                             (long long)a.P);
+    }
+    return ZM_OK;
+}
+
+// the shapes and horizons of the one kernel for stage-varying dynamics (mpc_wave.hip: mpc_wave_ltv_dispatch), refused before any launch
+static int mpc_ltv_check_shape(const MpcCall& a) {
+    if (for_mpc_shape(a.n, a.m, [](auto ns, auto mc) { return ns.value + mc.value <= 16 ? ZM_OK : ZM_EUNSUPPORTED; }) != ZM_OK)
+        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, a.n, a.m);
+    if (!mpc_iterates_fit_lds(a.N))
+        return set_error(ZM_EUNSUPPORTED, "%s: N=%d beyond the horizons whose iterates fit LDS (N <= 75)", a.fn, a.N);
+    return ZM_OK;
+}
+
+static MpcTabs mpc_tabs(const MpcCall& a) { return {a.A, a.B, a.K, a.Minv, a.x_lb, a.x_ub, a.u_lb, a.u_ub}; }
+
+static int mpc_warm(const MpcCall& a) { return a.warm_start == 2 ? 2 : (a.warm_start ? 1 : 0); }
+
+// The kernels' options block; `warm` and the rollout arrays are those of a solve, or of the first step of a run.  With per-problem data
+// g.rho is unused (each instance takes its problem's rho_p[p]); 1.0 keeps the struct well-formed.
+static MpcArgs mpc_args(const MpcCall& a, int warm, double* xTraj, double* uTraj) {
+    return {a.x0,     a.problem ? 1.0 : a.rho, a.eps_abs, a.eps_rel,    a.eps_prim_inf, a.max_iter, warm,       a.workspace, xTraj, uTraj,
+            (int*)a.status, (int*)a.iters,     a.resid,   (long)a.batch, a.N,           a.n_levels, a.level0,   a.rho_step,  a.alpha};
+}
+
+// The workspace: the four blocks of a solve (batch, N, n + m each), with `tracking` a fifth for the linear term of the cost, then -- a
+// run that does not keep its predictions -- the one rollout every step overwrites.
+struct MpcLayout {
+    double* gbuf;            // the linear term; nullptr without `tracking`
+    double *xroll, *uroll;   // the rollout of step 0: the prediction arrays, else the scratch behind the blocks
+    long xstep, ustep;       // doubles from one step's rollout to the next: one rollout when predictions are kept, else 0
+};
+static MpcLayout mpc_layout(const MpcCall& a, bool tracking) {
+    const long blk = (long)a.batch * a.N * ((long)a.n + a.m);
+    const long xsz = (long)a.batch * (a.N + 1) * a.n, usz = (long)a.batch * a.N * a.m;
+    double* scratch = a.workspace + (tracking ? 5 : 4) * blk;
+    return {tracking ? a.workspace + 4 * blk : nullptr, a.xPred ? a.xPred : scratch, a.uPred ? a.uPred : scratch + xsz,
+            a.xPred ? xsz : 0, a.uPred ? usz : 0};
+}
+
+static MpcLoop mpc_loop(const MpcCall& a, const MpcLayout& lay) {
+    return {a.steps,  mpc_warm(a),    a.clip_tol,    a.x0,      a.disturbance, a.states, a.inputs, (int*)a.status,
+            (int*)a.iters, lay.xroll, lay.uroll, lay.xstep, lay.ustep};
+}
+
+// step s of a run sees the layouts of a single solve through offset pointers (the device's copy: mpc_closed_loop_wave_kernel)
+static MpcArgs mpc_step_args(MpcArgs g, const MpcLoop& lp, int n, int s) {
+    g.x0 = lp.states + (long)s * g.batch * n;
+    g.xTraj = lp.xPred + s * lp.xpred_step;
+    g.uTraj = lp.uPred + s * lp.upred_step;
+    g.status = lp.status + (long)s * g.batch;
+    g.iters = lp.iters + (long)s * g.batch;
+    g.warm = s ? lp.warm : 0;
+    return g;
+}
+
+// the linear term of step s of a run (s < 0: of a solve, whose references are one window) into lay.gbuf
+static int mpc_track_linear(const MpcCall& a, const MpcLayout& lay, int s, hipStream_t st) {
+    const dim3 grid((unsigned)blocks256((long)a.batch * a.N * ((long)a.n + a.m)));
+    if (s < 0)
+        hipLaunchKernelGGL(mpc_track_linear_kernel, grid, dim3(256), 0, st, a.Q, a.R, a.Qf, a.xRef, a.uRef, (const int*)a.problem,
+                           (long)a.batch, a.N, a.n, a.m, lay.gbuf);
+    else
+        hipLaunchKernelGGL(mpc_track_linear_window_kernel, grid, dim3(256), 0, st, a.Q, a.R, a.Qf, a.xRef, a.uRef, (const int*)a.problem,
+                           (long)a.batch, a.N, a.n, a.m, (long)a.xref_rows, (long)a.uref_rows, (long)s, lay.gbuf);
+    ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
 
@@ -530,40 +623,31 @@ static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcPro
     return rc;
 }
 
-// The three solve entry points.  `fn` is the entry point's name, the prefix of its error messages.
+// The four solve entry points.
 //   zm_mpc_solve_relaxed_f64 : one problem, scalar rho                          (problem, rho_p, Q, R, Qf, xRef, uRef NULL)
 //   zm_mpc_solve_batched_f64 : per_problem -- problem and rho_p are required    (Q, R, Qf, xRef, uRef NULL)
 //   zm_mpc_solve_tracking_f64: tracking -- Q, R, Qf are required, n and m are checked, the linear term is formed first; problem and
 //                              rho_p come together or not at all
-static int mpc_solve(const char* fn, bool per_problem, bool tracking, const double* A, const double* B, const double* Q, const double* R,
-                     const double* Qf, const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha,
-                     const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub, const double* x0,
-                     const double* xRef, const double* uRef, double rho, const double* rho_p, const int32_t* problem, int64_t P,
-                     double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
-                     double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    int rc = mpc_check_args(fn, per_problem, tracking, xTraj && uTraj && status, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha,
-                            x_lb, x_ub, u_lb, u_ub, x0, rho, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
+//   zm_mpc_solve_ltv_f64     : ltv -- per_problem and tracking (a zero linear term without a reference) with c, D, ABt; the one kernel
+//                              there is (mpc_wave.hip), so what it does not take is refused before anything is launched
+static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv) {
+    if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    int rc = mpc_check_args(a, per_problem, tracking, a.xTraj && a.uTraj && a.status && (!ltv || (a.c && a.D && a.ABt)));
     if (rc != ZM_OK) return rc;
-    const long W = (long)n + m;
-    hipStream_t st = (hipStream_t)stream;
-    rc = mpc_check_map(fn, problem, P, batch, st);
-    if (rc != ZM_OK) return rc;
-    // tracking: the fifth block of the workspace holds the linear term g (batch, N, n + m)
-    double* gbuf = tracking ? workspace + 4L * batch * N * W : nullptr;
-    if (tracking) {
-        const long blocks = ((long)batch * N * W + 255) / 256;
-        hipLaunchKernelGGL(mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
-                           (long)batch, N, n, m, gbuf);
-        ZM_HIP_CHECK(hipGetLastError());
-    }
-    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    // with per-problem data g.rho is unused (each instance takes its problem's pb.rho[p]); 1.0 keeps the struct well-formed
-    const MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace,
-                    xTraj, uTraj, (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
-    const MpcProb pbv{(const int*)problem, rho_p};
-    const MpcTrack trkv{gbuf};
-    return mpc_enqueue(fn, t, g, problem ? &pbv : nullptr, tracking ? &trkv : nullptr, n, m, st);
+    if (ltv && (rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
+    hipStream_t st = (hipStream_t)a.stream;
+    if ((rc = mpc_check_map(a, false, st)) != ZM_OK) return rc;
+    const MpcLayout lay = mpc_layout(a, tracking);
+    if (tracking && (rc = mpc_track_linear(a, lay, -1, st)) != ZM_OK) return rc;
+    const MpcTabs t = mpc_tabs(a);
+    const MpcArgs g = mpc_args(a, mpc_warm(a), a.xTraj, a.uTraj);
+    const MpcProb pb{(const int*)a.problem, a.rho_p};
+    const MpcTrack trk{lay.gbuf};
+    if (!ltv) return mpc_enqueue(a.fn, t, g, a.problem ? &pb : nullptr, tracking ? &trk : nullptr, a.n, a.m, st);
+    rc = mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.n, a.m, st);
+    if (rc == ZM_EUNSUPPORTED)
+        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, a.n, a.m);
+    return rc;
 }
 
 // zm_mpc_closed_loop_f64: `steps` receding-horizon solves of every instance, nothing but launches on `st` after the argument checks.
@@ -571,72 +655,43 @@ static int mpc_solve(const char* fn, bool per_problem, bool tracking, const doub
 //       (mpc_wave.hip: mpc_closed_loop_wave_kernel);
 //   (b) everything else -- tracking, (24, 8), horizons beyond LDS, ZOPT_AMD_MPC_PATH=lane: a loop that enqueues, per step, the launches
 //       of a single solve and mpc_advance_kernel, with no host synchronisation in between.
-static int mpc_closed_loop(const char* fn, const double* A, const double* B, const double* Q, const double* R, const double* Qf,
-                           const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
-                           const double* x_ub, const double* u_lb, const double* u_ub, const double* x0, const double* xRef,
-                           const double* uRef, int xref_rows, int uref_rows, double rho, const double* rho_p, const int32_t* problem,
-                           int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start, int steps,
-                           double clip_tol, const double* disturbance, double* workspace, double* states, double* inputs, int32_t* status,
-                           int32_t* iters, double* xPred, double* uPred, int64_t batch, int N, int n, int m, void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    const bool tracking = xRef || uRef;
-    int rc = mpc_check_args(fn, false, tracking, states && inputs && status && iters, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step,
-                            alpha, x_lb, x_ub, u_lb, u_ub, x0, rho, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
+static int mpc_closed_loop(const MpcCall& a) {
+    if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    const bool tracking = a.xRef || a.uRef;
+    const int N = a.N, n = a.n, m = a.m;
+    int rc = mpc_check_args(a, false, tracking, a.states && a.inputs && a.status && a.iters);
     if (rc != ZM_OK) return rc;
-    if (steps < 1) return set_error(ZM_EINVAL, "%s: steps must be at least 1", fn);
-    if (n < 1 || m < 1) return set_error(ZM_EINVAL, "%s: bad size", fn);
-    if ((xPred == nullptr) != (uPred == nullptr)) return set_error(ZM_EINVAL, "%s: the two prediction arrays come together", fn);
-    if ((xRef && xref_rows != steps + N) || (uRef && uref_rows != steps + N - 1))
-        return set_error(ZM_EINVAL, "%s: a reference needs steps + N rows of xRef and steps + N - 1 rows of uRef", fn);
-    const long W = (long)n + m;
-    const long ablocks = ((long)batch * W + 255) / 256;           // of mpc_advance_kernel
-    const long gblocks = ((long)batch * N * W + 255) / 256;       // of mpc_track_linear_window_kernel
-    if (ablocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x (n + m) too large", fn);
-    hipStream_t st = (hipStream_t)stream;
-    rc = mpc_check_map(fn, problem, P, batch, st);
-    if (rc != ZM_OK) return rc;
+    if ((rc = mpc_check_run(a, n >= 1 && m >= 1)) != ZM_OK) return rc;
+    const long ablocks = blocks256((long)a.batch * ((long)n + m));   // of mpc_advance_kernel
+    if (ablocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x (n + m) too large", a.fn);
+    hipStream_t st = (hipStream_t)a.stream;
+    if ((rc = mpc_check_map(a, false, st)) != ZM_OK) return rc;
 
-    // workspace: the blocks of a solve (the fifth: the linear term of a tracking step), then -- unless the predictions are kept -- the
-    // rollout every step overwrites
-    double* gbuf = tracking ? workspace + 4L * batch * N * W : nullptr;
-    double* scratch = workspace + (tracking ? 5L : 4L) * batch * N * W;
-    const long xsz = (long)batch * (N + 1) * n, usz = (long)batch * N * m;
-    const MpcLoop lp{steps, warm_start == 2 ? 2 : (warm_start ? 1 : 0), clip_tol, x0, disturbance, states, inputs, (int*)status, (int*)iters,
-                     xPred ? xPred : scratch, uPred ? uPred : scratch + xsz, xPred ? xsz : 0, uPred ? usz : 0};
-    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    const MpcArgs g{x0, problem ? 1.0 : rho, eps_abs, eps_rel, eps_prim_inf, max_iter, 0, workspace, lp.xPred, lp.uPred, lp.status, lp.iters,
-                    nullptr, (long)batch, N, n_levels, level0, rho_step, alpha};
-    const MpcProb pbv{(const int*)problem, rho_p};
-    const MpcProb* pb = problem ? &pbv : nullptr;
+    const MpcLayout lay = mpc_layout(a, tracking);
+    const MpcLoop lp = mpc_loop(a, lay);
+    const MpcTabs t = mpc_tabs(a);
+    const MpcArgs g = mpc_args(a, 0, lay.xroll, lay.uroll);
+    const MpcProb pbv{(const int*)a.problem, a.rho_p};
+    const MpcProb* pb = a.problem ? &pbv : nullptr;
     if (!tracking && !mpc_force_lane()) {
         rc = mpc_wave_closed_loop_dispatch(t, g, pb, lp, n, m, st);
         if (rc != ZM_EUNSUPPORTED) return rc;
     }
-    const MpcTrack trkv{gbuf};
+    const MpcTrack trkv{lay.gbuf};
     const auto advance = [&](const double* src, long src_stride, const double* dist, double* dst, const double* usrc, double* udst) -> int {
-        hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, x_lb, x_ub,
-                           (const int*)problem, clip_tol, dst, usrc, (long)N * m, udst, (long)batch, n, m);
+        hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, a.x_lb, a.x_ub,
+                           (const int*)a.problem, a.clip_tol, dst, usrc, (long)N * m, udst, (long)a.batch, n, m);
         ZM_HIP_CHECK(hipGetLastError());
         return ZM_OK;
     };
-    rc = advance(x0, n, nullptr, states, nullptr, nullptr);
-    for (int s = 0; s < steps && rc == ZM_OK; ++s) {
-        if (tracking) {
-            hipLaunchKernelGGL(mpc_track_linear_window_kernel, dim3((unsigned)gblocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef,
-                               (const int*)problem, (long)batch, N, n, m, (long)xref_rows, (long)uref_rows, (long)s, gbuf);
-            ZM_HIP_CHECK(hipGetLastError());
-        }
-        MpcArgs gs = g;
-        gs.x0 = states + (long)s * batch * n;
-        gs.xTraj = lp.xPred + s * lp.xpred_step;
-        gs.uTraj = lp.uPred + s * lp.upred_step;
-        gs.status = lp.status + (long)s * batch;
-        gs.iters = lp.iters + (long)s * batch;
-        gs.warm = s ? lp.warm : 0;
-        rc = mpc_enqueue(fn, t, gs, pb, tracking ? &trkv : nullptr, n, m, st);
+    rc = advance(a.x0, n, nullptr, a.states, nullptr, nullptr);
+    for (int s = 0; s < a.steps && rc == ZM_OK; ++s) {
+        if (tracking && (rc = mpc_track_linear(a, lay, s, st)) != ZM_OK) break;
+        const MpcArgs gs = mpc_step_args(g, lp, n, s);
+        rc = mpc_enqueue(a.fn, t, gs, pb, tracking ? &trkv : nullptr, n, m, st);
         if (rc != ZM_OK) break;
-        rc = advance(gs.xTraj + n, (long)(N + 1) * n, disturbance ? disturbance + (long)s * batch * n : nullptr,
-                     states + (long)(s + 1) * batch * n, gs.uTraj, inputs + (long)s * batch * m);
+        rc = advance(gs.xTraj + n, (long)(N + 1) * n, a.disturbance ? a.disturbance + (long)s * a.batch * n : nullptr,
+                     a.states + (long)(s + 1) * a.batch * n, gs.uTraj, a.inputs + (long)s * a.batch * m);
     }
     return rc;
 }
@@ -651,110 +706,61 @@ static int mpc_rti_check_model(const char* fn, const char* what, const zm_model_
     return ZM_OK;
 }
 
-// the shapes and horizons of the one kernel for stage-varying dynamics (mpc_wave.hip: mpc_wave_ltv_dispatch), refused before any launch
-static int mpc_ltv_check_shape(const char* fn, int N, int n, int m) {
-    if (for_mpc_shape(n, m, [](auto ns, auto mc) { return ns.value + mc.value <= 16 ? ZM_OK : ZM_EUNSUPPORTED; }) != ZM_OK)
-        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
-    if ((size_t)4 * N * 64 * sizeof(double) > 150 * 1024)
-        return set_error(ZM_EUNSUPPORTED, "%s: N=%d beyond the horizons whose iterates fit LDS (N <= 75)", fn, N);
-    return ZM_OK;
-}
-
-static int mpc_relinearize(const char* fn, const zm_model_t* model, const double* xPlan, const double* uPlan, double* A, double* B,
-                           double* c, int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!xPlan || !uPlan || !A || !B || !c) return set_error(ZM_EINVAL, "%s: null pointer", fn);
-    if (batch < 0 || N < 1 || n_user < 1 || m_user < 1 || ns < n_user || mc < m_user) return set_error(ZM_EINVAL, "%s: bad size", fn);
-    if (ns > SN || mc > SM) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (n <= 12, m <= 4)", fn, ns, mc);
-    if (((long)batch * N + 15) / 16 > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x N too large", fn);
-    zm_model_t md;
-    const int rc = mpc_rti_check_model(fn, "model", model, md, n_user, m_user);
-    if (rc != ZM_OK) return rc;
-    return mpc_relinearize_enqueue(md, xPlan, uPlan, A, B, c, (long)batch, N, ns, mc, (hipStream_t)stream);
-}
+// what zm_mpc_rti_f64 writes at every step besides its outputs: the plan it expands about, the expansion, the tables of the expansion
+// (the record holds the same A .. ABt as the read-only pointers the solve takes)
+struct MpcRtiWork {
+    double *xPlan, *uPlan, *A, *B, *c, *K, *Minv, *D, *ABt;
+};
 
 // zm_mpc_rti_f64: `steps` real-time iterations of every instance, nothing but launches on `st` after the argument checks and the one
 // read-back of the problem map -- mpc_closed_loop's form (b) with the expansion and the table setup inside the loop:
 //     relinearise about the plan -> mpc_setup_ltv_kernel -> mpc_track_linear_window_kernel -> the LTV solve -> plant step, plan shift
-static int mpc_rti(const char* fn, const zm_model_t* model, const zm_model_t* plant, double* xPlan, double* uPlan, double* A, double* B,
-                   double* c, const double* Q, const double* R, const double* Qf, const double* rho_tab, double* K, double* Minv, double* D,
-                   double* ABt, int n_levels, int level0, double rho_step, double alpha, const double* x_lb, const double* x_ub,
-                   const double* u_lb, const double* u_ub, const double* x0, const double* xRef, const double* uRef, int xref_rows,
-                   int uref_rows, const double* rho_p, const int32_t* problem, double eps_abs, double eps_rel, double eps_prim_inf,
-                   int max_iter, int warm_start, int steps, double clip_tol, const double* disturbance, double* workspace, double* states,
-                   double* inputs, int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred, int64_t batch, int N,
-                   int n_user, int m_user, int n, int m, void* stream) {
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    int rc = mpc_check_args(fn, true, true, states && inputs && status && iters && xPlan && uPlan && c && D && ABt && rho_tab, A, B, Q, R,
-                            Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub, x0, 0.0, rho_p, problem, batch,
-                            max_iter, workspace, batch, N, n, m);
+// Every instance is its own problem (P = batch, the map the identity); the steps and the shape are refused before the map is read.
+static int mpc_rti(const MpcCall& a, const zm_model_t* model, const zm_model_t* plant, const MpcRtiWork& w) {
+    if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    const int N = a.N, n = a.n, m = a.m;
+    const long batch = (long)a.batch;
+    int rc = mpc_check_args(a, true, true,
+                            a.states && a.inputs && a.status && a.iters && w.xPlan && w.uPlan && a.c && a.D && a.ABt && a.rho_tab);
     if (rc != ZM_OK) return rc;
-    if (steps < 1) return set_error(ZM_EINVAL, "%s: steps must be at least 1", fn);
-    if (n_user < 1 || m_user < 1 || n_user > n || m_user > m) return set_error(ZM_EINVAL, "%s: bad size", fn);
-    if ((xPred == nullptr) != (uPred == nullptr)) return set_error(ZM_EINVAL, "%s: the two prediction arrays come together", fn);
-    if ((xRef && xref_rows != steps + N) || (uRef && uref_rows != steps + N - 1))
-        return set_error(ZM_EINVAL, "%s: a reference needs steps + N rows of xRef and steps + N - 1 rows of uRef", fn);
-    if ((rc = mpc_ltv_check_shape(fn, N, n, m)) != ZM_OK) return rc;
+    if ((rc = mpc_check_run(a, a.n_user >= 1 && a.m_user >= 1 && a.n_user <= n && a.m_user <= m)) != ZM_OK) return rc;
+    if ((rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
     zm_model_t md, pl;
-    if ((rc = mpc_rti_check_model(fn, "model", model, md, n_user, m_user)) != ZM_OK) return rc;
-    if ((rc = mpc_rti_check_model(fn, "plant", plant ? plant : model, pl, n_user, m_user)) != ZM_OK) return rc;
-    const long W = (long)n + m;
-    const long ablocks = ((long)batch * W + 255) / 256;                                         // of mpc_advance_kernel
-    const long gblocks = ((long)batch * N * W + 255) / 256;                                     // of mpc_track_linear_window_kernel
-    const long sblocks = ((long)batch * ((long)(N + 1) * n_user + (long)N * m_user) + 255) / 256;   // of mpc_rti_shift_kernel
-    if (gblocks > 0x7fffffffL || sblocks > 0x7fffffffL || (long)batch * n_levels > 0x7fffffffL)
-        return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", fn);
-    hipStream_t st = (hipStream_t)stream;
-    {   // every instance is its own problem: the map must be the identity (one small copy, as mpc_check_map's)
-        static thread_local std::vector<int32_t> h;
-        h.resize((size_t)batch);
-        ZM_HIP_CHECK(hipMemcpyAsync(h.data(), problem, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ZM_HIP_CHECK(hipStreamSynchronize(st));
-        for (int64_t i = 0; i < batch; ++i)
-            if (h[i] != (int32_t)i)
-                return set_error(ZM_EINVAL, "%s: instance %lld maps to problem %d; every instance is its own problem here", fn, (long long)i,
-                                 (int)h[i]);
-    }
+    if ((rc = mpc_rti_check_model(a.fn, "model", model, md, a.n_user, a.m_user)) != ZM_OK) return rc;
+    if ((rc = mpc_rti_check_model(a.fn, "plant", plant ? plant : model, pl, a.n_user, a.m_user)) != ZM_OK) return rc;
+    const long ablocks = blocks256(batch * ((long)n + m));                                          // of mpc_advance_kernel
+    const long sblocks = blocks256(batch * ((long)(N + 1) * a.n_user + (long)N * a.m_user));        // of mpc_rti_shift_kernel
+    if (blocks256(batch * N * ((long)n + m)) > 0x7fffffffL || sblocks > 0x7fffffffL || batch * a.n_levels > 0x7fffffffL)
+        return set_error(ZM_EINVAL, "%s: batch x N x (n + m) too large", a.fn);
+    hipStream_t st = (hipStream_t)a.stream;
+    if ((rc = mpc_check_map(a, true, st)) != ZM_OK) return rc;
 
-    // workspace: the five blocks of a tracking solve, then -- unless the predictions are kept -- the rollout every step overwrites
-    double* gbuf = workspace + 4L * batch * N * W;
-    double* scratch = workspace + 5L * batch * N * W;
-    const long xsz = (long)batch * (N + 1) * n, usz = (long)batch * N * m;
-    const long xstep = xPred ? xsz : 0, ustep = uPred ? usz : 0;
-    double* xroll = xPred ? xPred : scratch;
-    double* uroll = uPred ? uPred : scratch + xsz;
-    const MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    const MpcArgs g{x0, 1.0, eps_abs, eps_rel, eps_prim_inf, max_iter, 0, workspace, xroll, uroll, (int*)status, (int*)iters, resid, (long)batch,
-                    N, n_levels, level0, rho_step, alpha};
-    const MpcProb pb{(const int*)problem, rho_p};
-    const int warm = warm_start == 2 ? 2 : (warm_start ? 1 : 0);
-    hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, x0, (long)n, (const double*)nullptr, x_lb, x_ub,
-                       (const int*)problem, clip_tol, states, (const double*)nullptr, 0L, (double*)nullptr, (long)batch, n, m);
+    const MpcLayout lay = mpc_layout(a, true);
+    const MpcLoop lp = mpc_loop(a, lay);
+    const MpcTabs t = mpc_tabs(a);
+    const MpcArgs g = mpc_args(a, 0, lay.xroll, lay.uroll);
+    const MpcProb pb{(const int*)a.problem, a.rho_p};
+    hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, a.x0, (long)n, (const double*)nullptr, a.x_lb, a.x_ub,
+                       (const int*)a.problem, a.clip_tol, a.states, (const double*)nullptr, 0L, (double*)nullptr, batch, n, m);
     ZM_HIP_CHECK(hipGetLastError());
-    for (int s = 0; s < steps; ++s) {
-        if ((rc = mpc_relinearize_enqueue(md, xPlan, uPlan, A, B, c, (long)batch, N, n, m, st)) != ZM_OK) return rc;
-        hipLaunchKernelGGL((mpc_setup_ltv_kernel<SN, SM>), dim3((unsigned)(batch * n_levels)), dim3(256), 0, st, A, B, c, Q, R, Qf, rho_tab,
-                           n_levels, N, n, m, K, Minv, D, ABt);
+    for (int s = 0; s < a.steps; ++s) {
+        if ((rc = mpc_relinearize_enqueue(md, w.xPlan, w.uPlan, w.A, w.B, w.c, batch, N, n, m, st)) != ZM_OK) return rc;
+        // (a.X and w.X are one buffer: `a` holds what the kernels read, `w` what this call writes -- the expansion, then its tables)
+        hipLaunchKernelGGL((mpc_setup_ltv_kernel<SN, SM>), dim3((unsigned)(batch * a.n_levels)), dim3(256), 0, st, a.A, a.B, a.c, a.Q, a.R,
+                           a.Qf, a.rho_tab, a.n_levels, N, n, m, w.K, w.Minv, w.D, w.ABt);
         ZM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(mpc_track_linear_window_kernel, dim3((unsigned)gblocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
-                           (long)batch, N, n, m, (long)xref_rows, (long)uref_rows, (long)s, gbuf);
-        ZM_HIP_CHECK(hipGetLastError());
-        MpcArgs gs = g;
-        gs.x0 = states + (long)s * batch * n;
-        gs.xTraj = xroll + s * xstep;
-        gs.uTraj = uroll + s * ustep;
-        gs.status = g.status + (long)s * batch;
-        gs.iters = g.iters + (long)s * batch;
-        gs.warm = s ? warm : 0;
-        rc = mpc_wave_ltv_dispatch(t, gs, pb, MpcTrack{gbuf}, MpcLtv{c, D, ABt}, n, m, st);
-        if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
+        if ((rc = mpc_track_linear(a, lay, s, st)) != ZM_OK) return rc;
+        const MpcArgs gs = mpc_step_args(g, lp, n, s);
+        rc = mpc_wave_ltv_dispatch(t, gs, pb, MpcTrack{lay.gbuf}, MpcLtv{a.c, a.D, a.ABt}, n, m, st);
+        if (rc == ZM_EUNSUPPORTED)
+            return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, n, m);
         if (rc != ZM_OK) return rc;
         hipLaunchKernelGGL(mpc_rti_plant_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, pl, gs.x0, (long)n, gs.uTraj,
-                           (long)N * m, disturbance ? disturbance + (long)s * batch * n : nullptr, x_lb, x_ub, clip_tol,
-                           states + (long)(s + 1) * batch * n, n, inputs + (long)s * batch * m, m, (long)batch);
+                           (long)N * m, a.disturbance ? a.disturbance + (long)s * batch * n : nullptr, a.x_lb, a.x_ub, a.clip_tol,
+                           a.states + (long)(s + 1) * batch * n, n, a.inputs + (long)s * batch * m, m, batch);
         ZM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(mpc_rti_shift_kernel, dim3((unsigned)sblocks), dim3(256), 0, st, gs.xTraj, gs.uTraj, xPlan, uPlan, (long)batch, N,
-                           n_user, m_user, n, m);
+        hipLaunchKernelGGL(mpc_rti_shift_kernel, dim3((unsigned)sblocks), dim3(256), 0, st, gs.xTraj, gs.uTraj, w.xPlan, w.uPlan, batch, N,
+                           a.n_user, a.m_user, n, m);
         ZM_HIP_CHECK(hipGetLastError());
     }
     return ZM_OK;
@@ -814,9 +820,15 @@ extern "C" int zm_mpc_solve_relaxed_f64(const double* A, const double* B, const 
                                         double eps_rel, double eps_prim_inf, int max_iter, int warm_start, double* workspace,
                                         double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
                                         int64_t batch, int N, int n, int m, void* stream) {
-    return zm::mpc_solve("zm_mpc_solve_relaxed_f64", false, false, A, B, nullptr, nullptr, nullptr, K, Minv, n_levels, level0, rho_step,
-                         alpha, x_lb, x_ub, u_lb, u_ub, x0, nullptr, nullptr, rho, nullptr, nullptr, 0, eps_abs, eps_rel, eps_prim_inf,
-                         max_iter, warm_start, workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_relaxed_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.rho = rho;
+    return zm::mpc_solve(a, false, false, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -850,9 +862,15 @@ extern "C" int zm_mpc_solve_batched_f64(const double* A, const double* B, const 
                                         int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj,
                                         int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
                                         void* stream) {
-    return zm::mpc_solve("zm_mpc_solve_batched_f64", true, false, A, B, nullptr, nullptr, nullptr, K, Minv, n_levels, level0, rho_step,
-                         alpha, x_lb, x_ub, u_lb, u_ub, x0, nullptr, nullptr, 0.0, rho, problem, P, eps_abs, eps_rel, eps_prim_inf,
-                         max_iter, warm_start, workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_batched_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.rho_p = rho, a.problem = problem, a.P = P;
+    return zm::mpc_solve(a, true, false, false);
 }
 
 // reference tracking: xRef, uRef -> g (mpc_track_linear_kernel), then the tracking variants of the solve kernels
@@ -864,9 +882,15 @@ extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const
                                          double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj,
                                          double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n,
                                          int m, void* stream) {
-    return zm::mpc_solve("zm_mpc_solve_tracking_f64", false, true, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb,
-                         x_ub, u_lb, u_ub, x0, xRef, uRef, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start,
-                         workspace, xTraj, uTraj, status, iters, resid, batch, N, n, m, stream);
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_tracking_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.rho = rho, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    return zm::mpc_solve(a, false, true, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -894,33 +918,15 @@ extern "C" int zm_mpc_solve_ltv_f64(const double* A, const double* B, const doub
                                     const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter,
                                     int warm_start, double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters,
                                     double* resid, int64_t batch, int N, int n, int m, void* stream) {
-    const char* fn = "zm_mpc_solve_ltv_f64";
-    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    int rc = zm::mpc_check_args(fn, true, true, xTraj && uTraj && status && c && D && ABt, A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step,
-                                alpha, x_lb, x_ub, u_lb, u_ub, x0, 0.0, rho_p, problem, P, max_iter, workspace, batch, N, n, m);
-    if (rc != ZM_OK) return rc;
-    // the one kernel there is: refuse what it does not take before anything is launched
-    if (zm::for_mpc_shape(n, m, [](auto ns, auto mc) { return ns.value + mc.value <= 16 ? ZM_OK : ZM_EUNSUPPORTED; }) != ZM_OK)
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
-    if ((size_t)4 * N * 64 * sizeof(double) > 150 * 1024)
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: N=%d beyond the horizons whose iterates fit LDS (N <= 75)", fn, N);
-    hipStream_t st = (hipStream_t)stream;
-    rc = zm::mpc_check_map(fn, problem, P, batch, st);
-    if (rc != ZM_OK) return rc;
-    const long W = (long)n + m;
-    // the fifth block of the workspace holds the linear term g (batch, N, n + m): a zero block without a reference
-    double* gbuf = workspace + 4L * batch * N * W;
-    const long blocks = ((long)batch * N * W + 255) / 256;
-    hipLaunchKernelGGL(zm::mpc_track_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Q, R, Qf, xRef, uRef, (const int*)problem,
-                       (long)batch, N, n, m, gbuf);
-    ZM_HIP_CHECK(hipGetLastError());
-    const zm::MpcTabs t{A, B, K, Minv, x_lb, x_ub, u_lb, u_ub};
-    const zm::MpcArgs g{x0, 1.0, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start == 2 ? 2 : (warm_start ? 1 : 0), workspace, xTraj, uTraj,
-                        (int*)status, (int*)iters, resid, (long)batch, N, n_levels, level0, rho_step, alpha};
-    rc = zm::mpc_wave_ltv_dispatch(t, g, zm::MpcProb{(const int*)problem, rho_p}, zm::MpcTrack{gbuf}, zm::MpcLtv{c, D, ABt}, n, m, st);
-    if (rc == ZM_EUNSUPPORTED)
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", fn, n, m);
-    return rc;
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_ltv_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.c = c, a.D = D, a.ABt = ABt, a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    return zm::mpc_solve(a, true, true, true);
 }
 
 // the receding-horizon loop as one call: see mpc_closed_loop
@@ -932,10 +938,17 @@ extern "C" int zm_mpc_closed_loop_f64(const double* A, const double* B, const do
                                       int warm_start, int steps, double clip_tol, const double* disturbance, double* workspace,
                                       double* states, double* inputs, int32_t* status, int32_t* iters, double* xPred, double* uPred,
                                       int64_t batch, int N, int n, int m, void* stream) {
-    return zm::mpc_closed_loop("zm_mpc_closed_loop_f64", A, B, Q, R, Qf, K, Minv, n_levels, level0, rho_step, alpha, x_lb, x_ub, u_lb, u_ub,
-                               x0, xRef, uRef, xref_rows, uref_rows, rho, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter,
-                               warm_start, steps, clip_tol, disturbance, workspace, states, inputs, status, iters, xPred, uPred, batch, N,
-                               n, m, stream);
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_closed_loop_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.xref_rows = xref_rows, a.uref_rows = uref_rows;
+    a.rho_p = rho_p, a.problem = problem, a.steps = steps, a.clip_tol = clip_tol, a.disturbance = disturbance;
+    a.workspace = workspace, a.states = states, a.inputs = inputs, a.status = status, a.iters = iters, a.xPred = xPred, a.uPred = uPred;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.rho = rho, a.P = P;
+    return zm::mpc_closed_loop(a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -959,9 +972,19 @@ extern "C" int zm_model_step_f64(const zm_model_t* model, const double* x, const
 
 extern "C" int zm_mpc_relinearize_f64(const zm_model_t* model, const double* xPlan, const double* uPlan, double* A, double* B, double* c,
                                       int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream) {
-    return zm::mpc_relinearize("zm_mpc_relinearize_f64", model, xPlan, uPlan, A, B, c, batch, N, n_user, m_user, ns, mc, stream);
+    const char* fn = "zm_mpc_relinearize_f64";
+    if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
+    if (!xPlan || !uPlan || !A || !B || !c) return zm::set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if (batch < 0 || N < 1 || n_user < 1 || m_user < 1 || ns < n_user || mc < m_user) return zm::set_error(ZM_EINVAL, "%s: bad size", fn);
+    if (ns > zm::SN || mc > zm::SM) return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (n <= 12, m <= 4)", fn, ns, mc);
+    if (((long)batch * N + 15) / 16 > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "%s: batch x N too large", fn);
+    zm_model_t md;
+    const int rc = zm::mpc_rti_check_model(fn, "model", model, md, n_user, m_user);
+    if (rc != ZM_OK) return rc;
+    return zm::mpc_relinearize_enqueue(md, xPlan, uPlan, A, B, c, (long)batch, N, ns, mc, (hipStream_t)stream);
 }
 
+// every instance is its own problem: P = batch, and no shared rho
 extern "C" int zm_mpc_rti_f64(const zm_model_t* model, const zm_model_t* plant, double* xPlan, double* uPlan, double* A, double* B, double* c,
                               const double* Q, const double* R, const double* Qf, const double* rho_tab, double* K, double* Minv,
                               double* D, double* ABt, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
@@ -971,8 +994,15 @@ extern "C" int zm_mpc_rti_f64(const zm_model_t* model, const zm_model_t* plant, 
                               double clip_tol, const double* disturbance, double* workspace, double* states, double* inputs,
                               int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred, int64_t batch, int N,
                               int n_user, int m_user, int ns, int mc, void* stream) {
-    return zm::mpc_rti("zm_mpc_rti_f64", model, plant, xPlan, uPlan, A, B, c, Q, R, Qf, rho_tab, K, Minv, D, ABt, n_levels, level0, rho_step,
-                       alpha, x_lb, x_ub, u_lb, u_ub, x0, xRef, uRef, xref_rows, uref_rows, rho_p, problem, eps_abs, eps_rel, eps_prim_inf,
-                       max_iter, warm_start, steps, clip_tol, disturbance, workspace, states, inputs, status, iters, resid, xPred, uPred,
-                       batch, N, n_user, m_user, ns, mc, stream);
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_rti_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.xref_rows = xref_rows, a.uref_rows = uref_rows;
+    a.rho_p = rho_p, a.problem = problem, a.steps = steps, a.clip_tol = clip_tol, a.disturbance = disturbance;
+    a.workspace = workspace, a.states = states, a.inputs = inputs, a.status = status, a.iters = iters, a.xPred = xPred, a.uPred = uPred;
+    a.batch = batch, a.N = N, a.n = ns, a.m = mc, a.n_user = n_user, a.m_user = m_user, a.stream = stream;
+    a.c = c, a.D = D, a.ABt = ABt, a.rho_tab = rho_tab, a.P = batch, a.resid = resid;
+    return zm::mpc_rti(a, model, plant, zm::MpcRtiWork{xPlan, uPlan, A, B, c, K, Minv, D, ABt});
 }

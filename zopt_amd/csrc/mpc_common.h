@@ -83,9 +83,31 @@ struct MpcLoop {
     u_ub += p * MC;                             \
     g.rho = pb.rho[p];
 
-// the (n, m) of a compiled kernel as a value: what for_mpc_shape() (one per file: the files compile different sets) hands to its callback
+// the (n, m) of a compiled kernel as a value: what for_mpc_shape() hands to its callback
 template <int V>
 using Int = std::integral_constant<int, V>;
+
+// f(Int<NS>, Int<MC>) for the compiled shape (n, m); ZM_EUNSUPPORTED for any other.  (24, 8) is beyond the 16-index tile: only the
+// lane-per-instance kernels have it (registers + scratch); mpc_wave.hip keeps to NS + MC <= 16.
+template <typename F>
+static int for_mpc_shape(int n, int m, F f) {
+    if (n == 24 && m == 8) return f(Int<24>{}, Int<8>{});
+    if (n == 12 && m == 4) return f(Int<12>{}, Int<4>{});
+    if (n == 8 && m == 4) return f(Int<8>{}, Int<4>{});
+    if (n == 4 && m == 2) return f(Int<4>{}, Int<2>{});
+    if (n == 4 && m == 1) return f(Int<4>{}, Int<1>{});
+    if (n == 2 && m == 2) return f(Int<2>{}, Int<2>{});
+    if (n == 2 && m == 1) return f(Int<2>{}, Int<1>{});
+    if (n == 1 && m == 1) return f(Int<1>{}, Int<1>{});
+    return ZM_EUNSUPPORTED;
+}
+
+// The 16-lanes-per-instance kernels keep the iterates of a block's 4 instances in LDS, 64 doubles per instance and stage (mpc_wave.hip:
+// WS_STAGE), and may ask for 150 KiB of it: horizons up to N = 75.  The refusals of mpc.hip (mpc_ltv_check_shape) and ltvMpc.N_MAX
+// (mpcUtils.py) spell that "N <= 75" out as text: a change here changes them.
+constexpr int MPC_LDS_MAX = 150 * 1024;
+inline size_t mpc_iterate_bytes(int N) { return (size_t)4 * N * 64 * sizeof(double); }
+inline bool mpc_iterates_fit_lds(int N) { return mpc_iterate_bytes(N) <= (size_t)MPC_LDS_MAX; }
 
 // mpc_wave.hip: 16 lanes per instance, iterates in LDS.  ZM_EUNSUPPORTED if the shape / horizon does not fit.  pb: per-problem data,
 // trk: reference tracking; either may be nullptr.

@@ -264,76 +264,54 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
 // stage-varying dynamics (zm_mpc_solve_ltv_f64): mpc_solve_wave_ltv_kernel, in this translation unit with the kernels it borrows from
 #include "mpc_solve_wave_ltv.h"
 
-// f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16; ZM_EUNSUPPORTED for any other
+// for_mpc_shape() without (24, 8): f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16, ZM_EUNSUPPORTED for any other,
+// and no kernel of this file is instantiated beyond the 16 lanes
 template <typename F>
-static int for_mpc_shape(int n, int m, F f) {
-    if (n == 12 && m == 4) return f(Int<12>{}, Int<4>{});
-    if (n == 8 && m == 4) return f(Int<8>{}, Int<4>{});
-    if (n == 4 && m == 2) return f(Int<4>{}, Int<2>{});
-    if (n == 4 && m == 1) return f(Int<4>{}, Int<1>{});
-    if (n == 2 && m == 2) return f(Int<2>{}, Int<2>{});
-    if (n == 2 && m == 1) return f(Int<2>{}, Int<1>{});
-    if (n == 1 && m == 1) return f(Int<1>{}, Int<1>{});
-    return ZM_EUNSUPPORTED;
+static int for_wave_shape(int n, int m, F f) {
+    return for_mpc_shape(n, m, [&](auto ns, auto mc) -> int {
+        if constexpr (ns.value + mc.value <= 16)
+            return f(ns, mc);
+        else
+            return ZM_EUNSUPPORTED;
+    });
 }
 
-// pb != nullptr: per-problem data; trk != nullptr: the tracking variants
-template <int NS, int MC>
-static int launch_wave(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, hipStream_t st) {
-    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
-    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // horizon too long for LDS: the lane-per-instance kernel takes it
-    const auto go = [&](auto kernel, auto... more) -> int {
-        // per launch (cheap): the attribute is per device, and several devices may be driven from one process
-        ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
-                           t.u_ub, g, more...);
-        ZM_HIP_CHECK(hipGetLastError());
-        return ZM_OK;
-    };
-    if (trk && pb) return go(mpc_solve_wave_track_kernel<NS, MC, true>, *pb, *trk);
-    if (trk) return go(mpc_solve_wave_track_kernel<NS, MC, false>, MpcProb{}, *trk);
-    return pb ? go(mpc_solve_wave_batched_kernel<NS, MC>, *pb) : go(mpc_solve_wave_kernel<NS, MC>);
-}
-
-int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
-    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave<ns.value, mc.value>(t, g, pb, trk, st); });
-}
-
-// the stage-varying kernel: grid and LDS of launch_wave; nothing else takes a horizon that does not fit
-template <int NS, int MC>
-static int launch_wave_ltv(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, hipStream_t st) {
-    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
-    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;
-    const auto kernel = mpc_solve_wave_ltv_kernel<NS, MC>;
-    ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb, t.u_ub,
-                       g, pb, trk, lv);
+// One launch of a kernel of this file: 4 instances per one-wave block, their iterates in dynamic LDS; `more`: the kernel's arguments after
+// MpcArgs.  ZM_EUNSUPPORTED if the horizon is too long for LDS: the lane-per-instance kernels take it, where there are any.
+template <typename Kernel, typename... More>
+static int launch_wave(Kernel kernel, const MpcTabs& t, const MpcArgs& g, hipStream_t st, const More&... more) {
+    if (!mpc_iterates_fit_lds(g.N)) return ZM_EUNSUPPORTED;
+    // per launch (cheap): the attribute is per device, and several devices may be driven from one process
+    ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MPC_LDS_MAX));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), mpc_iterate_bytes(g.N), st, t.A, t.B, t.K, t.Minv, t.x_lb,
+                       t.x_ub, t.u_lb, t.u_ub, g, more...);
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
 
-int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
-                          hipStream_t st) {
-    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave_ltv<ns.value, mc.value>(t, g, pb, trk, lv, st); });
+// pb != nullptr: per-problem data; trk != nullptr: the tracking variants
+int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        constexpr int NS = ns.value, MC = mc.value;
+        if (trk && pb) return launch_wave(mpc_solve_wave_track_kernel<NS, MC, true>, t, g, st, *pb, *trk);
+        if (trk) return launch_wave(mpc_solve_wave_track_kernel<NS, MC, false>, t, g, st, MpcProb{}, *trk);
+        if (pb) return launch_wave(mpc_solve_wave_batched_kernel<NS, MC>, t, g, st, *pb);
+        return launch_wave(mpc_solve_wave_kernel<NS, MC>, t, g, st);
+    });
 }
 
-// the closed-loop kernel: grid and LDS of launch_wave
-template <int NS, int MC>
-static int launch_wave_closed_loop(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, hipStream_t st) {
-    const size_t bytes = (size_t)4 * g.N * WS_STAGE * sizeof(double);
-    if (bytes > 150 * 1024) return ZM_EUNSUPPORTED;   // horizon too long for LDS: the host loop over the lane-per-instance kernel takes it
-    const auto go = [&](auto kernel, const MpcProb& pbv) -> int {
-        ZM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((g.batch + 3) / 4)), dim3(64), bytes, st, t.A, t.B, t.K, t.Minv, t.x_lb, t.x_ub, t.u_lb,
-                           t.u_ub, g, pbv, lp);
-        ZM_HIP_CHECK(hipGetLastError());
-        return ZM_OK;
-    };
-    return pb ? go(mpc_closed_loop_wave_kernel<NS, MC, true>, *pb) : go(mpc_closed_loop_wave_kernel<NS, MC, false>, MpcProb{});
+int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
+                          hipStream_t st) {
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        return launch_wave(mpc_solve_wave_ltv_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv);
+    });
 }
 
 int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, int n, int m, hipStream_t st) {
-    return for_mpc_shape(n, m, [&](auto ns, auto mc) { return launch_wave_closed_loop<ns.value, mc.value>(t, g, pb, lp, st); });
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        return pb ? launch_wave(mpc_closed_loop_wave_kernel<ns.value, mc.value, true>, t, g, st, *pb, lp)
+                  : launch_wave(mpc_closed_loop_wave_kernel<ns.value, mc.value, false>, t, g, st, MpcProb{}, lp);
+    });
 }
 
 }  // namespace zm

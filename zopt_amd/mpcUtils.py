@@ -107,9 +107,8 @@ class lqrMpc():
             rtab = arr.to_device(rho.reshape(Pn, 1) * fac[None, :], torch.float64, dev)
             K = torch.empty((Pn, nl, self.N, self.m, self.n), dtype=torch.float64, device=dev)
             Mi = torch.empty((Pn, nl, self.N, self.m, self.m), dtype=torch.float64, device=dev)
-            rc = _lib.lib().zm_mpc_setup_batched_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["Q"].data_ptr(), d["R"].data_ptr(),
-                                                     d["Qf"].data_ptr(), rtab.data_ptr(), Pn, nl, self.N, self.n, self.m,
-                                                     K.data_ptr(), Mi.data_ptr(), ctypes.c_void_p(arr.stream_ptr(K)))
+            rc = _lib.lib().zm_mpc_setup_batched_f64(*_ptrs(d, "A B Q R Qf", rtab), Pn, nl, self.N, self.n, self.m, *_ptrs(d, "", K, Mi),
+                                                     ctypes.c_void_p(arr.stream_ptr(K)))
             _lib.check(rc, "lqrMpc setup")
             self._tables[key] = (K, Mi, nl, l0, arr.to_device(rho.reshape(Pn), torch.float64, dev), rtab)
         return self._dev, self._tables[key]
@@ -127,17 +126,16 @@ class lqrMpc():
             K = torch.empty((nl, self.N, self.m, self.n), dtype=torch.float64, device=d["A"].device)
             Mi = torch.empty((nl, self.N, self.m, self.m), dtype=torch.float64, device=d["A"].device)
             for l in range(nl):
-                rc = _lib.lib().zm_mpc_setup_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["Q"].data_ptr(), d["R"].data_ptr(),
-                                                 d["Qf"].data_ptr(), float(rho) * self.RHO_STEP ** (l - l0), self.N, self.n,
-                                                 self.m, K[l].data_ptr(), Mi[l].data_ptr(),
-                                                 ctypes.c_void_p(arr.stream_ptr(K)))
+                rc = _lib.lib().zm_mpc_setup_f64(*_ptrs(d, "A B Q R Qf"), float(rho) * self.RHO_STEP ** (l - l0), self.N, self.n, self.m,
+                                                 *_ptrs(d, "", K[l], Mi[l]), ctypes.c_void_p(arr.stream_ptr(K)))
                 _lib.check(rc, "lqrMpc setup")
             self._tables[key] = (K, Mi, nl, l0)
         return self._dev, self._tables[key]
 
     def _solver_options(self, kwargs, warm_default):
         """The solver options of `solve` (and `simulate`) taken out of `kwargs`, which must be empty afterwards:
-        (eps_abs, eps_rel, max_iter, rho, adaptive_rho, eps_prim_inf, alpha, warm, shift)."""
+        (eps_abs, eps_rel, max_iter, rho, adaptive_rho, eps_prim_inf, alpha, warm) -- warm: the C side's warm_start, 0: cold, 1: from
+        the previous iterates, 2: from those advanced by one horizon step."""
         solver = kwargs.pop("solver", None)
         if solver not in (None, "OSQP"):
             raise ValueError(f"solver {solver!r} is not available in zopt_amd (ADMM only; pass solver='OSQP' or None)")
@@ -160,13 +158,70 @@ class lqrMpc():
         if not (0.0 < alpha < 2.0):
             raise ValueError("alpha must lie in (0, 2)")
         warm = kwargs.pop("warm_start", kwargs.pop("warm_starting", warm_default))
-        shift = isinstance(warm, str) and warm == "shift"     # extension: previous iterates advanced by one horizon step
-        warm = bool(warm)
+        warm = 2 if isinstance(warm, str) and warm == "shift" else int(bool(warm))   # "shift": an extension
         for k in ("eps_dual_inf", "verbose", "polish", "polishing"):
             kwargs.pop(k, None)
         if kwargs:
             raise TypeError(f"unknown solver options {sorted(kwargs)}")
-        return eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift
+        return eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm
+
+    def _problem_on_device(self, rho, adaptive):
+        """(device data, (K, Minv, n_levels, level0, rho per problem | None, ...), number of problems -- 0: the one shared problem)"""
+        if self.P is None:
+            d, tabs = self._device_problem(rho, adaptive)
+            return d, tabs + (None,), 0
+        d, tabs = self._device_problem_batched(rho, adaptive)
+        return d, tabs, int(np.prod(self.P))
+
+    def _batch_shape(self, x0, arrays, suffix="", plural=True, own=False, plan=None):
+        """The batch shape `lead` that x0 (..., n) and the per-instance `arrays` -- (name, X | None, (rows, user width), padded width)
+        each -- broadcast to with the problem shape, and its number of instances.  `suffix` ends the message about an array of another
+        shape; plural / own pick the sentence about shapes that do not broadcast (own: realTimeIteration, where every instance is its own
+        problem and `lead` must be the problem shape; its `plan` joins the broadcast)."""
+        shp = _shape_of(x0)
+        if len(shp) < 1 or shp[-1] != self._n_user:
+            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
+        leads = {"x0": (shp, shp[:-1])}
+        for name, X, want, _ in arrays:
+            if X is not None:
+                sh = _shape_of(X)
+                if len(sh) < 2 or sh[-2:] != want:
+                    raise ValueError(f"{name} has shape {sh}, expected (..., {want[0]}, {want[1]}){suffix}")
+                leads[name] = (sh, sh[:-2])
+        if plan is not None:
+            xs, us, pl = _plan_shapes("ltvMpc.realTimeIteration", plan, self.N, self._n_user, self._m_user)
+            leads["plan.xTraj"], leads["plan.uTraj"] = (xs, pl), (us, pl)
+        try:
+            lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
+        except ValueError:
+            lead = None
+        if lead is None or (own and lead != self.P):
+            who = ", ".join(f"{k} of shape {sh}" for k, (sh, _) in leads.items())
+            if own:
+                who += f" do not broadcast to the problem shape {self.P} (every instance is its own problem)"
+            elif plural:
+                who += " do not broadcast against each other" + ("" if self.P is None else f" and the problem shape {self.P}")
+            else:   # (x0 alone: only a problem shape can be in its way)
+                who += f" does not broadcast against the problem shape {self.P}"
+            raise ValueError(who + ": inconsistent shapes")
+        lead = tuple(int(v) for v in lead)
+        return lead, int(np.prod(lead))
+
+    def _device_rows(self, lead, Bn, d, tracking, x0, arrays, identity=False):
+        """(device, x0, [each of `arrays` | None], instance -> problem map | None): one row per instance, the padded components zero.  A
+        plain solve runs where x0 is (host data: on the current device), the others where the problem's tables are -- unless a single
+        problem tracks from an x0 that is on a device already."""
+        dx0 = _flat(x0, lead, Bn, (self._n_user,), self.n, d["A"].device if tracking or self.P is not None else None)
+        dev = dx0.device if self.P is None else d["A"].device
+        rows = [None if X is None else _flat(X, lead, Bn, want, width, dev) for _, X, want, width in arrays]
+        prob = None
+        if identity:   # (realTimeIteration: every instance its own problem)
+            prob = torch.arange(Bn, dtype=torch.int32, device=dev)
+        elif self.P is not None:
+            Pn = int(np.prod(self.P))
+            prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
+                                   device=dev)
+        return dev, dx0, rows, prob
 
     def solve(self, x0, **kwargs):
         """
@@ -197,7 +252,7 @@ class lqrMpc():
             status : problem status, one of [optimal, optimal_inaccurate, infeasible, user_limit] (a list of them for a batch)
         """
         xRef, uRef = kwargs.pop("xRef", None), kwargs.pop("uRef", None)
-        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(kwargs, True)
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm = self._solver_options(kwargs, True)
         if isinstance(xRef, Trajectory):
             if uRef is not None:
                 raise ValueError("a Trajectory given as xRef carries its own uTraj: pass it alone (uRef=None)")
@@ -207,28 +262,8 @@ class lqrMpc():
         N, n, m = self.N, self.n, self.m
 
         # 1. shapes: x0 and the references broadcast (with the problem shape) to the batch shape `lead`
-        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        shp = shape_of(x0)
-        if len(shp) < 1 or shp[-1] != self._n_user:
-            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
-        leads = {"x0": (shp, shp[:-1])}
-        for name, X, want in (("xRef", xRef, (N + 1, self._n_user)), ("uRef", uRef, (N, self._m_user))):
-            if X is not None:
-                s = shape_of(X)
-                if len(s) < 2 or s[-2:] != want:
-                    raise ValueError(f"{name} has shape {s}, expected (..., {want[0]}, {want[1]})")
-                leads[name] = (s, s[:-2])
-        try:
-            lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
-        except ValueError:
-            who = ", ".join(f"{k} of shape {s}" for k, (s, _) in leads.items())
-            if tracking:
-                who += " do not broadcast against each other" + ("" if self.P is None else f" and the problem shape {self.P}")
-            else:   # (x0 alone: only a problem shape can be in its way)
-                who += f" does not broadcast against the problem shape {self.P}"
-            raise ValueError(who + ": inconsistent shapes") from None
-        lead = tuple(int(v) for v in lead)
-        Bn = int(np.prod(lead))
+        refs = (("xRef", xRef, (N + 1, self._n_user), n), ("uRef", uRef, (N, self._m_user), m))
+        lead, Bn = self._batch_shape(x0, refs, plural=tracking)
         arr.require_gpu()
 
         # 2. nothing to solve: shaped empty results, nothing launched.  (Not for a plain solve: that one goes on, drops the warm start
@@ -242,36 +277,18 @@ class lqrMpc():
             return uo[..., 0, :], Trajectory(xo, uo), np.empty(lead, dtype=object)
 
         # 3. the problem on the device and its tables
-        if self.P is None:
-            d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
-            drho, Pn, rho_key = None, 0, rho
-        else:
-            d, tabs = self._device_problem_batched(rho, adaptive)
-            K, Mi, n_levels, level0, drho = tabs[:5]
-            Pn, rho_key = int(np.prod(self.P)), rho.tobytes()
+        d, tabs, Pn = self._problem_on_device(rho, adaptive)
+        K, Mi, n_levels, level0, drho = tabs[:5]
+        rho_key = rho if self.P is None else rho.tobytes()
 
-        # 4. one row per instance, the padded components zero.  A plain solve runs where x0 is (host data: on the current device), the
-        # others where the problem's tables are -- unless a single problem tracks from an x0 that is on a device already.
-        def flat(X, tail, width, dev):
-            t = arr.to_device(X, torch.float64, dev)
-            t = t.expand(lead + tail).reshape((Bn,) + tail)
-            if width != tail[-1]:
-                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
-            return t.contiguous()
-        dx0 = flat(x0, (self._n_user,), n, d["A"].device if tracking or self.P is not None else None)
-        dev = dx0.device if self.P is None else d["A"].device
-        dxr = None if xRef is None else flat(xRef, (N + 1, self._n_user), n, dev)
-        dur = None if uRef is None else flat(uRef, (N, self._m_user), m, dev)
-        prob = None   # instance -> problem
-        if self.P is not None:
-            prob = torch.as_tensor(np.ascontiguousarray(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
-                                   device=dev)
+        # 4. one row per instance and the instance -> problem map
+        dev, dx0, (dxr, dur), prob = self._device_rows(lead, Bn, d, tracking, x0, refs)
 
         # 5. workspace (y, lam, kf, rv; tracking: a fifth block for the linear term of the cost) and the warm start from it.  A plain solve
         # is keyed on the number of instances, the others on the batch shape, tracking as a kind of its own.
         key = (("tracking", lead) if linear else lead if self.P is not None else Bn, str(dev), rho_key, adaptive)
-        warm = warm and self._ws is not None and self._ws[0] == key
-        if not warm:
+        if not (warm and self._ws is not None and self._ws[0] == key):
+            warm = 0
             self._ws = (key, torch.empty((5 if linear else 4) * Bn * N * (n + m), dtype=torch.float64, device=dev))
         ws = self._ws[1]
 
@@ -283,23 +300,20 @@ class lqrMpc():
         res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
 
         # 7. the C call: the plain and the per-problem kernels, or the tracking variants of either (other kernels, slower per iteration)
-        p = lambda k: d[k].data_ptr()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        common = (K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP, alpha, p("x_lb"), p("x_ub"), p("u_lb"), p("u_ub"),
-                  dx0.data_ptr())
-        out = (eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, ws.data_ptr(), xT.data_ptr(), uT.data_ptr(),
-               st.data_ptr(), its.data_ptr(), res.data_ptr(), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+        opts = (n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, "x_lb x_ub u_lb u_ub", dx0))
+        out = (eps_abs, eps_rel, eps_pinf, max_iter, warm, *_ptrs(d, "", ws, xT, uT, st, its, res), Bn, N, n, m,
+               ctypes.c_void_p(arr.stream_ptr(dx0)))
         if self._LTV:   # (ltvMpc: stage-varying dynamics, always per-problem, a reference or none)
             D, ABt = tabs[6:8]
-            rc = _lib.lib().zm_mpc_solve_ltv_f64(p("A"), p("B"), p("c"), ABt.data_ptr(), p("Q"), p("R"), p("Qf"), K.data_ptr(), Mi.data_ptr(),
-                                                  D.data_ptr(), *common[2:], ptr(dxr), ptr(dur), drho.data_ptr(), prob.data_ptr(), Pn, *out)
+            rc = _lib.lib().zm_mpc_solve_ltv_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Q R Qf", K, Mi, D), *opts,
+                                                  *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
         elif tracking:
-            rc = _lib.lib().zm_mpc_solve_tracking_f64(p("A"), p("B"), p("Q"), p("R"), p("Qf"), *common, ptr(dxr), ptr(dur),
-                                                       rho if self.P is None else 0.0, ptr(drho), ptr(prob), Pn, *out)
+            rc = _lib.lib().zm_mpc_solve_tracking_f64(*_ptrs(d, "A B Q R Qf", K, Mi), *opts, *_ptrs(d, "", dxr, dur),
+                                                       rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, *out)
         elif self.P is not None:
-            rc = _lib.lib().zm_mpc_solve_batched_f64(p("A"), p("B"), *common, drho.data_ptr(), prob.data_ptr(), Pn, *out)
+            rc = _lib.lib().zm_mpc_solve_batched_f64(*_ptrs(d, "A B", K, Mi), *opts, *_ptrs(d, "", drho, prob), Pn, *out)
         else:
-            rc = _lib.lib().zm_mpc_solve_relaxed_f64(p("A"), p("B"), *common, rho, *out)
+            rc = _lib.lib().zm_mpc_solve_relaxed_f64(*_ptrs(d, "A B", K, Mi), *opts, rho, *out)
         _lib.check(rc, "lqrMpc.solve")
 
         # 8. results
@@ -351,96 +365,50 @@ class lqrMpc():
             MpcClosedLoop(xTraj (..., S+1, n), uTraj (..., S, m), status (..., S) strings, iterations (..., S) int32,
                           predictions: None or Trajectory((..., S, N+1, n), (..., S, N, m)))
         """
-        S = int(steps)
-        if S < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
-        if clip_tol is not None and not (float(clip_tol) >= 0.0):
-            raise ValueError(f"clip_tol must be non-negative (or None for no clip), got {clip_tol}")
-        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(solver_opts, "shift")
+        S, clip = _run_steps(steps, clip_tol)
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm = self._solver_options(solver_opts, "shift")
         if isinstance(xRef, Trajectory) or isinstance(uRef, Trajectory):
             raise ValueError("simulate takes xRef (..., steps + N, n) and uRef (..., steps + N - 1, m) as arrays, not a Trajectory")
         tracking = xRef is not None or uRef is not None
         N, n, m = self.N, self.n, self.m
 
         # 1. shapes
-        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        shp = shape_of(x0)
-        if len(shp) < 1 or shp[-1] != self._n_user:
-            raise ValueError(f"x0 has shape {shp}, expected (..., {self._n_user})")
-        leads = {"x0": (shp, shp[:-1])}
-        for name, X, want in (("disturbance", disturbance, (S, self._n_user)), ("xRef", xRef, (S + N, self._n_user)),
-                              ("uRef", uRef, (S + N - 1, self._m_user))):
-            if X is not None:
-                sh = shape_of(X)
-                if len(sh) < 2 or sh[-2:] != want:
-                    raise ValueError(f"{name} has shape {sh}, expected (..., {want[0]}, {want[1]}) for steps = {S}, N = {N}")
-                leads[name] = (sh, sh[:-2])
-        try:
-            lead = np.broadcast_shapes(*(l for _, l in leads.values()), *(() if self.P is None else (self.P,)))
-        except ValueError:
-            who = ", ".join(f"{k} of shape {sh}" for k, (sh, _) in leads.items())
-            raise ValueError(who + " do not broadcast against each other"
-                             + ("" if self.P is None else f" and the problem shape {self.P}") + ": inconsistent shapes") from None
-        lead = tuple(int(v) for v in lead)
-        Bn = int(np.prod(lead))
+        per = (("disturbance", disturbance, (S, self._n_user), n), ("xRef", xRef, (S + N, self._n_user), n),
+               ("uRef", uRef, (S + N - 1, self._m_user), m))
+        lead, Bn = self._batch_shape(x0, per, f" for steps = {S}, N = {N}")
         arr.require_gpu()
 
         # 2. the problem on the device and its tables (shared with `solve`: they depend on the problem and the penalty only)
-        if self.P is None:
-            d, (K, Mi, n_levels, level0) = self._device_problem(rho, adaptive)
-            drho, Pn = None, 0
-        else:
-            d, (K, Mi, n_levels, level0, drho, _) = self._device_problem_batched(rho, adaptive)
-            Pn = int(np.prod(self.P))
+        d, (K, Mi, n_levels, level0, drho, *_), Pn = self._problem_on_device(rho, adaptive)
 
-        # 3. one row per instance, the padded components zero; device placement as in `solve`
-        def flat(X, tail, width, dev):
-            t = arr.to_device(X, torch.float64, dev)
-            t = t.expand(lead + tail).reshape((Bn,) + tail)
-            if width != tail[-1]:
-                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
-            return t.contiguous()
-        dx0 = flat(x0, (self._n_user,), n, d["A"].device if tracking or self.P is not None else None)
-        dev = dx0.device if self.P is None else d["A"].device
-        dxr = None if xRef is None else flat(xRef, (S + N, self._n_user), n, dev)
-        dur = None if uRef is None else flat(uRef, (S + N - 1, self._m_user), m, dev)
-        dw = None if disturbance is None else flat(disturbance, (S, self._n_user), n, dev).transpose(0, 1).contiguous()   # step-major
-        prob = None   # instance -> problem
-        if self.P is not None:
-            prob = torch.as_tensor(np.array(np.broadcast_to(np.arange(Pn, dtype=np.int32).reshape(self.P), lead)).reshape(-1),
-                                   device=dev)
+        # 3. one row per instance (the disturbance step-major) and the instance -> problem map; device placement as in `solve`
+        dev, dx0, (dw, dxr, dur), prob = self._device_rows(lead, Bn, d, tracking, x0, per)
+        dw = None if dw is None else dw.transpose(0, 1).contiguous()
 
         # 4. outputs (step-major on the device) and the run's own workspace
-        f64 = dict(dtype=torch.float64, device=dev)
-        xs = torch.empty((S + 1, Bn, n), **f64)
-        us = torch.empty((S, Bn, m), **f64)
-        st = torch.empty((S, Bn), dtype=torch.int32, device=dev)
-        its = torch.empty((S, Bn), dtype=torch.int32, device=dev)
-        xp = torch.empty((S, Bn, N + 1, n), **f64) if return_predictions else None
-        up = torch.empty((S, Bn, N, m), **f64) if return_predictions else None
-        ws = torch.empty((5 if tracking else 4) * Bn * N * (n + m) + (0 if return_predictions else Bn * ((N + 1) * n + N * m)), **f64)
+        xs, us, st, its, xp, up, ws = _run_buffers(S, Bn, N, n, m, dev, return_predictions, tracking)
 
         # 5. the C call
         if Bn > 0:
-            p = lambda k: d[k].data_ptr()
-            ptr = lambda t: None if t is None else t.data_ptr()
             rc = _lib.lib().zm_mpc_closed_loop_f64(
-                p("A"), p("B"), p("Q"), p("R"), p("Qf"), K.data_ptr(), Mi.data_ptr(), n_levels, level0, self.RHO_STEP, alpha, p("x_lb"),
-                p("x_ub"), p("u_lb"), p("u_ub"), dx0.data_ptr(), ptr(dxr), ptr(dur), S + N, S + N - 1, rho if self.P is None else 0.0,
-                ptr(drho), ptr(prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, S,
-                -1.0 if clip_tol is None else float(clip_tol), ptr(dw), ws.data_ptr(), xs.data_ptr(), us.data_ptr(), st.data_ptr(),
-                its.data_ptr(), ptr(xp), ptr(up), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+                *_ptrs(d, "A B Q R Qf", K, Mi), n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, "x_lb x_ub u_lb u_ub", dx0, dxr, dur),
+                S + N, S + N - 1, rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter, warm,
+                S, clip, *_ptrs(d, "", dw, ws, xs, us, st, its, xp, up), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
             _lib.check(rc, "lqrMpc.simulate")
 
-        # 6. results: batch-leading views of the step-major arrays
+        return self._run_results(lead, S, x0, (xs, us, st, its, xp, up))
+
+    def _run_results(self, lead, S, x0, out):
+        """What a run returns: batch-leading views of its step-major device arrays (xs, us, st, its, xp | None, up | None)"""
+        xs, us, st, its, xp, up = out
+        N, n, m, nu, mu = self.N, self.n, self.m, self._n_user, self._m_user
         view = lambda t, tail, width: arr.result_like(t.transpose(0, 1).reshape(lead + tail)[..., :width], x0)
         codes = st.transpose(0, 1).reshape(lead + (S,)).cpu().numpy()
-        status = np.vectorize(_STATUS.get, otypes=[object])(codes) if Bn > 0 else np.empty(lead + (S,), dtype=object)
+        status = np.vectorize(_STATUS.get, otypes=[object])(codes) if codes.size > 0 else np.empty(lead + (S,), dtype=object)
         pred = None
-        if return_predictions:
-            pred = Trajectory(view(xp, (S, N + 1, n), self._n_user), view(up, (S, N, m), self._m_user))
-        return MpcClosedLoop(view(xs, (S + 1, n), self._n_user), view(us, (S, m), self._m_user), status,
-                             view(its, (S,), None), pred)
+        if xp is not None:
+            pred = Trajectory(view(xp, (S, N + 1, n), nu), view(up, (S, N, m), mu))
+        return MpcClosedLoop(view(xs, (S + 1, n), nu), view(us, (S, m), mu), status, view(its, (S,), None), pred)
 
 
 class ltvMpc(lqrMpc):
@@ -573,10 +541,8 @@ class ltvMpc(lqrMpc):
         if key not in self._tables:
             tabs = self._empty_tables(rho, adaptive)
             K, Mi, nl, _, _, rtab, D, ABt = tabs
-            rc = _lib.lib().zm_mpc_setup_ltv_f64(d["A"].data_ptr(), d["B"].data_ptr(), d["c"].data_ptr(), d["Q"].data_ptr(),
-                                                 d["R"].data_ptr(), d["Qf"].data_ptr(), rtab.data_ptr(), int(np.prod(self.P)), nl, self.N,
-                                                 self.n, self.m, K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(),
-                                                 ctypes.c_void_p(arr.stream_ptr(K)))
+            rc = _lib.lib().zm_mpc_setup_ltv_f64(*_ptrs(d, "A B c Q R Qf", rtab), int(np.prod(self.P)), nl, self.N, self.n, self.m,
+                                                 *_ptrs(d, "", K, Mi, D, ABt), ctypes.c_void_p(arr.stream_ptr(K)))
             _lib.check(rc, "ltvMpc setup")
             self._tables[key] = tabs
         return d, self._tables[key]
@@ -666,12 +632,8 @@ class ltvMpc(lqrMpc):
         -------
             MpcClosedLoop, as `lqrMpc.simulate` returns it
         """
-        S = int(steps)
-        if S < 1:
-            raise ValueError(f"steps must be at least 1, got {steps}")
-        if clip_tol is not None and not (float(clip_tol) >= 0.0):
-            raise ValueError(f"clip_tol must be non-negative (or None for no clip), got {clip_tol}")
-        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm, shift = self._solver_options(solver_opts, "shift")
+        S, clip = _run_steps(steps, clip_tol)
+        eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm = self._solver_options(solver_opts, "shift")
         if isinstance(xRef, Trajectory) or isinstance(uRef, Trajectory):
             raise ValueError("realTimeIteration takes xRef (..., steps + N, n) and uRef (..., steps + N - 1, m) as arrays, not a Trajectory")
         N, n, m, nu, mu = self.N, self.n, self.m, self._n_user, self._m_user
@@ -680,97 +642,50 @@ class ltvMpc(lqrMpc):
             _model_shape("ltvMpc.realTimeIteration", plant, (nu, mu), "plant")
 
         # 1. shapes: everything broadcasts to the problem shape (every instance is its own problem)
-        shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        shp = shape_of(x0)
-        if len(shp) < 1 or shp[-1] != nu:
-            raise ValueError(f"x0 has shape {shp}, expected (..., {nu})")
-        leads = {"x0": (shp, shp[:-1])}
-        for name, X, want in (("disturbance", disturbance, (S, nu)), ("xRef", xRef, (S + N, nu)), ("uRef", uRef, (S + N - 1, mu))):
-            if X is not None:
-                sh = shape_of(X)
-                if len(sh) < 2 or sh[-2:] != want:
-                    raise ValueError(f"{name} has shape {sh}, expected (..., {want[0]}, {want[1]}) for steps = {S}, N = {N}")
-                leads[name] = (sh, sh[:-2])
-        if plan is not None:
-            xs, us, pl = _plan_shapes("ltvMpc.realTimeIteration", plan, N, nu, mu)
-            leads["plan.xTraj"], leads["plan.uTraj"] = (xs, pl), (us, pl)
-        try:
-            ok = np.broadcast_shapes(*(l for _, l in leads.values()), self.P) == self.P
-        except ValueError:
-            ok = False
-        if not ok:
-            who = ", ".join(f"{k} of shape {sh}" for k, (sh, _) in leads.items())
-            raise ValueError(who + f" do not broadcast to the problem shape {self.P} (every instance is its own problem): inconsistent shapes")
-        lead = self.P
-        Bn = int(np.prod(lead))
+        per = (("disturbance", disturbance, (S, nu), n), ("xRef", xRef, (S + N, nu), n), ("uRef", uRef, (S + N - 1, mu), m))
+        lead, Bn = self._batch_shape(x0, per, f" for steps = {S}, N = {N}", own=True, plan=plan)
         arr.require_gpu()
 
         # 2. the problem on the device; the tables of every step are written by the call (those of the last step stay, as a solve's do)
         d = self._device_data()
-        dev = d["A"].device
         tabs = self._empty_tables(rho, adaptive)
         K, Mi, n_levels, level0, drho, rtab, D, ABt = tabs
 
-        # 3. one row per instance, the padded components zero
-        def flat(X, tail, width):
-            t = arr.to_device(X, torch.float64, dev)
-            t = t.expand(lead + tail).reshape((Bn,) + tail)
-            if width != tail[-1]:
-                t = torch.nn.functional.pad(t, (0, width - tail[-1]))
-            return t.contiguous()
-        dx0 = flat(x0, (nu,), n)
-        dxr = None if xRef is None else flat(xRef, (S + N, nu), n)
-        dur = None if uRef is None else flat(uRef, (S + N - 1, mu), m)
-        dw = None if disturbance is None else flat(disturbance, (S, nu), n).transpose(0, 1).contiguous()   # step-major
+        # 3. one row per instance (the disturbance step-major), the identity as the instance -> problem map, the first plan
+        dev, dx0, (dw, dxr, dur), prob = self._device_rows(lead, Bn, d, True, x0, per, identity=True)
+        dw = None if dw is None else dw.transpose(0, 1).contiguous()
         if plan is not None:   # (copies: the call moves its plan on)
-            xP = flat(tuple.__getitem__(plan, 0), (N + 1, nu), nu).clone()
-            uP = flat(tuple.__getitem__(plan, 1), (N, mu), mu).clone()
+            xP = _flat(tuple.__getitem__(plan, 0), lead, Bn, (N + 1, nu), nu, dev).clone()
+            uP = _flat(tuple.__getitem__(plan, 1), lead, Bn, (N, mu), mu, dev).clone()
         else:
             xh = dx0[:, :nu]
             if clip_tol is not None:
                 xh = torch.minimum(torch.maximum(xh, d["x_lb"][:, :nu] + float(clip_tol)), d["x_ub"][:, :nu] - float(clip_tol))
             xP = xh[:, None, :].expand(Bn, N + 1, nu).contiguous()
             uP = torch.zeros((Bn, N, mu), dtype=torch.float64, device=dev) if dur is None else dur[:, :N, :mu].contiguous()
-        prob = torch.arange(Bn, dtype=torch.int32, device=dev)
 
         # 4. outputs (step-major on the device); the workspace is the object's: step 0 starts cold, a later `solve` may start warm from it
-        f64 = dict(dtype=torch.float64, device=dev)
-        xs = torch.empty((S + 1, Bn, n), **f64)
-        us = torch.empty((S, Bn, m), **f64)
-        st = torch.empty((S, Bn), dtype=torch.int32, device=dev)
-        its = torch.empty((S, Bn), dtype=torch.int32, device=dev)
-        res = torch.empty((Bn, 2), **f64)
-        xp = torch.empty((S, Bn, N + 1, n), **f64) if return_predictions else None
-        up = torch.empty((S, Bn, N, m), **f64) if return_predictions else None
-        ws = torch.empty(5 * Bn * N * (n + m) + (0 if return_predictions else Bn * ((N + 1) * n + N * m)), **f64)
+        xs, us, st, its, xp, up, ws = _run_buffers(S, Bn, N, n, m, dev, return_predictions, True)
+        res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
         self._ws = ((("tracking", lead), str(dev), rho.tobytes(), adaptive), ws)
         self._tables = {(rho.tobytes(), bool(adaptive)): tabs}
 
         # 5. the C call
         if Bn > 0:
-            p = lambda k: d[k].data_ptr()
-            ptr = lambda t: None if t is None else t.data_ptr()
             cs = model.c_struct()
             cp = None if plant is None else plant.c_struct()
             rc = _lib.lib().zm_mpc_rti_f64(
-                ctypes.addressof(cs), None if cp is None else ctypes.addressof(cp), xP.data_ptr(), uP.data_ptr(), p("A"), p("B"), p("c"),
-                p("Q"), p("R"), p("Qf"), rtab.data_ptr(), K.data_ptr(), Mi.data_ptr(), D.data_ptr(), ABt.data_ptr(), n_levels, level0,
-                self.RHO_STEP, alpha, p("x_lb"), p("x_ub"), p("u_lb"), p("u_ub"), dx0.data_ptr(), ptr(dxr), ptr(dur), S + N, S + N - 1,
-                drho.data_ptr(), prob.data_ptr(), eps_abs, eps_rel, eps_pinf, max_iter, (2 if shift else 1) if warm else 0, S,
-                -1.0 if clip_tol is None else float(clip_tol), ptr(dw), ws.data_ptr(), xs.data_ptr(), us.data_ptr(), st.data_ptr(),
-                its.data_ptr(), res.data_ptr(), ptr(xp), ptr(up), Bn, N, nu, mu, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
+                ctypes.addressof(cs), None if cp is None else ctypes.addressof(cp), *_ptrs(d, "", xP, uP),
+                *_ptrs(d, "A B c Q R Qf", rtab, K, Mi, D, ABt), n_levels, level0, self.RHO_STEP, alpha,
+                *_ptrs(d, "x_lb x_ub u_lb u_ub", dx0, dxr, dur), S + N, S + N - 1, *_ptrs(d, "", drho, prob), eps_abs, eps_rel, eps_pinf,
+                max_iter, warm, S, clip, *_ptrs(d, "", dw, ws, xs, us, st, its, res, xp, up), Bn, N, nu, mu, n, m,
+                ctypes.c_void_p(arr.stream_ptr(dx0)))
             _lib.check(rc, "ltvMpc.realTimeIteration")
 
-        # 6. results: batch-leading views of the step-major arrays; the object's record of its last solve
+        # 6. results; the object's record of its last solve
         self.last_iterations = its[S - 1].reshape(lead).cpu().numpy()
         self.last_residuals = res.reshape(lead + (2,)).cpu().numpy()
-        view = lambda t, tail, width: arr.result_like(t.transpose(0, 1).reshape(lead + tail)[..., :width], x0)
-        codes = st.transpose(0, 1).reshape(lead + (S,)).cpu().numpy()
-        status = np.vectorize(_STATUS.get, otypes=[object])(codes) if Bn > 0 else np.empty(lead + (S,), dtype=object)
-        pred = None
-        if return_predictions:
-            pred = Trajectory(view(xp, (S, N + 1, n), nu), view(up, (S, N, m), mu))
-        return MpcClosedLoop(view(xs, (S + 1, n), nu), view(us, (S, m), mu), status, view(its, (S,), None), pred)
+        return self._run_results(lead, S, x0, (xs, us, st, its, xp, up))
 
 
 def modelStep(model, x, u):
@@ -778,8 +693,7 @@ def modelStep(model, x, u):
     m <= 4) by its step function on the device (zm_model_step_f64) -- the plant of `ltvMpc.realTimeIteration` as a call of its own.
     x (..., n), u (..., m) with leading axes that broadcast against each other; NumPy in, NumPy out, device tensors in, device tensors out."""
     n, m = _model_shape("modelStep", model)
-    shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-    sx, su = shape_of(x), shape_of(u)
+    sx, su = _shape_of(x), _shape_of(u)
     if len(sx) < 1 or sx[-1] != n or len(su) < 1 or su[-1] != m:
         raise ValueError(f"modelStep: x has shape {sx}, u has shape {su}, expected (..., {n}) and (..., {m})")
     try:
@@ -798,6 +712,50 @@ def modelStep(model, x, u):
                                       ctypes.c_void_p(arr.stream_ptr(dx)))
     _lib.check(rc, "modelStep")
     return arr.result_like(out.reshape(lead + (n,)), x)
+
+
+def _ptrs(d, names, *tensors):
+    """The addresses a C call takes: of d[name] for every name in the string `names`, then of `tensors`; None stays None (NULL)"""
+    return [None if t is None else t.data_ptr() for t in [d[k] for k in names.split()] + list(tensors)]
+
+
+def _shape_of(X):
+    return tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
+
+
+def _flat(X, lead, Bn, tail, width, dev):
+    """X (..., *tail) on `dev` as one contiguous row per instance of the batch shape `lead` (Bn instances), its last axis zero-padded to
+    `width`"""
+    t = arr.to_device(X, torch.float64, dev)
+    t = t.expand(lead + tail).reshape((Bn,) + tail)
+    if width != tail[-1]:
+        t = torch.nn.functional.pad(t, (0, width - tail[-1]))
+    return t.contiguous()
+
+
+def _run_steps(steps, clip_tol):
+    """(S, the C side's clip_tol: -1 for none) of a run's `steps` and `clip_tol`"""
+    S = int(steps)
+    if S < 1:
+        raise ValueError(f"steps must be at least 1, got {steps}")
+    if clip_tol is not None and not (float(clip_tol) >= 0.0):
+        raise ValueError(f"clip_tol must be non-negative (or None for no clip), got {clip_tol}")
+    return S, -1.0 if clip_tol is None else float(clip_tol)
+
+
+def _run_buffers(S, Bn, N, n, m, dev, keep, tracking):
+    """The outputs of a run, step-major on the device: states, inputs, status, iterations, the predictions (`keep`, else None, None); then
+    its workspace: the blocks of a solve (a fifth with `tracking`) and, unless the predictions are kept, the rollout every step
+    overwrites"""
+    f64 = dict(dtype=torch.float64, device=dev)
+    xs = torch.empty((S + 1, Bn, n), **f64)
+    us = torch.empty((S, Bn, m), **f64)
+    st = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+    its = torch.empty((S, Bn), dtype=torch.int32, device=dev)
+    xp = torch.empty((S, Bn, N + 1, n), **f64) if keep else None
+    up = torch.empty((S, Bn, N, m), **f64) if keep else None
+    ws = torch.empty((5 if tracking else 4) * Bn * N * (n + m) + (0 if keep else Bn * ((N + 1) * n + N * m)), **f64)
+    return xs, us, st, its, xp, up, ws
 
 
 def _model_shape(who, model, want=None, what="model"):
@@ -822,8 +780,7 @@ def _plan_shapes(who, plan, N, n, m, P=None):
         xT, uT = tuple.__getitem__(plan, 0), tuple.__getitem__(plan, 1)
     except Exception:
         raise ValueError(f"{who}: plan must be a Trajectory (xTraj, uTraj), got {type(plan).__name__}") from None
-    shape_of = lambda X: tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-    xs, us = shape_of(xT), shape_of(uT)
+    xs, us = _shape_of(xT), _shape_of(uT)
     stages = us[-2] if (N is None and len(us) >= 2) else N
     ok = len(xs) >= 2 and len(us) >= 2 and stages is not None and stages >= 1 and xs[-2:] == (stages + 1, n) and us[-2:] == (stages, m)
     lead = None
