@@ -2,9 +2,16 @@
 // instructions (it carries a Payne-Hanek path for huge arguments), three of them per model evaluation.  Here:
 // Cody-Waite reduction by pi/2 in two FMA steps (exact cancellation by the fused product; the neglected third term is
 // k * 1.5e-33) and the minimax kernels of fdlibm's __kernel_sin / __kernel_cos on [-pi/4, pi/4] (Sun Microsystems' public
-// coefficient tables): ~35 instructions; measured against 200-bit arithmetic (the same operation sequence in Python): <= 1.4 ulp
-// for |x| <= 1e6, except right next to the zeros of sin / cos at large arguments, where the error is <= 3e-22 absolute.  Beyond
-// that the absolute error grows like 1.5e-33 |x| (the neglected third term of pi/2) up to |x| ~ 2^52; inf and NaN give NaN.
+// coefficient tables): ~35 instructions.  Contract for |x| <= 1e6, with k = rint(2x/pi), asserted against 400-bit arithmetic on a
+// host build of this header (tests/trig_shim.cpp, tests/test_sincos.py) and bit for bit against that build on the device
+// (tests/test_sincos_gpu.py):
+//     |error| <= 1.4 ulp(result) + (|k| + 1) * 1.6e-33.
+// The second term is the neglected third term of pi/2.  It matters only right next to a zero of sin or cos (x = fl(k pi/2) and its
+// neighbours), where the result itself is ~1e-17 |k| or smaller: there the ulp bound alone does NOT hold, at small arguments
+// either (450 ulp measured for |k| <= 64, more for some larger k), while the absolute error stays near |k| * 1.5e-33.  Beyond
+// 1e6 the absolute error keeps growing like 1.5e-33 |x| up to |x| ~ 2^52; past that the reduction has no meaning and the results
+// need not be finite (1e300 gives inf / NaN).  +-inf and NaN give NaN.  sin(-0.0) is +0.0, not -0.0: the reduction's
+// fma(-k, pi/2, x) with k = -0.0 adds +0.0 to -0.0.  Tiny and subnormal x: sin(x) = x, cos(x) = 1 exactly.
 #pragma once
 #include <hip/hip_runtime.h>
 
