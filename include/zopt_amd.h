@@ -556,6 +556,35 @@ int zm_mpc_solve_ltv_f64(const double* A, const double* B, const double* c, cons
                          double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m,
                          void* stream);
 
+/* Stage-varying weights and bounds on top of the stage-varying dynamics (extension): the QP above with
+ *     cost  sum_{k<N} (x_{k+1} - xr_{k+1})' Qs_k (x_{k+1} - xr_{k+1}) + (u_k - ur_k)' Rs_k (u_k - ur_k)   (Qs_{N-1}: the terminal weight)
+ *     box   x_lb0 <= x_0 <= x_ub0,   lo_k <= [x_{k+1} ; u_k] <= hi_k,   k = 0 .. N-1    (+-inf allowed anywhere)
+ * -- corridors and gates that move along the horizon, a terminal set tighter than the stage box, tube tightening, waypoint weights,
+ * discounted costs.  ADMM, termination, certificate, status codes, workspace and outputs are zm_mpc_solve_ltv_f64's.
+ * zm_mpc_setup_ltv_stage_f64 replaces zm_mpc_setup_ltv_f64:  P_N = 2 Qs_{N-1} + rho I, stage k uses Rs_k, the value update that leaves
+ *     stage k >= 1 uses Qs_{k-1} (the one that leaves stage 0 is read by nothing).  The same products in the same order: with constant
+ *     rows (Qs_k = Q for k < N-1, Qs_{N-1} = Qf, Rs_k = R) the tables are zm_mpc_setup_ltv_f64's bit for bit.
+ *     in : A (P,N,n,n)  B (P,N,n,m)  c (P,N,n) or NULL (zero)  Qs (P,N,n,n)  Rs (P,N,m,m)  rho (P,L)   [device]
+ *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m)  D (P,L,N,n)  ABt (P,N,n+m,n), as zm_mpc_setup_ltv_f64 writes them   [device]
+ *     ZM_EINVAL for a null pointer or a bad size, ZM_EUNSUPPORTED beyond n <= 12, m <= 4; both before any launch.
+ * zm_mpc_solve_ltv_stage_f64 replaces zm_mpc_solve_ltv_f64: its arguments with (Q, R, Qf) -> (Qs, Rs) -- read for the linear term of a
+ *     reference only, g_x,k = -(Qs_k + Qs_k') xr_{k+1}, g_u,k = -(Rs_k + Rs_k') ur_k -- and (x_lb, x_ub, u_lb, u_ub) ->
+ *     x_lb0, x_ub0 (P,n): the box of x_0, an x0 outside it is ZM_MPC_INFEASIBLE at once;
+ *     lo, hi (P,N,n+m):  row k = [bound of x_{k+1} ; bound of u_k], the kernels' stacked stage layout.                [device]
+ *     The stage's bounds are fetched with the stage's other data, three stages ahead; with constant rows the iterates are
+ *     zm_mpc_solve_ltv_f64's bit for bit.  The same refusals: ZM_EINVAL for a null pointer, a bad size, bad penalty levels or a map
+ *     entry outside [0, P); ZM_EUNSUPPORTED for (n, m) outside the compiled shapes with n + m <= 16 and for N > 75; all but the map
+ *     check before any launch. */
+int zm_mpc_setup_ltv_stage_f64(const double* A, const double* B, const double* c, const double* Qs, const double* Rs, const double* rho,
+                               int64_t P, int L, int N, int n, int m, double* K, double* Minv, double* D, double* ABt, void* stream);
+int zm_mpc_solve_ltv_stage_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Qs, const double* Rs,
+                               const double* K, const double* Minv, const double* D, int n_levels, int level0, double rho_step,
+                               double alpha, const double* x_lb0, const double* x_ub0, const double* lo, const double* hi,
+                               const double* x0, const double* xRef, const double* uRef, const double* rho_p, const int32_t* problem,
+                               int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start,
+                               double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
+                               int64_t batch, int N, int n, int m, void* stream);
+
 /* Real-time-iteration nonlinear MPC (extension): zm_mpc_solve_ltv_f64 on the linearisation of a REGISTERED MODEL about a plan, every
  * instance its own problem (P = batch, problem[i] = i).  Shapes: the model's (n_user, m_user) embedded in a compiled (ns, mc) of the
  * 16-lanes-per-instance kernels, as zopt_amd/mpcUtils.py embeds them; models: ZM_MODEL_QUADCOPTER (12, 4) and ZM_MODEL_QUADCOPTER_RB

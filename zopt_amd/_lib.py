@@ -102,6 +102,15 @@ SYMBOLS = {
     "zm_mpc_solve_ltv_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
                              [_c_dp] * 9 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                              [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (A, B, c | NULL, Qs (P,N,n,n), Rs (P,N,m,m), rho (P,L), P, L, N, n, m, K, Minv, D, ABt, stream)
+    "zm_mpc_setup_ltv_stage_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
+                                   [_c_dp] * 4 + [ctypes.c_void_p]),
+    # (A, B, c, ABt, Qs, Rs, K, Minv, D, n_levels, level0, rho_step, alpha, x_lb0 (P,n), x_ub0, lo (P,N,n+m), hi, x0, xRef | NULL,
+    #  uRef | NULL, rho_p, problem, P, eps_abs, eps_rel, eps_prim_inf, max_iter, warm_start, ws, xTraj, uTraj, status, iters, resid, batch,
+    #  N, n, m, stream)
+    "zm_mpc_solve_ltv_stage_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                                   [_c_dp] * 9 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
+                                   [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (model*, x, u, xNext, batch, stream)
     "zm_model_step_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
     # (model*, xPlan, uPlan, A, B, c, batch, N, n_user, m_user, ns, mc, stream)

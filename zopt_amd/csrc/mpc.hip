@@ -181,6 +181,96 @@ __global__ __launch_bounds__(256) void mpc_setup_ltv_kernel(const double* __rest
     }
 }
 
+// Stage-varying weights (zm_mpc_setup_ltv_stage_f64): mpc_setup_ltv_kernel with Qs (P,N,n,n), Rs (P,N,m,m) in place of Q, R, Qf -- Qs_k
+// weights x_{k+1} (row N - 1 is the terminal weight), Rs_k weights u_k:  P_N = 2 Qs_{N-1} + rho I, stage k adds 2 Rs_k + rho I to Suu, and
+// the value update that leaves stage k >= 1 adds 2 Qs_{k-1} + rho I.  A sibling, not a flag: that kernel stays as it is.  The same products
+// in the same order, so constant rows (Qs_k = Q, Qs_{N-1} = Qf, Rs_k = R) give that kernel's K, Minv, D and ABt bit for bit.
+template <int SN, int SM>
+__global__ __launch_bounds__(256) void mpc_setup_ltv_stage_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                                  const double* __restrict__ c, const double* __restrict__ Qs,
+                                                                  const double* __restrict__ Rs, const double* __restrict__ rho_tab,
+                                                                  const int L, const int N, const int n, const int m,
+                                                                  double* __restrict__ Kout, double* __restrict__ Minvout,
+                                                                  double* __restrict__ Dout, double* __restrict__ ABt) {
+    const long b = blockIdx.x, p = b / L;
+    const bool pack = (b % L) == 0;
+    A += p * N * n * n;
+    B += p * N * n * m;
+    if (c) c += p * N * n;
+    Qs += p * N * n * n;
+    Rs += p * N * m * m;
+    Kout += b * N * m * n;
+    Minvout += b * N * m * m;
+    Dout += b * N * n;
+    ABt += p * N * (n + m) * n;
+    const double rho = rho_tab[b];
+    __shared__ double As[SN * SN], Bs[SN * SM], P[SN * SN], PA[SN * SN], PB[SN * SM], Sux[SM * SN], Suu[SM * SM], Mi[SM * SM], K[SM * SN],
+        T1[SN * SN], T2[SN * SN];
+    const int t = threadIdx.x;
+    for (int e = t; e < n * n; e += blockDim.x) P[e] = 2.0 * Qs[(long)(N - 1) * n * n + e] + ((e / n == e % n) ? rho : 0.0);  // P_N = 2 Qs_{N-1} + rho I
+    __syncthreads();
+    for (int k = N - 1; k >= 0; --k) {
+        // (As, Bs of the stage above were last read before the barrier that ends it; P holds P_{k+1})
+        for (int e = t; e < n * n; e += blockDim.x) As[e] = A[(long)k * n * n + e];
+        for (int e = t; e < n * m; e += blockDim.x) Bs[e] = B[(long)k * n * m + e];
+        if (t < n) {
+            double s = 0.0;
+            if (c)
+                for (int j = 0; j < n; ++j) s = __builtin_fma(P[t * n + j], c[(long)k * n + j], s);
+            Dout[(long)k * n + t] = s;
+        }
+        __syncthreads();
+        if (pack)
+            for (int e = t; e < (n + m) * n; e += blockDim.x) {
+                const int i = e / n, l = e % n;
+                ABt[(long)k * (n + m) * n + e] = i < n ? As[l * n + i] : Bs[l * m + (i - n)];
+            }
+        mm_nn(PA, P, As, n, n, n);
+        mm_nn(PB, P, Bs, n, n, m);
+        mm_tn(Sux, Bs, PA, n, m, n);  // B_k^T P A_k
+        mm_tn(Suu, Bs, PB, n, m, m);  // B_k^T P B_k
+        if (t < m * m) Suu[t] += 2.0 * Rs[(long)k * m * m + t] + ((t / m == t % m) ? rho : 0.0);
+        __syncthreads();
+        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= 4), as in mpc_setup_body.h
+            double a[SM][2 * SM];
+            for (int i = 0; i < m; ++i)
+                for (int j = 0; j < m; ++j) {
+                    a[i][j] = Suu[i * m + j];
+                    a[i][m + j] = (i == j) ? 1.0 : 0.0;
+                }
+            for (int cc = 0; cc < m; ++cc) {
+                int pv = cc;
+                for (int i = cc + 1; i < m; ++i)
+                    if (__builtin_fabs(a[i][cc]) > __builtin_fabs(a[pv][cc])) pv = i;
+                for (int j = 0; j < 2 * m; ++j) {
+                    const double tmp = a[cc][j];
+                    a[cc][j] = a[pv][j];
+                    a[pv][j] = tmp;
+                }
+                const double inv = 1.0 / a[cc][cc];
+                for (int j = 0; j < 2 * m; ++j) a[cc][j] *= inv;
+                for (int i = 0; i < m; ++i)
+                    if (i != cc) {
+                        const double f = a[i][cc];
+                        for (int j = 0; j < 2 * m; ++j) a[i][j] = __builtin_fma(-f, a[cc][j], a[i][j]);
+                    }
+            }
+            for (int i = 0; i < m; ++i)
+                for (int j = 0; j < m; ++j) Mi[i * m + j] = a[i][m + j];
+        }
+        __syncthreads();
+        mm_nn(K, Mi, Sux, m, m, n);     // K_k = Suu^-1 B_k^T P A_k
+        mm_tn(T1, As, PA, n, n, n);     // A_k^T P A_k
+        mm_tn(T2, Sux, K, m, n, n);     // Sux^T K
+        const double* Q = Qs + (long)(k >= 1 ? k - 1 : 0) * n * n;   // the weight of x_k; nothing reads the value matrix of x_0
+        for (int e = t; e < n * n; e += blockDim.x)
+            P[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+        for (int e = t; e < m * n; e += blockDim.x) Kout[(long)k * m * n + e] = K[e];
+        for (int e = t; e < m * m; e += blockDim.x) Minvout[(long)k * m * m + e] = Mi[e];
+        __syncthreads();
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // solve: one lane per instance
 // ----------------------------------------------------------------------------------------------------------------
@@ -256,6 +346,37 @@ __global__ __launch_bounds__(256) void mpc_track_linear_kernel(const double* __r
     } else if (uRef) {
         const int r = i - n;
         const double* Rm = R + p * m * m;
+        const double* ur = uRef + (b * N + k) * m;
+        for (int j = 0; j < m; ++j) acc = __builtin_fma(Rm[r * m + j] + Rm[j * m + r], ur[j], acc);
+    }
+    g[e] = -acc;
+}
+
+// mpc_track_linear_kernel with the stage's own weights (zm_mpc_solve_ltv_stage_f64): Qs (P,N,n,n) weights x_{k+1}, Rs (P,N,m,m) weights u_k,
+//     g_x,k = -(Qs_k + Qs_k') xr_{k+1},      g_u,k = -(Rs_k + Rs_k') ur_k,
+// one thread per component, that kernel's sums in its order (constant rows give its bits).  prob is required here.
+__global__ __launch_bounds__(256) void mpc_track_linear_stage_kernel(const double* __restrict__ Qs, const double* __restrict__ Rs,
+                                                                     const double* __restrict__ xRef, const double* __restrict__ uRef,
+                                                                     const int* __restrict__ prob, const long batch, const int N,
+                                                                     const int n, const int m, double* __restrict__ g) {
+    const int W = n + m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * N * W) return;
+    const int i = (int)(e % W);
+    const long s = e / W;
+    const int k = (int)(s % N);
+    const long b = s / N;
+    const long p = prob[b];
+    double acc = 0.0;
+    if (i < n) {
+        if (xRef) {
+            const double* Wm = Qs + (p * N + k) * n * n;
+            const double* xr = xRef + (b * (N + 1) + k + 1) * n;
+            for (int j = 0; j < n; ++j) acc = __builtin_fma(Wm[i * n + j] + Wm[j * n + i], xr[j], acc);
+        }
+    } else if (uRef) {
+        const int r = i - n;
+        const double* Rm = Rs + (p * N + k) * m * m;
         const double* ur = uRef + (b * N + k) * m;
         for (int j = 0; j < m; ++j) acc = __builtin_fma(Rm[r * m + j] + Rm[j * m + r], ur[j], acc);
     }
@@ -467,6 +588,9 @@ struct MpcCall {
     int64_t batch;
     int N, n, m;                                                       // (n, m): the compiled shape the data is laid out in
     int n_user, m_user;                                                // zm_mpc_rti_f64: the model's own (n, m) inside it
+    // zm_mpc_solve_ltv_stage_f64: Q, R hold Qs (P,N,n,n), Rs (P,N,m,m) and Qf stays NULL; x_lb, x_ub hold the box of x_0 (P,n) and
+    // u_lb, u_ub the stacked lo, hi (P,N,n+m) -- the slots the kernel takes them in (mpc_common.h: mpc_wave_ltv_dispatch)
+    bool stage;
     void* stream;
 };
 
@@ -492,7 +616,7 @@ static long blocks256(long threads) { return (threads + 255) / 256; }
 static int mpc_check_args(const MpcCall& a, bool per_problem, bool tracking, bool outputs) {
     if (!(a.alpha > 0.0 && a.alpha < 2.0)) return set_error(ZM_EINVAL, "%s: alpha must lie in (0, 2)", a.fn);
     if (!a.A || !a.B || !a.K || !a.Minv || !a.x_lb || !a.x_ub || !a.u_lb || !a.u_ub || !a.x0 || !a.workspace || !outputs ||
-        (tracking && (!a.Q || !a.R || !a.Qf)) || (per_problem && (!a.rho_p || !a.problem)))
+        (tracking && (!a.Q || !a.R || (!a.Qf && !a.stage))) || (per_problem && (!a.rho_p || !a.problem)))
         return set_error(ZM_EINVAL, "%s: null pointer", a.fn);
     if ((a.problem == nullptr) != (a.rho_p == nullptr))
         return set_error(ZM_EINVAL, "%s: the problem map and the per-problem rho come together", a.fn);
@@ -589,7 +713,10 @@ static MpcArgs mpc_step_args(MpcArgs g, const MpcLoop& lp, int n, int s) {
 // the linear term of step s of a run (s < 0: of a solve, whose references are one window) into lay.gbuf
 static int mpc_track_linear(const MpcCall& a, const MpcLayout& lay, int s, hipStream_t st) {
     const dim3 grid((unsigned)blocks256((long)a.batch * a.N * ((long)a.n + a.m)));
-    if (s < 0)
+    if (a.stage)   // (a solve: there is no run with stage-varying weights)
+        hipLaunchKernelGGL(mpc_track_linear_stage_kernel, grid, dim3(256), 0, st, a.Q, a.R, a.xRef, a.uRef, (const int*)a.problem,
+                           (long)a.batch, a.N, a.n, a.m, lay.gbuf);
+    else if (s < 0)
         hipLaunchKernelGGL(mpc_track_linear_kernel, grid, dim3(256), 0, st, a.Q, a.R, a.Qf, a.xRef, a.uRef, (const int*)a.problem,
                            (long)a.batch, a.N, a.n, a.m, lay.gbuf);
     else
@@ -630,6 +757,7 @@ static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcPro
 //                              rho_p come together or not at all
 //   zm_mpc_solve_ltv_f64     : ltv -- per_problem and tracking (a zero linear term without a reference) with c, D, ABt; the one kernel
 //                              there is (mpc_wave.hip), so what it does not take is refused before anything is launched
+//   zm_mpc_solve_ltv_stage_f64: the same with a.stage -- weights and box per stage, the sibling kernels for the linear term and the solve
 static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv) {
     if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     int rc = mpc_check_args(a, per_problem, tracking, a.xTraj && a.uTraj && a.status && (!ltv || (a.c && a.D && a.ABt)));
@@ -644,7 +772,7 @@ static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv
     const MpcProb pb{(const int*)a.problem, a.rho_p};
     const MpcTrack trk{lay.gbuf};
     if (!ltv) return mpc_enqueue(a.fn, t, g, a.problem ? &pb : nullptr, tracking ? &trk : nullptr, a.n, a.m, st);
-    rc = mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.n, a.m, st);
+    rc = mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.stage, a.n, a.m, st);
     if (rc == ZM_EUNSUPPORTED)
         return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, a.n, a.m);
     return rc;
@@ -751,7 +879,7 @@ static int mpc_rti(const MpcCall& a, const zm_model_t* model, const zm_model_t* 
         ZM_HIP_CHECK(hipGetLastError());
         if ((rc = mpc_track_linear(a, lay, s, st)) != ZM_OK) return rc;
         const MpcArgs gs = mpc_step_args(g, lp, n, s);
-        rc = mpc_wave_ltv_dispatch(t, gs, pb, MpcTrack{lay.gbuf}, MpcLtv{a.c, a.D, a.ABt}, n, m, st);
+        rc = mpc_wave_ltv_dispatch(t, gs, pb, MpcTrack{lay.gbuf}, MpcLtv{a.c, a.D, a.ABt}, false, n, m, st);
         if (rc == ZM_EUNSUPPORTED)
             return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, n, m);
         if (rc != ZM_OK) return rc;
@@ -926,6 +1054,40 @@ extern "C" int zm_mpc_solve_ltv_f64(const double* A, const double* B, const doub
     a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
     a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
     a.c = c, a.D = D, a.ABt = ABt, a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    return zm::mpc_solve(a, true, true, true);
+}
+
+// stage-varying weights and bounds on top of the stage-varying dynamics
+extern "C" int zm_mpc_setup_ltv_stage_f64(const double* A, const double* B, const double* c, const double* Qs, const double* Rs,
+                                          const double* rho, int64_t P, int L, int N, int n, int m, double* K, double* Minv, double* D,
+                                          double* ABt, void* stream) {
+    const char* fn = "zm_mpc_setup_ltv_stage_f64";
+    if (P == 0) return ZM_OK;   /* no problems: nothing to do (pointers of empty arrays may be NULL) */
+    if (!A || !B || !Qs || !Rs || !rho || !K || !Minv || !D || !ABt) return zm::set_error(ZM_EINVAL, "%s: null pointer", fn);
+    if (P < 0 || L < 1 || N < 1 || n < 1 || m < 1 || P * L > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "%s: bad size", fn);
+    if (n > zm::SN || m > zm::SM) return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (n <= 12, m <= 4)", fn, n, m);
+    hipLaunchKernelGGL((zm::mpc_setup_ltv_stage_kernel<zm::SN, zm::SM>), dim3((unsigned)(P * L)), dim3(256), 0, (hipStream_t)stream, A, B, c,
+                       Qs, Rs, rho, L, N, n, m, K, Minv, D, ABt);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_mpc_solve_ltv_stage_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Qs,
+                                          const double* Rs, const double* K, const double* Minv, const double* D, int n_levels, int level0,
+                                          double rho_step, double alpha, const double* x_lb0, const double* x_ub0, const double* lo,
+                                          const double* hi, const double* x0, const double* xRef, const double* uRef, const double* rho_p,
+                                          const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf,
+                                          int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj, int32_t* status,
+                                          int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream) {
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_ltv_stage_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb0, a.x_ub = x_ub0, a.u_lb = lo, a.u_ub = hi;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.c = c, a.D = D, a.ABt = ABt, a.Q = Qs, a.R = Rs, a.xRef = xRef, a.uRef = uRef, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    a.stage = true;
     return zm::mpc_solve(a, true, true, true);
 }
 

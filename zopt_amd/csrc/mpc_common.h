@@ -116,9 +116,10 @@ int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, con
 // options and the workspace of every step (its x0, outputs and warm are set per step from `lp`).  ZM_EUNSUPPORTED as above.
 int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, int n, int m, hipStream_t st);
 // mpc_wave.hip: stage-varying dynamics, always per-problem and with a linear term (mpc_solve_wave_ltv.h).  ZM_EUNSUPPORTED as above; there
-// is no other kernel to take what does not fit.
-int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
-                          hipStream_t st);
+// is no other kernel to take what does not fit.  stage_box (zm_mpc_solve_ltv_stage_f64): the box varies by stage -- t.x_lb, t.x_ub are
+// the box of x_0 (P,n) and t.u_lb, t.u_ub the stacked lo, hi (P,N,n+m), row k = [bound of x_{k+1} ; bound of u_k].
+int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, bool stage_box,
+                          int n, int m, hipStream_t st);
 
 // linearize.hip (where the model expansions live): the argument check of the entry points that take a registered model, and the launch
 // of mpc_rti_relinearize_kernel -- the expansion of `md` about every stage of the plans xPlan (batch,N+1,n), uPlan (batch,N,m), written

@@ -17,8 +17,14 @@
 // the cycle guard of the adaptive penalty (ZM_TRK_LEVEL) is on when g != 0 or the problem's c != 0 -- offsets drive the same ping-pong
 // between adjacent levels as a reference outside the box does.  With constant A_k, B_k, c = 0 the sums are those of
 // mpc_solve_wave_track_kernel<NS, MC, true> in the same order.
+// Included twice by mpc_wave.hip, which sets the ZM_LTV_* hooks before each: first with one box per problem (x_lb, x_ub (P,n), u_lb, u_ub
+// (P,m), resident in the lane's lo / hi; every hook expands to the tokens this file had before it had hooks), then as
+// mpc_solve_wave_ltv_stage_kernel (zm_mpc_solve_ltv_stage_f64) with the STAGE's box: x_lb, x_ub are the box of x_0 (P,n), read for the x0
+// test only, and u_lb, u_ub carry lo, hi (P,N,n+m) in the stacked stage layout, row k = [bound of x_{k+1} ; bound of u_k].  The lane's
+// lo_k, hi_k ride in the forward prefetch set (TabF), 16 consecutive doubles per group and stage like g; they enter the projection and the
+// support term of the certificate, nothing else.  Lanes outside every role keep -inf / +inf.  The weights never enter this kernel.
 template <int NS, int MC>
-__global__ __launch_bounds__(64) void mpc_solve_wave_ltv_kernel(const double* __restrict__ A, const double* __restrict__ B,
+__global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A, const double* __restrict__ B,
                                                                 const double* __restrict__ Ktab, const double* __restrict__ Mtab,
                                                                 const double* __restrict__ x_lb, const double* __restrict__ x_ub,
                                                                 const double* __restrict__ u_lb, const double* __restrict__ u_ub,
@@ -44,9 +50,9 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_ltv_kernel(const double* __
     double* kf = base + 48 + li;                   // (control lanes)
 
     const double inf = __builtin_inf();
-    const double lo = sx ? x_lb[p * NS + ix] : (su ? u_lb[p * MC + iu] : -inf), hi = sx ? x_ub[p * NS + ix] : (su ? u_ub[p * MC + iu] : inf);
+    ZM_LTV_BOX
     const double x0 = sx ? g.x0[inst * NS + ix] : 0.0;
-    const double viol = (sx && !(x0 >= lo && x0 <= hi)) ? 1.0 : 0.0;
+    const double viol = (sx && !(x0 >= ZM_LTV_X0_LO && x0 <= ZM_LTV_X0_HI)) ? 1.0 : 0.0;
     const bool x0_in = row_max(viol) == 0.0;
 
     // per-instance block of the caller's workspace, as in the body: [y (N,W) | lam (N,W) | kf (N,MC), ok flag, level | unused]
@@ -91,6 +97,7 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_ltv_kernel(const double* __
     struct TabF {
         double fwd[NS], brow[MC];
         double y, lam, kf, c;
+        ZM_LTV_TABF
     };
     auto load_b = [&](int k, TabB& t) {
         k = k < 0 ? 0 : (k >= N ? N - 1 : k);
@@ -117,6 +124,7 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_ltv_kernel(const double* __
         t.y = yw[k * WS_STAGE];
         t.lam = lw[k * WS_STAGE];
         t.kf = kf[k * WS_STAGE];
+        ZM_LTV_LOAD_BOX(k, t)
         if (su) {
             const double* pf = fwd_base + (long)k * (MC * NS);
 #pragma unroll
@@ -205,14 +213,14 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_ltv_kernel(const double* __
                 const double lold = t.lam, yold = t.y;
                 const double wh = __builtin_fma(alpha, w, om_alpha * yold);   // relaxed iterate (alpha = 1: w exactly)
                 double yn = wh + lold;
-                yn = yn < lo ? lo : (yn > hi ? hi : yn);
+                yn = yn < ZM_LTV_LO(t) ? ZM_LTV_LO(t) : (yn > ZM_LTV_HI(t) ? ZM_LTV_HI(t) : yn);
                 const double r = w - yn, dl = wh - yn, ln = lold + dl;        // primal residual; dual step
                 yw[k * WS_STAGE] = (done || !sw) ? yold : yn;
                 lw[k * WS_STAGE] = (done || !sw) ? lold : ln;
                 if (chk) rw[k * WS_STAGE] = sw ? dl : 0.0;
                 if (sw) {
                     if (chk) {
-                        sup += (dl > 0.0) ? dl * hi : ((dl < 0.0) ? dl * lo : 0.0);
+                        sup += (dl > 0.0) ? dl * ZM_LTV_HI(t) : ((dl < 0.0) ? dl * ZM_LTV_LO(t) : 0.0);
                         amax(ndl, dl);
                     }
                     amax(nrp, r);

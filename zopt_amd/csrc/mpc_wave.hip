@@ -261,7 +261,42 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
 #include "mpc_solve_wave_body.h"
 }
 
-// stage-varying dynamics (zm_mpc_solve_ltv_f64): mpc_solve_wave_ltv_kernel, in this translation unit with the kernels it borrows from
+// stage-varying dynamics (zm_mpc_solve_ltv_f64): mpc_solve_wave_ltv_kernel, in this translation unit with the kernels it borrows from.
+// The hooks of mpc_solve_wave_ltv.h for one box per problem: the lane's bounds are read once and stay in lo / hi.
+#define ZM_LTV_KERNEL mpc_solve_wave_ltv_kernel
+#define ZM_LTV_BOX \
+    const double lo = sx ? x_lb[p * NS + ix] : (su ? u_lb[p * MC + iu] : -inf), hi = sx ? x_ub[p * NS + ix] : (su ? u_ub[p * MC + iu] : inf);
+#define ZM_LTV_X0_LO lo
+#define ZM_LTV_X0_HI hi
+#define ZM_LTV_TABF
+#define ZM_LTV_LOAD_BOX(k, t)
+#define ZM_LTV_LO(t) lo
+#define ZM_LTV_HI(t) hi
+#include "mpc_solve_wave_ltv.h"
+
+// stage-varying weights and bounds (zm_mpc_solve_ltv_stage_f64): mpc_solve_wave_ltv_stage_kernel, the same file with the stage's box in
+// the forward prefetch set.  x_lb, x_ub: the box of x_0 (P,n); u_lb, u_ub: lo, hi (P,N,n+m), row k = [bound of x_{k+1} ; bound of u_k].
+// The load is outside the lane-role branches of load_f and a select, so every lane writes both members (see the header's note).
+#undef ZM_LTV_KERNEL
+#undef ZM_LTV_BOX
+#undef ZM_LTV_X0_LO
+#undef ZM_LTV_X0_HI
+#undef ZM_LTV_TABF
+#undef ZM_LTV_LOAD_BOX
+#undef ZM_LTV_LO
+#undef ZM_LTV_HI
+#define ZM_LTV_KERNEL mpc_solve_wave_ltv_stage_kernel
+#define ZM_LTV_BOX                                                                                            \
+    const double lo0 = sx ? x_lb[p * NS + ix] : -inf, hi0 = sx ? x_ub[p * NS + ix] : inf;                     \
+    const double *lo_base = u_lb + (p * N * W + iw), *hi_base = u_ub + (p * N * W + iw); /* + k * W */
+#define ZM_LTV_X0_LO lo0
+#define ZM_LTV_X0_HI hi0
+#define ZM_LTV_TABF double lo, hi;
+#define ZM_LTV_LOAD_BOX(k, t)                   \
+    t.lo = sw ? lo_base[(long)k * W] : -inf;    \
+    t.hi = sw ? hi_base[(long)k * W] : inf;
+#define ZM_LTV_LO(t) t.lo
+#define ZM_LTV_HI(t) t.hi
 #include "mpc_solve_wave_ltv.h"
 
 // for_mpc_shape() without (24, 8): f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16, ZM_EUNSUPPORTED for any other,
@@ -300,10 +335,11 @@ int mpc_wave_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, con
     });
 }
 
-int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, int n, int m,
-                          hipStream_t st) {
+int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, bool stage_box,
+                          int n, int m, hipStream_t st) {
     return for_wave_shape(n, m, [&](auto ns, auto mc) {
-        return launch_wave(mpc_solve_wave_ltv_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv);
+        return stage_box ? launch_wave(mpc_solve_wave_ltv_stage_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv)
+                         : launch_wave(mpc_solve_wave_ltv_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv);
     });
 }
 

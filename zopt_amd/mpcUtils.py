@@ -86,6 +86,7 @@ class lqrMpc():
     _COMPILED = ((24, 8), (12, 4), (8, 4), (4, 2), (4, 1), (2, 2), (2, 1), (1, 1))
 
     _LTV = False                     # ltvMpc (below) shares `solve` and overrides this
+    stage_varying = frozenset()      # ltvMpc: the names among Q, R and the four bounds that carry a stage axis
 
     N_LEVELS, RHO_STEP = 7, 5.0      # adaptive penalty: rho * 5^(l - 3), l = 0..6  (OSQP changes rho only by factors >= 5)
 
@@ -300,13 +301,18 @@ class lqrMpc():
         res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
 
         # 7. the C call: the plain and the per-problem kernels, or the tracking variants of either (other kernels, slower per iteration)
-        opts = (n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, "x_lb x_ub u_lb u_ub", dx0))
+        box = "x_lb0 x_ub0 lo hi" if self.stage_varying else "x_lb x_ub u_lb u_ub"
+        opts = (n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, box, dx0))
         out = (eps_abs, eps_rel, eps_pinf, max_iter, warm, *_ptrs(d, "", ws, xT, uT, st, its, res), Bn, N, n, m,
                ctypes.c_void_p(arr.stream_ptr(dx0)))
         if self._LTV:   # (ltvMpc: stage-varying dynamics, always per-problem, a reference or none)
             D, ABt = tabs[6:8]
-            rc = _lib.lib().zm_mpc_solve_ltv_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Q R Qf", K, Mi, D), *opts,
-                                                  *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
+            if self.stage_varying:   # (weights and box per stage: the sibling entry, the same kernels with the stage's box prefetched)
+                rc = _lib.lib().zm_mpc_solve_ltv_stage_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Qs Rs", K, Mi, D), *opts,
+                                                            *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
+            else:
+                rc = _lib.lib().zm_mpc_solve_ltv_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Q R Qf", K, Mi, D), *opts,
+                                                      *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
         elif tracking:
             rc = _lib.lib().zm_mpc_solve_tracking_f64(*_ptrs(d, "A B Q R Qf", K, Mi), *opts, *_ptrs(d, "", dxr, dur),
                                                        rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, *out)
@@ -421,20 +427,38 @@ class ltvMpc(lqrMpc):
     starts and tracking keywords; the kernels read their dynamics per stage and carry the offset (zm_mpc_setup_ltv_f64,
     zm_mpc_solve_ltv_f64).  Only the 16-lanes-per-instance kernels exist for this form: n <= 12, m <= 4 (smaller shapes are embedded per
     stage, as lqrMpc embeds them) and horizons whose iterates fit LDS, N <= 75; ZOPT_AMD_MPC_PATH does not apply.
+
+    With `stage_varying=` the weights and the box vary by stage as well (zm_mpc_setup_ltv_stage_f64, zm_mpc_solve_ltv_stage_f64):
+
+        minimise   sum_{k<N} (x_k - xr_k)' Q_k (x_k - xr_k) + (u_k - ur_k)' R_k (u_k - ur_k)  +  (x_N - xr_N)' Q_N (x_N - xr_N)
+        subject to x_lb[k] <= x_k <= x_ub[k],  k = 0 .. N;     u_lb[k] <= u_k <= u_ub[k],  k = 0 .. N-1
+
+    -- a corridor or gate that moves along the horizon, a terminal set tighter than the stage box, tube tightening, a waypoint weight,
+    a discounted cost, the blocks c_xx, c_uu of a cost expanded about the plan.  Row 0 of the state box is the test on x0 (an x0 outside
+    it is "infeasible"); Q[..., 0] weights a fixed state and is only checked.
     """
 
     _LTV = True
     _COMPILED = tuple(s for s in lqrMpc._COMPILED if s[0] + s[1] <= 16)
     N_MAX = 75   # 4 instances x N stages x 64 doubles of LDS <= 150 KiB
 
-    def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None):
+    _STAGED = {"Q": 1, "R": 0, "x_lb": 1, "x_ub": 1, "u_lb": 0, "u_ub": 0}   # what may vary by stage: rows beyond N of its stage axis
+
+    def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None, stage_varying=()):
         """
         Arguments
         ---------
             A : (..., N, n, n)   B : (..., N, n, m)   c : (..., N, n) or None (zeros) -- the dynamics of every stage
             Q, R, Qf, x_lb, x_ub, u_lb, u_ub, N : as lqrMpc takes them, leading axes included
+            stage_varying : names among "Q", "R", "x_lb", "x_ub", "u_lb", "u_ub"; a named argument carries a stage axis in front of its
+                trailing axes -- Q (..., N+1, n, n), R (..., N, m, m), x_lb, x_ub (..., N+1, n), u_lb, u_ub (..., N, m).  (Named, because a
+                stage axis cannot be told from a leading problem axis by its shape.)  With "Q" named, Q[..., N] is the terminal weight
+                and Qf must be None.  The attributes keep the stage-axis shapes.
         The leading axes broadcast to the problem shape `P`; () is one problem.  Nothing here touches a GPU.
         """
+        self.stage_varying = frozenset(stage_varying)
+        if self.stage_varying:
+            return self._init_stage_varying(A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c)
         if Qf is None:
             Qf = Q
         self.N = int(N)
@@ -462,20 +486,86 @@ class ltvMpc(lqrMpc):
         for k, X in {**stage, **fixed, "c": cs}.items():
             setattr(self, k, X)
 
+    def _init_stage_varying(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c):
+        """The constructor with a non-empty `stage_varying`: the same checks, per stage where an array has a stage axis."""
+        sv = self.stage_varying
+        if not sv <= set(self._STAGED):
+            raise ValueError(f"ltvMpc: stage_varying names {sorted(sv - set(self._STAGED))}, expected names among {sorted(self._STAGED)}")
+        if "Q" in sv:
+            if Qf is not None:
+                raise ValueError("ltvMpc: with \"Q\" in stage_varying Q[..., N] is the terminal weight: Qf must be None")
+        elif Qf is None:
+            Qf = Q
+        self.N = N = int(N)
+        data = {k: None if X is None else _host_f64(X) for k, X in zip(_ARRAYS, (A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub))}
+        data["c"] = None if c is None else _host_f64(c)
+        n, m, P = _ltv_problem_shape(data, N, {k: N + self._STAGED[k] for k in sv})
+        self.P = P
+        _check_psd_stages(data, P, sv)
+        if n > 12 or m > 4:
+            raise ValueError(f"ltvMpc: (n={n}, m={m}) outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")
+        if N > self.N_MAX:
+            raise ValueError(f"ltvMpc: N={N} beyond the horizons whose iterates fit LDS (N <= {self.N_MAX})")
+        self._dev = None
+        self._tables = {}
+        self._ws = None
+        # one penalty per problem: lqrMpc's rule on (the weight of x_{k+1}, the weight of u_k) of every stage, then the median over the
+        # stages -- of constant rows the value itself.  (A Q without a stage axis stands for every row, as in ltvMpc's own rule.)
+        Qn = data["Q"][..., 1:, :, :] if "Q" in sv else data["Q"][..., None, :, :]
+        Rn = data["R"] if "R" in sv else data["R"][..., None, :, :]
+        self.rho = np.asarray(np.median(_penalty(Qn, Rn, P + (N,)), axis=-1))
+        self._n_user, self._m_user = n, m
+        self.n, self.m = min(((ns, mc) for (ns, mc) in self._COMPILED if ns >= n and mc >= m), key=lambda t: (t[0] * t[1], t[0]))
+        # per stage what _embed does per problem: extra weights 1, extra bounds +-inf
+        out = _embed({k: data[k] for k in ("A", "B")}, P + (N,), self.n, self.m)
+        for k in _ARRAYS[2:]:
+            if data[k] is not None:
+                out.update(_embed({k: data[k]}, P + ((N + self._STAGED[k],) if k in sv else ()), self.n, self.m))
+        if "Q" in sv:
+            out["Qf"] = out["Q"][..., N, :, :]
+        cs = np.zeros(P + (N, self.n))
+        if data["c"] is not None:
+            cs[..., :n] = data["c"]
+        for k, X in {**out, "c": cs}.items():
+            setattr(self, k, X)
+
+    def _stage_form(self):
+        """The six in stage form (host): Qs (P,N,n,n) with Qs[k] the weight of x_{k+1}, Rs (P,N,m,m), the box in the kernels' stacked
+        stage layout lo, hi (P,N,n+m) with row k = [bound of x_{k+1} ; bound of u_k], and row 0 of the state box x_lb0, x_ub0 (P,n)."""
+        N, sv, P = self.N, self.stage_varying, self.P
+        rows = lambda X, name, r: X if name in sv else np.broadcast_to(X[..., None, :], P + (r, X.shape[-1]))
+        if "Q" in sv:
+            Qs = self.Q[..., 1:, :, :]
+        else:
+            Qs = np.concatenate([np.broadcast_to(self.Q[..., None, :, :], P + (N - 1, self.n, self.n)), self.Qf[..., None, :, :]], axis=-3)
+        Rs = self.R if "R" in sv else np.broadcast_to(self.R[..., None, :, :], P + (N, self.m, self.m))
+        xl, xu = rows(self.x_lb, "x_lb", N + 1), rows(self.x_ub, "x_ub", N + 1)
+        ul, uu = rows(self.u_lb, "u_lb", N), rows(self.u_ub, "u_ub", N)
+        return {"Qs": Qs, "Rs": Rs, "lo": np.concatenate([xl[..., 1:, :], ul], axis=-1), "hi": np.concatenate([xu[..., 1:, :], uu], axis=-1),
+                "x_lb0": xl[..., 0, :], "x_ub0": xu[..., 0, :]}
+
     @classmethod
-    def fromExpansion(cls, dyn, traj, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None):
+    def fromExpansion(cls, dyn, traj, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=()):
         """The problem of an `AffineDynamics` (f, f_x, f_u) expanded about `traj` (AffineDynamics.from_trajectory(model, traj)): in absolute
         coordinates x+ ~ f + f_x (x - xbar_k) + f_u (u - ubar_k), i.e. A_k = f_x, B_k = f_u, c_k = f - f_x xbar_k - f_u ubar_k.  N is the
         number of stages of the expansion; bounds and references are in absolute coordinates."""
         f, f_x, f_u = (_host_f64(X) for X in tuple.__iter__(dyn))
         xbar, ubar = _host_f64(tuple.__getitem__(traj, 0))[..., :-1, :], _host_f64(tuple.__getitem__(traj, 1))
         c = f - np.einsum("...ij,...j->...i", f_x, xbar) - np.einsum("...ij,...j->...i", f_u, ubar)
-        return cls(f_x, f_u, Q, R, f.shape[-2], x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=c)
+        return cls(f_x, f_u, Q, R, f.shape[-2], x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=c, stage_varying=stage_varying)
 
-    def update(self, A=None, B=None, c=None):
+    def update(self, A=None, B=None, c=None, Q=None, R=None, x_lb=None, x_ub=None, u_lb=None, u_ub=None):
         """New dynamics data of the same shapes (the next linearisation of a real-time-iteration loop).  NumPy arrays or torch tensors; a
         device tensor is copied device to device, without a host copy (the attributes A, B, c then keep the data they had).  The tables
-        are rebuilt by one setup launch before the next solve; the warm-start workspace survives."""
+        are rebuilt by one setup launch before the next solve; the warm-start workspace survives.
+
+        An object built with `stage_varying=` also takes new weights and bounds, in the shapes its constructor took them (the next window
+        of a moving corridor).  New bounds rewrite the device boxes and keep the tables: nothing is launched but the copies.  New Q or R
+        are checked as the constructor checks them (on the host: a device tensor is copied there for it) and drop the tables.  The
+        penalty `rho` stays what the constructor chose.  The warm-start workspace survives either."""
+        more = {k: X for k, X in (("Q", Q), ("R", R), ("x_lb", x_lb), ("x_ub", x_ub), ("u_lb", u_lb), ("u_ub", u_ub)) if X is not None}
+        if more:
+            self._update_stage_data(more)
         n, m, N = self._n_user, self._m_user, self.N
         new = {}
         for name, X, tail in (("A", A, (N, n, n)), ("B", B, (N, n, m)), ("c", c, (N, n))):
@@ -504,6 +594,55 @@ class ltvMpc(lqrMpc):
                 getattr(self, name)[(Ellipsis,) + tuple(slice(0, w) for w in tail[1:])] = _host_f64(X)
         self._tables = {}
 
+    def _update_stage_data(self, new):
+        """update()'s weights and bounds: shape checks first, then the host attributes and the stage-form device arrays"""
+        if not self.stage_varying:
+            raise ValueError(f"ltvMpc.update: new {', '.join(new)} need an object built with stage_varying= (this one keeps one set of "
+                             f"weights and bounds per problem: build a new object)")
+        n, m, N, sv, P = self._n_user, self._m_user, self.N, self.stage_varying, self.P
+        tails = {"Q": (n, n), "R": (m, m), "x_lb": (n,), "x_ub": (n,), "u_lb": (m,), "u_ub": (m,)}
+        for name, X in new.items():
+            tail = ((N + self._STAGED[name],) if name in sv else ()) + tails[name]
+            shp = _shape_of(X)
+            ok = len(shp) >= len(tail) and shp[len(shp) - len(tail):] == tail
+            if ok:
+                try:
+                    ok = np.broadcast_shapes(shp[:len(shp) - len(tail)], P) == P
+                except ValueError:
+                    ok = False
+            if not ok:
+                raise ValueError(f"ltvMpc.update: {name} has shape {shp}, expected {('...',) + tail} with leading axes that broadcast "
+                                 f"to the problem shape {P} (N = {N})")
+            tails[name] = tail
+        if "Q" in new and "Q" not in sv and self.N == 1:
+            raise ValueError("ltvMpc.update: with N = 1 and no stage axis on Q the only weight is Qf, which update() does not take")
+        host = {k: _host_f64(X) for k, X in new.items() if k in ("Q", "R") or not (arr.is_torch(X) and X.is_cuda)}
+        _check_psd_stages({k: host.get(k) for k in ("Q", "R", "Qf")}, P, sv)
+        arr.require_gpu()
+        d = self._device_data()
+        Pn = int(np.prod(P))
+        ns = self.n
+        for name, X in new.items():
+            tail = tails[name]
+            if name in host:
+                getattr(self, name)[(Ellipsis,) + tuple(slice(0, w) for w in tail[-(2 if name in ("Q", "R") else 1):])] = host[name]
+            t = arr.to_device(X, torch.float64, d["A"].device).expand(P + tail).reshape((Pn,) + tail)
+            if name not in sv:   # (one row for every stage)
+                t = t[:, None]
+            if name == "Q":      # row 0 weights the fixed x_0; without a stage axis the terminal row stays Qf
+                src = t[:, 1:] if name in sv else t
+                d["Qs"][:, :(N if name in sv else N - 1), :n, :n].copy_(src.expand((Pn, N if name in sv else N - 1, n, n)))
+            elif name == "R":
+                d["Rs"][:, :, :m, :m].copy_(t.expand((Pn, N, m, m)))
+            elif name in ("x_lb", "x_ub"):
+                box, row0 = ("lo", "x_lb0") if name == "x_lb" else ("hi", "x_ub0")
+                d[row0][:, :n].copy_(t[:, 0])
+                d[box][:, :, :n].copy_((t[:, 1:] if name in sv else t).expand((Pn, N, n)))
+            else:
+                d["lo" if name == "u_lb" else "hi"][:, :, ns:ns + m].copy_(t.expand((Pn, N, m)))
+        if "Q" in new or "R" in new:
+            self._tables = {}
+
     def simulate(self, *args, **kwargs):
         raise NotImplementedError("ltvMpc.simulate: a moving window needs new tables at every step; loop over update() and solve(), or -- "
                                   "for a registered model linearised about the moving plan -- call realTimeIteration()")
@@ -514,8 +653,11 @@ class ltvMpc(lqrMpc):
     def _device_data(self):
         if self._dev is None:
             Pn = int(np.prod(self.P))
-            self._dev = {k: arr.to_device(getattr(self, k).reshape((Pn,) + getattr(self, k).shape[len(self.P):]), torch.float64)
-                         for k in _ARRAYS + ("c",)}
+            flat = lambda X: arr.to_device(np.ascontiguousarray(X).reshape((Pn,) + X.shape[len(self.P):]), torch.float64)
+            if self.stage_varying:   # (the six once, in the stage form the two stage entry points read)
+                self._dev = {**{k: flat(getattr(self, k)) for k in ("A", "B", "c")}, **{k: flat(X) for k, X in self._stage_form().items()}}
+            else:
+                self._dev = {k: flat(getattr(self, k)) for k in _ARRAYS + ("c",)}
         return self._dev
 
     def _empty_tables(self, rho, adaptive):
@@ -541,8 +683,10 @@ class ltvMpc(lqrMpc):
         if key not in self._tables:
             tabs = self._empty_tables(rho, adaptive)
             K, Mi, nl, _, _, rtab, D, ABt = tabs
-            rc = _lib.lib().zm_mpc_setup_ltv_f64(*_ptrs(d, "A B c Q R Qf", rtab), int(np.prod(self.P)), nl, self.N, self.n, self.m,
-                                                 *_ptrs(d, "", K, Mi, D, ABt), ctypes.c_void_p(arr.stream_ptr(K)))
+            setup, weights = ((_lib.lib().zm_mpc_setup_ltv_stage_f64, "Qs Rs") if self.stage_varying else
+                              (_lib.lib().zm_mpc_setup_ltv_f64, "Q R Qf"))
+            rc = setup(*_ptrs(d, "A B c " + weights, rtab), int(np.prod(self.P)), nl, self.N, self.n, self.m,
+                       *_ptrs(d, "", K, Mi, D, ABt), ctypes.c_void_p(arr.stream_ptr(K)))
             _lib.check(rc, "ltvMpc setup")
             self._tables[key] = tabs
         return d, self._tables[key]
@@ -550,7 +694,7 @@ class ltvMpc(lqrMpc):
     # ---- real-time iteration: a registered model linearised about the moving plan --------------------------------------------------
 
     @classmethod
-    def fromModel(cls, model, plan, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None):
+    def fromModel(cls, model, plan, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=()):
         """The problem of a registered model (models.QuadcopterEuler, models.QuadcopterRigidBody with dt > 0, models.LinearModel; n <= 12,
         m <= 4) linearised about `plan`, a Trajectory (xTraj (..., N+1, n), uTraj (..., N, m)) in absolute coordinates: what
         `fromExpansion(AffineDynamics.from_trajectory(model, plan), plan, ...)` builds, with c_k formed on the device as `relinearize` forms
@@ -570,7 +714,8 @@ class ltvMpc(lqrMpc):
                                                Bn, N, n, m, n, m, ctypes.c_void_p(arr.stream_ptr(xP)))
         _lib.check(rc, "ltvMpc.fromModel")
         host = lambda t, tail: t.cpu().numpy().reshape(lead + tail)
-        return cls(host(A, (N, n, n)), host(B, (N, n, m)), Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=host(c, (N, n)))
+        return cls(host(A, (N, n, n)), host(B, (N, n, m)), Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=host(c, (N, n)),
+                   stage_varying=stage_varying)
 
     def relinearize(self, model, plan):
         """The next linearisation of a real-time-iteration loop, on the device: `model` expanded about `plan` (a Trajectory, xTraj
@@ -631,7 +776,13 @@ class ltvMpc(lqrMpc):
         Returns
         -------
             MpcClosedLoop, as `lqrMpc.simulate` returns it
+
+        Not with stage_varying= (NotImplementedError): the loop inside the call keeps one set of weights and bounds per problem.
         """
+        if self.stage_varying:
+            raise NotImplementedError("ltvMpc.realTimeIteration: the loop inside zm_mpc_rti_f64 keeps one set of weights and bounds per "
+                                      "problem; with stage_varying= write the loop out: relinearize(model, plan), update(x_lb=..., "
+                                      "x_ub=...), solve(x, warm_start=\"shift\"), modelStep(plant, x, u)")
         S, clip = _run_steps(steps, clip_tol)
         eps_abs, eps_rel, max_iter, rho, adaptive, eps_pinf, alpha, warm = self._solver_options(solver_opts, "shift")
         if isinstance(xRef, Trajectory) or isinstance(uRef, Trajectory):
@@ -797,8 +948,9 @@ def _plan_shapes(who, plan, N, n, m, P=None):
     return xs, us, lead
 
 
-def _ltv_problem_shape(data, N):
-    """(n, m, P) of ltvMpc's arrays: A (..., N, n, n), B (..., N, n, m), c (..., N, n) | None, the rest as lqrMpc's."""
+def _ltv_problem_shape(data, N, stage_rows=None):
+    """(n, m, P) of ltvMpc's arrays: A (..., N, n, n), B (..., N, n, m), c (..., N, n) | None, the rest as lqrMpc's -- or, for a name in
+    `stage_rows` (name -> rows), with a stage axis of that many rows in front of its trailing axes."""
     if data["B"].ndim < 3:
         raise ValueError("ltvMpc: B must have shape (..., N, n, m)")
     n, m = data["B"].shape[-2:]
@@ -806,17 +958,19 @@ def _ltv_problem_shape(data, N):
         raise ValueError(f"ltvMpc: N = {N}, expected at least one stage")
     tails = {"A": (N, n, n), "B": (N, n, m), "c": (N, n), "Q": (n, n), "R": (m, m), "Qf": (n, n), "x_lb": (n,), "x_ub": (n,),
              "u_lb": (m,), "u_ub": (m,)}
+    for k, r in (stage_rows or {}).items():
+        tails[k] = (r,) + tails[k]
     lead = {}
     for k, t in tails.items():
         X = data[k]
         if X is None:
             continue
-        staged = k in ("A", "B", "c")   # (the stage axis is checked on its own: its message names N)
+        staged = k in ("A", "B", "c") or k in (stage_rows or {})   # (the stage axis is checked on its own: its message names N)
         if X.ndim < len(t) or X.shape[X.ndim - len(t) + staged:] != t[staged:]:
             raise ValueError(f"inconsistent ltvMpc problem shapes: {k} has shape {X.shape}, expected (..., {', '.join(map(str, t))})")
-        if staged and X.shape[X.ndim - len(t)] != N:
+        if staged and X.shape[X.ndim - len(t)] != t[0]:
             raise ValueError(f"inconsistent ltvMpc problem shapes: {k} of shape {X.shape} has {X.shape[X.ndim - len(t)]} stages, "
-                             f"expected N = {N}")
+                             f"expected N = {N}" + ("" if t[0] == N else f" + {t[0] - N}"))
         lead[k] = X.shape[:X.ndim - len(t)]
     try:
         P = np.broadcast_shapes(*lead.values())
@@ -875,6 +1029,27 @@ def _check_psd(data, P):
             which = f"[{', '.join(map(str, i))}]" if i else ""
             raise ValueError(f"lqrMpc: {name}{which} is not positive semidefinite (smallest eigenvalue {lo:.3g}): "
                              f"the problem is not convex (cvxpy raises DCPError for the reference's quad_form)")
+
+
+def _check_psd_stages(data, P, sv):
+    """_check_psd for ltvMpc with stage_varying=: a weight named in `sv` is checked at every stage, and the first offender is named by
+    its problem and its stage.  Entries that are None are skipped."""
+    for name in ("Q", "R", "Qf"):
+        W = data.get(name)
+        if W is None:
+            continue
+        if name not in sv:
+            _check_psd({k: (W if k == name else np.zeros((1, 1))) for k in ("Q", "R", "Qf")}, P)
+            continue
+        w = np.linalg.eigvalsh(0.5 * (W + np.swapaxes(W, -1, -2)))
+        shape = P + (W.shape[-3],)
+        bad = np.broadcast_to(w[..., 0] < -1e-10 * np.maximum(1.0, np.abs(w[..., -1])), shape)
+        if bad.any():
+            i = tuple(int(v) for v in np.argwhere(bad)[0])
+            lo = float(np.broadcast_to(w[..., 0], shape)[i])
+            which = f"[{', '.join(map(str, i[:-1]))}]" if i[:-1] else ""
+            raise ValueError(f"ltvMpc: {name}{which} at stage {i[-1]} is not positive semidefinite (smallest eigenvalue {lo:.3g}): "
+                             f"the problem is not convex")
 
 
 def _penalty(Q, R, P):
