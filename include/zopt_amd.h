@@ -585,6 +585,35 @@ int zm_mpc_solve_ltv_stage_f64(const double* A, const double* B, const double* c
                                double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
                                int64_t batch, int N, int n, int m, void* stream);
 
+/* Soft box constraints on top of the stage form (extension): with d_i(v) = max(0, v - hi_k,i, lo_k,i - v) the QP of
+ * zm_mpc_solve_ltv_stage_f64 gains
+ *     + sum_{k<N} sum_i  l1_i d_i(w_k,i) + l2_i d_i(w_k,i)^2,     w_k = [x_{k+1} ; u_k],  i over the n + m stacked components
+ * for every component i with a finite l1_i >= 0 (soft: its bounds no longer constrain w; l2_i >= 0 finite).  l1_i = +inf is a hard
+ * component, exactly as in zm_mpc_solve_ltv_stage_f64 (l2_i must be 0 there).  The weights are per problem and per component, constant
+ * over the stages: soft_l1, soft_l2 (P,n+m) in the stacked layout [x ; u]  [device]; soft_l2 may be NULL (zeros).  A violation is paid
+ * for, not forbidden, so a soft problem always has a solution; with l1 above the hard problem's multipliers (an exact penalty) the hard
+ * solution comes back whenever there is one.  The tables do not depend on the weights: zm_mpc_setup_ltv_stage_f64 sets up.
+ * What changes in the ADMM of zm_mpc_solve_ltv_stage_f64, and nothing else does (residuals, tolerances, the level rule, the workspace
+ * and the statuses are its own):
+ *     x0:          a soft state component of x0 is not tested against x_lb0, x_ub0 (its violation is a constant of the problem); a hard
+ *                  one is, as before.
+ *     projection:  the y-update is the proximal map of the penalty.  With v = w_hat + lam, t = l1 / rho, a = rho / (rho + 2 l2):
+ *                      v < lo:  e = a ((lo - v) - t);  y = e > 0 ? lo - e : lo
+ *                      v > hi:  e = a ((v - hi) - t);  y = e > 0 ? hi + e : hi          else y = v
+ *                  t and a follow rho whenever the adaptive penalty moves.  l1 = +inf gives y = the bound, bit for bit the clip.
+ *     certificate: in the support term of the primal-infeasibility certificate a soft component has the bounds -inf / +inf (its y
+ *                  ranges over the whole line), so no certificate can rest on it.
+ *     cycle guard: on when g != 0, or the problem's c != 0, or the problem has a soft component.
+ * With every l1 = +inf the solve is zm_mpc_solve_ltv_stage_f64's bit for bit.  The same refusals as zm_mpc_solve_ltv_stage_f64, and
+ * ZM_EINVAL for a NULL soft_l1; all but the map check before any launch. */
+int zm_mpc_solve_ltv_soft_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Qs, const double* Rs,
+                              const double* K, const double* Minv, const double* D, int n_levels, int level0, double rho_step,
+                              double alpha, const double* x_lb0, const double* x_ub0, const double* lo, const double* hi,
+                              const double* soft_l1, const double* soft_l2, const double* x0, const double* xRef, const double* uRef,
+                              const double* rho_p, const int32_t* problem, int64_t P, double eps_abs, double eps_rel,
+                              double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj,
+                              int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream);
+
 /* Real-time-iteration nonlinear MPC (extension): zm_mpc_solve_ltv_f64 on the linearisation of a REGISTERED MODEL about a plan, every
  * instance its own problem (P = batch, problem[i] = i).  Shapes: the model's (n_user, m_user) embedded in a compiled (ns, mc) of the
  * 16-lanes-per-instance kernels, as zopt_amd/mpcUtils.py embeds them; models: ZM_MODEL_QUADCOPTER (12, 4) and ZM_MODEL_QUADCOPTER_RB

@@ -111,6 +111,10 @@ SYMBOLS = {
     "zm_mpc_solve_ltv_stage_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
                                    [_c_dp] * 9 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
                                    [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # zm_mpc_solve_ltv_stage_f64's arguments with soft_l1 (P,n+m), soft_l2 (P,n+m) | NULL after hi
+    "zm_mpc_solve_ltv_soft_f64": (ctypes.c_int, [_c_dp] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                                  [_c_dp] * 11 + [ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_int] * 2 + [_c_dp] * 6 +
+                                  [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (model*, x, u, xNext, batch, stream)
     "zm_model_step_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int64, ctypes.c_void_p]),
     # (model*, xPlan, uPlan, A, B, c, batch, N, n_user, m_user, ns, mc, stream)

@@ -591,6 +591,9 @@ struct MpcCall {
     // zm_mpc_solve_ltv_stage_f64: Q, R hold Qs (P,N,n,n), Rs (P,N,m,m) and Qf stays NULL; x_lb, x_ub hold the box of x_0 (P,n) and
     // u_lb, u_ub the stacked lo, hi (P,N,n+m) -- the slots the kernel takes them in (mpc_common.h: mpc_wave_ltv_dispatch)
     bool stage;
+    // zm_mpc_solve_ltv_soft_f64: the stage form with penalty weights (P,n+m) on the box; soft_l2 may be NULL (zeros)
+    bool soft;
+    const double *soft_l1, *soft_l2;
     void* stream;
 };
 
@@ -758,9 +761,10 @@ static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcPro
 //   zm_mpc_solve_ltv_f64     : ltv -- per_problem and tracking (a zero linear term without a reference) with c, D, ABt; the one kernel
 //                              there is (mpc_wave.hip), so what it does not take is refused before anything is launched
 //   zm_mpc_solve_ltv_stage_f64: the same with a.stage -- weights and box per stage, the sibling kernels for the linear term and the solve
+//   zm_mpc_solve_ltv_soft_f64: the stage entry with a.soft -- penalty weights on the box, the solve kernel that takes them
 static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv) {
     if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    int rc = mpc_check_args(a, per_problem, tracking, a.xTraj && a.uTraj && a.status && (!ltv || (a.c && a.D && a.ABt)));
+    int rc = mpc_check_args(a, per_problem, tracking, a.xTraj && a.uTraj && a.status && (!ltv || (a.c && a.D && a.ABt)) && (!a.soft || a.soft_l1));
     if (rc != ZM_OK) return rc;
     if (ltv && (rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
     hipStream_t st = (hipStream_t)a.stream;
@@ -772,7 +776,8 @@ static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv
     const MpcProb pb{(const int*)a.problem, a.rho_p};
     const MpcTrack trk{lay.gbuf};
     if (!ltv) return mpc_enqueue(a.fn, t, g, a.problem ? &pb : nullptr, tracking ? &trk : nullptr, a.n, a.m, st);
-    rc = mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.stage, a.n, a.m, st);
+    rc = a.soft ? mpc_wave_ltv_soft_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, MpcSoft{a.soft_l1, a.soft_l2}, a.n, a.m, st)
+                : mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.stage, a.n, a.m, st);
     if (rc == ZM_EUNSUPPORTED)
         return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, a.n, a.m);
     return rc;
@@ -1088,6 +1093,27 @@ extern "C" int zm_mpc_solve_ltv_stage_f64(const double* A, const double* B, cons
     a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
     a.c = c, a.D = D, a.ABt = ABt, a.Q = Qs, a.R = Rs, a.xRef = xRef, a.uRef = uRef, a.rho_p = rho_p, a.problem = problem, a.P = P;
     a.stage = true;
+    return zm::mpc_solve(a, true, true, true);
+}
+
+// soft box constraints on top of the stage form: the same call with the penalty weights, its own solve kernel
+extern "C" int zm_mpc_solve_ltv_soft_f64(const double* A, const double* B, const double* c, const double* ABt, const double* Qs,
+                                         const double* Rs, const double* K, const double* Minv, const double* D, int n_levels, int level0,
+                                         double rho_step, double alpha, const double* x_lb0, const double* x_ub0, const double* lo,
+                                         const double* hi, const double* soft_l1, const double* soft_l2, const double* x0,
+                                         const double* xRef, const double* uRef, const double* rho_p, const int32_t* problem, int64_t P,
+                                         double eps_abs, double eps_rel, double eps_prim_inf, int max_iter, int warm_start,
+                                         double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
+                                         int64_t batch, int N, int n, int m, void* stream) {
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_ltv_soft_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb0, a.x_ub = x_ub0, a.u_lb = lo, a.u_ub = hi;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.c = c, a.D = D, a.ABt = ABt, a.Q = Qs, a.R = Rs, a.xRef = xRef, a.uRef = uRef, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    a.stage = true, a.soft = true, a.soft_l1 = soft_l1, a.soft_l2 = soft_l2;
     return zm::mpc_solve(a, true, true, true);
 }
 

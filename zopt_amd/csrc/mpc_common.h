@@ -53,6 +53,12 @@ struct MpcLtv {
     const double *c, *D, *ABt;
 };
 
+// soft box constraints (zm_mpc_solve_ltv_soft_f64): the penalty weights l1, l2 (P,n+m) of every problem's stacked component [x ; u];
+// l1 = +inf is a hard component, l2 may be nullptr (zeros).  Its own kernel argument, after MpcLtv: the kernels without it keep theirs.
+struct MpcSoft {
+    const double *l1, *l2;
+};
+
 // closed-loop run (zm_mpc_closed_loop_f64): `steps` receding-horizon solves in a row, step-major arrays -- step s of an array is one
 // batch-sized slab further on, so a step's solve sees the layouts of a single solve through offset pointers.
 struct MpcLoop {
@@ -120,6 +126,9 @@ int mpc_wave_closed_loop_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcP
 // the box of x_0 (P,n) and t.u_lb, t.u_ub the stacked lo, hi (P,N,n+m), row k = [bound of x_{k+1} ; bound of u_k].
 int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv, bool stage_box,
                           int n, int m, hipStream_t st);
+// mpc_wave.hip: the stage form of the above (stage_box) with soft box constraints, weights sf (mpc_solve_wave_ltv_soft_kernel)
+int mpc_wave_ltv_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv,
+                               const MpcSoft& sf, int n, int m, hipStream_t st);
 
 // linearize.hip (where the model expansions live): the argument check of the entry points that take a registered model, and the launch
 // of mpc_rti_relinearize_kernel -- the expansion of `md` about every stage of the plans xPlan (batch,N+1,n), uPlan (batch,N,m), written

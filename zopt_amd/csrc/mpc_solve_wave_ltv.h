@@ -23,12 +23,19 @@
 // test only, and u_lb, u_ub carry lo, hi (P,N,n+m) in the stacked stage layout, row k = [bound of x_{k+1} ; bound of u_k].  The lane's
 // lo_k, hi_k ride in the forward prefetch set (TabF), 16 consecutive doubles per group and stage like g; they enter the projection and the
 // support term of the certificate, nothing else.  Lanes outside every role keep -inf / +inf.  The weights never enter this kernel.
+// A third time as mpc_solve_wave_ltv_soft_kernel (zm_mpc_solve_ltv_soft_f64): the stage form with soft box constraints, a penalty
+// l1 d + l2 d^2 on the distance d of a component from its box, weights per problem and component (P,n+m) in one more argument block
+// (ZM_LTV_ARGS; MpcSoft).  The lane keeps l1, l2 and, of the penalty it runs at, t = l1 / rho and a = rho / (rho + 2 l2) (ZM_LTV_RHO: at
+// entry and after every level move).  Three places differ: a soft component of x0 is not tested against row 0 (ZM_LTV_BOX gives it
+// -inf / +inf there), the projection is the proximal map of the penalty (ZM_LTV_PROJECT), and the support term of the certificate takes
+// -inf / +inf for a soft component, whose y ranges over the whole line (ZM_LTV_SUP_LO / _HI).  The cycle guard is also on when the
+// problem has a soft component (ZM_LTV_GUARD).  l1 = +inf is a hard component: t = inf, and every one of these is the stage kernel's.
 template <int NS, int MC>
 __global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A, const double* __restrict__ B,
                                                                 const double* __restrict__ Ktab, const double* __restrict__ Mtab,
                                                                 const double* __restrict__ x_lb, const double* __restrict__ x_ub,
                                                                 const double* __restrict__ u_lb, const double* __restrict__ u_ub,
-                                                                const MpcArgs g, const MpcProb pb, const MpcTrack trk, const MpcLtv lv) {
+                                                                const MpcArgs g, const MpcProb pb, const MpcTrack trk, const MpcLtv lv ZM_LTV_ARGS) {
     static_assert(NS + MC <= 16, "the stacked index must fit the 16 lanes of a group");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int W = NS + MC;
@@ -66,6 +73,7 @@ __global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A
             rho = rho0 * pow(g.rho_step, (double)(lvl - g.level0));
         }
     }
+    ZM_LTV_RHO
     for (int k = 0; k < N; ++k) {
         const int ks = (g.warm == 2 && k + 1 < N) ? k + 1 : k;    // shifted warm start: iterate k <- iterate k+1
         const double wy = warm ? wsi[(long)ks * W + iw] : 0.0, wl = warm ? wsi[(long)N * W + (long)ks * W + iw] : 0.0;
@@ -153,7 +161,7 @@ __global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A
     }
     gnorm = row_max(gnorm);
     cnorm = row_max(cnorm);
-    const bool guard = gnorm > 0.0 || cnorm > 0.0;
+    const bool guard = gnorm > 0.0 || cnorm > 0.0 ZM_LTV_GUARD;
     int trk_last = 0, trk_rev = 0;   // the last level move; consecutive reversals of it
     bool trk_locked = false;
 
@@ -213,14 +221,14 @@ __global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A
                 const double lold = t.lam, yold = t.y;
                 const double wh = __builtin_fma(alpha, w, om_alpha * yold);   // relaxed iterate (alpha = 1: w exactly)
                 double yn = wh + lold;
-                yn = yn < ZM_LTV_LO(t) ? ZM_LTV_LO(t) : (yn > ZM_LTV_HI(t) ? ZM_LTV_HI(t) : yn);
+                ZM_LTV_PROJECT(yn, t)
                 const double r = w - yn, dl = wh - yn, ln = lold + dl;        // primal residual; dual step
                 yw[k * WS_STAGE] = (done || !sw) ? yold : yn;
                 lw[k * WS_STAGE] = (done || !sw) ? lold : ln;
                 if (chk) rw[k * WS_STAGE] = sw ? dl : 0.0;
                 if (sw) {
                     if (chk) {
-                        sup += (dl > 0.0) ? dl * ZM_LTV_HI(t) : ((dl < 0.0) ? dl * ZM_LTV_LO(t) : 0.0);
+                        sup += (dl > 0.0) ? dl * ZM_LTV_SUP_HI(t) : ((dl < 0.0) ? dl * ZM_LTV_SUP_LO(t) : 0.0);
                         amax(ndl, dl);
                     }
                     amax(nrp, r);
@@ -301,6 +309,7 @@ __global__ __launch_bounds__(64) void ZM_LTV_KERNEL(const double* __restrict__ A
                 for (int k = 0; k < N; ++k) lw[k * WS_STAGE] *= sc;
                 rho = rnew;
                 lvl = nl_;
+                ZM_LTV_RHO
             }
         }
         // ---- primal infeasibility certificate: adjoint sweep over r = w - y with the stage's own A_k^T, B_k^T; the free response

@@ -272,6 +272,13 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
 #define ZM_LTV_LOAD_BOX(k, t)
 #define ZM_LTV_LO(t) lo
 #define ZM_LTV_HI(t) hi
+// (the hooks of the soft-constrained variant below: nothing, or the tokens the file had before it had them)
+#define ZM_LTV_ARGS
+#define ZM_LTV_RHO
+#define ZM_LTV_GUARD
+#define ZM_LTV_PROJECT(yn, t) yn = yn < ZM_LTV_LO(t) ? ZM_LTV_LO(t) : (yn > ZM_LTV_HI(t) ? ZM_LTV_HI(t) : yn);
+#define ZM_LTV_SUP_LO(t) ZM_LTV_LO(t)
+#define ZM_LTV_SUP_HI(t) ZM_LTV_HI(t)
 #include "mpc_solve_wave_ltv.h"
 
 // stage-varying weights and bounds (zm_mpc_solve_ltv_stage_f64): mpc_solve_wave_ltv_stage_kernel, the same file with the stage's box in
@@ -297,6 +304,44 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
     t.hi = sw ? hi_base[(long)k * W] : inf;
 #define ZM_LTV_LO(t) t.lo
 #define ZM_LTV_HI(t) t.hi
+#include "mpc_solve_wave_ltv.h"
+
+// soft box constraints (zm_mpc_solve_ltv_soft_f64): mpc_solve_wave_ltv_soft_kernel, the stage form once more with the penalty weights of
+// the lane's component, sf.l1, sf.l2 (P,n+m) in the stacked layout [x ; u] (l2 may be NULL: zeros).  Lanes outside every role carry
+// l1 = +inf, l2 = 0, as the padded components of an embedded shape do in the caller's arrays.  The branches of the proximal map are
+// tested in the order of the stage kernel's clip (lo first) and written with selects: l1 = +inf gives t = +inf, e = -inf and y = the
+// bound bit for bit, where bound + max(0, e) would turn a bound of -0.0 into +0.0.
+#undef ZM_LTV_KERNEL
+#undef ZM_LTV_BOX
+#undef ZM_LTV_ARGS
+#undef ZM_LTV_RHO
+#undef ZM_LTV_GUARD
+#undef ZM_LTV_PROJECT
+#undef ZM_LTV_SUP_LO
+#undef ZM_LTV_SUP_HI
+#define ZM_LTV_KERNEL mpc_solve_wave_ltv_soft_kernel
+#define ZM_LTV_ARGS , const MpcSoft sf
+#define ZM_LTV_BOX                                                                                            \
+    const double l1 = sw ? sf.l1[p * W + iw] : inf, l2 = (sw && sf.l2) ? sf.l2[p * W + iw] : 0.0;            \
+    const bool soft = l1 < inf;                                                                               \
+    const bool any_soft = row_max(soft ? 1.0 : 0.0) > 0.0; /* uniform over the group: its problem's */        \
+    double prox_t = inf, prox_a = 1.0;                             /* t = l1 / rho, a = rho / (rho + 2 l2) */         \
+    const double lo0 = (sx && !soft) ? x_lb[p * NS + ix] : -inf, hi0 = (sx && !soft) ? x_ub[p * NS + ix] : inf; \
+    const double *lo_base = u_lb + (p * N * W + iw), *hi_base = u_ub + (p * N * W + iw); /* + k * W */
+#define ZM_LTV_RHO       \
+    prox_t = l1 / rho;       \
+    prox_a = rho / (rho + 2.0 * l2);
+#define ZM_LTV_GUARD || any_soft
+#define ZM_LTV_PROJECT(yn, t)                              \
+    if (yn < t.lo) {                                       \
+        const double e = prox_a * ((t.lo - yn) - prox_t);          \
+        yn = (e > 0.0) ? t.lo - e : t.lo;                  \
+    } else if (yn > t.hi) {                                \
+        const double e = prox_a * ((yn - t.hi) - prox_t);          \
+        yn = (e > 0.0) ? t.hi + e : t.hi;                  \
+    }
+#define ZM_LTV_SUP_LO(t) (soft ? -inf : t.lo)
+#define ZM_LTV_SUP_HI(t) (soft ? inf : t.hi)
 #include "mpc_solve_wave_ltv.h"
 
 // for_mpc_shape() without (24, 8): f(Int<NS>, Int<MC>) for the compiled shape (n, m) with NS + MC <= 16, ZM_EUNSUPPORTED for any other,
@@ -340,6 +385,13 @@ int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb,
     return for_wave_shape(n, m, [&](auto ns, auto mc) {
         return stage_box ? launch_wave(mpc_solve_wave_ltv_stage_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv)
                          : launch_wave(mpc_solve_wave_ltv_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv);
+    });
+}
+
+int mpc_wave_ltv_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv,
+                               const MpcSoft& sf, int n, int m, hipStream_t st) {
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        return launch_wave(mpc_solve_wave_ltv_soft_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv, sf);
     });
 }
 

@@ -87,6 +87,8 @@ class lqrMpc():
 
     _LTV = False                     # ltvMpc (below) shares `solve` and overrides this
     stage_varying = frozenset()      # ltvMpc: the names among Q, R and the four bounds that carry a stage axis
+    _soft = None                     # ltvMpc: the penalty weights of soft box constraints, as given (None: every bound is hard)
+    _stage_entry = False             # ltvMpc: the data is kept in stage form and goes through the stage entry points
 
     N_LEVELS, RHO_STEP = 7, 5.0      # adaptive penalty: rho * 5^(l - 3), l = 0..6  (OSQP changes rho only by factors >= 5)
 
@@ -301,13 +303,18 @@ class lqrMpc():
         res = torch.empty((Bn, 2), dtype=torch.float64, device=dev)
 
         # 7. the C call: the plain and the per-problem kernels, or the tracking variants of either (other kernels, slower per iteration)
-        box = "x_lb0 x_ub0 lo hi" if self.stage_varying else "x_lb x_ub u_lb u_ub"
+        box = "x_lb0 x_ub0 lo hi" if self._stage_entry else "x_lb x_ub u_lb u_ub"
+        if self._soft is not None:
+            box += " soft_l1 soft_l2"
         opts = (n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, box, dx0))
         out = (eps_abs, eps_rel, eps_pinf, max_iter, warm, *_ptrs(d, "", ws, xT, uT, st, its, res), Bn, N, n, m,
                ctypes.c_void_p(arr.stream_ptr(dx0)))
         if self._LTV:   # (ltvMpc: stage-varying dynamics, always per-problem, a reference or none)
             D, ABt = tabs[6:8]
-            if self.stage_varying:   # (weights and box per stage: the sibling entry, the same kernels with the stage's box prefetched)
+            if self._soft is not None:   # (soft box constraints: the stage form with the penalty weights behind the box)
+                rc = _lib.lib().zm_mpc_solve_ltv_soft_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Qs Rs", K, Mi, D), *opts,
+                                                           *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
+            elif self._stage_entry:   # (weights and box per stage: the sibling entry, the same kernels with the stage's box prefetched)
                 rc = _lib.lib().zm_mpc_solve_ltv_stage_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Qs Rs", K, Mi, D), *opts,
                                                             *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
             else:
@@ -436,6 +443,11 @@ class ltvMpc(lqrMpc):
     -- a corridor or gate that moves along the horizon, a terminal set tighter than the stage box, tube tightening, a waypoint weight,
     a discounted cost, the blocks c_xx, c_uu of a cost expanded about the plan.  Row 0 of the state box is the test on x0 (an x0 outside
     it is "infeasible"); Q[..., 0] weights a fixed state and is only checked.
+
+    With soft weights (x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2; zm_mpc_solve_ltv_soft_f64) a component of x_k (k >= 1) or u_k whose l1
+    is finite is not held inside its box: it pays l1 d + l2 d^2 for its distance d from it.  Such a problem always has a solution -- a
+    state that a disturbance has pushed outside a corridor is solved from, not "infeasible" --, and with l1 above the constraint's
+    multiplier the solution is the hard one whenever that exists.  `update` takes new weights without a setup launch.
     """
 
     _LTV = True
@@ -444,7 +456,10 @@ class ltvMpc(lqrMpc):
 
     _STAGED = {"Q": 1, "R": 0, "x_lb": 1, "x_ub": 1, "u_lb": 0, "u_ub": 0}   # what may vary by stage: rows beyond N of its stage axis
 
-    def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None, stage_varying=()):
+    _SOFT = ("x_soft_l1", "x_soft_l2", "u_soft_l1", "u_soft_l2")
+
+    def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None, stage_varying=(), x_soft_l1=None, x_soft_l2=None,
+                 u_soft_l1=None, u_soft_l2=None):
         """
         Arguments
         ---------
@@ -454,11 +469,18 @@ class ltvMpc(lqrMpc):
                 trailing axes -- Q (..., N+1, n, n), R (..., N, m, m), x_lb, x_ub (..., N+1, n), u_lb, u_ub (..., N, m).  (Named, because a
                 stage axis cannot be told from a leading problem axis by its shape.)  With "Q" named, Q[..., N] is the terminal weight
                 and Qf must be None.  The attributes keep the stage-axis shapes.
+            x_soft_l1, x_soft_l2 (..., n), u_soft_l1, u_soft_l2 (..., m) : penalty weights of soft box constraints, per problem and
+                component, constant over the stages.  With d the distance of a component of x_k (k >= 1) or u_k from its box the cost gains
+                l1 d + l2 d^2 and the bounds of that component no longer constrain it; l1 = +inf (the default of a weight not given)
+                keeps the component hard, and l2 must be 0 there.  A start x0 outside row 0 of the state box in a soft component is
+                solved from; in a hard one it is "infeasible" as before.  With an l1 above the hard problem's multipliers the hard
+                solution comes back whenever there is one.  All four None: every bound is hard, nothing changes.
         The leading axes broadcast to the problem shape `P`; () is one problem.  Nothing here touches a GPU.
         """
         self.stage_varying = frozenset(stage_varying)
         if self.stage_varying:
-            return self._init_stage_varying(A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c)
+            self._init_stage_varying(A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c)
+            return self._init_soft(x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2)
         if Qf is None:
             Qf = Q
         self.N = int(N)
@@ -485,6 +507,45 @@ class ltvMpc(lqrMpc):
             cs[..., :n] = data["c"]
         for k, X in {**stage, **fixed, "c": cs}.items():
             setattr(self, k, X)
+        self._init_soft(x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2)
+
+    def _init_soft(self, *weights):
+        """The constructor's last step: the penalty weights of soft box constraints.  With any of them the object keeps its data in stage
+        form (constant rows without stage_varying=, which give the plain tables and iterates bit for bit) and solves through
+        zm_mpc_solve_ltv_soft_f64."""
+        self._stage_entry = bool(self.stage_varying)
+        if all(w is None for w in weights):
+            return
+        self._soft = dict(zip(self._SOFT, weights))
+        self.soft_l1, self.soft_l2 = self._soft_stacked("ltvMpc", self._soft)
+        self._stage_entry = True
+
+    def _soft_stacked(self, who, given):
+        """(l1, l2), each P + (n + m,) in the kernels' stacked layout [x ; u] of the compiled shape, from the four weights as given (None:
+        l1 = +inf, l2 = 0).  A padded component is hard: l1 = +inf, l2 = 0."""
+        P = self.P
+        l1, l2 = np.full(P + (self.n + self.m,), np.inf), np.zeros(P + (self.n + self.m,))
+        for name, at, k in (("x_soft_l1", 0, self._n_user), ("x_soft_l2", 0, self._n_user), ("u_soft_l1", self.n, self._m_user),
+                            ("u_soft_l2", self.n, self._m_user)):
+            if given[name] is None:
+                continue
+            w = _host_f64(given[name])
+            try:
+                ok = w.ndim >= 1 and w.shape[-1] == k and np.broadcast_shapes(w.shape[:-1], P) == P
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError(f"{who}: {name} has shape {w.shape}, expected (..., {k}) with leading axes that broadcast to the problem "
+                                 f"shape {P}")
+            if np.any(np.isnan(w)) or np.any(w < 0):
+                raise ValueError(f"{who}: {name} has a negative or NaN entry: a penalty weight is >= 0 (l1 = +inf: a hard component)")
+            if name.endswith("l2") and not np.all(np.isfinite(w)):
+                raise ValueError(f"{who}: {name} has a non-finite entry: the quadratic weight is finite (a hard component is l1 = +inf)")
+            (l1 if name.endswith("l1") else l2)[..., at:at + k] = w
+        if np.any((l2 > 0) & np.isinf(l1)):
+            raise ValueError(f"{who}: a quadratic weight l2 > 0 on a component whose l1 is +inf (hard): give that component a finite l1 "
+                             f"(0 for a purely quadratic penalty)")
+        return l1, l2
 
     def _init_stage_varying(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c):
         """The constructor with a non-empty `stage_varying`: the same checks, per stage where an array has a stage axis."""
@@ -545,16 +606,18 @@ class ltvMpc(lqrMpc):
                 "x_lb0": xl[..., 0, :], "x_ub0": xu[..., 0, :]}
 
     @classmethod
-    def fromExpansion(cls, dyn, traj, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=()):
+    def fromExpansion(cls, dyn, traj, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=(), **soft):
         """The problem of an `AffineDynamics` (f, f_x, f_u) expanded about `traj` (AffineDynamics.from_trajectory(model, traj)): in absolute
         coordinates x+ ~ f + f_x (x - xbar_k) + f_u (u - ubar_k), i.e. A_k = f_x, B_k = f_u, c_k = f - f_x xbar_k - f_u ubar_k.  N is the
-        number of stages of the expansion; bounds and references are in absolute coordinates."""
+        number of stages of the expansion; bounds and references are in absolute coordinates.  **soft: the constructor's x_soft_l1,
+        x_soft_l2, u_soft_l1, u_soft_l2."""
         f, f_x, f_u = (_host_f64(X) for X in tuple.__iter__(dyn))
         xbar, ubar = _host_f64(tuple.__getitem__(traj, 0))[..., :-1, :], _host_f64(tuple.__getitem__(traj, 1))
         c = f - np.einsum("...ij,...j->...i", f_x, xbar) - np.einsum("...ij,...j->...i", f_u, ubar)
-        return cls(f_x, f_u, Q, R, f.shape[-2], x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=c, stage_varying=stage_varying)
+        return cls(f_x, f_u, Q, R, f.shape[-2], x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=c, stage_varying=stage_varying, **soft)
 
-    def update(self, A=None, B=None, c=None, Q=None, R=None, x_lb=None, x_ub=None, u_lb=None, u_ub=None):
+    def update(self, A=None, B=None, c=None, Q=None, R=None, x_lb=None, x_ub=None, u_lb=None, u_ub=None, x_soft_l1=None, x_soft_l2=None,
+               u_soft_l1=None, u_soft_l2=None):
         """New dynamics data of the same shapes (the next linearisation of a real-time-iteration loop).  NumPy arrays or torch tensors; a
         device tensor is copied device to device, without a host copy (the attributes A, B, c then keep the data they had).  The tables
         are rebuilt by one setup launch before the next solve; the warm-start workspace survives.
@@ -562,7 +625,14 @@ class ltvMpc(lqrMpc):
         An object built with `stage_varying=` also takes new weights and bounds, in the shapes its constructor took them (the next window
         of a moving corridor).  New bounds rewrite the device boxes and keep the tables: nothing is launched but the copies.  New Q or R
         are checked as the constructor checks them (on the host: a device tensor is copied there for it) and drop the tables.  The
-        penalty `rho` stays what the constructor chose.  The warm-start workspace survives either."""
+        penalty `rho` stays what the constructor chose.  The warm-start workspace survives either.
+
+        An object built with soft weights also takes new ones (x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2, in the constructor's shapes
+        and under its checks; the others stay): the device weights are rewritten, the tables and the workspace stay, nothing is
+        launched but the copy.  All-inf l1 makes every bound hard again."""
+        soft = {k: X for k, X in zip(self._SOFT, (x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2)) if X is not None}
+        if soft:
+            self._update_soft(soft)
         more = {k: X for k, X in (("Q", Q), ("R", R), ("x_lb", x_lb), ("x_ub", x_ub), ("u_lb", u_lb), ("u_ub", u_ub)) if X is not None}
         if more:
             self._update_stage_data(more)
@@ -593,6 +663,19 @@ class ltvMpc(lqrMpc):
             if not (arr.is_torch(X) and X.is_cuda):
                 getattr(self, name)[(Ellipsis,) + tuple(slice(0, w) for w in tail[1:])] = _host_f64(X)
         self._tables = {}
+
+    def _update_soft(self, new):
+        """update()'s penalty weights: checked with the ones that stay, then the host attributes and the device copies"""
+        if self._soft is None:
+            raise ValueError(f"ltvMpc.update: new {', '.join(new)} need an object built with soft weights (this one keeps every bound hard "
+                             f"and solves through the entry points without them: build a new object)")
+        given = {**self._soft, **new}
+        l1, l2 = self._soft_stacked("ltvMpc.update", given)
+        self._soft, self.soft_l1, self.soft_l2 = given, l1, l2
+        if self._dev is not None:
+            Pn = int(np.prod(self.P))
+            for k, X in (("soft_l1", l1), ("soft_l2", l2)):
+                self._dev[k].copy_(arr.to_device(X.reshape(Pn, -1), torch.float64, self._dev[k].device))
 
     def _update_stage_data(self, new):
         """update()'s weights and bounds: shape checks first, then the host attributes and the stage-form device arrays"""
@@ -654,8 +737,10 @@ class ltvMpc(lqrMpc):
         if self._dev is None:
             Pn = int(np.prod(self.P))
             flat = lambda X: arr.to_device(np.ascontiguousarray(X).reshape((Pn,) + X.shape[len(self.P):]), torch.float64)
-            if self.stage_varying:   # (the six once, in the stage form the two stage entry points read)
+            if self._stage_entry:   # (the six once, in the stage form the stage entry points read; the soft weights behind them)
                 self._dev = {**{k: flat(getattr(self, k)) for k in ("A", "B", "c")}, **{k: flat(X) for k, X in self._stage_form().items()}}
+                if self._soft is not None:
+                    self._dev.update(soft_l1=flat(self.soft_l1), soft_l2=flat(self.soft_l2))
             else:
                 self._dev = {k: flat(getattr(self, k)) for k in _ARRAYS + ("c",)}
         return self._dev
@@ -683,7 +768,7 @@ class ltvMpc(lqrMpc):
         if key not in self._tables:
             tabs = self._empty_tables(rho, adaptive)
             K, Mi, nl, _, _, rtab, D, ABt = tabs
-            setup, weights = ((_lib.lib().zm_mpc_setup_ltv_stage_f64, "Qs Rs") if self.stage_varying else
+            setup, weights = ((_lib.lib().zm_mpc_setup_ltv_stage_f64, "Qs Rs") if self._stage_entry else
                               (_lib.lib().zm_mpc_setup_ltv_f64, "Q R Qf"))
             rc = setup(*_ptrs(d, "A B c " + weights, rtab), int(np.prod(self.P)), nl, self.N, self.n, self.m,
                        *_ptrs(d, "", K, Mi, D, ABt), ctypes.c_void_p(arr.stream_ptr(K)))
@@ -694,7 +779,7 @@ class ltvMpc(lqrMpc):
     # ---- real-time iteration: a registered model linearised about the moving plan --------------------------------------------------
 
     @classmethod
-    def fromModel(cls, model, plan, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=()):
+    def fromModel(cls, model, plan, Q, R, x_lb, x_ub, u_lb, u_ub, Qf=None, stage_varying=(), **soft):
         """The problem of a registered model (models.QuadcopterEuler, models.QuadcopterRigidBody with dt > 0, models.LinearModel; n <= 12,
         m <= 4) linearised about `plan`, a Trajectory (xTraj (..., N+1, n), uTraj (..., N, m)) in absolute coordinates: what
         `fromExpansion(AffineDynamics.from_trajectory(model, plan), plan, ...)` builds, with c_k formed on the device as `relinearize` forms
@@ -715,7 +800,7 @@ class ltvMpc(lqrMpc):
         _lib.check(rc, "ltvMpc.fromModel")
         host = lambda t, tail: t.cpu().numpy().reshape(lead + tail)
         return cls(host(A, (N, n, n)), host(B, (N, n, m)), Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=Qf, c=host(c, (N, n)),
-                   stage_varying=stage_varying)
+                   stage_varying=stage_varying, **soft)
 
     def relinearize(self, model, plan):
         """The next linearisation of a real-time-iteration loop, on the device: `model` expanded about `plan` (a Trajectory, xTraj
@@ -777,8 +862,13 @@ class ltvMpc(lqrMpc):
         -------
             MpcClosedLoop, as `lqrMpc.simulate` returns it
 
-        Not with stage_varying= (NotImplementedError): the loop inside the call keeps one set of weights and bounds per problem.
+        Not with stage_varying= (NotImplementedError): the loop inside the call keeps one set of weights and bounds per problem.  Not
+        with soft weights either: the loop inside the call solves with hard bounds.
         """
+        if self._soft is not None:
+            raise NotImplementedError("ltvMpc.realTimeIteration: the loop inside zm_mpc_rti_f64 solves with hard bounds; with soft weights "
+                                      "write the loop out: relinearize(model, plan), solve(x, warm_start=\"shift\"), "
+                                      "modelStep(plant, x, u)")
         if self.stage_varying:
             raise NotImplementedError("ltvMpc.realTimeIteration: the loop inside zm_mpc_rti_f64 keeps one set of weights and bounds per "
                                       "problem; with stage_varying= write the loop out: relinearize(model, plan), update(x_lb=..., "
