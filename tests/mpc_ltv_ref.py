@@ -1,10 +1,12 @@
 """CPU checkers and cases for mpcUtils.ltvMpc (stage-varying dynamics x+ = A_k x + B_k u + c_k); a helper module, not collected as a test.
 
   * `admm_levels_ltv`     -- the whole solve of ONE instance restated in NumPy in the kernel's order (zopt_amd/csrc/mpc_solve_wave_ltv.h):
-                             oracle.mpc_oracle.admm_levels with the stage's own A_k, B_k, the offset's share D_k = P_{k+1} c_k of the costate,
-                             c_k in the rollout and in the free response of the infeasibility certificate, and the cycle guard on whenever
-                             g != 0 or c != 0.  Same arguments and the same returned namespace, margins included.
-  * `solve_reference_ltv` -- an independent solve: the QP condensed in u with the offsets carried through, SciPy trust-constr.
+                             an adapter of the one body of every family, oracle.mpc_oracle.admm_levels_stage, which has the stage's own
+                             A_k, B_k, the offset's share D_k = P_{k+1} c_k of the costate, c_k in the rollout and in the free response of
+                             the infeasibility certificate, and the cycle guard on whenever g != 0 or c != 0.  The arguments of
+                             oracle.mpc_oracle.admm_levels with A_k, B_k, c_k, and the same returned namespace, margins included.
+  * `solve_reference_ltv` -- an independent solve, an adapter of oracle.mpc_oracle.solve_reference_stage: the QP condensed in u with the
+                             offsets carried through, SciPy trust-constr.
   * the cases of tests/test_mpc_ltv.py (their decisions are checked there, without a GPU) and tests/test_mpc_ltv_gpu.py, with `reference`,
     `run_steps` and `compare` in the manner of tests/mpc_iterates_cases.py (whose `compare` is tied to its own cases: the rule is restated).
 """
@@ -14,210 +16,26 @@ import functools
 from types import SimpleNamespace
 
 import numpy as np
-import scipy.optimize as spo
 
-from oracle.mpc_oracle import CHECK_EVERY
+from oracle import mpc_oracle as mo
 from tests import mpc_iterates_cases as mc
 from tests import mpc_tracking_ref as tr
 
 
-def rollout_ltv(A, B, c, x0, u):
-    x = [np.asarray(x0, dtype=np.float64)]
-    for k in range(u.shape[0]):
-        x.append(A[k] @ x[-1] + B[k] @ u[k] + c[k])
-    return np.stack(x)
-
-
 def admm_levels_ltv(A, B, c, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, eps_rel=1e-5, max_iter=10000,
                     eps_prim_inf=1e-4, alpha=1.6, n_levels=7, rho_step=5.0, g=None, warm=None, shift=False, guard=True):
-    """oracle.mpc_oracle.admm_levels (see there for the arguments, the order of an iteration and the returned namespace) for
-    A (N, n, n), B (N, n, m), c (N, n) or None (zeros).  The differences, as the kernel spells them:
-        tables:    the recursion of mpc_setup_body.h with A_k, B_k, and D_k = P_{k+1} c_k from the value matrix on entering stage k
-        backward:  p = p' + z_x + g_x + D_k;  Qu = z_u + g_u + B_k' p;  kf = Suu_k^-1 Qu;  p' = A_k' p - K_k' Qu
-        forward:   u = -K_k x - kf;  x+ = A_k x + B_k u + c_k
-        certificate: v.w(u=0) = s_0.x0 + sum_k sigma_k.c_k, sigma_k the adjoint vector on entering stage k of the adjoint sweep
-        guard:     on when g != 0 or c != 0 (and `guard`)
-    The dual tolerance scales with max(rho |lam|, |g|): c does not enter it."""
-    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else np.asarray(c, dtype=np.float64)
-    assert A.shape == (N, n, n) and B.shape == (N, n, m) and c.shape == (N, n)
-    level0 = n_levels // 2
-    rho0 = float(rho)
-    tabs = {}
-
-    def tables(l):
-        if l not in tabs:
-            r_ = rho0 * rho_step ** (l - level0)
-            Hx, Hu = 2 * Q + r_ * np.eye(n), 2 * R + r_ * np.eye(m)
-            P = 2 * Qf + r_ * np.eye(n)
-            K, Mi, D = [None] * N, [None] * N, [None] * N
-            for k in range(N - 1, -1, -1):
-                D[k] = P @ c[k]
-                Suu = Hu + B[k].T @ P @ B[k]
-                Sux = B[k].T @ P @ A[k]
-                Mi[k] = np.linalg.inv(Suu)
-                K[k] = Mi[k] @ Sux
-                P = Hx + A[k].T @ P @ A[k] - Sux.T @ K[k]
-            tabs[l] = (r_, K, Mi, D)
-        return tabs[l]
-
-    lvl = level0
-    yx, yu, lx, lu = np.zeros((N, n)), np.zeros((N, m)), np.zeros((N, n)), np.zeros((N, m))
-    if warm is not None:
-        wy, wl, wlvl = warm
-        if n_levels > 1 and 0 <= int(wlvl) < n_levels:
-            lvl = int(wlvl)
-        ks = [k + 1 if (shift and k + 1 < N) else k for k in range(N)]
-        wy, wl = np.asarray(wy, dtype=np.float64)[ks], np.asarray(wl, dtype=np.float64)[ks]
-        yx, yu, lx, lu = wy[:, :n].copy(), wy[:, n:].copy(), wl[:, :n].copy(), wl[:, n:].copy()
-    if g is None:
-        gx, gu = np.zeros((N, n)), np.zeros((N, m))
-    else:
-        gx, gu = np.asarray(g[0], dtype=np.float64), np.asarray(g[1], dtype=np.float64)
-    gn = max(np.max(np.abs(gx)), np.max(np.abs(gu)))
-    guard_on = bool(guard) and (gn > 0.0 or np.max(np.abs(c)) > 0.0)
-    rho_l, K, Mi, D = tables(lvl)
-    kf = np.zeros((N, m))
-
-    def roll(K, kf):
-        xs, us = [np.asarray(x0, dtype=np.float64)], []
-        for k in range(N):
-            us.append(-K[k] @ xs[-1] - kf[k])
-            xs.append(A[k] @ xs[-1] + B[k] @ us[-1] + c[k])
-        return np.stack(xs), np.stack(us)
-
-    out = SimpleNamespace(moves=[], locked=False, level_margin=np.inf, stop_margin=np.inf, near_margin=np.inf, rp=0.0, rd=0.0)
-    status, it, near_ok = None, 0, False
-    x, u = roll(K, kf)
-    if np.any(x0 < x_lb) or np.any(x0 > x_ub):
-        status = "infeasible"
-    last, rev = 0, 0
-    while status is None and it < max_iter:
-        it += 1
-        chk = (it % CHECK_EVERY) == 0
-        zx, zu = -rho_l * (yx - lx) + gx, -rho_l * (yu - lu) + gu
-        p = zx[N - 1] + D[N - 1]
-        for k in range(N - 1, -1, -1):
-            qu = zu[k] + B[k].T @ p
-            kf[k] = Mi[k] @ qu
-            p = ((zx[k - 1] + D[k - 1]) if k >= 1 else 0.0) + A[k].T @ p - K[k].T @ qu
-        x, u = roll(K, kf)
-        xh, uh = alpha * x[1:] + (1.0 - alpha) * yx, alpha * u + (1.0 - alpha) * yu
-        yxn = np.clip(xh + lx, x_lb, x_ub)
-        yun = np.clip(uh + lu, u_lb, u_ub)
-        rp = max(np.max(np.abs(x[1:] - yxn)), np.max(np.abs(u - yun)))
-        rx, ru = xh - yxn, uh - yun
-        nrd = max(np.max(np.abs(yxn - yx)), np.max(np.abs(yun - yu)))
-        rd = rho_l * nrd
-        lx, lu = lx + rx, lu + ru
-        yx, yu = yxn, yun
-        nwy = max(np.max(np.abs(x[1:])), np.max(np.abs(u)), np.max(np.abs(yx)), np.max(np.abs(yu)))
-        nl = max(np.max(np.abs(lx)), np.max(np.abs(lu)))
-        ep = eps_abs + eps_rel * nwy
-        ed = eps_abs + eps_rel * rho_l * nl
-        if gn > rho_l * nl:
-            ed = eps_abs + eps_rel * gn
-        out.rp, out.rd = rp, rd
-        near_ok = bool(rp <= 10.0 * ep and rd <= 10.0 * ed)
-        if rp == rp:
-            worst = max(rp / ep, rd / ed)
-            out.stop_margin = min(out.stop_margin, abs(worst - 1.0))
-            out.near_margin = abs(worst / 10.0 - 1.0)
-        if rp <= ep and rd <= ed:
-            status = "optimal"
-            break
-        if not (rp == rp):
-            break
-        if not chk:
-            continue
-        if n_levels > 1 and it < max_iter:
-            tiny = 1e-300
-            rpn = rp / max(nwy, tiny)
-            rdn = rd / max(rho_l * nl, tiny)
-            want = np.sqrt(rpn / max(rdn, tiny))
-            dl = 0
-            if want == want and want > 0.0:
-                t = np.log(want) / np.log(rho_step)
-                dl = int(np.rint(t))
-                out.level_margin = min(out.level_margin, abs(abs(t - np.floor(t)) - 0.5))
-            new = min(max(lvl + dl, 0), n_levels - 1)
-            if guard_on:
-                mv = new - lvl
-                if out.locked:
-                    new = lvl
-                elif mv != 0 and last != 0 and ((mv > 0) != (last > 0)):
-                    rev += 1
-                    if rev >= 3:
-                        out.locked = True
-                        new = lvl
-                else:
-                    rev = 0
-                last = new - lvl
-            if new != lvl:
-                out.moves.append((it, lvl, new))
-                r_new, K, Mi, D = tables(new)
-                sc = rho_l / r_new
-                lx, lu = lx * sc, lu * sc
-                rho_l, lvl = r_new, new
-        s = rx[N - 1].copy()
-        gmax, vc = 0.0, 0.0
-        for k in range(N - 1, -1, -1):
-            vc += s @ c[k]
-            gmax = max(gmax, np.max(np.abs(ru[k] + B[k].T @ s)))
-            s = (rx[k - 1] if k >= 1 else 0.0) + A[k].T @ s
-        sup = 0.0
-        for r_, lo_, hi_ in ((rx, x_lb, x_ub), (ru, u_lb, u_ub)):
-            lo_b, hi_b = np.broadcast_to(lo_, r_.shape), np.broadcast_to(hi_, r_.shape)
-            pos, neg = r_ > 0, r_ < 0
-            sup += np.sum(r_[pos] * hi_b[pos]) + np.sum(r_[neg] * lo_b[neg])
-        dn = max(np.max(np.abs(rx)), np.max(np.abs(ru)))
-        if gmax <= eps_prim_inf * dn and (s @ x0 + vc - sup) > eps_prim_inf * dn:
-            status = "infeasible"
-    if status is None:
-        status = "optimal_inaccurate" if near_ok else "user_limit"
-    out.x, out.u, out.status, out.iters = x, u, status, it
-    out.y, out.lam, out.level, out.rho_final = np.hstack([yx, yu]), np.hstack([lx, lu]), lvl, rho_l
-    return out
+    """oracle.mpc_oracle.admm_levels_stage (see there for the options, the order of an iteration and the returned namespace) for
+    A (N, n, n), B (N, n, m), c (N, n) or None (zeros) with one set of weights and bounds, as constant rows, every component hard.
+    g: tests/mpc_tracking_ref.py: linear_term.  The guard is then on when g != 0 or c != 0."""
+    return mo.admm_levels_stage(A, B, c, *mo.stage_args(Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub), x0, None, None, rho, eps_abs, eps_rel,
+                                max_iter, eps_prim_inf, alpha, n_levels, rho_step, g, warm, shift, guard)
 
 
 def solve_reference_ltv(A, B, c, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, xRef=None, uRef=None):
-    """Independent reference: x_k = phi_k + Gam_k u with the offsets inside the free response phi, the cost (about the references, zero
-    if None) condensed in u, linear inequality constraints on the states, SciPy trust-constr.  Returns (x, u, cost)."""
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else c
-    xRef = np.zeros((N + 1, n)) if xRef is None else xRef
-    uRef = np.zeros((N, m)) if uRef is None else uRef
-    phi = [np.asarray(x0, dtype=np.float64)]
-    Gam = [np.zeros((n, N * m))]
-    for k in range(N):
-        phi.append(A[k] @ phi[-1] + c[k])
-        G = A[k] @ Gam[-1]
-        G[:, k * m:(k + 1) * m] += B[k]
-        Gam.append(G)
-    H, gv = np.zeros((N * m, N * m)), np.zeros(N * m)
-    for k in range(1, N + 1):
-        Wm = Qf if k == N else Q
-        Ws = 0.5 * (Wm + Wm.T)
-        H += Gam[k].T @ Ws @ Gam[k]
-        gv += Gam[k].T @ Ws @ (phi[k] - xRef[k])
-    Rs = 0.5 * (R + R.T)
-    for k in range(N):
-        H[k * m:(k + 1) * m, k * m:(k + 1) * m] += Rs
-        gv[k * m:(k + 1) * m] -= Rs @ uRef[k]
-    rows, lo, hi = [], [], []
-    for k in range(1, N + 1):
-        for i in range(n):
-            if np.isfinite(x_lb[i]) or np.isfinite(x_ub[i]):
-                rows.append(Gam[k][i])
-                lo.append(x_lb[i] - phi[k][i])
-                hi.append(x_ub[i] - phi[k][i])
-    cons = [spo.LinearConstraint(np.array(rows), np.array(lo), np.array(hi))] if rows else []
-    res = spo.minimize(lambda v: v @ H @ v + 2 * gv @ v, np.zeros(N * m), jac=lambda v: 2 * (H @ v + gv), hess=lambda v: 2 * H,
-                       method="trust-constr", bounds=spo.Bounds(np.tile(u_lb, N), np.tile(u_ub, N)), constraints=cons,
-                       options=dict(gtol=1e-12, xtol=1e-14, barrier_tol=1e-14, maxiter=5000))
-    u = res.x.reshape(N, m)
-    x = rollout_ltv(A, B, c, x0, u)
+    """Independent reference: oracle.mpc_oracle.solve_reference_stage (the QP condensed in u with the offsets carried through, SciPy
+    trust-constr) with one set of weights and bounds.  Returns (x, u, cost about the references, zero if None)."""
+    x, u, _ = mo.solve_reference_stage(A, B, c, *mo.stage_args(Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub), x0, xRef=xRef, uRef=uRef)
+    xRef, uRef = np.zeros_like(x) if xRef is None else xRef, np.zeros_like(u) if uRef is None else uRef
     return x, u, tr.cost(Q, R, Qf, x, u, xRef, uRef)
 
 

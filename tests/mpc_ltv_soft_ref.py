@@ -2,13 +2,13 @@
 l1 d + l2 d^2 on the distance d of a component of [x_{k+1} ; u_k] from its box, per problem and component, constant over the stages;
 l1 = +inf is a hard component); a helper module, not collected as a test.
 
-  * `admm_levels_ltv_soft`     -- tests/mpc_ltv_stage_ref.py: admm_levels_ltv_stage restated with the three changes of
-                                  zm_mpc_solve_ltv_soft_f64 (x0 test, proximal map, support term) and its guard rule.  Same options and
-                                  returned namespace.
-  * `solve_reference_ltv_soft` -- the condensed SciPy trust-constr solve with one slack e >= 0 per soft (stage, component) that has a
-                                  finite bound: lo - e <= w <= hi + e, cost + l1 e + l2 e^2.
+  * `admm_levels_ltv_soft`     -- the NumPy restatement of zm_mpc_solve_ltv_soft_f64: the one body of every family itself,
+                                  oracle.mpc_oracle.admm_levels_stage, whose data this entry takes in full (x0 test, proximal map `prox`,
+                                  support term and guard rule of a soft component: see there).
+  * `solve_reference_ltv_soft` -- oracle.mpc_oracle.solve_reference_stage: the condensed SciPy trust-constr solve with one slack e >= 0
+                                  per soft (stage, component) that has a finite bound: lo - e <= w <= hi + e, cost + l1 e + l2 e^2.
   * the named cases of tests/test_mpc_ltv_soft.py and tests/test_mpc_ltv_soft_gpu.py, built from the recipes of
-    tests/mpc_ltv_stage_ref.py, with its `run_steps` and comparison rule.
+    tests/mpc_ltv_stage_ref.py and run through its case glue, with its `run_steps` and comparison rule.
 
 An instance's data is that of tests/mpc_ltv_stage_ref.py followed by the weights l1, l2, each (n + m,) in the stacked layout [x ; u].
 """
@@ -18,268 +18,14 @@ import functools
 from types import SimpleNamespace
 
 import numpy as np
-import scipy.optimize as spo
 
-from oracle.mpc_oracle import CHECK_EVERY
+from oracle.mpc_oracle import admm_levels_stage as admm_levels_ltv_soft  # noqa: F401  (l1 is its 12th argument, l2 its 13th)
+from oracle.mpc_oracle import prox, violation  # noqa: F401
+from oracle.mpc_oracle import solve_reference_stage as solve_reference_ltv_soft  # noqa: F401
 from tests import mpc_ltv_ref as lr
 from tests import mpc_ltv_stage_ref as sr
 
 INF = np.inf
-
-
-def prox(v, lo, hi, t, a):
-    """the y-update of zm_mpc_solve_ltv_soft_f64, written with its selects: t = l1 / rho, a = rho / (rho + 2 l2); t = +inf is the clip"""
-    with np.errstate(invalid="ignore"):
-        eh, el = a * ((v - hi) - t), a * ((lo - v) - t)
-        return np.where(v > hi, np.where(eh > 0, hi + eh, hi), np.where(v < lo, np.where(el > 0, lo - el, lo), v))
-
-
-def admm_levels_ltv_soft(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, l1, l2=None, rho=1.0, eps_abs=1e-5, eps_rel=1e-5,
-                         max_iter=10000, eps_prim_inf=1e-4, alpha=1.6, n_levels=7, rho_step=5.0, g=None, warm=None, shift=False,
-                         guard=True):
-    """tests/mpc_ltv_stage_ref.py: admm_levels_ltv_stage (see there and tests/mpc_ltv_ref.py for the order of an iteration and the
-    returned namespace) with the penalty weights l1, l2 (n + m,) of the stacked components [x ; u]; l2 None: zeros.  The differences:
-        x0 test:     a soft state component (finite l1) is not tested against row 0 of the state box
-        projection:  the proximal map `prox` of the penalty, its thresholds t = l1 / rho, a = rho / (rho + 2 l2) at the penalty the
-                     iteration runs at
-        certificate: in the support term a soft component has the bounds -inf / +inf
-        guard:       also on when any component is soft"""
-    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else np.asarray(c, dtype=np.float64)
-    assert A.shape == (N, n, n) and B.shape == (N, n, m) and c.shape == (N, n)
-    assert Qs.shape == (N, n, n) and Rs.shape == (N, m, m)
-    assert x_lb.shape == x_ub.shape == (N + 1, n) and u_lb.shape == u_ub.shape == (N, m)
-    l1 = np.asarray(l1, dtype=np.float64)
-    l2 = np.zeros(n + m) if l2 is None else np.asarray(l2, dtype=np.float64)
-    assert l1.shape == l2.shape == (n + m,) and np.all(l1 >= 0) and np.all(l2 >= 0) and not np.any((l2 > 0) & np.isinf(l1))
-    l1x, l1u, l2x, l2u = l1[:n], l1[n:], l2[:n], l2[n:]
-    soft_x, soft_u = np.isfinite(l1x), np.isfinite(l1u)
-    xl, xu = x_lb[1:], x_ub[1:]
-    # the bounds the certificate sees
-    cxl, cxu = np.where(soft_x, -INF, xl), np.where(soft_x, INF, xu)
-    cul, cuu = np.where(soft_u, -INF, u_lb), np.where(soft_u, INF, u_ub)
-    level0 = n_levels // 2
-    rho0 = float(rho)
-    tabs = {}
-
-    def tables(l):
-        if l not in tabs:
-            r_ = rho0 * rho_step ** (l - level0)
-            P = 2 * Qs[N - 1] + r_ * np.eye(n)
-            K, Mi, D = [None] * N, [None] * N, [None] * N
-            for k in range(N - 1, -1, -1):
-                D[k] = P @ c[k]
-                Suu = (2 * Rs[k] + r_ * np.eye(m)) + B[k].T @ P @ B[k]
-                Sux = B[k].T @ P @ A[k]
-                Mi[k] = np.linalg.inv(Suu)
-                K[k] = Mi[k] @ Sux
-                P = (2 * Qs[max(k - 1, 0)] + r_ * np.eye(n)) + A[k].T @ P @ A[k] - Sux.T @ K[k]
-            tabs[l] = (r_, K, Mi, D)
-        return tabs[l]
-
-    lvl = level0
-    yx, yu, lx, lu = np.zeros((N, n)), np.zeros((N, m)), np.zeros((N, n)), np.zeros((N, m))
-    if warm is not None:
-        wy, wl, wlvl = warm
-        if n_levels > 1 and 0 <= int(wlvl) < n_levels:
-            lvl = int(wlvl)
-        ks = [k + 1 if (shift and k + 1 < N) else k for k in range(N)]
-        wy, wl = np.asarray(wy, dtype=np.float64)[ks], np.asarray(wl, dtype=np.float64)[ks]
-        yx, yu, lx, lu = wy[:, :n].copy(), wy[:, n:].copy(), wl[:, :n].copy(), wl[:, n:].copy()
-    if g is None:
-        gx, gu = np.zeros((N, n)), np.zeros((N, m))
-    else:
-        gx, gu = np.asarray(g[0], dtype=np.float64), np.asarray(g[1], dtype=np.float64)
-    gn = max(np.max(np.abs(gx)), np.max(np.abs(gu)))
-    guard_on = bool(guard) and (gn > 0.0 or np.max(np.abs(c)) > 0.0 or bool(np.any(soft_x) or np.any(soft_u)))
-    rho_l, K, Mi, D = tables(lvl)
-    kf = np.zeros((N, m))
-
-    def roll(K, kf):
-        xs, us = [np.asarray(x0, dtype=np.float64)], []
-        for k in range(N):
-            us.append(-K[k] @ xs[-1] - kf[k])
-            xs.append(A[k] @ xs[-1] + B[k] @ us[-1] + c[k])
-        return np.stack(xs), np.stack(us)
-
-    out = SimpleNamespace(moves=[], locked=False, level_margin=np.inf, stop_margin=np.inf, near_margin=np.inf, rp=0.0, rd=0.0)
-    status, it, near_ok = None, 0, False
-    x, u = roll(K, kf)
-    if np.any((x0 < x_lb[0]) & ~soft_x) or np.any((x0 > x_ub[0]) & ~soft_x):
-        status = "infeasible"
-    last, rev = 0, 0
-    while status is None and it < max_iter:
-        it += 1
-        chk = (it % CHECK_EVERY) == 0
-        zx, zu = -rho_l * (yx - lx) + gx, -rho_l * (yu - lu) + gu
-        p = zx[N - 1] + D[N - 1]
-        for k in range(N - 1, -1, -1):
-            qu = zu[k] + B[k].T @ p
-            kf[k] = Mi[k] @ qu
-            p = ((zx[k - 1] + D[k - 1]) if k >= 1 else 0.0) + A[k].T @ p - K[k].T @ qu
-        x, u = roll(K, kf)
-        xh, uh = alpha * x[1:] + (1.0 - alpha) * yx, alpha * u + (1.0 - alpha) * yu
-        yxn = prox(xh + lx, xl, xu, l1x / rho_l, rho_l / (rho_l + 2.0 * l2x))
-        yun = prox(uh + lu, u_lb, u_ub, l1u / rho_l, rho_l / (rho_l + 2.0 * l2u))
-        rp = max(np.max(np.abs(x[1:] - yxn)), np.max(np.abs(u - yun)))
-        rx, ru = xh - yxn, uh - yun
-        nrd = max(np.max(np.abs(yxn - yx)), np.max(np.abs(yun - yu)))
-        rd = rho_l * nrd
-        lx, lu = lx + rx, lu + ru
-        yx, yu = yxn, yun
-        nwy = max(np.max(np.abs(x[1:])), np.max(np.abs(u)), np.max(np.abs(yx)), np.max(np.abs(yu)))
-        nl = max(np.max(np.abs(lx)), np.max(np.abs(lu)))
-        ep = eps_abs + eps_rel * nwy
-        ed = eps_abs + eps_rel * rho_l * nl
-        if gn > rho_l * nl:
-            ed = eps_abs + eps_rel * gn
-        out.rp, out.rd = rp, rd
-        near_ok = bool(rp <= 10.0 * ep and rd <= 10.0 * ed)
-        if rp == rp:
-            worst = max(rp / ep, rd / ed)
-            out.stop_margin = min(out.stop_margin, abs(worst - 1.0))
-            out.near_margin = abs(worst / 10.0 - 1.0)
-        if rp <= ep and rd <= ed:
-            status = "optimal"
-            break
-        if not (rp == rp):
-            break
-        if not chk:
-            continue
-        if n_levels > 1 and it < max_iter:
-            tiny = 1e-300
-            rpn = rp / max(nwy, tiny)
-            rdn = rd / max(rho_l * nl, tiny)
-            want = np.sqrt(rpn / max(rdn, tiny))
-            dl = 0
-            if want == want and want > 0.0:
-                t = np.log(want) / np.log(rho_step)
-                dl = int(np.rint(t))
-                out.level_margin = min(out.level_margin, abs(abs(t - np.floor(t)) - 0.5))
-            new = min(max(lvl + dl, 0), n_levels - 1)
-            if guard_on:
-                mv = new - lvl
-                if out.locked:
-                    new = lvl
-                elif mv != 0 and last != 0 and ((mv > 0) != (last > 0)):
-                    rev += 1
-                    if rev >= 3:
-                        out.locked = True
-                        new = lvl
-                else:
-                    rev = 0
-                last = new - lvl
-            if new != lvl:
-                out.moves.append((it, lvl, new))
-                r_new, K, Mi, D = tables(new)
-                sc = rho_l / r_new
-                lx, lu = lx * sc, lu * sc
-                rho_l, lvl = r_new, new
-        s = rx[N - 1].copy()
-        gmax, vc = 0.0, 0.0
-        for k in range(N - 1, -1, -1):
-            vc += s @ c[k]
-            gmax = max(gmax, np.max(np.abs(ru[k] + B[k].T @ s)))
-            s = (rx[k - 1] if k >= 1 else 0.0) + A[k].T @ s
-        sup = 0.0
-        for r_, lo_, hi_ in ((rx, cxl, cxu), (ru, cul, cuu)):
-            pos, neg = r_ > 0, r_ < 0
-            sup += np.sum(r_[pos] * hi_[pos]) + np.sum(r_[neg] * lo_[neg])
-        dn = max(np.max(np.abs(rx)), np.max(np.abs(ru)))
-        if gmax <= eps_prim_inf * dn and (s @ x0 + vc - sup) > eps_prim_inf * dn:
-            status = "infeasible"
-    if status is None:
-        status = "optimal_inaccurate" if near_ok else "user_limit"
-    out.x, out.u, out.status, out.iters = x, u, status, it
-    out.y, out.lam, out.level, out.rho_final = np.hstack([yx, yu]), np.hstack([lx, lu]), lvl, rho_l
-    return out
-
-
-def violation(x, u, x_lb, x_ub, u_lb, u_ub):
-    """d of every (stage, stacked component): (N, n + m)"""
-    w, lo, hi = np.hstack([x[1:], u]), np.hstack([x_lb[1:], u_lb]), np.hstack([x_ub[1:], u_ub])
-    return np.maximum(0.0, np.maximum(w - hi, lo - w))
-
-
-def solve_reference_ltv_soft(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, l1, l2=None, xRef=None, uRef=None):
-    """Independent reference: tests/mpc_ltv_stage_ref.py: solve_reference_ltv_stage over (u, e) with one slack e >= 0 per soft (stage,
-    component) that has a finite bound, lo - e <= w <= hi + e and the cost + l1 e + l2 e^2; a soft input gets slacks instead of Bounds.
-    x0 is not tested against row 0 here.  Returns (x, u, cost with the penalty)."""
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else c
-    l2 = np.zeros(n + m) if l2 is None else np.asarray(l2, dtype=np.float64)
-    l1 = np.asarray(l1, dtype=np.float64)
-    xRef = np.zeros((N + 1, n)) if xRef is None else xRef
-    uRef = np.zeros((N, m)) if uRef is None else uRef
-    phi = [np.asarray(x0, dtype=np.float64)]
-    Gam = [np.zeros((n, N * m))]
-    for k in range(N):
-        phi.append(A[k] @ phi[-1] + c[k])
-        G = A[k] @ Gam[-1]
-        G[:, k * m:(k + 1) * m] += B[k]
-        Gam.append(G)
-    H, gv = np.zeros((N * m, N * m)), np.zeros(N * m)
-    for k in range(1, N + 1):
-        Ws = 0.5 * (Qs[k - 1] + Qs[k - 1].T)
-        H += Gam[k].T @ Ws @ Gam[k]
-        gv += Gam[k].T @ Ws @ (phi[k] - xRef[k])
-    for k in range(N):
-        Rk = 0.5 * (Rs[k] + Rs[k].T)
-        H[k * m:(k + 1) * m, k * m:(k + 1) * m] += Rk
-        gv[k * m:(k + 1) * m] -= Rk @ uRef[k]
-    # rows over u alone, each with its bounds and, soft, its weights: the slacks are numbered as the soft rows come
-    rows = []    # (row over u, lo, hi, l1, l2)
-    ulo, uhi = u_lb.reshape(-1).copy(), u_ub.reshape(-1).copy()
-    for k in range(1, N + 1):
-        for i in range(n):
-            if np.isfinite(x_lb[k, i]) or np.isfinite(x_ub[k, i]):
-                rows.append((Gam[k][i], x_lb[k, i] - phi[k][i], x_ub[k, i] - phi[k][i], l1[i], l2[i]))
-    for k in range(N):
-        for j in range(m):
-            if np.isfinite(l1[n + j]) and (np.isfinite(u_lb[k, j]) or np.isfinite(u_ub[k, j])):
-                e_ = np.zeros(N * m)
-                e_[k * m + j] = 1.0
-                rows.append((e_, u_lb[k, j], u_ub[k, j], l1[n + j], l2[n + j]))
-                ulo[k * m + j], uhi[k * m + j] = -INF, INF
-    ns = sum(1 for r in rows if np.isfinite(r[3]))
-    nv = N * m + ns
-    Cm, lo, hi = [], [], []
-    w1, w2 = np.zeros(ns), np.zeros(ns)
-    j = 0
-    for row, lo_, hi_, a1, a2 in rows:
-        if not np.isfinite(a1):
-            Cm.append(np.concatenate([row, np.zeros(ns)]))
-            lo.append(lo_)
-            hi.append(hi_)
-            continue
-        e_ = np.zeros(ns)
-        e_[j] = 1.0
-        w1[j], w2[j] = a1, a2
-        j += 1
-        if np.isfinite(lo_):
-            Cm.append(np.concatenate([row, e_]))
-            lo.append(lo_)
-            hi.append(INF)
-        if np.isfinite(hi_):
-            Cm.append(np.concatenate([row, -e_]))
-            lo.append(-INF)
-            hi.append(hi_)
-    Hf = np.zeros((nv, nv))
-    Hf[:N * m, :N * m] = H
-    Hf[N * m:, N * m:] = np.diag(w2)
-    gf = np.concatenate([gv, 0.5 * w1])
-    cons = [spo.LinearConstraint(np.array(Cm), np.array(lo), np.array(hi))] if Cm else []
-    bounds = spo.Bounds(np.concatenate([ulo, np.zeros(ns)]), np.concatenate([uhi, np.full(ns, INF)]))
-    res = spo.minimize(lambda v: v @ Hf @ v + 2 * gf @ v, np.zeros(nv), jac=lambda v: 2 * (Hf @ v + gf), hess=lambda v: 2 * Hf,
-                       method="trust-constr", bounds=bounds, constraints=cons,
-                       options=dict(gtol=1e-12, xtol=1e-14, barrier_tol=1e-14, maxiter=5000))
-    u = res.x[:N * m].reshape(N, m)
-    x = lr.rollout_ltv(A, B, c, x0, u)
-    d = violation(x, u, x_lb, x_ub, u_lb, u_ub)
-    fin = np.isfinite(l1)
-    pen = np.sum(d[:, fin] * l1[fin] + d[:, fin] ** 2 * l2[fin])
-    return x, u, sr.cost_stage(Qs, Rs, x, u, xRef, uRef) + pen
 
 
 # ---- the scalar problem with known answers -------------------------------------------------------------------------------------------------
@@ -404,84 +150,28 @@ def scipy_instances(name):
 
 def make_problem(mpcUtils, c, soft=None):
     """the ltvMpc object of a case (host side only); soft: other weights per problem than the case's"""
-    soft = c.soft if soft is None else soft
-
-    def args(d, w):
-        A, B, ck, Qs, Rs, xl, xu, ul, uu = d
-        n = B.shape[-2]
-        return A, B, ck, np.concatenate([Qs[:1], Qs]), Rs, xl, xu, ul, uu, w[0][:n], w[1][:n], w[0][n:], w[1][n:]
-    if c.shared:
-        A, B, ck, Q, R, xl, xu, ul, uu, x1, x2, u1, u2 = args(c.inst[0], soft[0])
-    else:
-        A, B, ck, Q, R, xl, xu, ul, uu, x1, x2, u1, u2 = (np.stack(v) for v in zip(*(args(d, w) for d, w in zip(c.inst, soft))))
-    return mpcUtils.ltvMpc(A, B, Q, R, c.N, xl, xu, ul, uu, c=ck, stage_varying=sr.ALL_SIX, x_soft_l1=x1, x_soft_l2=x2, u_soft_l1=u1,
-                           u_soft_l2=u2)
+    return sr.make_problem(mpcUtils, c, soft=c.soft if soft is None else soft)
 
 
-def case_rho(mpcUtils, c):
-    nb = len(c.x0)
-    if c.rho is not None:
-        return np.full(nb, float(c.rho))
-    rho = np.atleast_1d(make_problem(mpcUtils, c).rho)
-    return np.array([rho[problem_of(c, b)] for b in range(nb)])
-
-
-def reference_steps(c, rho, soft=None):
-    """[step][instance] -> result of admm_levels_ltv_soft, each fed its own previous final state"""
-    soft = c.soft if soft is None else soft
-    out = []
-    for s, step in enumerate(c.steps):
-        row = []
-        for b in range(len(c.x0)):
-            A, B, ck, Qs, Rs, xl, xu, ul, uu = c.inst[problem_of(c, b)]
-            l1, l2 = soft[problem_of(c, b)]
-            prev = out[-1][b] if s else None
-            x0 = prev.x[1] if step["x0"] == "x1" else (prev.x0 if step["x0"] == "same" else c.x0[b])
-            warm = (prev.y, prev.lam, prev.level) if (step["warm"] and prev.status == "optimal") else None
-            g = None if c.xRef is None else sr.linear_term_stage(Qs, Rs, c.N, c.xRef[b], c.uRef[b])
-            r = admm_levels_ltv_soft(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, x0, l1, l2, rho=float(rho[b]), g=g, warm=warm,
-                                     shift=step["warm"] == "shift", **step["kw"])
-            r.x0 = x0
-            row.append(r)
-        out.append(row)
-    return out
+case_rho, reference_steps = sr.case_rho, sr.reference_steps     # (the case's own weights are their default)
 
 
 @functools.lru_cache(maxsize=None)
 def reference(name):
-    from zopt_amd import mpcUtils
-    c = build(name)
-    return reference_steps(c, case_rho(mpcUtils, c))
+    return sr.reference_case(build(name))
 
 
 @functools.lru_cache(maxsize=None)
 def scipy_solution(name, b=0):
     """(x, u) of the slack QP of instance b"""
-    c = build(name)
-    xr, ur = (None, None) if c.xRef is None else (c.xRef[b], c.uRef[b])
-    p = problem_of(c, b)
-    x, u, _ = solve_reference_ltv_soft(*c.inst[p][:5], c.N, *c.inst[p][5:], c.x0[b], *c.soft[p], xRef=xr, uRef=ur)
-    return x, u
+    return sr.scipy_case(build(name), b)
 
 
 @functools.lru_cache(maxsize=None)
 def variant_solution(name, variant, b=0):
     """the restatement's result for instance b with every component hard ("hard": its status may be "infeasible"), or with the bounds of
     the soft components removed ("free"): what a case's solution must differ from for its weights to matter"""
-    from zopt_amd import mpcUtils
-    c = build(name)
-    p = problem_of(c, b)
-    A, B, ck, Qs, Rs, xl, xu, ul, uu = c.inst[p]
-    n = B.shape[-2]
-    l1, l2 = c.soft[p]
-    if variant == "hard":
-        l1, l2 = np.full_like(l1, INF), np.zeros_like(l2)
-    else:
-        fx, fu = np.isfinite(l1[:n]), np.isfinite(l1[n:])
-        xl, xu, ul, uu = np.where(fx, -INF, xl), np.where(fx, INF, xu), np.where(fu, -INF, ul), np.where(fu, INF, uu)
-    g = None if c.xRef is None else sr.linear_term_stage(Qs, Rs, c.N, c.xRef[b], c.uRef[b])
-    return admm_levels_ltv_soft(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, c.x0[b], l1, l2, rho=float(case_rho(mpcUtils, c)[b]), g=g,
-                                **lr._kw(max_iter=3000))
+    return sr.variant_case(build(name), variant, b, max_iter=3000)
 
 
 def run_steps(prob, c, ref):

@@ -5,11 +5,15 @@ Stage form, as the kernels take it (zm_mpc_setup_ltv_stage_f64, zm_mpc_solve_ltv
 x_{k+1} (row N - 1 is terminal), Rs (N, m, m), and the box as the constructor takes it, x_lb, x_ub (N + 1, n) -- row 0 is the test on x0 --
 and u_lb, u_ub (N, m).
 
-  * `admm_levels_ltv_stage`     -- tests/mpc_ltv_ref.py: admm_levels_ltv restated with per-stage weights in the tables and per-stage boxes in
-                                   the clip, the x0 test and the support term of the certificate.  Same options and returned namespace.
-  * `solve_reference_ltv_stage` -- the condensed SciPy trust-constr solve with per-stage weights and bounds.
+  * `admm_levels_ltv_stage`     -- the NumPy restatement of the whole solve, an adapter of the one body of every family
+                                   (oracle.mpc_oracle.admm_levels_stage, which takes this form) with every component hard: per-stage
+                                   weights in the tables and per-stage boxes in the clip, the x0 test and the support term of the
+                                   certificate.  Same options and returned namespace as tests/mpc_ltv_ref.py: admm_levels_ltv.
+  * `solve_reference_ltv_stage` -- the condensed SciPy trust-constr solve with per-stage weights and bounds, an adapter likewise.
   * the named cases of tests/test_mpc_ltv_stage.py (their decisions and their non-vacuity are checked there, without a GPU) and
     tests/test_mpc_ltv_stage_gpu.py, with `reference`, `run_steps` and the comparison rule of tests/mpc_ltv_ref.py.
+  * the case glue (`make_problem`, `reference_steps`, `scipy_case`, `variant_case`) takes the per-problem penalty weights `soft` of
+    tests/mpc_ltv_soft_ref.py, whose cases are these with weights: [(l1, l2)] per problem, each (n + m,) in the stacked layout [x ; u].
 """
 from __future__ import annotations
 
@@ -17,225 +21,27 @@ import functools
 from types import SimpleNamespace
 
 import numpy as np
-import scipy.optimize as spo
 
-from oracle.mpc_oracle import CHECK_EVERY
+from oracle.mpc_oracle import admm_levels_stage, cost_stage, linear_term_stage, solve_reference_stage, stage_form  # noqa: F401
 from tests import mpc_iterates_cases as mc
 from tests import mpc_ltv_ref as lr
 
 ALL_SIX = ("Q", "R", "x_lb", "x_ub", "u_lb", "u_ub")
-
-
-def stage_form(Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub):
-    """one set of weights and bounds as constant rows: (Qs (N,n,n), Rs (N,m,m), x_lb (N+1,n), x_ub, u_lb (N,m), u_ub)"""
-    Qs = np.stack([Q] * (N - 1) + [Qf])
-    rows = lambda v, r: np.tile(np.asarray(v, dtype=np.float64), (r, 1))
-    return Qs, np.stack([R] * N), rows(x_lb, N + 1), rows(x_ub, N + 1), rows(u_lb, N), rows(u_ub, N)
-
-
-def linear_term_stage(Qs, Rs, N, xRef, uRef):
-    """g in the kernels' stage layout: gx[k] = -(Qs_k + Qs_k') xr_{k+1}, gu[k] = -(Rs_k + Rs_k') ur_k"""
-    gx = np.stack([-(Qs[k] + Qs[k].T) @ xRef[k + 1] for k in range(N)])
-    gu = np.stack([-(Rs[k] + Rs[k].T) @ uRef[k] for k in range(N)])
-    return gx, gu
-
-
-def cost_stage(Qs, Rs, x, u, xRef, uRef):
-    dx, du = x - xRef, u - uRef
-    return sum(dx[k + 1] @ Qs[k] @ dx[k + 1] + du[k] @ Rs[k] @ du[k] for k in range(u.shape[0]))
+SOFT = ("x_soft_l1", "x_soft_l2", "u_soft_l1", "u_soft_l2")     # the constructor's names of (l1, l2) of the states, of the inputs
 
 
 def admm_levels_ltv_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, eps_rel=1e-5, max_iter=10000,
                           eps_prim_inf=1e-4, alpha=1.6, n_levels=7, rho_step=5.0, g=None, warm=None, shift=False, guard=True):
-    """tests/mpc_ltv_ref.py: admm_levels_ltv (see there for the order of an iteration and the returned namespace) with the data in stage
-    form.  The differences, as the kernels spell them:
-        tables:      P_N = 2 Qs_{N-1} + rho I;  Suu_k = 2 Rs_k + rho I + B_k' P B_k;  the value update leaving stage k >= 1 adds
-                     2 Qs_{k-1} + rho I (the one leaving stage 0 is read by nothing)
-        x0 test:     against row 0 of the state box
-        projection:  [x_{k+1} ; u_k] into [x_lb[k+1] ; u_lb[k]], [x_ub[k+1] ; u_ub[k]]
-        certificate: the support term with the stage's own bounds"""
-    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else np.asarray(c, dtype=np.float64)
-    assert A.shape == (N, n, n) and B.shape == (N, n, m) and c.shape == (N, n)
-    assert Qs.shape == (N, n, n) and Rs.shape == (N, m, m)
-    assert x_lb.shape == x_ub.shape == (N + 1, n) and u_lb.shape == u_ub.shape == (N, m)
-    xl, xu = x_lb[1:], x_ub[1:]
-    level0 = n_levels // 2
-    rho0 = float(rho)
-    tabs = {}
-
-    def tables(l):
-        if l not in tabs:
-            r_ = rho0 * rho_step ** (l - level0)
-            P = 2 * Qs[N - 1] + r_ * np.eye(n)
-            K, Mi, D = [None] * N, [None] * N, [None] * N
-            for k in range(N - 1, -1, -1):
-                D[k] = P @ c[k]
-                Suu = (2 * Rs[k] + r_ * np.eye(m)) + B[k].T @ P @ B[k]
-                Sux = B[k].T @ P @ A[k]
-                Mi[k] = np.linalg.inv(Suu)
-                K[k] = Mi[k] @ Sux
-                P = (2 * Qs[max(k - 1, 0)] + r_ * np.eye(n)) + A[k].T @ P @ A[k] - Sux.T @ K[k]
-            tabs[l] = (r_, K, Mi, D)
-        return tabs[l]
-
-    lvl = level0
-    yx, yu, lx, lu = np.zeros((N, n)), np.zeros((N, m)), np.zeros((N, n)), np.zeros((N, m))
-    if warm is not None:
-        wy, wl, wlvl = warm
-        if n_levels > 1 and 0 <= int(wlvl) < n_levels:
-            lvl = int(wlvl)
-        ks = [k + 1 if (shift and k + 1 < N) else k for k in range(N)]
-        wy, wl = np.asarray(wy, dtype=np.float64)[ks], np.asarray(wl, dtype=np.float64)[ks]
-        yx, yu, lx, lu = wy[:, :n].copy(), wy[:, n:].copy(), wl[:, :n].copy(), wl[:, n:].copy()
-    if g is None:
-        gx, gu = np.zeros((N, n)), np.zeros((N, m))
-    else:
-        gx, gu = np.asarray(g[0], dtype=np.float64), np.asarray(g[1], dtype=np.float64)
-    gn = max(np.max(np.abs(gx)), np.max(np.abs(gu)))
-    guard_on = bool(guard) and (gn > 0.0 or np.max(np.abs(c)) > 0.0)
-    rho_l, K, Mi, D = tables(lvl)
-    kf = np.zeros((N, m))
-
-    def roll(K, kf):
-        xs, us = [np.asarray(x0, dtype=np.float64)], []
-        for k in range(N):
-            us.append(-K[k] @ xs[-1] - kf[k])
-            xs.append(A[k] @ xs[-1] + B[k] @ us[-1] + c[k])
-        return np.stack(xs), np.stack(us)
-
-    out = SimpleNamespace(moves=[], locked=False, level_margin=np.inf, stop_margin=np.inf, near_margin=np.inf, rp=0.0, rd=0.0)
-    status, it, near_ok = None, 0, False
-    x, u = roll(K, kf)
-    if np.any(x0 < x_lb[0]) or np.any(x0 > x_ub[0]):
-        status = "infeasible"
-    last, rev = 0, 0
-    while status is None and it < max_iter:
-        it += 1
-        chk = (it % CHECK_EVERY) == 0
-        zx, zu = -rho_l * (yx - lx) + gx, -rho_l * (yu - lu) + gu
-        p = zx[N - 1] + D[N - 1]
-        for k in range(N - 1, -1, -1):
-            qu = zu[k] + B[k].T @ p
-            kf[k] = Mi[k] @ qu
-            p = ((zx[k - 1] + D[k - 1]) if k >= 1 else 0.0) + A[k].T @ p - K[k].T @ qu
-        x, u = roll(K, kf)
-        xh, uh = alpha * x[1:] + (1.0 - alpha) * yx, alpha * u + (1.0 - alpha) * yu
-        yxn = np.clip(xh + lx, xl, xu)
-        yun = np.clip(uh + lu, u_lb, u_ub)
-        rp = max(np.max(np.abs(x[1:] - yxn)), np.max(np.abs(u - yun)))
-        rx, ru = xh - yxn, uh - yun
-        nrd = max(np.max(np.abs(yxn - yx)), np.max(np.abs(yun - yu)))
-        rd = rho_l * nrd
-        lx, lu = lx + rx, lu + ru
-        yx, yu = yxn, yun
-        nwy = max(np.max(np.abs(x[1:])), np.max(np.abs(u)), np.max(np.abs(yx)), np.max(np.abs(yu)))
-        nl = max(np.max(np.abs(lx)), np.max(np.abs(lu)))
-        ep = eps_abs + eps_rel * nwy
-        ed = eps_abs + eps_rel * rho_l * nl
-        if gn > rho_l * nl:
-            ed = eps_abs + eps_rel * gn
-        out.rp, out.rd = rp, rd
-        near_ok = bool(rp <= 10.0 * ep and rd <= 10.0 * ed)
-        if rp == rp:
-            worst = max(rp / ep, rd / ed)
-            out.stop_margin = min(out.stop_margin, abs(worst - 1.0))
-            out.near_margin = abs(worst / 10.0 - 1.0)
-        if rp <= ep and rd <= ed:
-            status = "optimal"
-            break
-        if not (rp == rp):
-            break
-        if not chk:
-            continue
-        if n_levels > 1 and it < max_iter:
-            tiny = 1e-300
-            rpn = rp / max(nwy, tiny)
-            rdn = rd / max(rho_l * nl, tiny)
-            want = np.sqrt(rpn / max(rdn, tiny))
-            dl = 0
-            if want == want and want > 0.0:
-                t = np.log(want) / np.log(rho_step)
-                dl = int(np.rint(t))
-                out.level_margin = min(out.level_margin, abs(abs(t - np.floor(t)) - 0.5))
-            new = min(max(lvl + dl, 0), n_levels - 1)
-            if guard_on:
-                mv = new - lvl
-                if out.locked:
-                    new = lvl
-                elif mv != 0 and last != 0 and ((mv > 0) != (last > 0)):
-                    rev += 1
-                    if rev >= 3:
-                        out.locked = True
-                        new = lvl
-                else:
-                    rev = 0
-                last = new - lvl
-            if new != lvl:
-                out.moves.append((it, lvl, new))
-                r_new, K, Mi, D = tables(new)
-                sc = rho_l / r_new
-                lx, lu = lx * sc, lu * sc
-                rho_l, lvl = r_new, new
-        s = rx[N - 1].copy()
-        gmax, vc = 0.0, 0.0
-        for k in range(N - 1, -1, -1):
-            vc += s @ c[k]
-            gmax = max(gmax, np.max(np.abs(ru[k] + B[k].T @ s)))
-            s = (rx[k - 1] if k >= 1 else 0.0) + A[k].T @ s
-        sup = 0.0
-        for r_, lo_, hi_ in ((rx, xl, xu), (ru, u_lb, u_ub)):
-            pos, neg = r_ > 0, r_ < 0
-            sup += np.sum(r_[pos] * hi_[pos]) + np.sum(r_[neg] * lo_[neg])
-        dn = max(np.max(np.abs(rx)), np.max(np.abs(ru)))
-        if gmax <= eps_prim_inf * dn and (s @ x0 + vc - sup) > eps_prim_inf * dn:
-            status = "infeasible"
-    if status is None:
-        status = "optimal_inaccurate" if near_ok else "user_limit"
-    out.x, out.u, out.status, out.iters = x, u, status, it
-    out.y, out.lam, out.level, out.rho_final = np.hstack([yx, yu]), np.hstack([lx, lu]), lvl, rho_l
-    return out
+    """oracle.mpc_oracle.admm_levels_stage (see there for the options, the order of an iteration and the returned namespace) with every
+    component hard"""
+    return admm_levels_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, None, None, rho, eps_abs, eps_rel, max_iter, eps_prim_inf,
+                             alpha, n_levels, rho_step, g, warm, shift, guard)
 
 
 def solve_reference_ltv_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, xRef=None, uRef=None):
-    """Independent reference: tests/mpc_ltv_ref.py: solve_reference_ltv with the stage's own weights in the condensed cost and the
-    stage's own bounds as the linear constraints on the states (rows with a finite side only) and the bounds on the inputs.  x0 is not
-    tested against row 0 here.  Returns (x, u, cost)."""
-    n, m = B.shape[-2:]
-    c = np.zeros((N, n)) if c is None else c
-    xRef = np.zeros((N + 1, n)) if xRef is None else xRef
-    uRef = np.zeros((N, m)) if uRef is None else uRef
-    phi = [np.asarray(x0, dtype=np.float64)]
-    Gam = [np.zeros((n, N * m))]
-    for k in range(N):
-        phi.append(A[k] @ phi[-1] + c[k])
-        G = A[k] @ Gam[-1]
-        G[:, k * m:(k + 1) * m] += B[k]
-        Gam.append(G)
-    H, gv = np.zeros((N * m, N * m)), np.zeros(N * m)
-    for k in range(1, N + 1):
-        Ws = 0.5 * (Qs[k - 1] + Qs[k - 1].T)
-        H += Gam[k].T @ Ws @ Gam[k]
-        gv += Gam[k].T @ Ws @ (phi[k] - xRef[k])
-    for k in range(N):
-        Rk = 0.5 * (Rs[k] + Rs[k].T)
-        H[k * m:(k + 1) * m, k * m:(k + 1) * m] += Rk
-        gv[k * m:(k + 1) * m] -= Rk @ uRef[k]
-    rows, lo, hi = [], [], []
-    for k in range(1, N + 1):
-        for i in range(n):
-            if np.isfinite(x_lb[k, i]) or np.isfinite(x_ub[k, i]):
-                rows.append(Gam[k][i])
-                lo.append(x_lb[k, i] - phi[k][i])
-                hi.append(x_ub[k, i] - phi[k][i])
-    cons = [spo.LinearConstraint(np.array(rows), np.array(lo), np.array(hi))] if rows else []
-    res = spo.minimize(lambda v: v @ H @ v + 2 * gv @ v, np.zeros(N * m), jac=lambda v: 2 * (H @ v + gv), hess=lambda v: 2 * H,
-                       method="trust-constr", bounds=spo.Bounds(u_lb.reshape(-1), u_ub.reshape(-1)), constraints=cons,
-                       options=dict(gtol=1e-12, xtol=1e-14, barrier_tol=1e-14, maxiter=5000))
-    u = res.x.reshape(N, m)
-    x = lr.rollout_ltv(A, B, c, x0, u)
-    return x, u, cost_stage(Qs, Rs, x, u, xRef, uRef)
+    """Independent reference: oracle.mpc_oracle.solve_reference_stage with every component hard, the QP in u alone.  Returns
+    (x, u, cost)."""
+    return solve_reference_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, xRef=xRef, uRef=uRef)
 
 
 # ---- cases -------------------------------------------------------------------------------------------------------------------------------
@@ -389,21 +195,29 @@ def scipy_instances(name):
     return (0,) if name == "waypoint_weights" else (0, 1)[:len(build(name).x0)]
 
 
-def make_problem(mpcUtils, c, stage_varying=None):
-    """the ltvMpc object of a case (host side only): Q as the constructor takes it, (N + 1, n, n) with a row 0 that nothing reads"""
+def weights_of(c, soft=None):
+    """per problem (l1, l2): `soft`, else the case's own (a case of tests/mpc_ltv_soft_ref.py), else all hard (None, None)"""
+    return soft or getattr(c, "soft", None) or [(None, None)] * len(c.inst)
+
+
+def make_problem(mpcUtils, c, stage_varying=None, soft=None):
+    """the ltvMpc object of a case (host side only): Q as the constructor takes it, (N + 1, n, n) with a row 0 that nothing reads.
+    soft: weights per problem; None: the object of the stage entry, every component hard, whatever the case's own weights"""
     sv = c.stage_varying if stage_varying is None else stage_varying
 
-    def args(d):
+    def args(d, w):
         A, B, ck, Qs, Rs, xl, xu, ul, uu = d
-        return A, B, ck, np.concatenate([Qs[:1], Qs]), Rs, xl, xu, ul, uu
+        n = B.shape[-2]
+        return (A, B, np.concatenate([Qs[:1], Qs]), Rs, xl, xu, ul, uu, ck) + (() if w is None else (w[0][:n], w[1][:n], w[0][n:], w[1][n:]))
     if c.shared:
-        A, B, ck, Q, R, xl, xu, ul, uu = args(c.inst[0])
+        A, B, Q, R, xl, xu, ul, uu, ck, *w = args(c.inst[0], soft and soft[0])
     else:
-        A, B, ck, Q, R, xl, xu, ul, uu = (np.stack(v) for v in zip(*(args(d) for d in c.inst)))
-    return mpcUtils.ltvMpc(A, B, Q, R, c.N, xl, xu, ul, uu, c=ck, stage_varying=sv)
+        A, B, Q, R, xl, xu, ul, uu, ck, *w = (np.stack(v) for v in zip(*(args(d, soft and soft[p]) for p, d in enumerate(c.inst))))
+    return mpcUtils.ltvMpc(A, B, Q, R, c.N, xl, xu, ul, uu, c=ck, stage_varying=sv, **dict(zip(SOFT, w)))
 
 
 def case_rho(mpcUtils, c):
+    """the penalty per instance: the case's own or the constructor's default, which the penalty weights do not enter"""
     nb = len(c.x0)
     if c.rho is not None:
         return np.full(nb, float(c.rho))
@@ -411,8 +225,9 @@ def case_rho(mpcUtils, c):
     return np.array([rho[problem_of(c, b)] for b in range(nb)])
 
 
-def reference_steps(c, rho):
-    """[step][instance] -> result of admm_levels_ltv_stage, each fed its own previous final state"""
+def reference_steps(c, rho, soft=None):
+    """[step][instance] -> result of admm_levels_stage, each fed its own previous final state"""
+    soft = weights_of(c, soft)
     out = []
     for s, step in enumerate(c.steps):
         row = []
@@ -422,19 +237,22 @@ def reference_steps(c, rho):
             x0 = prev.x[1] if step["x0"] == "x1" else (prev.x0 if step["x0"] == "same" else c.x0[b])
             warm = (prev.y, prev.lam, prev.level) if (step["warm"] and prev.status == "optimal") else None
             g = None if c.xRef is None else linear_term_stage(Qs, Rs, c.N, c.xRef[b], c.uRef[b])
-            r = admm_levels_ltv_stage(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, x0, rho=float(rho[b]), g=g, warm=warm,
-                                      shift=step["warm"] == "shift", **step["kw"])
+            r = admm_levels_stage(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, x0, *soft[problem_of(c, b)], rho=float(rho[b]), g=g, warm=warm,
+                                  shift=step["warm"] == "shift", **step["kw"])
             r.x0 = x0
             row.append(r)
         out.append(row)
     return out
 
 
+def reference_case(c):
+    from zopt_amd import mpcUtils
+    return reference_steps(c, case_rho(mpcUtils, c))
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name):
-    from zopt_amd import mpcUtils
-    c = build(name)
-    return reference_steps(c, case_rho(mpcUtils, c))
+    return reference_case(build(name))
 
 
 def envelope(xl, xu, ul, uu):
@@ -446,27 +264,45 @@ def envelope(xl, xu, ul, uu):
     return exl, exu, np.tile(ul.min(axis=0), (N, 1)), np.tile(uu.max(axis=0), (N, 1))
 
 
-@functools.lru_cache(maxsize=None)
-def scipy_solution(name, b=0):
-    """(x, u) of the SciPy solve of instance b"""
-    c = build(name)
+def scipy_case(c, b=0, soft=None):
+    """(x, u) of the SciPy solve of instance b of a case: the slack QP where a component is soft"""
     xr, ur = (None, None) if c.xRef is None else (c.xRef[b], c.uRef[b])
-    x, u, _ = solve_reference_ltv_stage(*c.inst[problem_of(c, b)][:5], c.N, *c.inst[problem_of(c, b)][5:], c.x0[b], xRef=xr, uRef=ur)
+    p = problem_of(c, b)
+    x, u, _ = solve_reference_stage(*c.inst[p][:5], c.N, *c.inst[p][5:], c.x0[b], *weights_of(c, soft)[p], xRef=xr, uRef=ur)
     return x, u
 
 
-def variant_solution(name, variant, b=0):
-    """the restatement's solution of instance b with every bound replaced by its envelope ("envelope") or every weight by its mean over
-    the stages ("mean"): what a case's solution must differ from for its stage data to matter"""
+@functools.lru_cache(maxsize=None)
+def scipy_solution(name, b=0):
+    return scipy_case(build(name), b)
+
+
+def variant_case(c, variant, b=0, soft=None, **kw):
+    """the restatement's result for instance b of a case with one thing replaced -- what a case's solution must differ from for its data
+    to matter:  "envelope": every bound by its envelope over the stages;  "mean": every weight by its mean over the stages;  "hard": every
+    penalty weight by a hard component (the status may then be "infeasible");  "free": the bounds of the soft components by none.
+    kw: options other than those of tests/mpc_ltv_ref.py: _kw"""
     from zopt_amd import mpcUtils
-    c = build(name)
-    A, B, ck, Qs, Rs, xl, xu, ul, uu = c.inst[problem_of(c, b)]
+    p = problem_of(c, b)
+    A, B, ck, Qs, Rs, xl, xu, ul, uu = c.inst[p]
+    l1, l2 = weights_of(c, soft)[p]
     if variant == "envelope":
         xl, xu, ul, uu = envelope(xl, xu, ul, uu)
-    else:
+    elif variant == "mean":
         Qs, Rs = np.tile(Qs.mean(axis=0), (c.N, 1, 1)), np.tile(Rs.mean(axis=0), (c.N, 1, 1))
+    elif variant == "hard":
+        l1 = l2 = None
+    else:
+        n = B.shape[-2]
+        fx, fu = np.isfinite(l1[:n]), np.isfinite(l1[n:])
+        xl, xu, ul, uu = np.where(fx, -np.inf, xl), np.where(fx, np.inf, xu), np.where(fu, -np.inf, ul), np.where(fu, np.inf, uu)
     g = None if c.xRef is None else linear_term_stage(Qs, Rs, c.N, c.xRef[b], c.uRef[b])
-    r = admm_levels_ltv_stage(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, c.x0[b], rho=float(case_rho(mpcUtils, c)[b]), g=g, **lr._kw())
+    return admm_levels_stage(A, B, ck, Qs, Rs, c.N, xl, xu, ul, uu, c.x0[b], l1, l2, rho=float(case_rho(mpcUtils, c)[b]), g=g, **lr._kw(**kw))
+
+
+def variant_solution(name, variant, b=0):
+    """(x, u) of `variant_case` "envelope" or "mean", which has a solution"""
+    r = variant_case(build(name), variant, b)
     assert r.status == "optimal", (name, variant, r.status)
     return r.x, r.u
 

@@ -28,7 +28,8 @@ def _same(a, b):
 @pytest.mark.parametrize("n,m,N", [(4, 2, 4), (12, 4, 7), (2, 1, 5)])
 def test_constant_dynamics_and_zero_offset_are_the_time_invariant_solve(n, m, N):
     """constant A_k, B_k and c = 0: admm_levels_ltv is admm_levels -- status, iterations, level moves, and x, u, y, lam to 1e-12; cold, then
-    a warm and a shifted solve each fed its own previous state"""
+    a warm and a shifted solve each fed its own previous state.  (Both are adapters of oracle.mpc_oracle.admm_levels_stage now: this
+    holds the tiling of A, B and c = None to the stage-varying data.)"""
     (A, B, Q, R, Qf, xl, xu, ul, uu), x0 = _lti(n, m, N)
     Ak, Bk = np.tile(A, (N, 1, 1)), np.tile(B, (N, 1, 1))
     rho = tr.default_rho(Q, R)

@@ -25,7 +25,8 @@ def _equal(a, b):
 def test_all_hard_weights_are_the_restatement_it_extends(n, m, N):
     """every l1 = +inf: admm_levels_ltv_soft returns exactly what admm_levels_ltv_stage returns -- x, u, y, lam, iterations, status with
     == -- cold (loose), then a warm and a shifted solve each fed its own previous state, and an instance with a reference.  (The guard is
-    on in both: the recipe has offsets.)"""
+    on in both: the recipe has offsets.)  Both are adapters of oracle.mpc_oracle.admm_levels_stage now: this holds l1 = None to l1 = +inf.
+    (test_the_proximal_map_is_the_clip_on_a_hard_component_bit_for_bit holds its `prox` to the clip.)"""
     (A, B, c, Q, R, Qf, xl, xu, ul, uu), x0 = lr.recipe(n, m, N, 2)
     st = sr.stage_form(Q, R, Qf, N, xl, xu, ul, uu)
     hard = np.full(n + m, INF)

@@ -17,7 +17,8 @@ from zopt_amd import mpcUtils
 def test_constant_rows_are_the_restatement_it_extends(n, m, N):
     """constant rows: admm_levels_ltv_stage is admm_levels_ltv on the recipe's stage-varying dynamics with offsets -- status, iterations,
     level moves, and x, u, y, lam to 1e-12; cold (loose), then a warm and a shifted solve each fed its own previous state.  Instance 1
-    runs with a reference (the linear term by stage is the linear term)."""
+    runs with a reference (the linear term by stage is the linear term).  (Both are adapters of oracle.mpc_oracle.admm_levels_stage now:
+    this holds `stage_form` and `linear_term_stage` to the one set of weights and bounds.)"""
     (A, B, c, Q, R, Qf, xl, xu, ul, uu), x0 = lr.recipe(n, m, N, 2)
     st = sr.stage_form(Q, R, Qf, N, xl, xu, ul, uu)
     old = lambda x, **kw: lr.admm_levels_ltv(A, B, c, Q, R, Qf, N, xl, xu, ul, uu, x, **kw)
