@@ -351,6 +351,10 @@ int zm_condition_dynamics_f64(const double* f_xx, const double* f_ux, const doub
 
 /* Riccati tables of the ADMM w-update for penalty rho:  K (N,m,n), Minv (N,m,m)   [all device pointers]
  * in : A (n,n) B (n,m) Q (n,n) R (m,m) Qf (n,n); n <= 24, m <= 8.
+ * The weights Q, R, Qf (and Qs, Rs of the stage-varying entry points below) must be SYMMETRIC: the setup forms the Hessians as 2 W, the
+ * tracking kernels the linear term with W + W', and the recursion stores its value matrix symmetrised -- P_N = 2 Qf + rho I,
+ * P <- sym((2 Q + rho I) + A'PA - (B'PA)' K), sym(X) = (X + X') / 2 -- which removes the antisymmetric rounding error that an
+ * open-loop-unstable A would otherwise amplify along the horizon.  (The Python mirror passes the symmetric part of what it is given.)
  * Shapes of the solve entry points: (n, m) in {(12,4), (8,4), (4,2), (4,1), (2,2), (2,1), (1,1)} (16 lanes per instance, adaptive penalty
  * levels; the Python mirror embeds any smaller shape with inert padding) and (24, 8) (one lane per instance, the penalty of `level0`
  * only; registers + scratch: a coverage path for problems beyond the 16-index tile). */
@@ -450,7 +454,7 @@ int zm_mpc_solve_relaxed_f64(const double* A, const double* B, const double* K, 
 /* Per-problem data (reference: zopt/mpcUtils.py:14-81, class lqrMpc, one problem per object there): P problems of the same
  * (N, n, m), each with its own A, B, Q, R, Qf, bounds and penalty, set up and solved in one launch each.
  * zm_mpc_setup_batched_f64: the tables of zm_mpc_setup_f64 for every problem p and level l, bit for bit those of P * L calls of it
- *     (one workgroup per (p, l), the same arithmetic).
+ *     (one workgroup per (p, l), the same arithmetic).  Symmetric weights, as there.
  *     in : A (P,n,n) B (P,n,m) Q (P,n,n) R (P,m,m) Qf (P,n,n) rho (P,L) -- the penalty of each (problem, level)   [device]
  *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m), problem-major (one problem's levels are contiguous)                    [device] */
 int zm_mpc_setup_batched_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
@@ -529,7 +533,7 @@ int zm_mpc_closed_loop_f64(const double* A, const double* B, const double* Q, co
  * zm_mpc_setup_ltv_f64: the Riccati recursion of zm_mpc_setup_batched_f64 with the stage's own A_k, B_k (constant A_k, B_k give its
  *     tables bit for bit), one workgroup per (problem, level), one launch.  It also emits D_k = P_{k+1} c_k, the offset's share of the
  *     costate (P_{k+1}: the value matrix the recursion holds on entering stage k, P_N = 2 Qf + rho I), and ABt, the columns of
- *     [A_k | B_k] as contiguous rows, which the backward sweep of the solve reads per lane.
+ *     [A_k | B_k] as contiguous rows, which the backward sweep of the solve reads per lane.  Symmetric weights, as zm_mpc_setup_f64.
  *     in : A (P,N,n,n)  B (P,N,n,m)  c (P,N,n) or NULL (zero)  Q (P,n,n)  R (P,m,m)  Qf (P,n,n)  rho (P,L)   [device]
  *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m)  D (P,L,N,n)  ABt (P,N,n+m,n): row i < n is column i of A_k, row n + j column j of B_k [device]
  *     n <= 12 and m <= 4 (ZM_EUNSUPPORTED beyond: there is no lane-per-instance kernel for stage-varying dynamics).
@@ -563,7 +567,7 @@ int zm_mpc_solve_ltv_f64(const double* A, const double* B, const double* c, cons
  * discounted costs.  ADMM, termination, certificate, status codes, workspace and outputs are zm_mpc_solve_ltv_f64's.
  * zm_mpc_setup_ltv_stage_f64 replaces zm_mpc_setup_ltv_f64:  P_N = 2 Qs_{N-1} + rho I, stage k uses Rs_k, the value update that leaves
  *     stage k >= 1 uses Qs_{k-1} (the one that leaves stage 0 is read by nothing).  The same products in the same order: with constant
- *     rows (Qs_k = Q for k < N-1, Qs_{N-1} = Qf, Rs_k = R) the tables are zm_mpc_setup_ltv_f64's bit for bit.
+ *     rows (Qs_k = Q for k < N-1, Qs_{N-1} = Qf, Rs_k = R) the tables are zm_mpc_setup_ltv_f64's bit for bit.  Every Qs_k, Rs_k symmetric.
  *     in : A (P,N,n,n)  B (P,N,n,m)  c (P,N,n) or NULL (zero)  Qs (P,N,n,n)  Rs (P,N,m,m)  rho (P,L)   [device]
  *     out: K (P,L,N,m,n)  Minv (P,L,N,m,m)  D (P,L,N,n)  ABt (P,N,n+m,n), as zm_mpc_setup_ltv_f64 writes them   [device]
  *     ZM_EINVAL for a null pointer or a bad size, ZM_EUNSUPPORTED beyond n <= 12, m <= 4; both before any launch.

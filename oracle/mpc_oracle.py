@@ -8,11 +8,14 @@ that solver is not part of the reference tree and not installed here, and the re
                             mpcUtils.py:48-59 (dynamics, bounds, and the reduced-gradient / complementarity
                             condition in the condensed variables);
   * `solve_reference`    -- an independent high-accuracy solve (condensed QP, SciPy trust-constr) for small problems;
+  * `riccati_tables`     -- the NumPy restatement of the setup kernels' tables K, Minv, D (one problem, one penalty, stage form), which
+                            `admm` and `admm_levels_stage` use and tests/test_mpc_tables*.py hold to a long-double reference;
   * `admm`               -- a NumPy restatement of the build's own ADMM (zopt_amd/csrc/mpc.hip) for iterate-level checks;
   * `admm_levels_stage`  -- the restatement of the WHOLE solve, once for every MPC family (stage-varying dynamics, weights and boxes,
                             soft components): adaptive penalty levels, warm and shifted starts, the linear term and the cycle guard, the
                             stored state.  `admm_levels` (zopt_amd/csrc/mpc_solve_wave_body.h, lqrMpc's data) and the admm_levels_ltv*
                             of tests/mpc_ltv*_ref.py are its adapters;
+  * `kkt_residuals_stage` -- `kkt_residuals` in the data of `admm_levels_stage` (stage-varying dynamics with offsets, weights and boxes);
   * `solve_reference_stage` -- the independent condensed solve of the LTV families in the same data, slacks for the soft components.
 """
 from __future__ import annotations
@@ -123,6 +126,33 @@ def kkt_residuals(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, x, u, act_tol=1
     return dict(dyn=dyn, bound=viol, stat=stat / max(1.0, np.linalg.norm(grad)))
 
 
+def riccati_tables(A, B, c, Qs, Rs, rho):
+    """The tables of the setup kernels (zopt_amd/csrc/mpc_setup_body.h and its two stage-varying copies in mpc.hip) for ONE problem at ONE
+    penalty, in the stage form zm_mpc_setup_ltv_stage_f64 documents: A (N, n, n), B (N, n, m), c (N, n) or None (zeros), Qs (N, n, n) with
+    Qs[k] the weight of x_{k+1} (row N - 1 is terminal), Rs (N, m, m); the weights are symmetric.
+
+        P_N = 2 Qs_{N-1} + rho I;   k = N-1 .. 0:   D_k = P_{k+1} c_k;   Suu_k = 2 Rs_k + rho I + B_k' P B_k;   Minv_k = Suu_k^-1;
+        K_k = Minv_k B_k' P A_k;    P <- sym((2 Qs_{k-1} + rho I) + A_k' P A_k - (B_k' P A_k)' K_k),   sym(X) = (X + X') / 2
+
+    (the update that leaves stage 0 is read by nothing).  The value matrix is symmetrised whenever it is stored: the update's antisymmetric
+    rounding error is propagated through A . A_cl rather than A_cl . A_cl, so on an open-loop-unstable plant it grows along the horizon
+    unless it is removed at every stage.  Returns (K (N, m, n), Minv (N, m, m), D (N, n))."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    N, n, m = B.shape
+    c = np.zeros((N, n)) if c is None else np.asarray(c, dtype=np.float64)
+    P = 2 * Qs[N - 1] + rho * np.eye(n)
+    K, Mi, D = np.empty((N, m, n)), np.empty((N, m, m)), np.empty((N, n))
+    for k in range(N - 1, -1, -1):
+        D[k] = P @ c[k]
+        Suu = (2 * Rs[k] + rho * np.eye(m)) + B[k].T @ P @ B[k]
+        Sux = B[k].T @ P @ A[k]
+        Mi[k] = np.linalg.inv(Suu)
+        K[k] = Mi[k] @ Sux
+        P = (2 * Qs[max(k - 1, 0)] + rho * np.eye(n)) + A[k].T @ P @ A[k] - Sux.T @ K[k]
+        P = 0.5 * (P + P.T)
+    return K, Mi, D
+
+
 def admm(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, eps_rel=1e-5, max_iter=10000,
          eps_prim_inf=1e-4, alpha=1.0):
     """NumPy restatement of zopt_amd/csrc/mpc.hip for ONE instance (fixed penalty).  `alpha` is OSQP's over-relaxation: the
@@ -130,15 +160,7 @@ def admm(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, e
     n, m = B.shape
     if np.any(x0 < x_lb) or np.any(x0 > x_ub):
         return rollout(A, B, x0, np.zeros((N, m))), np.zeros((N, m)), "infeasible", 0
-    Hx, Hu = 2 * Q + rho * np.eye(n), 2 * R + rho * np.eye(m)
-    P = 2 * Qf + rho * np.eye(n)
-    K, Mi = [None] * N, [None] * N
-    for k in range(N - 1, -1, -1):
-        Suu = Hu + B.T @ P @ B
-        Sux = B.T @ P @ A
-        Mi[k] = np.linalg.inv(Suu)
-        K[k] = Mi[k] @ Sux
-        P = Hx + A.T @ P @ A - Sux.T @ K[k]
+    K, Mi, _ = riccati_tables(np.tile(A, (N, 1, 1)), np.tile(B, (N, 1, 1)), None, np.stack([Q] * (N - 1) + [Qf]), np.stack([R] * N), rho)
     yx, yu = np.zeros((N, n)), np.zeros((N, m))      # yx[k] is the copy of x_{k+1}
     lx, lu = np.zeros((N, n)), np.zeros((N, m))
     status, it = "user_limit", 0
@@ -298,19 +320,10 @@ def admm_levels_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, l1=None, l
     rho0 = float(rho)
     tabs = {}
 
-    def tables(l):   # K_k, Suu_k^-1, D_k at the level's penalty (mpc_setup_body.h)
+    def tables(l):   # K_k, Suu_k^-1, D_k at the level's penalty (`riccati_tables`)
         if l not in tabs:
             r_ = rho0 * rho_step ** (l - level0)
-            P = 2 * Qs[N - 1] + r_ * np.eye(n)
-            K, Mi, D = [None] * N, [None] * N, [None] * N
-            for k in range(N - 1, -1, -1):
-                D[k] = P @ c[k]
-                Suu = (2 * Rs[k] + r_ * np.eye(m)) + B[k].T @ P @ B[k]
-                Sux = B[k].T @ P @ A[k]
-                Mi[k] = np.linalg.inv(Suu)
-                K[k] = Mi[k] @ Sux
-                P = (2 * Qs[max(k - 1, 0)] + r_ * np.eye(n)) + A[k].T @ P @ A[k] - Sux.T @ K[k]
-            tabs[l] = (r_, K, Mi, D)
+            tabs[l] = (r_, *riccati_tables(A, B, c, Qs, Rs, r_))
         return tabs[l]
 
     lvl = level0
@@ -430,6 +443,45 @@ def admm_levels_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, l1=None, l
     out.x, out.u, out.status, out.iters = x, u, status, it
     out.y, out.lam, out.level, out.rho_final = np.hstack([yx, yu]), np.hstack([lx, lu]), lvl, rho_l
     return out
+
+
+def kkt_residuals_stage(A, B, c, Qs, Rs, N, x_lb, x_ub, u_lb, u_ub, x0, x, u, act_tol=1e-6):
+    """`kkt_residuals` for the data of `admm_levels_stage` (hard bounds, no reference): dict(dyn, bound, stat) of a candidate (x (N+1, n),
+    u (N, m)) -- the largest defect of x+ = A_k x + B_k u + c_k, the largest violation of the stage's own bounds (row 0 of the state box
+    is not tested), and the distance of the reduced gradient from the cone of the active constraints' normals, relative to max(1, |grad|).
+    The gradient by the adjoint sweep lam_N = 2 Qs_{N-1} x_N, grad_k = 2 Rs_k u_k + B_k' lam_{k+1}, lam_k = 2 Qs_{k-1} x_k + A_k' lam_{k+1}."""
+    n, m = B.shape[-2:]
+    c = np.zeros((N, n)) if c is None else c
+    dyn = max(np.max(np.abs(x[0] - x0)), max(np.max(np.abs(x[k + 1] - (A[k] @ x[k] + B[k] @ u[k] + c[k]))) for k in range(N)))
+    viol = float(np.max(violation(x, u, x_lb, x_ub, u_lb, u_ub)))
+    Gam = [np.zeros((n, N * m))]
+    for k in range(N):
+        G = A[k] @ Gam[-1]
+        G[:, k * m:(k + 1) * m] += B[k]
+        Gam.append(G)
+    grad = np.zeros((N, m))
+    lam = (Qs[N - 1] + Qs[N - 1].T) @ x[N]
+    for k in range(N - 1, -1, -1):
+        grad[k] = (Rs[k] + Rs[k].T) @ u[k] + B[k].T @ lam
+        lam = ((Qs[k - 1] + Qs[k - 1].T) @ x[k] if k >= 1 else 0.0) + A[k].T @ lam
+    grad = grad.reshape(-1)
+    normals = []
+    for k in range(N):
+        for j in range(m):
+            e = np.zeros(N * m)
+            e[k * m + j] = 1.0
+            if u[k, j] >= u_ub[k, j] - act_tol:
+                normals.append(e)
+            if u[k, j] <= u_lb[k, j] + act_tol:
+                normals.append(-e)
+    for k in range(1, N + 1):
+        for i in range(n):
+            if x[k, i] >= x_ub[k, i] - act_tol:
+                normals.append(Gam[k][i])
+            if x[k, i] <= x_lb[k, i] + act_tol:
+                normals.append(-Gam[k][i])
+    stat = spo.nnls(np.array(normals).T, -grad)[1] if normals else np.linalg.norm(grad)
+    return dict(dyn=dyn, bound=viol, stat=stat / max(1.0, np.linalg.norm(grad)))
 
 
 def admm_levels(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, rho=1.0, eps_abs=1e-5, eps_rel=1e-5, max_iter=10000, eps_prim_inf=1e-4,

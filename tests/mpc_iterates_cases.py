@@ -130,6 +130,13 @@ def build(name):
         c = _shared(data, N, x0, CHAIN(1e-4, 1e-6))
         c.n_levels, c.lane = 1, True
         return c
+    if kind == "unstable":    # an open-loop-unstable plant (problems.hard_mpc: lti_unstable, spectral radius 1.3), inputs within 0.5, no state
+        n, m, N = shape       # box; x0 = 1.2 randn is small enough to be feasible and large enough for active input bounds
+        from tests import problems
+        A, B, _, Qs, Rs, _ = (X[0] for X in problems.hard_mpc("lti_unstable", n, m, N))
+        inf, u_ub = np.full(n, np.inf), np.full(m, 0.5)
+        x0 = 1.2 * np.random.default_rng(100 * n + N).standard_normal((5, n))
+        return _shared((A[0], B[0], Qs[0], Rs[0], Qs[N - 1], -inf, inf, -u_ub, u_ub), N, x0, COLD(1e-6))
     raise KeyError(name)
 
 
@@ -145,6 +152,7 @@ GROUPS = {
     "tracking": (["track:4,1,8", "trackquad", "trackperproblem"], {"optimal"}),
     "lane": ([f"lane:{n},{m},{N}" for n, m, N in LANE], {"optimal"}),
     "lane_child": ([f"lanechild:{n},{m},{N}" for n, m, N in LANE_CHILD], {"optimal"}),
+    "unstable": (["unstable:12,4,40"], {"optimal"}),
 }
 ALL = [name for names, _ in GROUPS.values() for name in names]
 

@@ -176,6 +176,13 @@ def build(name):
     if kind == "infeasible":
         (d1, x0), (d0, _) = infeasible_data(True), infeasible_data(False)
         return _case([d1, d0], np.stack([x0, x0]), 3, False, rho=2.0)
+    if kind == "ltvunstable":   # every A_k at spectral radius 1.3 (problems.hard_mpc: unstable), B_k, c_k = 0.3 f_k, the weights of stage 0 and
+        n, m, N = shape         # the family's terminal one; inputs within 0.6, no state box; x0 = 0.8 randn is feasible with active bounds
+        from tests import problems
+        A, B, ck, Qs, Rs, _ = (X[0] for X in problems.hard_mpc("unstable", n, m, N))
+        inf, u_ub = np.full(n, np.inf), np.full(m, 0.6)
+        x0 = 0.8 * np.random.default_rng(_seed(n, m, N) + 360).standard_normal((5, n))
+        return _case([(A, B, 0.3 * ck, Qs[0], Rs[0], Qs[N - 1], -inf, inf, -u_ub, u_ub)] * 5, x0, N, True)
     raise KeyError(name)
 
 
@@ -187,6 +194,7 @@ GROUPS = {
     "tracking": ["track:4,1,8", "trackquad"],
     "quadcopter": ["quad"],
     "infeasible": ["infeasible"],
+    "unstable": ["ltvunstable:8,4,30"],
 }
 ALL = [name for names in GROUPS.values() for name in names]
 

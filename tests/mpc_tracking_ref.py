@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import scipy.optimize as spo
 
-from oracle.mpc_oracle import CHECK_EVERY, condense, rollout
+from oracle.mpc_oracle import CHECK_EVERY, condense, riccati_tables, rollout
 
 
 def linear_term(Q, R, Qf, N, xRef, uRef):
@@ -110,15 +110,7 @@ def admm(A, B, Q, R, Qf, N, x_lb, x_ub, u_lb, u_ub, x0, xRef, uRef, rho=1.0, eps
         return rollout(A, B, x0, np.zeros((N, m))), np.zeros((N, m)), "infeasible", 0
     gx, gu = linear_term(Q, R, Qf, N, xRef, uRef)
     gn = max(np.max(np.abs(gx)), np.max(np.abs(gu)))
-    Hx, Hu = 2 * Q + rho * np.eye(n), 2 * R + rho * np.eye(m)
-    P = 2 * Qf + rho * np.eye(n)
-    K, Mi = [None] * N, [None] * N
-    for k in range(N - 1, -1, -1):
-        Suu = Hu + B.T @ P @ B
-        Sux = B.T @ P @ A
-        Mi[k] = np.linalg.inv(Suu)
-        K[k] = Mi[k] @ Sux
-        P = Hx + A.T @ P @ A - Sux.T @ K[k]
+    K, Mi, _ = riccati_tables(np.tile(A, (N, 1, 1)), np.tile(B, (N, 1, 1)), None, np.stack([Q] * (N - 1) + [Qf]), np.stack([R] * N), rho)
     yx, yu = np.zeros((N, n)), np.zeros((N, m))      # yx[k] is the copy of x_{k+1}
     lx, lu = np.zeros((N, n)), np.zeros((N, m))
     status, it = "user_limit", 0

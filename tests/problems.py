@@ -639,3 +639,71 @@ AFFINE_SHAPES = [(12, 4), (8, 4), (5, 3), (20, 6), (48, 16)]
 DDP_SHAPES = {(12, 4): 8, (5, 3): 6, (2, 2): 5, (16, 4): 4, (20, 6): 3}      # (n, m) -> T
 RING_HORIZONS = [1, 2, 3, 4, 7]                                               # around the DMA ring's depth, on `unstable`
 PSD_SIZES = [2, 7, 16, 17, 32, 33, 48, 49, 64]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Hard families for the MPC setup kernels (mpc_setup_body.h and its stage-varying copies in mpc.hip): the Riccati tables K, Minv, D of a
+# problem at its penalty levels.  Every family has Q >= 0, R > 0, symmetric weights and a non-zero offset c; each has ONE hard feature
+# (tests/test_mpc_tables.py asserts that it has it).  Stage form, as zm_mpc_setup_ltv_stage_f64 documents it: Qs[k] weights x_{k+1} (row
+# N - 1 is terminal), Rs[k] weights u_k; the cost's Hessians are 2 Qs, 2 Rs, so Qs = sym(c_xx) / 2 and Rs = sym(c_uu) / 2 of a sweep model.
+MPC_SWEEP_FAMILIES = ("plain", "unstable", "cheap_control", "expensive_control", "illcond_quu", "badly_scaled")
+MPC_LTI_FAMILIES = ("lti_unstable", "lti_marginal")           # constant A, B, Q, R (+ a terminal Qf): what zm_mpc_setup_f64 takes
+MPC_FAMILIES = MPC_SWEEP_FAMILIES + MPC_LTI_FAMILIES + ("stage_weights",)
+MPC_LTI_RADIUS = {"lti_unstable": 1.3, "lti_marginal": 1.05}
+MPC_N_LEVELS, MPC_RHO_STEP = 7, 5.0                             # lqrMpc.N_LEVELS, RHO_STEP
+
+# (n, m, N): the smallest shapes that still show the defect of an unsymmetrised recursion, the horizon edges, the <24, 8> instantiation of
+# the time-invariant kernels (the stage-varying entry points stop at (12, 4)), and a shape that does not fill the <12, 4> template
+MPC_TABLE_SHAPES = [(12, 4, 75), (8, 4, 75), (4, 2, 75), (2, 1, 75), (1, 1, 75), (12, 4, 1), (12, 4, 2), (13, 2, 40), (24, 8, 40), (5, 3, 20)]
+
+
+def _sym(X):
+    return 0.5 * (X + _sT(X))
+
+
+def mpc_penalty(Qs, Rs):
+    """mpcUtils' rule for the penalty of level `n_levels // 2`, per problem: the geometric mean of the mean curvatures of 2 Qs_k and
+    2 Rs_k (each floored at 1e-12), then the median over the stages.  Qs (P, N, n, n), Rs (P, N, m, m) -> (P,)"""
+    tq = np.trace(2 * Qs, axis1=-2, axis2=-1) / Qs.shape[-1]
+    tr = np.trace(2 * Rs, axis1=-2, axis2=-1) / Rs.shape[-1]
+    return np.median(np.sqrt(np.maximum(tq, 1e-12) * np.maximum(tr, 1e-12)), axis=-1)
+
+
+def mpc_levels(rho):
+    """(P,) -> (P, L): the penalty of every level, rho * 5^(l - 3), as the host layer tabulates them"""
+    fac = np.array([MPC_RHO_STEP ** (l - MPC_N_LEVELS // 2) for l in range(MPC_N_LEVELS)])
+    return np.asarray(rho, dtype=np.float64).reshape(-1, 1) * fac[None, :]
+
+
+def hard_mpc(name: str, n: int, m: int, N: int, P: int = 2):
+    """The seeded batch of P problems of the MPC family `name` at (n, m, N) that the CPU property tests and the GPU tests both use:
+    (A (P, N, n, n), B (P, N, n, m), c (P, N, n), Qs (P, N, n, n), Rs (P, N, m, m), rho (P, L)), rho from `mpc_penalty` and `mpc_levels`.
+
+        the MPC_SWEEP_FAMILIES   the model of `hard_sweep` (its generator at the horizon N): A = f_x, B = f_u, c = f, Qs = sym(c_xx) / 2,
+                                 Rs = sym(c_uu) / 2, all stage-varying
+        lti_unstable, _marginal  ONE random A per problem scaled to the spectral radius 1.3 / 1.05, one B, Q, R for every stage and a
+                                 terminal Qf; c varies by stage
+        stage_weights            the plain dynamics with Q_k = 0 at most stages (every tenth keeps its weight), a terminal weight 100
+                                 times the plain one, and R_k growing by 1e4 along the horizon"""
+    seed = 7000 + 97 * n + 13 * m + N
+    if name in MPC_SWEEP_FAMILIES:
+        gen = random_ilqr_model if name == "plain" else HARD_SWEEP[name]
+        (f, f_x, f_u), (_, _, _, c_xx, _, c_uu), _ = gen(P, N, n, m, seed)
+        A, B, c, Qs, Rs = f_x, f_u, f, _sym(c_xx) / 2, _sym(c_uu) / 2
+    elif name in MPC_LTI_FAMILIES:
+        (f, f_x, f_u), (_, _, _, c_xx, _, c_uu), (_, _, v_xx) = random_ilqr_model(P, N, n, m, seed)
+        A0 = f_x[:, 0] * (MPC_LTI_RADIUS[name] / np.max(np.abs(np.linalg.eigvals(f_x[:, 0])), axis=-1))[:, None, None]
+        rep = lambda X: np.array(np.broadcast_to(X[:, None], (P, N) + X.shape[1:]))      # noqa: E731
+        A, B, c, Qs, Rs = rep(A0), rep(f_u[:, 0]), f, rep(_sym(c_xx[:, 0]) / 2), rep(_sym(c_uu[:, 0]) / 2)
+        Qs[:, N - 1] = _sym(v_xx) / 2
+    elif name == "stage_weights":
+        (f, f_x, f_u), (_, _, _, c_xx, _, c_uu), _ = random_ilqr_model(P, N, n, m, seed)
+        keep = (np.arange(N) % 10 == 9).astype(np.float64)
+        keep[N - 1] = 100.0
+        grow = 10.0 ** (4.0 * np.arange(N) / max(N - 1, 1))
+        A, B, c = f_x, f_u, f
+        Qs, Rs = _sym(c_xx) / 2 * keep[None, :, None, None], _sym(c_uu) / 2 * grow[None, :, None, None]
+    else:
+        raise KeyError(name)
+    A, B, c, Qs, Rs = (np.ascontiguousarray(X, dtype=np.float64) for X in (A, B, c, Qs, Rs))
+    return A, B, c, Qs, Rs, mpc_levels(mpc_penalty(Qs, Rs))

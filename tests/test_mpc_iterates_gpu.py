@@ -97,6 +97,26 @@ def test_lane_kernel(mpc, name):
     _hold(mpc, name)
 
 
+@pytest.mark.parametrize("name", ic.GROUPS["unstable"][0])
+def test_unstable_plant_with_active_input_bounds(mpc, name):
+    """an open-loop-unstable plant (spectral radius 1.3) at N = 40 with active input bounds: the restatement's rule, and the KKT
+    certificate of tests/test_mpc_gpu.py: test_constrained_small_problems_against_independent_solve on the kernel's own result.  (With
+    tables from an unsymmetrised value matrix both sides share the tables' error; the certificate does not.)"""
+    from oracle import mpc_oracle as mo
+    got = ic.run_kernel(mpc, name)
+    print(f"{name}: largest deviation {ic.compare(name, got) * ic.TOL:.1e} x scale (bound {ic.TOL:.0e})")
+    c = ic.build(name)
+    A, B, Q, R, N = c.ctor[:5]
+    n_active = 0
+    for b in range(len(c.x0)):
+        x, u = got[0]["x"][b], got[0]["u"][b]
+        kkt = mo.kkt_residuals(A, B, Q, R, c.Qf, N, *c.ctor[5:], c.x0[b], x, u, act_tol=1e-4)
+        print(f"{name} instance {b}: {kkt}")
+        assert kkt["dyn"] <= 1e-12 and kkt["bound"] <= 1e-4 and kkt["stat"] <= 1e-3
+        n_active += int(np.max(np.abs(u)) >= c.ctor[8][0] - 1e-5)
+    assert n_active >= 1 and np.all(got[0]["status"] == "optimal")
+
+
 def test_forced_lane_path_in_a_child_process(tmp_path):
     out_file = str(tmp_path / "lane.npz")
     env = dict(os.environ, ZOPT_AMD_MPC_PATH="lane")

@@ -78,6 +78,24 @@ def test_tracking(mpc, name):
     _hold(mpc, name, prob=_quad_problem(mpc, lr.build(name)) if name == "trackquad" else None)
 
 
+@pytest.mark.parametrize("name", lr.GROUPS["unstable"])
+def test_unstable_stage_matrices_with_active_input_bounds(mpc, name):
+    """every A_k at spectral radius 1.3, c_k != 0, N = 30, active input bounds: the restatement's rule, and the KKT certificate (the
+    thresholds of tests/test_mpc_gpu.py: test_constrained_small_problems_against_independent_solve) on the kernel's own result"""
+    from oracle import mpc_oracle as mo
+    got = _hold(mpc, name)
+    c = lr.build(name)
+    A, B, ck, Q, R, Qf, xl, xu, ul, uu = c.inst[0]
+    n_active = 0
+    for b in range(len(c.x0)):
+        x, u = got[0]["x"][b], got[0]["u"][b]
+        kkt = mo.kkt_residuals_stage(A, B, ck, *mo.stage_args(Q, R, Qf, c.N, xl, xu, ul, uu), c.x0[b], x, u, act_tol=1e-4)
+        print(f"{name} instance {b}: {kkt}")
+        assert kkt["dyn"] <= 1e-12 and kkt["bound"] <= 1e-4 and kkt["stat"] <= 1e-3
+        n_active += int(np.max(np.abs(u)) >= uu[0] - 1e-5)
+    assert n_active >= 1 and np.all(got[0]["status"] == "optimal")
+
+
 @pytest.mark.parametrize("n,m,N", [(4, 2, 6), (12, 4, 7)])
 def test_constant_dynamics_are_lqrMpc(mpc, n, m, N):
     """the anchor: constant A_k, B_k and c = 0 against lqrMpc with the same per-problem data -- same status, iterations and level,

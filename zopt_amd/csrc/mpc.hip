@@ -69,7 +69,8 @@ __global__ __launch_bounds__(256) void mpc_setup_kernel(const double* __restrict
 
 // P problems x L penalty levels in ONE launch: workgroup b = p * L + l factors problem p (its A, B, Q, R, Qf at p x their size) at the
 // penalty rho_tab[b] into its own slice of the problem-major tables K (P, L, N, m, n), Minv (P, L, N, m, m).  The body is that of
-// mpc_setup_kernel, so every (p, l) slice is bit for bit what zm_mpc_setup_f64 writes for that problem and penalty.
+// mpc_setup_kernel, so every (p, l) slice is bit for bit what zm_mpc_setup_f64 writes for that problem and penalty.  The weights are
+// symmetric (the host layer passes symmetric parts) and the body stores its value matrix symmetrised; so do the two copies below.
 template <int SN, int SM>
 __global__ __launch_bounds__(256) void mpc_setup_batched_kernel(const double* __restrict__ A, const double* __restrict__ B,
                                                                 const double* __restrict__ Q, const double* __restrict__ R,
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void mpc_setup_ltv_kernel(const double* __rest
         mm_tn(Suu, Bs, PB, n, m, m);  // B_k^T P B_k
         if (t < m * m) Suu[t] += 2.0 * R[t] + ((t / m == t % m) ? rho : 0.0);
         __syncthreads();
-        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= 4), as in mpc_setup_body.h
+        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= SM), as in mpc_setup_body.h
             double a[SM][2 * SM];
             for (int i = 0; i < m; ++i)
                 for (int j = 0; j < m; ++j) {
@@ -174,7 +175,9 @@ __global__ __launch_bounds__(256) void mpc_setup_ltv_kernel(const double* __rest
         mm_tn(T1, As, PA, n, n, n);     // A_k^T P A_k
         mm_tn(T2, Sux, K, m, n, n);     // Sux^T K
         for (int e = t; e < n * n; e += blockDim.x)
-            P[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+            T1[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+        __syncthreads();
+        for (int e = t; e < n * n; e += blockDim.x) P[e] = 0.5 * (T1[e] + T1[(e % n) * n + e / n]);   // symmetrised, as in mpc_setup_body.h
         for (int e = t; e < m * n; e += blockDim.x) Kout[(long)k * m * n + e] = K[e];
         for (int e = t; e < m * m; e += blockDim.x) Minvout[(long)k * m * m + e] = Mi[e];
         __syncthreads();
@@ -231,7 +234,7 @@ __global__ __launch_bounds__(256) void mpc_setup_ltv_stage_kernel(const double* 
         mm_tn(Suu, Bs, PB, n, m, m);  // B_k^T P B_k
         if (t < m * m) Suu[t] += 2.0 * Rs[(long)k * m * m + t] + ((t / m == t % m) ? rho : 0.0);
         __syncthreads();
-        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= 4), as in mpc_setup_body.h
+        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= SM), as in mpc_setup_body.h
             double a[SM][2 * SM];
             for (int i = 0; i < m; ++i)
                 for (int j = 0; j < m; ++j) {
@@ -264,7 +267,9 @@ __global__ __launch_bounds__(256) void mpc_setup_ltv_stage_kernel(const double* 
         mm_tn(T2, Sux, K, m, n, n);     // Sux^T K
         const double* Q = Qs + (long)(k >= 1 ? k - 1 : 0) * n * n;   // the weight of x_k; nothing reads the value matrix of x_0
         for (int e = t; e < n * n; e += blockDim.x)
-            P[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+            T1[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+        __syncthreads();
+        for (int e = t; e < n * n; e += blockDim.x) P[e] = 0.5 * (T1[e] + T1[(e % n) * n + e / n]);   // symmetrised, as in mpc_setup_body.h
         for (int e = t; e < m * n; e += blockDim.x) Kout[(long)k * m * n + e] = K[e];
         for (int e = t; e < m * m; e += blockDim.x) Minvout[(long)k * m * m + e] = Mi[e];
         __syncthreads();

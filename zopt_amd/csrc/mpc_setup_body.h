@@ -18,7 +18,7 @@
         mm_tn(Suu, Bs, PB, n, m, m);  // B^T P B
         if (t < m * m) Suu[t] += 2.0 * R[t] + ((t / m == t % m) ? rho : 0.0);
         __syncthreads();
-        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= 4)
+        if (t == 0) {  // m x m inverse by Gauss-Jordan with partial pivoting (m <= SM)
             double a[SM][2 * SM];
             for (int i = 0; i < m; ++i)
                 for (int j = 0; j < m; ++j) {
@@ -50,7 +50,11 @@
         mm_tn(T1, As, PA, n, n, n);     // A^T P A
         mm_tn(T2, Sux, K, m, n, n);     // Sux^T K
         for (int e = t; e < n * n; e += blockDim.x)
-            P[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+            T1[e] = (2.0 * Q[e] + ((e / n == e % n) ? rho : 0.0)) + T1[e] - T2[e];
+        __syncthreads();
+        // the value matrix is stored symmetrised: the antisymmetric rounding error of the update above is propagated through A . A_cl, not
+        // A_cl . A_cl, and grows along the horizon of an open-loop-unstable plant unless it is removed at every stage
+        for (int e = t; e < n * n; e += blockDim.x) P[e] = 0.5 * (T1[e] + T1[(e % n) * n + e / n]);
         for (int e = t; e < m * n; e += blockDim.x) Kout[(long)k * m * n + e] = K[e];
         for (int e = t; e < m * m; e += blockDim.x) Minvout[(long)k * m * m + e] = Mi[e];
         __syncthreads();

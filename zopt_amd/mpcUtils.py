@@ -50,6 +50,10 @@ class lqrMpc():
             u_lb, u_ub : Control lower / upper bound
             Qf : Terminal cost matrix, optional; shape = (n,n).  Defaults to Q
 
+        A weight enters the cost through its quadratic form alone, so Q, R and Qf are replaced by their symmetric parts (W + W') / 2
+        before anything is derived from them (exact, hence bit-neutral, for a symmetric weight): the setup entry points of the C ABI
+        expect symmetric weights, and the attributes Q, R, Qf hold the symmetric parts.
+
         Extension: every array may carry leading axes (A, Q, Qf (..., n, n), B (..., n, m), R (..., m, m), bounds (..., n) /
         (..., m)); they broadcast to the problem shape `P` and each problem has its own data (gain-scheduled MPC, fleets,
         per-instance boxes).  `rho` then has shape `P` and `solve` runs every problem in one launch.
@@ -60,6 +64,7 @@ class lqrMpc():
         data = {k: _host_f64(X) for k, X in zip(_ARRAYS, (A, B, Q, R, Qf, x_lb, x_ub, u_lb, u_ub))}
         self.N = int(N)
         n, m, P = _problem_shape(data, self.N, batched)
+        _symmetric_part(data)
         # one problem: P is None, rho a float -- solve() then runs the shared-problem kernels (scalar table loads)
         self.P = P if batched else None
         _check_psd(data, P)
@@ -464,7 +469,8 @@ class ltvMpc(lqrMpc):
         Arguments
         ---------
             A : (..., N, n, n)   B : (..., N, n, m)   c : (..., N, n) or None (zeros) -- the dynamics of every stage
-            Q, R, Qf, x_lb, x_ub, u_lb, u_ub, N : as lqrMpc takes them, leading axes included
+            Q, R, Qf, x_lb, x_ub, u_lb, u_ub, N : as lqrMpc takes them, leading axes included (the weights, with or without a stage axis,
+                are replaced by their symmetric parts, as lqrMpc replaces them; `update` does the same with new ones)
             stage_varying : names among "Q", "R", "x_lb", "x_ub", "u_lb", "u_ub"; a named argument carries a stage axis in front of its
                 trailing axes -- Q (..., N+1, n, n), R (..., N, m, m), x_lb, x_ub (..., N+1, n), u_lb, u_ub (..., N, m).  (Named, because a
                 stage axis cannot be told from a leading problem axis by its shape.)  With "Q" named, Q[..., N] is the terminal weight
@@ -488,6 +494,7 @@ class ltvMpc(lqrMpc):
         data["c"] = None if c is None else _host_f64(c)
         n, m, P = _ltv_problem_shape(data, self.N)
         self.P = P
+        _symmetric_part(data)
         _check_psd(data, P)
         if n > 12 or m > 4:
             raise ValueError(f"ltvMpc: (n={n}, m={m}) outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")
@@ -562,6 +569,7 @@ class ltvMpc(lqrMpc):
         data["c"] = None if c is None else _host_f64(c)
         n, m, P = _ltv_problem_shape(data, N, {k: N + self._STAGED[k] for k in sv})
         self.P = P
+        _symmetric_part(data)
         _check_psd_stages(data, P, sv)
         if n > 12 or m > 4:
             raise ValueError(f"ltvMpc: (n={n}, m={m}) outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")
@@ -700,6 +708,8 @@ class ltvMpc(lqrMpc):
         if "Q" in new and "Q" not in sv and self.N == 1:
             raise ValueError("ltvMpc.update: with N = 1 and no stage axis on Q the only weight is Qf, which update() does not take")
         host = {k: _host_f64(X) for k, X in new.items() if k in ("Q", "R") or not (arr.is_torch(X) and X.is_cuda)}
+        _symmetric_part(host)
+        new = {k: host[k] if k in ("Q", "R") else X for k, X in new.items()}   # (the weights go to the device as their symmetric parts)
         _check_psd_stages({k: host.get(k) for k in ("Q", "R", "Qf")}, P, sv)
         arr.require_gpu()
         d = self._device_data()
@@ -1103,6 +1113,17 @@ def _problem_shape(data, N, batched):
         raise ValueError("inconsistent lqrMpc problem shapes: the leading (problem) axes do not broadcast: "
                          + ", ".join(f"{k} {data[k].shape}" for k in tails)) from None
     return n, m, tuple(int(v) for v in P)
+
+
+def _symmetric_part(data):
+    """The weights of `data` (Q, R, Qf where present and not None; trailing axes (k, k), any leading ones) replaced in place by their
+    symmetric parts (W + W') / 2.  Only the quadratic form x'Wx enters the cost, which the antisymmetric part does not change; the setup
+    kernels form the Hessian as 2 W and the tracking kernels the linear term with W + W', which agree for a symmetric W only.  For a
+    symmetric W the result is W bit for bit (W + W is exact, and so is the halving)."""
+    for name in ("Q", "R", "Qf"):
+        W = data.get(name)
+        if W is not None:
+            data[name] = np.ascontiguousarray(0.5 * (W + np.swapaxes(W, -1, -2)))
 
 
 def _check_psd(data, P):
