@@ -442,6 +442,60 @@ int zm_ilqr_solve_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, 
                             double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations,
                             int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace);
 
+/* ---- tracking cost: the quadratic cost about a goal or a reference trajectory -------------------------------------------------
+ *     J = sum_{k<T} (x_k - xr_k)'Q(x_k - xr_k) + (u_k - ur_k)'R(u_k - ur_k)  +  (x_T - xr_T)'Qf(x_T - xr_T)          (no 1/2)
+ *     c_x = (Q+Q')(x_k - xr_k)   c_u = (R+R')(u_k - ur_k)   v_x = (Qf+Qf')(x_T - xr_T);   c_xx, c_ux, c_uu, v_xx as zm_quadcost_t's
+ * The reference's drivers take cost callables (zopt/ilqrUtils.py:260-269); the fused drivers took zm_quadcost_t only, i.e. the
+ * demo's cost about the origin (demos/iterativeLqr.py:12-13,37).  Q, R, Qf, diagonal: as zm_quadcost_t.
+ * xRef, uRef: device pointers, NULL = zeros.  Row k of trajectory t (k = 0..T for xRef, 0..T-1 for uRef) starts at
+ *     xRef + t * xref_traj_stride + k * xref_step_stride          (strides in doubles; the n resp. m entries of a row are contiguous)
+ * and a stride may be 0: (0, 0) is one goal for every step and trajectory, (n, 0) a goal per trajectory, ((T+1) n, n) a full
+ * reference per trajectory, (0, n) one reference shared by the batch.  Every kernel forms the difference first and then applies
+ * the operations of its zm_quadcost_t sibling to it: a zero (or NULL) reference gives that sibling's results bit for bit.
+ * Shapes: n <= 12, m <= 4 (the fused drivers' shapes; the wide rollouts take no tracking cost). */
+typedef struct zm_trackcost_t {
+    const double* Q;        /* (n,n) */
+    const double* R;        /* (m,m) */
+    const double* Qf;       /* (n,n) */
+    int32_t diagonal;       /* as zm_quadcost_t.diagonal */
+    int32_t reserved;
+    const double* xRef;     /* NULL: zeros */
+    const double* uRef;     /* NULL: zeros */
+    int64_t xref_traj_stride, xref_step_stride;
+    int64_t uref_traj_stride, uref_step_stride;
+} zm_trackcost_t;
+
+/* zm_rollout_linesearch_f64 / zm_rollout_linesearch_list_f64 (zopt/ilqrUtils.py:33-66, :116-150; CostFunction.__call__,
+ * pytrees.py:49-52) with the tracking cost.  `cost` is required.  References are read by (trajectory id, step), also through a list. */
+int zm_rollout_linesearch_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* l,
+                                       const double* L, const double* xPrev, const double* uPrev, const double* alphas,
+                                       int n_alpha, const int32_t* active, double* xTraj, double* uTraj, double* J,
+                                       int32_t* alpha_idx, int64_t batch, int T, void* stream);
+int zm_rollout_linesearch_tracking_list_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* l,
+                                            const double* L, const double* xPrev, const double* uPrev, const double* alphas,
+                                            int n_alpha, const int32_t* list, int64_t count, const int32_t* active, double* xTraj,
+                                            double* uTraj, double* J, int32_t* alpha_idx, int64_t batch, int T, void* stream);
+/* zm_quadratize_cost_f64 / zm_quadratize_cost_list_f64 (zopt/pytrees.py:100-115, :72-81) with the tracking cost: c, c_x, c_u about
+ * (xr_k, ur_k), v, v_x about xr_T; the Hessians do not depend on the reference. */
+int zm_quadratize_cost_tracking_f64(const zm_trackcost_t* cost, int n, int m, const double* xTraj, const double* uTraj,
+                                    const int32_t* active, double* c, double* c_x, double* c_u, double* v, double* v_x,
+                                    double* c_xx, double* c_ux, double* c_uu, double* v_xx, int64_t batch, int T, void* stream);
+int zm_quadratize_cost_tracking_list_f64(const zm_trackcost_t* cost, int n, int m, const double* xTraj, const double* uTraj,
+                                         const int32_t* list, int64_t count, const int32_t* active, double* c, double* c_x,
+                                         double* c_u, double* v, double* v_x, double* c_xx, double* c_ux, double* c_uu,
+                                         double* v_xx, int64_t batch, int T, void* stream);
+/* zm_ilqr_solve_f64 / zm_ilqr_solve_trace_f64 (zopt/ilqrUtils.py:290-327, :360-397) with the tracking cost: the same loop and the
+ * same launches; workspace and iwork as there (zm_ilqr_solve_workspace_f64). */
+int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess, int ddp,
+                               int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
+                               int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
+                               int32_t* iterations, int64_t batch, int T, void* stream);
+int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess,
+                                     int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                                     int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
+                                     int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
+                                     int32_t* alpha_trace);
+
 /* Same, with OSQP's over-relaxation `alpha` in (0, 2) (OSQP / cvxpy default 1.6, which is what the reference's
  * `prob.solve(**kwargs)` runs with, mpcUtils.py:77): the relaxed iterate alpha w + (1 - alpha) y_prev enters the projection and
  * the dual update; residuals are those of the unrelaxed iterate.  alpha = 1 is zm_mpc_solve_adaptive_f64. */

@@ -161,6 +161,20 @@ SYMBOLS = {
     "zm_shutdown": (ctypes.c_int, []),
     "zm_ilqr_solve_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] +
                                 [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
+    # the tracking-cost siblings (zm_trackcost_t* in place of zm_quadcost_t*): same argument lists
+    "zm_rollout_linesearch_tracking_f64": (ctypes.c_int, [_c_dp] * 8 + [ctypes.c_int] + [_c_dp] * 5 +
+                                           [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_rollout_linesearch_tracking_list_f64": (ctypes.c_int, [_c_dp] * 8 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 5 +
+                                                [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_quadratize_cost_tracking_f64": (ctypes.c_int, [_c_dp, ctypes.c_int, ctypes.c_int] + [_c_dp] * 12 +
+                                        [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_quadratize_cost_tracking_list_f64": (ctypes.c_int, [_c_dp, ctypes.c_int, ctypes.c_int] + [_c_dp] * 3 + [ctypes.c_int64] +
+                                             [_c_dp] * 10 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_solve_tracking_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                              ctypes.c_int64] + [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_solve_tracking_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                                    ctypes.c_int64] + [_c_dp] * 7 +
+                                         [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
     "zm_model_nonlinear_mask": (ctypes.c_int, [_c_dp, _c_dp]),
     "zm_psd_project_f64": (ctypes.c_int, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "zm_condition_cost_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,

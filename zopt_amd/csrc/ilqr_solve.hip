@@ -17,6 +17,7 @@
 
 #include "models.h"
 #include "quad_derivs_gen.h"
+#include "track_cost.h"
 #include "zm_common.h"
 
 namespace zm {
@@ -112,7 +113,7 @@ static long ilqr_tail_slots(long batch) {
 
 int expand_list(const zm_model_t* model, const zm_quadcost_t* cost, const double* xTraj, const double* uTraj, const int32_t* list,
                 int64_t count, const int32_t* active, double* f_x, double* f_u, double* c_x, double* c_u, double* v_x, int64_t batch,
-                int T, void* stream, int packed);
+                int T, void* stream, int packed, const TrackRef* track);
 struct TrajList {
     const int* list;
     long count;
@@ -128,12 +129,37 @@ bool rollout_all_store_model_ok(const zm_model_t* model);
 int rollout_linesearch_all_store(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* l, const double* L,
                                  const double* xPrev, const double* uPrev, const double* alphas, const int32_t* list, int64_t count,
                                  const int32_t* active, double* scratch, double* J, int32_t* alpha_idx, int64_t batch, int T,
-                                 void* stream);
+                                 void* stream, const TrackRef* track);
 int ilqr_accept(const int32_t* list, int64_t count, double* J, const double* Jn, double* xTraj, const double* xTrajNew, double* uTraj,
                 const double* uTrajNew, int32_t* converged, int32_t* active, double tol, int64_t batch, int T, int n, int m,
                 void* stream, const double* scratch, const int32_t* idx, int32_t* where, int where_val);
 int ilqr_collect(const int32_t* where, double* xTraj, const double* xAlt, double* uTraj, const double* uAlt, int64_t batch, int T, int n,
                  int m, void* stream);
+
+// The cost of a solve, as the loop sees it: the weights (the Hessians, the conditioning and the kernels' cost arithmetic read only
+// these) and, for a tracking cost (zm_trackcost_t), the reference that the line search's cost values and the expansion's gradients
+// are taken about.  One loop serves both; `track` == nullptr is the zm_quadcost_t path with exactly its launches.
+struct IlqrCost {
+    bool given;
+    zm_quadcost_t w;
+    const zm_trackcost_t* track;
+    TrackRef ref;
+    const TrackRef* ref_ptr() const { return track ? &ref : nullptr; }
+};
+// the line search of the loop: dense (list == nullptr) or over the id list
+static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const double* x0, const double* l, const double* L,
+                           const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* list,
+                           int64_t count, const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
+                           int64_t batch, int T, void* stream) {
+    if (ck.track)
+        return zm_rollout_linesearch_tracking_list_f64(model, ck.track, x0, l, L, xPrev, uPrev, alphas, n_alpha, list, count, active, xTraj,
+                                                       uTraj, J, alpha_idx, batch, T, stream);
+    if (list)
+        return zm_rollout_linesearch_list_f64(model, &ck.w, x0, l, L, xPrev, uPrev, alphas, n_alpha, list, count, active, xTraj, uTraj, J,
+                                              alpha_idx, batch, T, stream);
+    return zm_rollout_linesearch_f64(model, &ck.w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, xTraj, uTraj, J, alpha_idx, batch, T,
+                                     stream);
+}
 
 static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_ux, int npairs) {
     const long n = model->n, m = model->m;
@@ -273,15 +299,22 @@ extern "C" int64_t zm_ilqr_solve_workspace_f64(const zm_model_t* model, int64_t 
     return zm::carve(model, batch, T, ddp, (mask >> model->n) != 0, npairs).total;
 }
 
-static int ilqr_solve_impl(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* uGuess,
+static zm::IlqrCost quad_cost(const zm_quadcost_t* c) {
+    return zm::IlqrCost{c != nullptr, c ? *c : zm_quadcost_t{nullptr, nullptr, nullptr, 0, 0}, nullptr, zm::TrackRef{}};
+}
+
+static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, const double* x0, const double* uGuess,
                            int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
                            int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
                            int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace) {
     if (batch == 0) return ZM_OK;
+    const zm_quadcost_t* cost = ck.given ? &ck.w : nullptr;   // the weights
     if (!model || !cost || !x0 || !uGuess || !workspace || !iwork || !xTraj || !uTraj || !L || !J || !converged)
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: null pointer");
     if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
+    if (ck.track && model->kind == ZM_MODEL_LINEAR && (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_tracking_f64: (n=%d, m=%d) not covered (tracking cost: n<=12, m<=4)", n, m);
     uint32_t mask = 0;
     int32_t npairs = 0;
     if (ddp) {
@@ -313,8 +346,8 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm_quadcost_t* cost, c
                            ws + w.uT2, ws + w.alphas, (int*)active, (int*)converged, (int*)where, (long)batch);
     }
     // initial rollout (alpha = 1) from the zero trajectory and its cost                                (:297-298)
-    int rc = zm_rollout_linesearch_f64(model, cost, x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, xTraj, uTraj, J,
-                                       nullptr, batch, T, st);
+    int rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0, nullptr, xTraj, uTraj,
+                                 J, nullptr, batch, T, st);
     if (rc) return rc;
     // trajectory-independent Hessians of the quadratic cost, PD-conditioned once                         (:309-313)
     rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.c_xx,
@@ -388,7 +421,7 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm_quadcost_t* cost, c
         }
         // expansions along the current trajectories: [f_x | f_u], c_x, c_u, v_x in one launch                  (:304-313)
         rc = zm::expand_list(model, cost, curX, curU, list, count, active, ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u,
-                             ws + w.v_x, batch, T, st, packed ? 1 : 0);
+                             ws + w.v_x, batch, T, st, packed ? 1 : 0, ck.ref_ptr());
         if (rc) return rc;
         if (sync_now) {
             int32_t c32 = 0;
@@ -432,21 +465,21 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm_quadcost_t* cost, c
         // rows (:316-320)
         if (can_all_store && count <= w.tail_slots) {
             rc = zm::rollout_linesearch_all_store(model, cost, x0, ws + w.l, L, curX, curU, ws + w.alphas, list, count, active,
-                                                  ws + w.scratch, ws + w.Jn, widx, batch, T, st);
+                                                  ws + w.scratch, ws + w.Jn, widx, batch, T, st, ck.ref_ptr());
             if (rc) return rc;
             rc = zm::ilqr_accept(list, count, J, ws + w.Jn, curX, nullptr, curU, nullptr, converged, active, tol, batch, T, n, m, st,
                                  ws + w.scratch, widx, swap_on ? where : nullptr, curX == xTraj ? 0 : 1);
         } else if (swap_on) {
-            rc = zm_rollout_linesearch_list_f64(model, cost, x0, ws + w.l, L, curX, curU, ws + w.alphas, 16, list, count, active, altX,
-                                                altU, ws + w.Jn, widx, batch, T, st);
+            rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, curX, curU, ws + w.alphas, 16, list, count, active, altX, altU, ws + w.Jn,
+                                     widx, batch, T, st);
             if (rc) return rc;
             rc = zm::ilqr_accept(list, count, J, ws + w.Jn, altX, nullptr, altU, nullptr, converged, active, tol, batch, T, n, m, st,
                                  nullptr, nullptr, where, altX == xTraj ? 0 : 1);
             std::swap(curX, altX);
             std::swap(curU, altU);
         } else {
-            rc = zm_rollout_linesearch_list_f64(model, cost, x0, ws + w.l, L, xTraj, uTraj, ws + w.alphas, 16, list, count, active,
-                                                ws + w.xT2, ws + w.uT2, ws + w.Jn, widx, batch, T, st);
+            rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, xTraj, uTraj, ws + w.alphas, 16, list, count, active, ws + w.xT2,
+                                     ws + w.uT2, ws + w.Jn, widx, batch, T, st);
             if (rc) return rc;
             rc = zm_ilqr_accept_f64(list, count, J, ws + w.Jn, xTraj, ws + w.xT2, uTraj, ws + w.uT2, converged, active, tol, batch, T,
                                     n, m, st);
@@ -470,8 +503,8 @@ extern "C" int zm_ilqr_solve_f64(const zm_model_t* model, const zm_quadcost_t* c
                                  int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
                                  int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
                                  int32_t* iterations, int64_t batch, int T, void* stream) {
-    return ilqr_solve_impl(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L,
-                           J, converged, iterations, batch, T, stream, nullptr, nullptr);
+    return ilqr_solve_impl(model, quad_cost(cost), x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
+                           uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
 }
 
 extern "C" int zm_ilqr_solve_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* uGuess,
@@ -479,8 +512,28 @@ extern "C" int zm_ilqr_solve_trace_f64(const zm_model_t* model, const zm_quadcos
                                        int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
                                        int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
                                        int32_t* alpha_trace) {
-    return ilqr_solve_impl(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L,
-                           J, converged, iterations, batch, T, stream, J_trace, alpha_trace);
+    return ilqr_solve_impl(model, quad_cost(cost), x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
+                           uTraj, L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace);
+}
+
+extern "C" int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess,
+                                                int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                                                int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L,
+                                                double* J, int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream,
+                                                double* J_trace, int32_t* alpha_trace) {
+    if (batch == 0) return ZM_OK;
+    if (const int rc = zm::track_check(cost, "zm_ilqr_solve_tracking_f64")) return rc;
+    const zm::IlqrCost ck{true, zm::track_weights(*cost), cost, zm::track_ref(*cost)};
+    return ilqr_solve_impl(model, ck, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J,
+                           converged, iterations, batch, T, stream, J_trace, alpha_trace);
+}
+
+extern "C" int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess,
+                                          int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                                          int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
+                                          int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream) {
+    return zm_ilqr_solve_tracking_trace_f64(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork,
+                                            xTraj, uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
 }
 
 extern "C" int zm_shutdown(void) { return zm::release_host_slots(); }

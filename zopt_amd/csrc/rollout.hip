@@ -10,6 +10,7 @@
 // trajectory -- the other 15 rollouts never touch HBM.  This chain is latency/ALU-bound, not HBM-bound: it reads
 // 8(mn + 2m + n) = 544 B per trajectory step.
 #include "models.h"
+#include "track_cost.h"
 #include "zm_common.h"
 
 #include <cstdlib>
@@ -17,12 +18,14 @@
 namespace zm {
 
 // one rollout; STORE: write xTraj/uTraj; returns J (0 when cost == nullptr)
-template <bool STORE>
+// TRK: tracking cost -- the cost of step k is that of (x_k - xr_k, u_k - ur_k), rows of trajectory `t` of `tr`
+template <bool STORE, bool TRK = false>
 __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_quadcost_t* cs, const double alpha,
                                               const double* __restrict__ x0, const double* __restrict__ l,
                                               const double* __restrict__ L, const double* __restrict__ xPrev,
                                               const double* __restrict__ uPrev, double* __restrict__ xTraj,
-                                              double* __restrict__ uTraj, const int T) {
+                                              double* __restrict__ uTraj, const int T, const TrackRef& tr = TrackRef{},
+                                              const long t = 0) {
     const int n = md.n, m = md.m;
     double x[MAXN], u[MAXM], xn[MAXN];
 #pragma unroll
@@ -51,7 +54,14 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
                 u[i] = 0.0;
             }
         }
-        if (cs) J += running_cost(*cs, n, m, x, u);
+        if constexpr (TRK) {
+            double ex[MAXN], eu[MAXM];
+            track_diff(ex, x, track_xrow(tr, t, k), n);
+            track_diff(eu, u, track_urow(tr, t, k), m);
+            J += running_cost(*cs, n, m, ex, eu);
+        } else {
+            if (cs) J += running_cost(*cs, n, m, x, u);
+        }
         model_step<double>(md, x, u, xn);
 #pragma unroll
         for (int i = 0; i < MAXN; ++i) x[i] = xn[i];
@@ -64,11 +74,19 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
                 if (i < n) xTraj[(long)(k + 1) * n + i] = x[i];
         }
     }
-    if (cs) J += terminal_cost(*cs, n, x);
+    if constexpr (TRK) {
+        double ex[MAXN];
+        track_diff(ex, x, track_xrow(tr, t, T), n);
+        J += terminal_cost(*cs, n, ex);
+    } else {
+        if (cs) J += terminal_cost(*cs, n, x);
+    }
     return J;
 }
 
 // NA = lanes per trajectory (power of two <= 16 that holds n_alpha)
+#define ZM_TRK_FLAG
+#define ZM_TRK_ARGS
 template <int NA>
 __global__ __launch_bounds__(64) void rollout_linesearch_kernel(const zm_model_t md, const zm_quadcost_t cost,
                                                                 const bool has_cost, const double* __restrict__ x0,
@@ -80,62 +98,35 @@ __global__ __launch_bounds__(64) void rollout_linesearch_kernel(const zm_model_t
                                                                 const long count, double* __restrict__ xTraj,
                                                                 double* __restrict__ uTraj, double* __restrict__ Jout,
                                                                 int* __restrict__ idx_out, const long batch, const int T) {
-    constexpr int TPW = 64 / NA;  // trajectories per wave
-    const int lane = threadIdx.x;
-    const int a = lane % NA;
-    const long slot = (long)blockIdx.x * TPW + lane / NA;   // slot -> trajectory id (through `list` when given)
-    const long nslot = list ? count : batch;
-    const long traj = (slot < nslot) ? (list ? (long)list[slot] : slot) : 0;
-    const bool live = (slot < nslot) && (a < n_alpha) && (active == nullptr || active[traj] != 0);
-    const long t = live ? traj : 0;
-    const int n = md.n, m = md.m;
-    const zm_quadcost_t* cs = has_cost ? &cost : nullptr;
-    const double alpha = alphas[a < n_alpha ? a : 0];
-    const double* x0t = x0 + t * n;
-    const double* lt = l + t * T * m;
-    const double* Lt = L + t * T * m * n;
-    const double* xpt = xPrev + t * (T + 1) * n;
-    const double* upt = uPrev + t * T * m;
-    double* xo = xTraj + t * (T + 1) * n;
-    double* uo = uTraj + t * T * m;
-
-    double J = 0.0;
-    int best = 0;
-    if (NA > 1) {
-        if (live) J = rollout_one<false>(md, cs, alpha, x0t, lt, Lt, xpt, upt, nullptr, nullptr, T);
-        // argmin over the NA lanes of this trajectory with jnp.argmin semantics: a NaN cost beats every number
-        // (also -inf), the first index wins among equals.  Dead lanes carry (+inf, index NA).
-        double key = live ? J : __builtin_inf();
-        int isn = (live && (J != J)) ? 1 : 0;
-        int who = live ? a : NA;
-#pragma unroll
-        for (int off = NA / 2; off >= 1; off >>= 1) {
-            const double ok = __shfl_xor(key, off);
-            const int on = __shfl_xor(isn, off);
-            const int ow = __shfl_xor(who, off);
-            const bool better = (on > isn) || (on == isn && ((on == 0 && ok < key) || ((on == 1 || ok == key) && ow < who)));
-            key = better ? ok : key;
-            isn = better ? on : isn;
-            who = better ? ow : who;
-        }
-        best = who < NA ? who : 0;
-    }
-    // every lane of the trajectory re-rolls the winning step size; lane 0 of the group stores
-    const double abest = alphas[best];
-    if (live) {
-        if (a == 0) {
-            const double Jb = rollout_one<true>(md, cs, abest, x0t, lt, Lt, xpt, upt, xo, uo, T);
-            if (Jout) Jout[t] = Jb;
-            if (idx_out) idx_out[t] = best;
-        }
-    }
+#include "rollout_linesearch_body.h"
 }
+#undef ZM_TRK_FLAG
+#undef ZM_TRK_ARGS
+// the same line search on the tracking cost (zm_trackcost_t): `cost` holds its weights, `tr` its reference
+#define ZM_TRK_FLAG , true
+#define ZM_TRK_ARGS , tr, t
+template <int NA>
+__global__ __launch_bounds__(64) void rollout_linesearch_track_kernel(const zm_model_t md, const zm_quadcost_t cost, const TrackRef tr,
+                                                                      const double* __restrict__ x0, const double* __restrict__ l,
+                                                                      const double* __restrict__ L, const double* __restrict__ xPrev,
+                                                                      const double* __restrict__ uPrev,
+                                                                      const double* __restrict__ alphas, const int n_alpha,
+                                                                      const int* __restrict__ active, const int* __restrict__ list,
+                                                                      const long count, double* __restrict__ xTraj,
+                                                                      double* __restrict__ uTraj, double* __restrict__ Jout,
+                                                                      int* __restrict__ idx_out, const long batch, const int T) {
+    constexpr bool has_cost = true;
+#include "rollout_linesearch_body.h"
+}
+#undef ZM_TRK_FLAG
+#undef ZM_TRK_ARGS
 
 // rollout_fast.hip: compile-time (n, m) = (12, 4), 16 step sizes
 int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R, const double* Qf, int diagonal, const double* x0,
                           const double* l, const double* L, const double* xPrev, const double* uPrev,
                           const double* alphas, int n_alpha, const int* active, const int* list, int64_t count, double* xTraj,
-                          double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch);
+                          double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch,
+                          const TrackRef* track);
 
 }  // namespace zm
 
@@ -149,7 +140,9 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
                                          const double* l, const double* L, const double* xPrev, const double* uPrev,
                                          const double* alphas, int n_alpha, const int32_t* active, const int32_t* list,
                                          int64_t count, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
-                                         int64_t batch, int T, void* stream, double* scratch = nullptr) {
+                                         int64_t batch, int T, void* stream, double* scratch = nullptr,
+                                         const zm::TrackRef* track = nullptr) {
+    // track != nullptr: `cost` holds the weights of a zm_trackcost_t and *track its reference (the *_tracking_* entry points)
     if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj)
         return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: null pointer");
     if (batch < 0 || T < 0 || n_alpha < 1 || n_alpha > 16)
@@ -177,6 +170,9 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
         return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: cost needs Q, R, Qf");
     if (batch == 0 || (list && count == 0)) return ZM_OK;
     if (count < 0 || count > batch) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch: bad list length");
+    if (wide && track)
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_rollout_linesearch_tracking_f64: (n=%d, m=%d) not covered (tracking cost: n<=12, m<=4)",
+                             md.n, md.m);
     if (wide) {
         if (scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: all-store mode needs the fast path");
         return zm::rollout_wide_dispatch(md, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, (const int*)active, (const int*)list,
@@ -197,9 +193,17 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
     //  redundant, and still several times faster than the generic lane-per-trajectory kernel with its uncoalesced policy reads)
     if (!force_generic && !windy && (n_alpha == 16 || n_alpha == 1) && md.n == 12 && md.m == 4 && cost && T >= 1)
         return zm::rollout_fast_dispatch(md, cs.Q, cs.R, cs.Qf, cs.diagonal, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, count, xTraj,
-                                         uTraj, J, (int*)alpha_idx, batch, T, st, scratch);
+                                         uTraj, J, (int*)alpha_idx, batch, T, st, scratch, track);
     if (scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: all-store mode needs the fast path");
-    if (n_alpha == 1) {
+    if (track && n_alpha == 1) {
+        const unsigned blocks = (unsigned)((nslot + 63) / 64);
+        hipLaunchKernelGGL((zm::rollout_linesearch_track_kernel<1>), dim3(blocks), dim3(64), 0, st, md, cs, *track, x0, l, L, xPrev,
+                           uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, (int*)alpha_idx, (long)batch, T);
+    } else if (track) {
+        const unsigned blocks = (unsigned)((nslot + 3) / 4);
+        hipLaunchKernelGGL((zm::rollout_linesearch_track_kernel<16>), dim3(blocks), dim3(64), 0, st, md, cs, *track, x0, l, L, xPrev,
+                           uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, (int*)alpha_idx, (long)batch, T);
+    } else if (n_alpha == 1) {
         const unsigned blocks = (unsigned)((nslot + 63) / 64);
         hipLaunchKernelGGL((zm::rollout_linesearch_kernel<1>), dim3(blocks), dim3(64), 0, st, md, cs, hc, x0, l, L, xPrev,
                            uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, (int*)alpha_idx, (long)batch, T);
@@ -232,6 +236,27 @@ extern "C" int zm_rollout_linesearch_list_f64(const zm_model_t* model, const zm_
                         batch, T, stream);
 }
 
+extern "C" int zm_rollout_linesearch_tracking_list_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0,
+                                                       const double* l, const double* L, const double* xPrev, const double* uPrev,
+                                                       const double* alphas, int n_alpha, const int32_t* list, int64_t count,
+                                                       const int32_t* active, double* xTraj, double* uTraj, double* J,
+                                                       int32_t* alpha_idx, int64_t batch, int T, void* stream) {
+    if (const int rc = zm::track_check(cost, "zm_rollout_linesearch_tracking_f64")) return rc;
+    if (batch == 0) return ZM_OK;
+    const zm_quadcost_t w = zm::track_weights(*cost);
+    const zm::TrackRef tr = zm::track_ref(*cost);
+    return rollout_impl(model, &w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
+                        stream, nullptr, &tr);
+}
+
+extern "C" int zm_rollout_linesearch_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* l,
+                                                  const double* L, const double* xPrev, const double* uPrev, const double* alphas,
+                                                  int n_alpha, const int32_t* active, double* xTraj, double* uTraj, double* J,
+                                                  int32_t* alpha_idx, int64_t batch, int T, void* stream) {
+    return zm_rollout_linesearch_tracking_list_f64(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, nullptr, 0, active, xTraj, uTraj,
+                                                   J, alpha_idx, batch, T, stream);
+}
+
 // Solver-internal (ilqr_solve.hip): the 16-way line search in all-store mode -- every step size's rollout goes to the scratch blocks
 // of its slot ((T+1) * 256 doubles per slot, layout in rollout_fast.hip), alpha_idx[t] names the winner, nothing is written to
 // xTraj / uTraj.
@@ -253,10 +278,10 @@ bool rollout_all_store_supported(const zm_model_t* model, const zm_quadcost_t* c
 int rollout_linesearch_all_store(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* l, const double* L,
                                  const double* xPrev, const double* uPrev, const double* alphas, const int32_t* list, int64_t count,
                                  const int32_t* active, double* scratch, double* J, int32_t* alpha_idx, int64_t batch, int T,
-                                 void* stream) {
+                                 void* stream, const TrackRef* track) {
     // (xTraj / uTraj are not written in this mode; the non-null placeholders only pass the argument check)
     return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, 16, active, list, count, scratch, scratch, J, alpha_idx, batch, T,
-                        stream, scratch);
+                        stream, scratch, track);
 }
 }  // namespace zm
 

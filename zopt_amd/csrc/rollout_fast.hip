@@ -14,6 +14,7 @@
 //    all -- the accept step copies the winner's row.  16x the stores, half the chain.
 #include "models.h"
 #include "quad_step.h"
+#include "track_cost.h"
 #include "zm_common.h"
 
 #include <cstdlib>
@@ -157,11 +158,31 @@ __device__ __forceinline__ void pol_controls(double (&u)[RM], const double (&dx)
     }
 }
 
-template <int KIND, bool DIAG, bool ALL>
+// Tracking cost (TRK): a step's reference row [xr_k | ur_k] is RN + RM = 16 doubles -- one element per lane of the group that rolls
+// the trajectory.  It travels like the policy data: one more rotating register, loaded by the group with ONE coalesced 128-byte
+// load per step (lanes 0..11 from xRef's row, 12..15 from uRef's; a stride of 0 re-reads the same row), three steps ahead, and
+// every use is an FMA with a DPP broadcast operand: d = fma(ref, -1, z) = z - ref with one rounding, exactly z for a zero
+// reference.  The terminal row xr_T rides in the same rotation (its lanes 12..15 load nothing).  Never through LDS.
+// acc += c * (reference element E of the row held in r)
+template <int E>
+__device__ __forceinline__ void ref_fma(double& acc, const double c, const double& r) {
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(r), "v"(c), "i"(E));
+}
+// d[j] = z[j] - ref[OFF + j]
+template <int K, int OFF, int J = 0>
+__device__ __forceinline__ void ref_diff(double (&d)[K], const double (&z)[K], const double neg1, const double& r) {
+    if constexpr (J < K) {
+        d[J] = z[J];
+        ref_fma<OFF + J>(d[J], neg1, r);
+        ref_diff<K, OFF, J + 1>(d, z, neg1, r);
+    }
+}
+
+template <int KIND, bool DIAG, bool ALL, bool TRK = false>
 // (no __restrict__ on the LDS tables: with it the loop-invariant LDS reads of Q, A, B ... are hoisted into registers --
 //  several hundred VGPRs -- instead of being re-read by broadcast every step)
 __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double* Qs, const double* Rs, const double* Qfs,
-                                                const double* As, const double* Bs) {
+                                                const double* As, const double* Bs, const TrackRef& tr = TrackRef{}) {
     const int lane = threadIdx.x;
     const int grp = lane >> 4, a = lane & 15;
     const long slot = (long)blockIdx.x * 4 + grp;
@@ -199,6 +220,18 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
             }
         }
     }
+    // this lane's element of the reference rows of trajectory t (nullptr: zeros), and its step stride
+    const double* rp = nullptr;
+    long rst = 0;
+    if constexpr (TRK) {
+        if (a < RN) {
+            rp = tr.x ? tr.x + t * tr.xt + a : nullptr;
+            rst = tr.xk;
+        } else {
+            rp = tr.u ? tr.u + t * tr.ut + (a - RN) : nullptr;
+            rst = tr.uk;
+        }
+    }
     const double* x0t = g.x0 + t * RN;
     double* xo = g.xTraj + t * (T + 1) * RN;
     double* uo = g.uTraj + t * T * RM;
@@ -233,13 +266,35 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
 #pragma unroll
             for (int i = 0; i < 5; ++i) r.v[i] = pp.p[i][(long)k * pp.st[i]];
         };
-        auto body = [&](PolRegs& cur, PolRegs& ahead, const int k) {
+        // reference row k (k = 0..T; row T has no uRef part)
+        auto fetch_ref = [&](double& r, const int k) {
+            if constexpr (TRK) r = (rp && (a < RN || k < T)) ? rp[(long)k * rst] : 0.0;
+        };
+        auto body = [&](PolRegs& cur, PolRegs& ahead, double& rcur, double& rahead, const int k) {
             if (k + 3 < T) fetch(ahead, k + 3);
+            if constexpr (TRK) {
+                if (k + 3 <= T) fetch_ref(rahead, k + 3);
+            }
             pol_settle(cur);
             double dx[RN];
             pol_dx(dx, x, neg1, cur);
             pol_controls(u, dx, al, one, cur);
-            if constexpr (ALL && DIAG) {   // the diagonal weights from registers (loaded before the loop); quad_form's arithmetic
+            if constexpr (TRK) {   // the cost of (x - xr_k, u - ur_k): quad_form's / the all-store form's arithmetic on the differences
+                asm("s_nop 1" : "+v"(rcur));
+                double ex[RN], eu[RM];
+                ref_diff<RN, 0>(ex, x, neg1, rcur);
+                ref_diff<RM, RN>(eu, u, neg1, rcur);
+                if constexpr (ALL && DIAG) {
+                    double jx = 0.0, ju = 0.0;
+#pragma unroll
+                    for (int j = 0; j < RN; ++j) jx = __builtin_fma(ex[j] * qd[j], ex[j], jx);
+#pragma unroll
+                    for (int j = 0; j < RM; ++j) ju = __builtin_fma(eu[j] * rd[j], eu[j], ju);
+                    J += jx + ju;
+                } else {
+                    J += quad_form<DIAG, RN>(Qs, ex) + quad_form<DIAG, RM>(Rs, eu);
+                }
+            } else if constexpr (ALL && DIAG) {   // the diagonal weights from registers (loaded before the loop); quad_form's arithmetic
                 double jx = 0.0, ju = 0.0;
 #pragma unroll
                 for (int j = 0; j < RN; ++j) jx = __builtin_fma(x[j] * qd[j], x[j], jx);
@@ -268,16 +323,30 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
             }
         };
         PolRegs pa, pb, pc, pd;
+        double ra = 0.0, rb = 0.0, rc = 0.0, rd_ = 0.0;   // reference rows, rotating with the policy sets (TRK)
         fetch(pa, 0);
         if (T > 1) fetch(pb, 1);
         if (T > 2) fetch(pc, 2);
-        for (int k = 0; k < T; k += 4) {   // rotating sets: no copies
-            body(pa, pd, k);
-            if (k + 1 < T) body(pb, pa, k + 1);
-            if (k + 2 < T) body(pc, pb, k + 2);
-            if (k + 3 < T) body(pd, pc, k + 3);
+        if constexpr (TRK) {
+            fetch_ref(ra, 0);
+            fetch_ref(rb, 1);               // (T >= 1: row 1 exists, the terminal one at the least)
+            if (T > 1) fetch_ref(rc, 2);
         }
-        J += quad_form<DIAG, RN>(Qfs, x);
+        for (int k = 0; k < T; k += 4) {   // rotating sets: no copies
+            body(pa, pd, ra, rd_, k);
+            if (k + 1 < T) body(pb, pa, rb, ra, k + 1);
+            if (k + 2 < T) body(pc, pb, rc, rb, k + 2);
+            if (k + 3 < T) body(pd, pc, rd_, rc, k + 3);
+        }
+        if constexpr (TRK) {   // the terminal row sits in set T mod 4
+            double rT = (T & 3) == 0 ? ra : (T & 3) == 1 ? rb : (T & 3) == 2 ? rc : rd_;
+            asm("s_nop 1" : "+v"(rT));
+            double ex[RN];
+            ref_diff<RN, 0>(ex, x, neg1, rT);
+            J += quad_form<DIAG, RN>(Qfs, ex);
+        } else {
+            J += quad_form<DIAG, RN>(Qfs, x);
+        }
         return J;
     };
 
@@ -350,11 +419,53 @@ __global__ __launch_bounds__(64) void rollout_ls_fast_kernel(const FastArgs g) {
     }
 }
 
+// The same kernel on the tracking cost (zm_trackcost_t: g.Q, g.R, g.Qf its weights, tr its reference).
+template <int KIND, bool DIAG_ONLY, bool ALL>
+__global__ __launch_bounds__(64) void rollout_ls_fast_track_kernel(const FastArgs g, const TrackRef tr) {
+    __shared__ double Qs[RN * RN], Rs[RM * RM], Qfs[RN * RN];
+    __shared__ double As[KIND == ZM_MODEL_LINEAR ? RN * RN : 1], Bs[KIND == ZM_MODEL_LINEAR ? RN * RM : 1];
+    const int lane = threadIdx.x;
+    bool offdiag = false;
+    for (int e = lane; e < RN * RN; e += 64) {
+        const double q = g.Q[e], qf = g.Qf[e];
+        Qs[e] = q;
+        Qfs[e] = qf;
+        offdiag |= (e / RN != e % RN) && (q != 0.0 || qf != 0.0);
+    }
+    for (int e = lane; e < RM * RM; e += 64) {
+        const double r = g.R[e];
+        Rs[e] = r;
+        offdiag |= (e / RM != e % RM) && (r != 0.0);
+    }
+    if constexpr (KIND == ZM_MODEL_LINEAR) {
+        for (int e = lane; e < RN * RN; e += 64) As[e] = g.A[e];
+        for (int e = lane; e < RN * RM; e += 64) Bs[e] = g.B[e];
+    }
+    __syncthreads();
+    if constexpr (DIAG_ONLY) {
+        rollout_ls_body<KIND, true, ALL, true>(g, Qs, Rs, Qfs, As, Bs, tr);
+    } else {
+        if (__ballot(offdiag) == 0ull)
+            rollout_ls_body<KIND, true, ALL, true>(g, Qs, Rs, Qfs, As, Bs, tr);
+        else
+            rollout_ls_body<KIND, false, ALL, true>(g, Qs, Rs, Qfs, As, Bs, tr);
+    }
+}
+
 template <int KIND>
-static int launch_fast(const FastArgs& g, const bool diag_only, hipStream_t st) {
+static int launch_fast(const FastArgs& g, const bool diag_only, hipStream_t st, const TrackRef* track) {
     const long nslot = g.list ? g.count : g.batch;
     const dim3 grid((unsigned)((nslot + 3) / 4)), block(64);
-    if (g.scratch) {
+    if (track) {
+        if (g.scratch && diag_only)
+            hipLaunchKernelGGL((rollout_ls_fast_track_kernel<KIND, true, true>), grid, block, 0, st, g, *track);
+        else if (g.scratch)
+            hipLaunchKernelGGL((rollout_ls_fast_track_kernel<KIND, false, true>), grid, block, 0, st, g, *track);
+        else if (diag_only)
+            hipLaunchKernelGGL((rollout_ls_fast_track_kernel<KIND, true, false>), grid, block, 0, st, g, *track);
+        else
+            hipLaunchKernelGGL((rollout_ls_fast_track_kernel<KIND, false, false>), grid, block, 0, st, g, *track);
+    } else if (g.scratch) {
         if (diag_only)
             hipLaunchKernelGGL((rollout_ls_fast_kernel<KIND, true, true>), grid, block, 0, st, g);
         else
@@ -387,7 +498,8 @@ int rollout_quad_reroll(const QuadArgs& g, hipStream_t st);
 int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R, const double* Qf, int diagonal,
                           const double* x0, const double* l, const double* L, const double* xPrev, const double* uPrev,
                           const double* alphas, int n_alpha, const int* active, const int* list, int64_t count, double* xTraj,
-                          double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch) {
+                          double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch,
+                          const TrackRef* track) {
     FastArgs g{md.A, md.B, md.dt, Q, R, Qf, x0, l, L, xPrev, uPrev, alphas, active, list, (long)count, xTraj, uTraj, J, idx,
                (long)batch, T, n_alpha, scratch, 0};
     // ZOPT_AMD_ROLLOUT_QUAD=0: everything in rollout_ls_fast_kernel (A/B; same results)
@@ -395,7 +507,9 @@ int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R
         const char* e = zm::lab_env("ZOPT_AMD_ROLLOUT_QUAD");
         return !(e && e[0] == '0');
     }();
-    const bool quad = quad_on && md.kind == ZM_MODEL_QUADCOPTER && diagonal == 1 && n_alpha == 16 && J && idx;
+    // (the four-lanes-per-rollout kernels have no tracking form: a tracking cost stays in rollout_ls_fast_track_kernel, whose own
+    //  second pass and all-store mode serve instead)
+    const bool quad = quad_on && !track && md.kind == ZM_MODEL_QUADCOPTER && diagonal == 1 && n_alpha == 16 && J && idx;
     const QuadArgs qa{md.dt, Q, R, Qf, x0, l, L, xPrev, uPrev, alphas, active, list, (long)count, xTraj, uTraj, J, idx, (long)batch, T, scratch};
     // all-store line search with at most one wave per SIMD: one trajectory per wave, 4 lanes per step size (78 against 104 us per
     // launch; four-wave workgroups so that up to 1024 waves each get a SIMD).  With more trajectories its 4x as many waves no longer
@@ -408,8 +522,8 @@ int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R
     if (quad && scratch && count <= quad_all_max) return rollout_quad_all(qa, st);
     if (quad && !scratch) g.no_pass2 = 1;                              // two-pass line search: the second pass as its own, densely packed launch
     int rc;
-    if (md.kind == ZM_MODEL_QUADCOPTER) rc = launch_fast<ZM_MODEL_QUADCOPTER>(g, diagonal == 1, st);
-    else rc = launch_fast<ZM_MODEL_LINEAR>(g, diagonal == 1, st);
+    if (md.kind == ZM_MODEL_QUADCOPTER) rc = launch_fast<ZM_MODEL_QUADCOPTER>(g, diagonal == 1, st, track);
+    else rc = launch_fast<ZM_MODEL_LINEAR>(g, diagonal == 1, st, track);
     if (rc || !quad || scratch) return rc;
     return rollout_quad_reroll(qa, st);
 }

@@ -216,8 +216,9 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     if not hasattr(dynFun, "c_struct"):
         raise TypeError("dynFun must be a registered device model (zopt_amd.models.LinearModel / QuadcopterEuler) or a torch "
                         "callable f(x, u) -> x+ (generic path, zopt_amd/generic.py)")
-    if costFun is not None and not hasattr(costFun, "c_struct"):
-        raise TypeError("costFun must be a registered zopt_amd.models.QuadraticCost")
+    tracking = isinstance(costFun, _models.TrackingCost)
+    if costFun is not None and not tracking and not hasattr(costFun, "c_struct"):
+        raise TypeError("costFun must be a registered zopt_amd.models.QuadraticCost or TrackingCost")
     l, L = _fields(policy)
     xPrev, uPrev = _fields(trajPrev)
     n, m = dynFun.n, dynFun.m
@@ -239,8 +240,9 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     uT = torch.empty(lead + (N, m), dtype=dt, device=dx0.device)
     J = torch.empty(lead, dtype=dt, device=dx0.device) if costFun is not None else None
     md = dynFun.c_struct()
-    cs = costFun.c_struct() if costFun is not None else None
-    rc = _lib.lib().zm_rollout_linesearch_f64(
+    cs = (costFun.track_struct(lead, N) if tracking else costFun.c_struct()) if costFun is not None else None
+    linesearch = _lib.lib().zm_rollout_linesearch_tracking_f64 if tracking else _lib.lib().zm_rollout_linesearch_f64
+    rc = linesearch(
         ctypes.addressof(md), ctypes.addressof(cs) if cs is not None else None, dx0.data_ptr(), dl.data_ptr(),
         dL.data_ptr(), dxp.data_ptr(), dup.data_ptr(), dal.data_ptr(), int(dal.numel()), None, xT.data_ptr(),
         uT.data_ptr(), J.data_ptr() if J is not None else None, None, batch, N, ctypes.c_void_p(arr.stream_ptr(dx0)))
@@ -252,6 +254,10 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
 def _torch_costs(runningCost, terminalCost):
     """torch callables (x, u) -> c, (x) -> cf from what the caller passed: torch callables as they are; a registered QuadraticCost (or
     its bound methods) as x'Qx + u'Ru, x'Qf x on device copies of its matrices"""
+    for c in (runningCost, getattr(runningCost, "__self__", None), terminalCost, getattr(terminalCost, "__self__", None)):
+        if isinstance(c, _models.TrackingCost):
+            raise TypeError("a TrackingCost cannot run on the generic-callable path: its callables carry no stage index, so a reference "
+                            "would be dropped -- register a device model, or close torch callables over a constant goal")
     for c in (runningCost, getattr(runningCost, "__self__", None)):
         if isinstance(c, _models.QuadraticCost):
             Q, R, Qf = (arr.to_device(M, torch.float64) for M in (c.Q, c.R, c.Qf))
@@ -265,6 +271,9 @@ def _rollout_generic(x0, dynFun, policy, trajPrev, alphas, costFun):
     """trajectoryRollout / forwardPass2 for a torch callable `dynFun(x, u) -> x+` (zopt_amd/generic.py); `costFun`: None, a
     registered QuadraticCost, or an object with torch callables `.runningCost(x, u)` / `.terminalCost(x)` (CostFunction of the
     reference, pytrees.py:27-38)."""
+    if isinstance(costFun, _models.TrackingCost):
+        raise TypeError("a TrackingCost needs a registered device model: the generic-callable rollout has no stage index to read the "
+                        "reference by")
     l, L = _fields(policy)
     xPrev, uPrev = _fields(trajPrev)
     shp = _shape(L)
@@ -376,14 +385,15 @@ def conditionQuadraticDynamics(quadratic_dynamics, v_x):
 
 
 def _registered_cost(runningCost, terminalCost):
-    """Accepts a zopt_amd.models.QuadraticCost handle (for both arguments) or its bound methods."""
+    """Accepts a zopt_amd.models.QuadraticCost or TrackingCost handle (for both arguments) or its bound methods."""
+    kinds = (_models.QuadraticCost, _models.TrackingCost)
     for c in (runningCost, getattr(runningCost, "__self__", None)):
-        if isinstance(c, _models.QuadraticCost):
-            other = terminalCost if isinstance(terminalCost, _models.QuadraticCost) else getattr(terminalCost, "__self__", None)
+        if isinstance(c, kinds):
+            other = terminalCost if isinstance(terminalCost, kinds) else getattr(terminalCost, "__self__", None)
             if other is not c:
-                raise TypeError("runningCost and terminalCost must come from the same QuadraticCost")
+                raise TypeError(f"runningCost and terminalCost must come from the same {type(c).__name__}")
             return c
-    raise TypeError("runningCost / terminalCost must be a registered zopt_amd.models.QuadraticCost (or its "
+    raise TypeError("runningCost / terminalCost must be a registered zopt_amd.models.QuadraticCost or TrackingCost (or its "
                     ".runningCost / .terminalCost methods); arbitrary Python callables cannot run inside a HIP kernel")
 
 
@@ -518,7 +528,10 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     dev = dx0.device
     B = dx0.shape[0]
     st = ctypes.c_void_p(arr.stream_ptr(dx0))
-    md, cs = model.c_struct(), cost.c_struct()
+    tracking = isinstance(cost, _models.TrackingCost)
+    if tracking and (cost.n != n or cost.m != m):
+        raise ValueError(f"the TrackingCost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
+    md, cs = model.c_struct(), (cost.track_struct(tuple(lead), N) if tracking else cost.c_struct())
     pmd, pcs = ctypes.addressof(md), ctypes.addressof(cs)
     L = torch.empty((B, N, m, n), dtype=dt, device=dev)
     xT = torch.empty((B, N + 1, n), dtype=dt, device=dev)
@@ -541,12 +554,14 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         common = (pmd, pcs, dx0.data_ptr(), dug.data_ptr(), 1 if ddp else 0, int(maxIter), float(tol), SYNC,
                   ws.data_ptr(), nws, iwork.data_ptr(), xT.data_ptr(), uT.data_ptr(), L.data_ptr(), J.data_ptr(),
                   converged.data_ptr(), ctypes.addressof(its), B, N, st)
+        solve, solve_trace = ((lib.zm_ilqr_solve_tracking_f64, lib.zm_ilqr_solve_tracking_trace_f64) if tracking else
+                              (lib.zm_ilqr_solve_f64, lib.zm_ilqr_solve_trace_f64))
         if _TRACE is None:
-            rc = lib.zm_ilqr_solve_f64(*common)
+            rc = solve(*common)
         else:
             Jtr = torch.full((max(int(maxIter), 1), B), float("nan"), dtype=dt, device=dev)
             atr = torch.full((max(int(maxIter), 1), B), -1, dtype=torch.int32, device=dev)
-            rc = lib.zm_ilqr_solve_trace_f64(*common, Jtr.data_ptr(), atr.data_ptr())
+            rc = solve_trace(*common, Jtr.data_ptr(), atr.data_ptr())
         _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
         if _TRACE is not None:
             _TRACE.append(("iterations", int(its.value)))

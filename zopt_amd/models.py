@@ -109,6 +109,117 @@ class QuadraticCost:
         return st
 
 
+class zm_trackcost_t(ctypes.Structure):
+    _fields_ = [("Q", ctypes.c_void_p), ("R", ctypes.c_void_p), ("Qf", ctypes.c_void_p), ("diagonal", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("xRef", ctypes.c_void_p), ("uRef", ctypes.c_void_p),
+                ("xref_traj_stride", ctypes.c_int64), ("xref_step_stride", ctypes.c_int64),
+                ("uref_traj_stride", ctypes.c_int64), ("uref_step_stride", ctypes.c_int64)]
+
+
+TRACKING_MAX_N, TRACKING_MAX_M = 12, 4     # the fused drivers' shapes (zm::MAXN, zm::MAXM)
+
+
+class TrackingCost:
+    """The quadratic cost about a goal or a reference trajectory (no 1/2, as QuadraticCost):
+
+        J = sum_{k<T} (x_k - xr_k)'Q(x_k - xr_k) + (u_k - ur_k)'R(u_k - ur_k)  +  (x_T - xr_T)'Qf(x_T - xr_T)
+
+    xRef: None (zeros), (n,) -- one goal for every step and trajectory -- or (..., T+1, n) with leading axes that broadcast to the
+    batch of the call; the step axis may have length 1 (`goal[:, None, :]`: a goal per trajectory, read with a step stride of 0, not
+    materialised per step).  uRef: None, (m,) or (..., T, m), likewise.  NumPy arrays or device tensors; a device tensor that is
+    contiguous in its trailing axes is read in place.  The reference's drivers take cost callables (ilqrUtils.py:260-269); this is
+    the registered form of `lambda x, u, k: (x - xr[k]) @ Q @ (x - xr[k]) + ...` for the fused drivers, accepted wherever
+    QuadraticCost is.  It is deliberately NOT a QuadraticCost: code that knows only that class would drop the reference."""
+
+    def __init__(self, Q, R, Qf=None, xRef=None, uRef=None):
+        self._w = QuadraticCost(Q, R, Qf)
+        self.Q, self.R, self.Qf, self.n, self.m = self._w.Q, self._w.R, self._w.Qf, self._w.n, self._w.m
+        self.xRef = self._checked(xRef, self.n, "xRef")
+        self.uRef = self._checked(uRef, self.m, "uRef")
+
+    @staticmethod
+    def _checked(r, width, what):
+        if r is None:
+            return None
+        if not arr.is_torch(r):
+            r = np.asarray(r, dtype=np.float64)
+        shp = tuple(r.shape)
+        if len(shp) == 0 or shp[-1] != width or (len(shp) >= 2 and shp[-2] < 1):
+            raise ValueError(f"TrackingCost: {what} has shape {shp}, expected ({width},) or (..., steps, {width})")
+        return r
+
+    # ---- host side (NumPy; a single trajectory or point) -------------------------------------------------------------------------
+    def _row(self, r, k, width):
+        if r is None:
+            return np.zeros(width)
+        r = r.detach().cpu().numpy() if arr.is_torch(r) else r
+        if r.ndim == 1:
+            return r
+        if r.ndim != 2:
+            raise ValueError("TrackingCost: the single-point form needs a reference without batch axes")
+        return r[0 if r.shape[0] == 1 else k]
+
+    def runningCost(self, x, u, k=0):
+        ex, eu = x - self._row(self.xRef, k, self.n), u - self._row(self.uRef, k, self.m)
+        return ex @ self.Q @ ex + eu @ self.R @ eu
+
+    def terminalCost(self, x):
+        ex = x - self._row(self.xRef, -1, self.n)
+        return ex @ self.Qf @ ex
+
+    def __call__(self, traj, k=None):
+        """Cost of a trajectory (CostFunction.__call__ of the reference, pytrees.py:40-55); with `k`, the running cost at step k."""
+        return QuadraticCost.__call__(self, traj, k)
+
+    # ---- device side -----------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _view(r, lead, rows, width, what, terminal):
+        """-> (device tensor or None, trajectory stride, step stride, offset) of a reference for a call with batch axes `lead` and
+        `rows` steps.  Only a reference whose leading axes broadcast PARTLY to `lead` is copied (per trajectory, never per step)."""
+        import torch
+        if r is None:
+            return None, 0, 0, 0
+        in_place = arr.is_torch(r) and r.is_cuda and r.dtype == torch.float64 and r.stride(-1) == 1 and (
+            r.ndim == 1 or r.shape[-2] == 1 or r.stride(-2) in (0, width))
+        t = r if in_place else arr.to_device(r, torch.float64)
+        if t.ndim == 1:
+            return t.contiguous(), 0, 0, 0
+        have = int(t.shape[-2])
+        if terminal:              # the terminal row of the cost's own horizon
+            rows = have
+        if have not in (1, rows):
+            raise ValueError(f"TrackingCost: {what} has {have} steps, the call needs {rows} (or 1)")
+        if have > 1 and t.stride(-2) == 0:
+            t, have = t[..., :1, :], 1
+        ls = tuple(int(d) for d in t.shape[:-2])
+        if len(ls) > len(lead) or any(a != 1 and a != b for a, b in zip(ls[::-1], tuple(lead)[::-1])):
+            raise ValueError(f"TrackingCost: leading axes {ls} of {what} do not broadcast to the batch {tuple(lead)}")
+        if all(d == 1 for d in ls):
+            t, ts = t.reshape(have, width).contiguous(), 0
+        elif ls == tuple(lead) and len(ls) == 1 and t.stride(-1) == 1 and (have == 1 or t.stride(-2) == width):
+            ts = int(t.stride(0))          # one batch axis: any trajectory stride is read in place
+        elif ls == tuple(lead):
+            t, ts = t.contiguous(), have * width
+        else:
+            t, ts = t.expand(tuple(lead) + (have, width)).contiguous(), have * width
+        ss = width if have > 1 else 0
+        return t, ts, ss, ((have - 1) * ss if terminal else 0)
+
+    def track_struct(self, lead, N, terminal=False):
+        """zm_trackcost_t for a call with batch axes `lead` and N steps.  terminal: every row is the reference's LAST one (the terminal
+        cost about xr_T evaluated on a short trajectory; uRef is not read)."""
+        if self.n > TRACKING_MAX_N or self.m > TRACKING_MAX_M:
+            raise ValueError(f"TrackingCost: (n={self.n}, m={self.m}) not covered -- the fused drivers take n <= {TRACKING_MAX_N}, "
+                             f"m <= {TRACKING_MAX_M}; the wide rollouts have no tracking form")
+        w = self._w.c_struct()
+        xr, xts, xss, xoff = self._view(self.xRef, lead, N + 1, self.n, "xRef", terminal)
+        ur, uts, uss, _ = (None, 0, 0, 0) if terminal else self._view(self.uRef, lead, N, self.m, "uRef", False)
+        st = zm_trackcost_t(w.Q, w.R, w.Qf, w.diagonal, 0, xr.data_ptr() + 8 * xoff if xr is not None else None,
+                            ur.data_ptr() if ur is not None else None, xts, 0 if terminal else xss, uts, uss)
+        st._owner = (self, w, xr, ur)      # raw device addresses: keep the arrays behind them alive with the struct
+        return st
+
+
 class QuadcopterRigidBody:
     """The 8-state model the reference trims and linearises: `rigidBodyDynamics(state, control, wind_body)`
     (quadcopter.py:70-113), state [u,v,w,p,q,r,phi,theta].  dt = 0: the continuous derivative; dt > 0: one Euler step."""

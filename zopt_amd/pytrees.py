@@ -21,8 +21,16 @@ def _expand(kind, fun, xTraj, uTraj):
     import torch
     from . import _arrays as arr
     from . import _lib
+    from . import models as _models
     arr.require_gpu()
-    if not hasattr(fun, "c_struct"):
+    tracking = isinstance(fun, _models.TrackingCost) or isinstance(getattr(fun, "__self__", None), _models.TrackingCost)
+    if tracking:
+        # the tracking cost's expansion runs in its own kernels (zm_quadratize_cost_tracking_f64); the torch.func path below would
+        # see callables without a stage index and drop the reference
+        fun = fun if isinstance(fun, _models.TrackingCost) else fun.__self__
+        if kind not in ("cost", "terminal"):
+            raise TypeError("a TrackingCost is a cost, not a dynamics model")
+    elif not hasattr(fun, "c_struct"):
         return _expand_callable(kind, fun, xTraj, uTraj)
     n, m = fun.n, fun.m
     dt = torch.float64
@@ -38,7 +46,7 @@ def _expand(kind, fun, xTraj, uTraj):
             raise ValueError("xTraj / uTraj batch axes differ")
     B, dev = x.shape[0], x.device
     st = ctypes.c_void_p(arr.stream_ptr(x))
-    cs = fun.c_struct()
+    cs = fun.track_struct(lead, N, terminal=(kind == "terminal")) if tracking else fun.c_struct()
     pc = ctypes.addressof(cs)
     lib = _lib.lib()
     E = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
@@ -57,7 +65,8 @@ def _expand(kind, fun, xTraj, uTraj):
     else:
         c, c_x, c_u, v, v_x = E(B, N), E(B, N, n), E(B, N, m), E(B), E(B, n)
         c_xx, c_ux, c_uu, v_xx = E(n, n), E(m, n), E(m, m), E(n, n)
-        _lib.check(lib.zm_quadratize_cost_f64(pc, n, m, x.data_ptr(), u.data_ptr(), None, c.data_ptr(), c_x.data_ptr(),
+        quadratize = lib.zm_quadratize_cost_tracking_f64 if tracking else lib.zm_quadratize_cost_f64
+        _lib.check(quadratize(pc, n, m, x.data_ptr(), u.data_ptr(), None, c.data_ptr(), c_x.data_ptr(),
                                               c_u.data_ptr(), v.data_ptr(), v_x.data_ptr(), c_xx.data_ptr(),
                                               c_ux.data_ptr(), c_uu.data_ptr(), v_xx.data_ptr(), B, N, st),
                    "QuadraticCostFunction.from_trajectory")
