@@ -289,7 +289,8 @@ def _rollout_abi(gpu, model, problem, n_alpha):
 def test_short_rollouts_from_hard_initial_states(gpu, fam, N):
     """trajectoryRollout from the first 17 points of the family (dt = 0.1): the generic lane-per-trajectory kernel (no cost), the fast
     kernel with one step size (one lane per rollout) and the 16-step-size line search with diagonal weights (winners other than
-    alpha_0 re-rolled on four lanes; the reference is rolled out with each trajectory's winning step size)"""
+    alpha_0 re-rolled on four lanes; the reference is rolled out with each trajectory's winning step size -- the step size the
+    kernel REPORTED: whether it is the right one, and whether J belongs to it, is held by tests/test_linesearch_hard_gpu.py)"""
     rc = hp.rollout_case(fam, N)
     assert rc.determined[:, 0].all()                   # every initial state is compared on its first step at least
     x0, l, L, xp, up = rc.problem
