@@ -496,6 +496,63 @@ int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost
                                      int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
                                      int32_t* alpha_trace);
 
+/* ---- input box: iLQR with bounds u_lb <= u <= u_ub on the inputs (control-limited DDP: Tassa, Mansard, Todorov 2014) -------------
+ * Every entry of this section is an extension; the reference has no counterpart (its iLQR is unconstrained, ilqrUtils.py:260-327).
+ *   rollout / line search:  u_k = clip(alpha l_k + L_k (x_k - xPrev_k) + uPrev_k, lb, ub); the clip lets a NaN through.  With
+ *                           infinite bounds the results are those of the unconstrained entries bit for bit.
+ *   backward step:          l_k = argmin_d 1/2 d' sym(Q_uu) d + Q_u' d  over  lb - u_k <= d <= ub - u_k  (u_k: the current trajectory's
+ *                           input); C = the components at a bound with a multiplier of the right sign (lb == ub: always), F the rest;
+ *                           L_k[C,:] = 0, L_k[F,:] = -Q_uu[F,F]^-1 Q_ux[F,:];  v_x' = Q_x + Q_ux' l_k,  v_xx' = Q_xx - L_k' Q_uu L_k.
+ * lb, ub: device pointers to m doubles per row, row t * stride belongs to trajectory t: stride 0 = one box for every trajectory,
+ * stride m = a box per trajectory.  An entry may be -inf / +inf; lb <= ub is the caller's to ensure.  Shapes: n <= 12, m <= 4. */
+typedef struct zm_inputbox_t {
+    const double* lb;
+    const double* ub;
+    int64_t stride;
+} zm_inputbox_t;
+
+/* The box-QP of the backward step, batched, one problem per lane (test entry of the device routine the sweep runs wave-uniform):
+ * d = argmin 1/2 d' sym(H) d + g' d over lo <= d <= hi.  H (batch, m, m), g, lo, hi, d_out (batch, m); m <= 4.  clamped_out
+ * (optional): bit i set where component i is clamped; iters_out (optional): passes of the active-set iteration (24 = its cap). */
+int zm_boxqp_f64(const double* H, const double* g, const double* lo, const double* hi, double* d_out, int32_t* clamped_out,
+                 int32_t* iters_out, int64_t batch, int m, void* stream);
+/* zm_ilqr_backward_list_f64 with the box: uTraj (batch, T, m) is the trajectory the expansions were taken along.  qp_capped
+ * (optional, int32 per trajectory): += the steps whose QP ended at its pass cap (the last feasible iterate is used there).
+ * list / active: as zm_ilqr_backward_list_f64 (list may be NULL). */
+int zm_ilqr_backward_box_list_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
+                                  const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* uTraj,
+                                  const zm_inputbox_t* box, const int32_t* list, int64_t count, const int32_t* active,
+                                  int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m,
+                                  void* stream);
+int zm_ilqr_backward_box_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
+                             const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* uTraj,
+                             const zm_inputbox_t* box, int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T,
+                             int n, int m, void* stream);
+/* zm_rollout_linesearch_f64 / _list_f64 with the box.  The cost is `cost` or `track` (exactly one; both NULL only for a plain
+ * rollout, n_alpha == 1).  One lane per rollout, two passes. */
+int zm_rollout_linesearch_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                  const zm_inputbox_t* box, const double* x0, const double* l, const double* L, const double* xPrev,
+                                  const double* uPrev, const double* alphas, int n_alpha, const int32_t* active, double* xTraj,
+                                  double* uTraj, double* J, int32_t* alpha_idx, int64_t batch, int T, void* stream);
+int zm_rollout_linesearch_box_list_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                       const zm_inputbox_t* box, const double* x0, const double* l, const double* L,
+                                       const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* list,
+                                       int64_t count, const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
+                                       int64_t batch, int T, void* stream);
+/* zm_ilqr_solve_f64 / zm_ilqr_solve_trace_f64 with the box: the same loop on the box sweep and the box line search (full Jacobians,
+ * alternating buffers; uGuess is clipped into the box by the initial rollout, every stored uTraj is feasible).  The cost is `cost`
+ * or `track` (exactly one).  ddp = 1 is refused with ZM_EUNSUPPORTED.  qp_capped (optional): int32 per trajectory, set to the number
+ * of capped QPs over the whole solve.  Workspace: zm_ilqr_solve_workspace_f64(model, batch, T, 0). */
+int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track, const zm_inputbox_t* box,
+                          const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                          int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
+                          int32_t* converged, int32_t* iterations, int32_t* qp_capped, int64_t batch, int T, void* stream);
+int zm_ilqr_solve_box_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                const zm_inputbox_t* box, const double* x0, const double* uGuess, int ddp, int max_iter, double tol,
+                                int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj,
+                                double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations, int32_t* qp_capped,
+                                int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace);
+
 /* Same, with OSQP's over-relaxation `alpha` in (0, 2) (OSQP / cvxpy default 1.6, which is what the reference's
  * `prob.solve(**kwargs)` runs with, mpcUtils.py:77): the relaxed iterate alpha w + (1 - alpha) y_prev enters the projection and
  * the dual update; residuals are those of the unrelaxed iterate.  alpha = 1 is zm_mpc_solve_adaptive_f64. */

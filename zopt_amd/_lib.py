@@ -175,6 +175,28 @@ SYMBOLS = {
     "zm_ilqr_solve_tracking_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
                                                                     ctypes.c_int64] + [_c_dp] * 7 +
                                          [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
+    # input box (extension; the reference has no counterpart)
+    # (H, g, lo, hi, d_out, clamped_out, iters_out, batch, m, stream)
+    "zm_boxqp_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box*, list, count, active, shared_hessian, l, L, qp_capped, batch, T, n,
+    #  m, stream)
+    "zm_ilqr_backward_box_list_f64": (ctypes.c_int, [_c_dp] * 12 + [ctypes.c_int64, _c_dp, ctypes.c_int] + [_c_dp] * 3 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_backward_box_f64": (ctypes.c_int, [_c_dp] * 11 + [ctypes.c_int] + [_c_dp] * 3 +
+                                 [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, cost* | NULL, track* | NULL, box*, x0, l, L, xPrev, uPrev, alphas, n_alpha, [list, count,] active, xTraj, uTraj, J,
+    #  alpha_idx, batch, T, stream)
+    "zm_rollout_linesearch_box_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int] + [_c_dp] * 5 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_rollout_linesearch_box_list_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 5 +
+                                           [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, cost* | NULL, track* | NULL, box*, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
+    #  uTraj, L, J, converged, iterations (host), qp_capped | NULL, batch, T, stream[, J_trace, alpha_trace])
+    "zm_ilqr_solve_box_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                         ctypes.c_int64] + [_c_dp] * 8 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_solve_box_trace_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                               ctypes.c_int64] + [_c_dp] * 8 +
+                                    [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
     "zm_model_nonlinear_mask": (ctypes.c_int, [_c_dp, _c_dp]),
     "zm_psd_project_f64": (ctypes.c_int, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "zm_condition_cost_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,

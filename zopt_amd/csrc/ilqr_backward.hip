@@ -35,6 +35,13 @@
 // (v0 / q0 never influence L or l and are not carried.)  V d is a row reduction of the V registers (4 xor-shuffles per
 // K-step), V^T d a column reduction (2 shuffles) re-laid out through LDS; both are kept apart so that a
 // nonsymmetric V is treated exactly as the reference does.
+//
+// BOX (MODE 0 only; an extension, the reference has no counterpart) = the backward pass of control-limited DDP for bounds lb <= u <= ub
+// on the inputs (Tassa, Mansard, Todorov 2014): per step, with u_k the current trajectory's input,
+//     l = argmin_d 1/2 d^T sym(Q_uu) d + Q_u^T d   over   lb - u_k <= d <= ub - u_k          (boxqp4.h, wave-uniform on registers)
+//     C = the components at a bound with a multiplier of the right sign, F the rest:  L[C,:] = 0,  L[F,:] = -Q_uu[F,F]^-1 Q_ux[F,:]
+//     v_x' = Q_x + Q_ux^T l        v_xx' = Q_xx - L^T Q_uu L
+#include "boxqp4.h"
 #include "dma_ring.h"
 #include "models.h"
 #include "ns16.h"
@@ -138,14 +145,31 @@ struct SweepLab {};
 
 __device__ __forceinline__ void ilqr_lds_sync() { wave_lds_sync(); }
 
+// BOX: what a step of the box-constrained sweep (ilqr_backward_box_t16_f64) carries besides the operands
+struct BoxStep {
+    const double* pu;      // u_k of the step (the current trajectory's input), walks back by m
+    double lb[4], ub[4];   // the trajectory's bounds; -inf / +inf beyond m
+    int capped;            // steps of this trajectory whose QP ended at its pass cap
+};
+
 // ZIN (MODE 2, the DMA kernel): the caller has contracted vf_zz = sum_i v_x[i] d2f_i/dz2 already (operands in its LDS ring) and
 // passes the tile in `zin`
-template <int KS, int MODE, bool PREFETCH, bool ZIN = false>
+// BOX (MODE 0): l_k is the minimiser of the step's QP over lb - u_k <= d <= ub - u_k (boxqp4.h), the rows of L_k of its clamped
+// components are zero, the others solve the system whose clamped rows and columns are the identity's; v_x' = Q_x + Q_ux^T l_k
+template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false>
 __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], IlqrStepRegs<KS>& d, IlqrAddr<KS>& a,
                                           double* sm, const int g, const int c, const int ob0, const int ob1,
                                           const int ob2, const int ob3, const int oqa, double* jA, const int n,
-                                          const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0}, SweepLab* lab = nullptr) {
+                                          const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0}, SweepLab* lab = nullptr,
+                                          BoxStep* bx = nullptr) {
     constexpr int NP = 4 * KS;
+    static_assert(!BOX || MODE == 0, "the box-constrained step is the iLQR one");
+    double uk[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (BOX) {   // in flight under the products of G; every lane reads the same row
+#pragma unroll
+        for (int i = 0; i < 4; ++i) uk[i] = bx->pu[i < m ? i : 0];
+        bx->pu -= m;
+    }
     // MODE 2: vf_zz = sum_i v_x[i] * d2f_i/dz2, PD-projected, as extra accumulator init
     d4 pz = zero4();
     if constexpr (MODE == 2 && ZIN) {
@@ -239,19 +263,54 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
     b[2] = sm[ob2];
     b[3] = sm[ob3];
     const double quu_a = sm[oqa];  // Q_uu[c][g]: A operand of Q_uu L (0-padded through the address choice below)
+    double gq[4] = {0.0, 0.0, 0.0, 0.0};
+    if constexpr (BOX) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) gq[i] = sm[64 + NP + i];   // Q_u (zero beyond m)
+    }
     __builtin_amdgcn_wave_barrier();
     const double b0[4] = {b[0], b[1], b[2], b[3]};  // original right-hand side (Sux column) for MODE 1's v' update
     ZM_SWEEP_STAMP(lab, 3);   // the exchange through LDS
+    double dq[4] = {0.0, 0.0, 0.0, 0.0};
+    int cl = 0;
+    if constexpr (BOX) {   // wave-uniform: every lane holds the same Q_uu, Q_u, bounds and u_k
+        double lo[4], hi[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            lo[i] = bx->lb[i] - uk[i];
+            hi[i] = bx->ub[i] - uk[i];
+        }
+        bool capped;
+        boxqp4(S, gq, lo, hi, dq, cl, capped);
+        bx->capped += capped ? 1 : 0;
+        double Sm[4][4];
+        boxqp_mask(Sm, S, cl);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) S[i][jj] = Sm[i][jj];
+            b[i] = ((cl >> i) & 1) ? 0.0 : b[i];
+        }
+    }
     if (__builtin_amdgcn_ballot_w64(!lu_solve4_nopivot(S, b, x)) != 0ull) lu_solve4_fallback(S, b, x);
     {
         double keep = x[0] + x[1] + x[2] + x[3];
         asm volatile("" : "+v"(keep));
     }
     ZM_SWEEP_STAMP(lab, 4);   // the 4 x 4 solve
+    if constexpr (BOX) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = ((cl >> i) & 1) ? 0.0 : x[i];   // (exact zeros also where another row holds a NaN)
+    }
     const double x01 = (g & 1) ? x[1] : x[0];
     const double x23 = (g & 1) ? x[3] : x[2];
     const double xg = (g & 2) ? x23 : x01;
-    const double out = (MODE == 1) ? xg : -xg;  // L_k[g][c] for c < n, l_k[g] for c == NP
+    double out = (MODE == 1) ? xg : -xg;  // L_k[g][c] for c < n, l_k[g] for c == NP
+    if constexpr (BOX) {
+        const double d01 = (g & 1) ? dq[1] : dq[0];
+        const double d23 = (g & 1) ? dq[3] : dq[2];
+        out = (c == NP) ? ((g & 2) ? d23 : d01) : out;
+    }
     if (a.vOut) *a.pOut = out;
     a.pOut -= a.sOut;
     const double lv = a.vL ? out : 0.0;
@@ -261,7 +320,7 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
 #pragma unroll
         for (int i = 0; i < 4; ++i) qu[i] = sm[64 + NP + i];
     }
-    if constexpr (MODE != 1) {
+    if constexpr (MODE != 1 && !BOX) {
         // -1/2 l^T Q_uu l with l = -x, Q_uu x = Q_u  (ilqrUtils.py:170 / :203), on the lanes that solved for l
         if (c == NP) a.vsum -= 0.5 * ((x[0] * qu[0] + x[1] * qu[1]) + (x[2] * qu[2] + x[3] * qu[3]));
     }
@@ -276,6 +335,11 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
         ilqr_lds_sync();
 #pragma unroll
         for (int i = 0; i < 4; ++i) vxn = __builtin_fma(-b0[i], sm[112 + i], vxn);
+    } else if constexpr (BOX) {
+        // v_x'[c] = Q_x[c] + sum_i Q_ux[i][c] l[i]     (the general form's other terms L^T (Q_u + Q_uu l) vanish: L is zero on the
+        //                                               clamped rows, Q_u + Q_uu l on the free ones)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vxn = __builtin_fma(b0[i], dq[i], vxn);
     } else {
         // v_x'[c] = Q_x[c] + sum_i L[i][c] Q_u[i]      (= Q_x - L^T Q_uu l with Q_uu l = -Q_u)
 #pragma unroll
@@ -308,183 +372,73 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
     const double* __restrict__ c_s, const double* __restrict__ vf_s, double* __restrict__ v_out,
     double* __restrict__ vx_out, double* __restrict__ vxx_out, const TrajList tl, const double* __restrict__ Hpk,
     const PairTab ptab) {
-    constexpr int NP = 4 * KS;
-    const int lane = threadIdx.x;
-    const long traj = tl.list ? (long)tl.list[blockIdx.x] : (long)blockIdx.x;
-    if (active && active[traj] == 0) return;  // whole wave leaves: this trajectory keeps its previous policy
-    const int g = lane >> 4, c = lane & 15;
-    __shared__ double sm[ILQR_LDS_DOUBLES];
-    __shared__ double jA[MODE == 2 ? NS_LDS_DOUBLES : 1];
+#define ZM_BOX_SETUP
+#define ZM_BOX_FLAGS
+#define ZM_BOX_ARGS
+#include "ilqr_backward_t16_body.h"
+#undef ZM_BOX_SETUP
+#undef ZM_BOX_FLAGS
+#undef ZM_BOX_ARGS
+}
 
-    IlqrAddr<KS> a;
-    const int nn = n * n, nm = n * m, mm = m * m;
-    const bool cA = c < n;
-    a.cA = cA;
-    const bool cB = (c >= NP) && (c < NP + m);
-    const long last = traj * T + (T - 1);
-    const double* fxt = f_x + last * nn;
-    const double* fut = f_u + last * nm;
-    const double* cxt = c_x + last * n;
-    const double* cut = c_u + last * m;
-    // shared_h: one time-invariant cost Hessian for every trajectory and step (strides 0)
-    const double* cxxt = shared_h ? c_xx : c_xx + last * nn;
-    const double* cuxt = shared_h ? c_ux : c_ux + last * nm;
-    const double* cuut = shared_h ? c_uu : c_uu + last * mm;
-    a.sC = shared_h ? 0 : nn;
-    const bool row0 = g < n;
-    const bool laneA = row0 && cA, laneB = row0 && cB;
-    a.dF = laneA ? 4 * n : laneB ? 4 * m : 0;
-    a.sF = laneB ? nm : nn;
-    a.dC = laneA ? 4 * n : 0;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const int row = 4 * s + g;
-        a.rowok[s] = row < n;
-        a.vF[s] = (row < n) && (cA || cB);
-        a.vC[s] = (row < n) && cA;
+// The same kernel (MODE 0) with input bounds lb <= u <= ub: per step it also reads u_k of the current trajectory and runs the box-QP
+// before the gain solve.  Bounds: row traj * bstride of lb / ub (bstride 0: one box for every trajectory).  qp_capped (optional):
+// += the steps of the trajectory whose QP ended at its pass cap.
+template <int KS>
+__global__ __launch_bounds__(64, 2) void ilqr_backward_box_t16_f64(
+    const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
+    const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
+    const double* __restrict__ c_uu, const double* __restrict__ vf_x, const double* __restrict__ vf_xx,
+    const double* __restrict__ uTraj, const double* __restrict__ lb, const double* __restrict__ ub, const long bstride,
+    const long svx, const long svxx, const int* __restrict__ active, const int shared_h, double* __restrict__ lout,
+    double* __restrict__ Lout, int* __restrict__ qp_capped, const int T, const int n, const int m, const TrajList tl) {
+    constexpr int MODE = 0;
+    // what the other modes and the value outputs of the shared body read
+    const double *const dvec = nullptr, *const f_xx = nullptr, *const f_ux = nullptr, *const f_uu = nullptr, *const Hpk = nullptr;
+    const double *const c_s = nullptr, *const vf_s = nullptr;
+    double *const v_out = nullptr, *const vx_out = nullptr, *const vxx_out = nullptr;
+    const PairTab ptab = PairTab{};
+    BoxStep bx;
+#define ZM_BOX_SETUP                                                              \
+    bx.pu = uTraj + last * m;                                                     \
+    bx.capped = 0;                                                                \
+    for (int i = 0; i < 4; ++i) {                                                 \
+        bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();           \
+        bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();            \
     }
-    a.pF0 = laneA ? (fxt + g * n + c) : laneB ? (fut + g * m + (c - NP)) : fxt;
-    a.pC0 = laneA ? (cxxt + g * n + c) : cxxt;
-    // row NP+g of the stacked Hessian: c_ux[g][c] under the state columns, c_uu[g][c-NP] under the control columns
-    const bool vux = (g < m) && cA, vuu = (g < m) && cB;
-    a.vCu = vux || vuu;
-    a.pCu = vux ? (cuxt + g * n + c) : vuu ? (cuut + g * m + (c - NP)) : cuxt;
-    a.sCu = shared_h ? 0 : (vuu ? mm : nm);
-    a.cu_pad = (g >= m && c == NP + g) ? 1.0 : 0.0;
-    a.vcv = cA || cB;
-    a.pcv = cA ? (cxt + c) : cB ? (cut + (c - NP)) : cxt;
-    a.scv = cB ? m : n;
-    if constexpr (MODE == 1) {
-        const double* dt_ = dvec + last * n;
-        a.pdc = cA ? (dt_ + c) : dt_;
-        a.pdr0 = row0 ? (dt_ + g) : dt_;
-        a.sd = n;
-    }
-    if constexpr (MODE == 2) {
-        const long nnn = (long)nn * n, nmn = (long)nm * n, nmm = (long)nm * m;
-        const double* fxxt = f_xx + last * nnn;
-        const double* fuxt = f_ux + last * nmn;
-        const double* fuut = f_uu + last * nmm;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 4 * r + g;
-            const bool rx = row < n, ru = (row >= NP) && (row < NP + m);
-            // compact index: states 0..n-1, controls n..n+m-1
-            const int ca = rx ? row : (ru ? n + (row - NP) : -1);
-            const int cb = cA ? c : (cB ? n + (c - NP) : -1);
-            a.zc[r] = (ca >= 0 && cb >= 0) ? ca * 17 + cb : -1;   // 17-wide compact index; only its sign is read (a 0/-1 flag changes the generated code)
-            a.zlive[r] = (ca >= 0) && (row == c);
-            if (Hpk != nullptr) {
-                // packed second derivatives (zm_quadratic_dynamics_pairs_list_f64): element (ca, cb) is pair p = (min, max) of the
-                // model's table or structurally zero; H[pt][p][i], i contiguous -> the contraction below runs unchanged with a
-                // unit stride over i and the same summation order as over the full tensors
-                int pidx = -1;
-                if (ca >= 0 && cb >= 0) {
-                    const int lo = ca < cb ? ca : cb, hi = ca < cb ? cb : ca;
-                    for (int q = 0; q < ptab.n; ++q) pidx = (ptab.ab[q] == (unsigned char)(lo * 16 + hi)) ? q : pidx;
-                }
-                const double* Hl = Hpk + last * (long)ptab.n * n;
-                if (pidx >= 0) {
-                    a.pz[r] = Hl + (long)pidx * n;  a.sz[r] = 1;  a.stz[r] = ptab.n * n;
-                } else {   // structurally zero (or padding): the lane contracts don't-care data and contributes an exact 0.0
-                    a.pz[r] = Hl;  a.sz[r] = 0;  a.stz[r] = ptab.n * n;
-                    a.zc[r] = -1;
-                }
-            } else if (f_ux == nullptr && !(rx && cA)) {   // dynamics affine in the controls: f_ux, f_uu are zero and not materialised
-                a.zc[r] = -1;
-                a.pz[r] = fxxt;  a.sz[r] = 0;  a.stz[r] = (int)nnn;
-            } else if (rx && cA) {     // f_xx[i][row][c]
-                a.pz[r] = fxxt + row * n + c;  a.sz[r] = nn;  a.stz[r] = (int)nnn;
-            } else if (rx && cB) {     // (vf_ux)^T: f_ux[i][c-NP][row]
-                a.pz[r] = fuxt + (c - NP) * n + row;  a.sz[r] = nm;  a.stz[r] = (int)nmn;
-            } else if (ru && cA) {     // f_ux[i][row-NP][c]
-                a.pz[r] = fuxt + (row - NP) * n + c;  a.sz[r] = nm;  a.stz[r] = (int)nmn;
-            } else if (ru && cB) {     // f_uu[i][row-NP][c-NP]
-                a.pz[r] = fuut + (row - NP) * m + (c - NP);  a.sz[r] = mm;  a.stz[r] = (int)nmm;
-            } else {                   // padding: finite don't-care data, dropped (zc = -1)
-                a.pz[r] = fxxt;  a.sz[r] = 0;  a.stz[r] = (int)nnn;
-            }
-        }
-    }
-    a.vL = (g < m) && cA;
-    const bool vl = (g < m) && (c == NP);
-    a.vOut = a.vL || vl;
-    a.pOut = a.vL ? (Lout + last * nm + g * n + c) : (lout + last * m + g);
-    a.sOut = vl ? m : nm;
+#define ZM_BOX_FLAGS , false, true
+#define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, &bx
+#include "ilqr_backward_t16_body.h"
+#undef ZM_BOX_SETUP
+#undef ZM_BOX_FLAGS
+#undef ZM_BOX_ARGS
+    if (qp_capped && lane == 0) qp_capped[traj] += bx.capped;
+}
 
-    // LDS addresses of this lane's right-hand side: column c of [Q_ux | .] for c < n, the row q (Q_u) for c == NP
-    const bool rhs_qu = (c == NP);
-    const int ob0 = rhs_qu ? (64 + NP + 0) : (0 * 16 + c);
-    const int ob1 = rhs_qu ? (64 + NP + 1) : (1 * 16 + c);
-    const int ob2 = rhs_qu ? (64 + NP + 2) : (2 * 16 + c);
-    const int ob3 = rhs_qu ? (64 + NP + 3) : (3 * 16 + c);
-    // Q_uu[c][g] as A operand (c < 4): tile row c, column NP+g.  Lanes c >= 4 only feed output rows >= 4 of
-    // Q_uu L, which are never used: they read their own (finite) tile element.
-    const int oqa = (c < 4) ? (c * 16 + NP + g) : (g * 16 + c);
-
-    // terminal value function
-    double Vxx[KS], vxr[KS];
-    {
-        const double* vxx = shared_h ? vf_xx : vf_xx + traj * svxx;
-        const double* vx = vf_x + traj * svx;
+// Test entry of the box-QP (boxqp4.h): one problem per lane.  H (batch, m, m), g, lo, hi (batch, m) -> d (batch, m), the clamped set
+// as a bit mask, the passes taken (BOXQP_CAP where the cap was reached).
+__global__ __launch_bounds__(64) void boxqp_kernel(const double* __restrict__ H, const double* __restrict__ g, const double* __restrict__ lo,
+                                                   const double* __restrict__ hi, double* __restrict__ d_out, int* __restrict__ clamped_out,
+                                                   int* __restrict__ iters_out, const long batch, const int m) {
+    const long p = (long)blockIdx.x * 64 + threadIdx.x;
+    if (p >= batch) return;
+    double Hm[4][4], gv[4], lv[4], hv[4], d[4];
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int row = 4 * s + g;
-            const bool ok = (row < n) && cA;
-            const double t = vxx[ok ? row * n + c : 0];
-            Vxx[s] = ok ? t : 0.0;
-            const double u = vx[row < n ? row : 0];
-            vxr[s] = (row < n) ? u : 0.0;
-        }
-    }
-
-    if (g == 0) sm[80 + c] = cA ? (vf_x + traj * svx)[c] : 0.0;  // v_x (column-indexed), read by MODE 2's contraction
-    ilqr_lds_sync();
-    if constexpr (MODE == 2) {
-        // a DDP step is ~100 matrix products long: operand prefetch buys nothing and its registers are needed elsewhere
-        for (int k2 = T - 1; k2 >= 0; --k2) {
-            IlqrStepRegs<KS> d;
-            ilqr_load_step<KS, MODE>(d, a);
-            ilqr_step<KS, MODE, false>(Vxx, vxr, d, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        }
-    } else {
-    IlqrStepRegs<KS> d0, d1;
-    ilqr_load_step<KS, MODE>(d0, a);
-    if (T >= 2) ilqr_load_step<KS, MODE>(d1, a);
-    int k = T - 1;
-    while (k >= 3) {
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        k -= 2;
-    }
-    if (k == 2) {
-        ilqr_step<KS, MODE, true>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-    } else if (k == 1) {
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d1, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-    } else {
-        ilqr_step<KS, MODE, false>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m);
-    }
-    }
-    // optional: the value function the sweep ends with (riccatiStep_ilqr / _ddp return it: ilqrUtils.py:170, :203)
-    if (vxx_out) {
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int row = 4 * s + g;
-            if (row < n && cA) vxx_out[traj * nn + row * n + c] = Vxx[s];
-        }
+        for (int j = 0; j < 4; ++j) Hm[i][j] = (i < m && j < m) ? H[p * m * m + i * m + j] : (i == j ? 1.0 : 0.0);
+        gv[i] = (i < m) ? g[p * m + i] : 0.0;
+        lv[i] = (i < m) ? lo[p * m + i] : -__builtin_inf();
+        hv[i] = (i < m) ? hi[p * m + i] : __builtin_inf();
     }
-    if (vx_out && g == 0 && cA) vx_out[traj * n + c] = sm[80 + c];
-    if (v_out) {
-        double cs = 0.0;   // sum_k c_k
-        if (c_s)
-            for (int k2 = lane; k2 < T; k2 += 64) cs += c_s[traj * T + k2];
+    int cl = 0;
+    bool capped = false;
+    const int it = boxqp4(Hm, gv, lv, hv, d, cl, capped);
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) cs += __shfl_xor(cs, off, 64);
-        if (g == 0 && c == NP) v_out[traj] = ((vf_s ? vf_s[traj] : 0.0) + cs) + a.vsum;
-    }
+    for (int i = 0; i < 4; ++i)
+        if (i < m) d_out[p * m + i] = d[i];
+    if (clamped_out) clamped_out[p] = cl;
+    if (iters_out) iters_out[p] = it;
 }
 
 }  // namespace zm
@@ -960,6 +914,55 @@ extern "C" int zm_ilqr_backward_list_f64(const double* f_x, const double* f_u, c
     return zm::launch_ilqr<0>(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, nullptr, (long)n, (long)n * n,
                               (const int*)active, shared_hessian ? 1 : 0, l, L, batch, T, n, m, (hipStream_t)stream,
                               zm::DdpTensors{nullptr, nullptr, nullptr}, zm::ValueIO{nullptr, nullptr, nullptr, nullptr, nullptr}, tl);
+}
+
+// Extension; the reference has no counterpart: the iLQR backward pass with input bounds (control-limited DDP).
+extern "C" int zm_ilqr_backward_box_list_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,
+                                             const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                                             const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, const int32_t* list,
+                                             int64_t count, const int32_t* active, int shared_hessian, double* l, double* L,
+                                             int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
+    if (batch == 0 || (list && count == 0)) return ZM_OK;
+    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_box_f64: bad list length");
+    if (!f_x || !f_u || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
+        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_box_f64: null pointer");
+    const int rc = zm_check_sweep_args("zm_ilqr_backward_box_f64", batch, T, n, m);
+    if (rc) return rc;
+    if (const int rb = zm::box_check(box, m, "zm_ilqr_backward_box_f64")) return rb;
+    const zm::TrajList tl{(const int*)list, (long)count};
+    const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const int sh = shared_hessian ? 1 : 0;
+#define ZM_LAUNCH_BOX(KS_)                                                                                                          \
+    hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,   \
+                       uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L, (int*)qp_capped, \
+                       T, n, m, tl)
+    if (n <= 4) ZM_LAUNCH_BOX(1);
+    else if (n <= 8) ZM_LAUNCH_BOX(2);
+    else ZM_LAUNCH_BOX(3);
+#undef ZM_LAUNCH_BOX
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_ilqr_backward_box_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,
+                                        const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                                        const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, int shared_hessian,
+                                        double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
+    return zm_ilqr_backward_box_list_f64(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, nullptr, 0, nullptr,
+                                         shared_hessian, l, L, qp_capped, batch, T, n, m, stream);
+}
+
+extern "C" int zm_boxqp_f64(const double* H, const double* g, const double* lo, const double* hi, double* d_out, int32_t* clamped_out,
+                            int32_t* iters_out, int64_t batch, int m, void* stream) {
+    if (batch == 0) return ZM_OK;
+    if (!H || !g || !lo || !hi || !d_out) return zm::set_error(ZM_EINVAL, "zm_boxqp_f64: null pointer");
+    if (batch < 0 || m < 1) return zm::set_error(ZM_EINVAL, "zm_boxqp_f64: bad size batch=%lld m=%d", (long long)batch, m);
+    if (m > 4) return zm::set_error(ZM_EUNSUPPORTED, "zm_boxqp_f64: m=%d not covered (need m<=4)", m);
+    hipLaunchKernelGGL(zm::boxqp_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, H, g, lo, hi, d_out,
+                       (int*)clamped_out, (int*)iters_out, (long)batch, m);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
 }
 
 extern "C" int zm_ilqr_backward_ex_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,

@@ -15,6 +15,7 @@
 #include <mutex>
 #include <vector>
 
+#include "input_box.h"
 #include "models.h"
 #include "quad_derivs_gen.h"
 #include "track_cost.h"
@@ -145,12 +146,18 @@ struct IlqrCost {
     const zm_trackcost_t* track;
     TrackRef ref;
     const TrackRef* ref_ptr() const { return track ? &ref : nullptr; }
+    // input bounds (zm_ilqr_solve_box_f64; nullptr: none): the sweep and the line search are then the box forms
+    const zm_inputbox_t* box = nullptr;
+    int32_t* qp_capped = nullptr;
 };
 // the line search of the loop: dense (list == nullptr) or over the id list
 static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const double* x0, const double* l, const double* L,
                            const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* list,
                            int64_t count, const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
                            int64_t batch, int T, void* stream) {
+    if (ck.box)
+        return zm_rollout_linesearch_box_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.box, x0, l, L, xPrev, uPrev, alphas,
+                                                  n_alpha, list, count, active, xTraj, uTraj, J, alpha_idx, batch, T, stream);
     if (ck.track)
         return zm_rollout_linesearch_tracking_list_f64(model, ck.track, x0, l, L, xPrev, uPrev, alphas, n_alpha, list, count, active, xTraj,
                                                        uTraj, J, alpha_idx, batch, T, stream);
@@ -313,6 +320,13 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: null pointer");
     if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
+    if (ck.box) {
+        if (ddp) return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: DDP has no box form (ddp must be 0)");
+        if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
+            return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);
+        if (const int rb = zm::box_check(ck.box, m, "zm_ilqr_solve_box_f64")) return rb;
+        if (ck.qp_capped) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
+    }
     if (ck.track && model->kind == ZM_MODEL_LINEAR && (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_tracking_f64: (n=%d, m=%d) not covered (tracking cost: n<=12, m<=4)", n, m);
     uint32_t mask = 0;
@@ -360,7 +374,8 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
 
     double* f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
     double* f_uu = (need_ux && npairs == 0) ? ws + w.f_uu : nullptr;
-    const bool can_all_store = w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
+    // (a box solve: one-lane two-pass line search and full Jacobians only)
+    const bool can_all_store = !ck.box && w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
     // Packed Jacobians (quadcopter): the expansion writes and the ring sweeps read only the structurally nonzero entries of
     // [f_x | f_u] -- 448 B (480 with wind) per point instead of 1 536 B.  ZOPT_AMD_JAC=full or ZOPT_AMD_ILQR_PATH=reg: the full matrices.
     static const bool packed_off = [] {
@@ -369,7 +384,7 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
         return (e && e[0] == 'f') || (r && r[0] == 'r');
     }();
     const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
-    const bool packed = !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
+    const bool packed = !ck.box && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
                         (!ddp || npairs == 28);
     const int njp = windy ? ((zm::QUAD_NJ_WIND + 1) & ~1) : ((zm::QUAD_NJ_STILL + 1) & ~1);
     const unsigned char* jpos = windy ? zm::QUAD_JPOS_WIND : zm::QUAD_JPOS_STILL;
@@ -456,6 +471,10 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
             rc = zm_ddp_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, f_ux, f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
                                           ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L,
                                           batch, T, n, m, st);
+        } else if (ck.box) {
+            rc = zm_ilqr_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
+                                               ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1, ws + w.l, L, ck.qp_capped,
+                                               batch, T, n, m, st);
         } else {
             rc = zm_ilqr_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
                                            ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch, T, n, m, st);
@@ -534,6 +553,36 @@ extern "C" int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trac
                                           int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream) {
     return zm_ilqr_solve_tracking_trace_f64(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork,
                                             xTraj, uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
+}
+
+// Extension; the reference has no counterpart: the iLQR loop with input bounds.
+extern "C" int zm_ilqr_solve_box_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                           const zm_inputbox_t* box, const double* x0, const double* uGuess, int ddp, int max_iter,
+                                           double tol, int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork,
+                                           double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations,
+                                           int32_t* qp_capped, int64_t batch, int T, void* stream, double* J_trace,
+                                           int32_t* alpha_trace) {
+    if (batch == 0) return ZM_OK;
+    if (!box) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_box_f64: null box");
+    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_box_f64: pass exactly one of cost and track");
+    zm::IlqrCost ck = quad_cost(cost);
+    if (track) {
+        if (const int rc = zm::track_check(track, "zm_ilqr_solve_box_f64")) return rc;
+        ck = zm::IlqrCost{true, zm::track_weights(*track), track, zm::track_ref(*track)};
+    }
+    ck.box = box;
+    ck.qp_capped = qp_capped;
+    return ilqr_solve_impl(model, ck, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J,
+                           converged, iterations, batch, T, stream, J_trace, alpha_trace);
+}
+
+extern "C" int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                     const zm_inputbox_t* box, const double* x0, const double* uGuess, int ddp, int max_iter, double tol,
+                                     int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj,
+                                     double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations, int32_t* qp_capped,
+                                     int64_t batch, int T, void* stream) {
+    return zm_ilqr_solve_box_trace_f64(model, cost, track, box, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles,
+                                       iwork, xTraj, uTraj, L, J, converged, iterations, qp_capped, batch, T, stream, nullptr, nullptr);
 }
 
 extern "C" int zm_shutdown(void) { return zm::release_host_slots(); }

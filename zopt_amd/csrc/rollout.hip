@@ -9,6 +9,7 @@
 // jnp.argmin) picks the step; pass 2 re-rolls that step size (bit-identical arithmetic) and its first lane stores the
 // trajectory -- the other 15 rollouts never touch HBM.  This chain is latency/ALU-bound, not HBM-bound: it reads
 // 8(mn + 2m + n) = 544 B per trajectory step.
+#include "input_box.h"
 #include "models.h"
 #include "track_cost.h"
 #include "zm_common.h"
@@ -19,15 +20,25 @@ namespace zm {
 
 // one rollout; STORE: write xTraj/uTraj; returns J (0 when cost == nullptr)
 // TRK: tracking cost -- the cost of step k is that of (x_k - xr_k, u_k - ur_k), rows of trajectory `t` of `tr`
-template <bool STORE, bool TRK = false>
+// BOX: u_k is clipped into [lb, ub], the bounds of trajectory `t` of `bx` (the clip lets a NaN through); the cost may then be absent
+// (cs == nullptr) also in the TRK form
+template <bool STORE, bool TRK = false, bool BOX = false>
 __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_quadcost_t* cs, const double alpha,
                                               const double* __restrict__ x0, const double* __restrict__ l,
                                               const double* __restrict__ L, const double* __restrict__ xPrev,
                                               const double* __restrict__ uPrev, double* __restrict__ xTraj,
                                               double* __restrict__ uTraj, const int T, const TrackRef& tr = TrackRef{},
-                                              const long t = 0) {
+                                              const long t = 0, const BoxRef& bx = BoxRef{}) {
     const int n = md.n, m = md.m;
     double x[MAXN], u[MAXM], xn[MAXN];
+    double blo[BOX ? MAXM : 1], bhi[BOX ? MAXM : 1];
+    if constexpr (BOX) {
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i) {
+            blo[i] = (i < m) ? bx.lb[t * bx.stride + i] : -__builtin_inf();
+            bhi[i] = (i < m) ? bx.ub[t * bx.stride + i] : __builtin_inf();
+        }
+    }
 #pragma unroll
     for (int i = 0; i < MAXN; ++i) x[i] = (i < n) ? x0[i] : 0.0;
     if (STORE) {
@@ -50,15 +61,18 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
                 for (int j = 0; j < MAXN; ++j)
                     if (j < n) s = __builtin_fma(Lk[i * n + j], dx[j], s);
                 u[i] = (alpha * l[(long)k * m + i] + s) + uPrev[(long)k * m + i];   // pytrees.py:220, ilqrUtils.py:60
+                if constexpr (BOX) u[i] = clip_nan(u[i], blo[i], bhi[i]);
             } else {
                 u[i] = 0.0;
             }
         }
         if constexpr (TRK) {
-            double ex[MAXN], eu[MAXM];
-            track_diff(ex, x, track_xrow(tr, t, k), n);
-            track_diff(eu, u, track_urow(tr, t, k), m);
-            J += running_cost(*cs, n, m, ex, eu);
+            if (!BOX || cs) {
+                double ex[MAXN], eu[MAXM];
+                track_diff(ex, x, track_xrow(tr, t, k), n);
+                track_diff(eu, u, track_urow(tr, t, k), m);
+                J += running_cost(*cs, n, m, ex, eu);
+            }
         } else {
             if (cs) J += running_cost(*cs, n, m, x, u);
         }
@@ -75,9 +89,11 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
         }
     }
     if constexpr (TRK) {
-        double ex[MAXN];
-        track_diff(ex, x, track_xrow(tr, t, T), n);
-        J += terminal_cost(*cs, n, ex);
+        if (!BOX || cs) {
+            double ex[MAXN];
+            track_diff(ex, x, track_xrow(tr, t, T), n);
+            J += terminal_cost(*cs, n, ex);
+        }
     } else {
         if (cs) J += terminal_cost(*cs, n, x);
     }
@@ -120,13 +136,31 @@ __global__ __launch_bounds__(64) void rollout_linesearch_track_kernel(const zm_m
 }
 #undef ZM_TRK_FLAG
 #undef ZM_TRK_ARGS
+// the same line search with input bounds (zm_inputbox_t), on either cost: the tracking form, whose reference is null for a
+// zm_quadcost_t (the differences are then the values themselves, bit for bit)
+#define ZM_TRK_FLAG , true, true
+#define ZM_TRK_ARGS , tr, t, bx
+template <int NA>
+__global__ __launch_bounds__(64) void rollout_linesearch_box_kernel(const zm_model_t md, const zm_quadcost_t cost, const bool has_cost,
+                                                                    const TrackRef tr, const BoxRef bx, const double* __restrict__ x0,
+                                                                    const double* __restrict__ l, const double* __restrict__ L,
+                                                                    const double* __restrict__ xPrev, const double* __restrict__ uPrev,
+                                                                    const double* __restrict__ alphas, const int n_alpha,
+                                                                    const int* __restrict__ active, const int* __restrict__ list,
+                                                                    const long count, double* __restrict__ xTraj,
+                                                                    double* __restrict__ uTraj, double* __restrict__ Jout,
+                                                                    int* __restrict__ idx_out, const long batch, const int T) {
+#include "rollout_linesearch_body.h"
+}
+#undef ZM_TRK_FLAG
+#undef ZM_TRK_ARGS
 
 // rollout_fast.hip: compile-time (n, m) = (12, 4), 16 step sizes
 int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R, const double* Qf, int diagonal, const double* x0,
                           const double* l, const double* L, const double* xPrev, const double* uPrev,
                           const double* alphas, int n_alpha, const int* active, const int* list, int64_t count, double* xTraj,
                           double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch,
-                          const TrackRef* track);
+                          const TrackRef* track, const BoxRef* box = nullptr);
 
 }  // namespace zm
 
@@ -141,7 +175,8 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
                                          const double* alphas, int n_alpha, const int32_t* active, const int32_t* list,
                                          int64_t count, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
                                          int64_t batch, int T, void* stream, double* scratch = nullptr,
-                                         const zm::TrackRef* track = nullptr) {
+                                         const zm::TrackRef* track = nullptr, const zm::BoxRef* box = nullptr) {
+    // box != nullptr: the inputs are clipped into it (the *_box_* entry points); one lane per rollout, two passes
     // track != nullptr: `cost` holds the weights of a zm_trackcost_t and *track its reference (the *_tracking_* entry points)
     if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj)
         return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: null pointer");
@@ -173,6 +208,9 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
     if (wide && track)
         return zm::set_error(ZM_EUNSUPPORTED, "zm_rollout_linesearch_tracking_f64: (n=%d, m=%d) not covered (tracking cost: n<=12, m<=4)",
                              md.n, md.m);
+    if (wide && box)
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_rollout_linesearch_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", md.n, md.m);
+    if (box && scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: the input box has no all-store form");
     if (wide) {
         if (scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: all-store mode needs the fast path");
         return zm::rollout_wide_dispatch(md, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, (const int*)active, (const int*)list,
@@ -193,8 +231,21 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
     //  redundant, and still several times faster than the generic lane-per-trajectory kernel with its uncoalesced policy reads)
     if (!force_generic && !windy && (n_alpha == 16 || n_alpha == 1) && md.n == 12 && md.m == 4 && cost && T >= 1)
         return zm::rollout_fast_dispatch(md, cs.Q, cs.R, cs.Qf, cs.diagonal, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, count, xTraj,
-                                         uTraj, J, (int*)alpha_idx, batch, T, st, scratch, track);
+                                         uTraj, J, (int*)alpha_idx, batch, T, st, scratch, track, box);
     if (scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: all-store mode needs the fast path");
+    if (box) {
+        const zm::TrackRef tr = track ? *track : zm::TrackRef{};
+        if (n_alpha == 1)
+            hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<1>), dim3((unsigned)((nslot + 63) / 64)), dim3(64), 0, st, md, cs, hc, tr,
+                               *box, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J,
+                               (int*)alpha_idx, (long)batch, T);
+        else
+            hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<16>), dim3((unsigned)((nslot + 3) / 4)), dim3(64), 0, st, md, cs, hc, tr,
+                               *box, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J,
+                               (int*)alpha_idx, (long)batch, T);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    }
     if (track && n_alpha == 1) {
         const unsigned blocks = (unsigned)((nslot + 63) / 64);
         hipLaunchKernelGGL((zm::rollout_linesearch_track_kernel<1>), dim3(blocks), dim3(64), 0, st, md, cs, *track, x0, l, L, xPrev,
@@ -255,6 +306,39 @@ extern "C" int zm_rollout_linesearch_tracking_f64(const zm_model_t* model, const
                                                   int32_t* alpha_idx, int64_t batch, int T, void* stream) {
     return zm_rollout_linesearch_tracking_list_f64(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, nullptr, 0, active, xTraj, uTraj,
                                                    J, alpha_idx, batch, T, stream);
+}
+
+// Extension; the reference has no counterpart: the line search with input bounds, on a zm_quadcost_t or a zm_trackcost_t.
+extern "C" int zm_rollout_linesearch_box_list_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                                  const zm_inputbox_t* box, const double* x0, const double* l, const double* L,
+                                                  const double* xPrev, const double* uPrev, const double* alphas, int n_alpha,
+                                                  const int32_t* list, int64_t count, const int32_t* active, double* xTraj,
+                                                  double* uTraj, double* J, int32_t* alpha_idx, int64_t batch, int T, void* stream) {
+    if (cost && track) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_box_f64: pass cost or track, not both");
+    if (track)
+        if (const int rc = zm::track_check(track, "zm_rollout_linesearch_box_f64")) return rc;
+    if (!model) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_box_f64: null pointer");
+    const int mm = (model->kind == ZM_MODEL_QUADCOPTER || model->kind == ZM_MODEL_QUADCOPTER_RB) ? 4 : model->m;
+    if (const int rc = zm::box_check(box, mm, "zm_rollout_linesearch_box_f64")) return rc;
+    if (batch == 0) return ZM_OK;
+    const zm::BoxRef bx = zm::box_ref(*box);
+    if (track) {
+        const zm_quadcost_t w = zm::track_weights(*track);
+        const zm::TrackRef tr = zm::track_ref(*track);
+        return rollout_impl(model, &w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
+                            stream, nullptr, &tr, &bx);
+    }
+    return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
+                        stream, nullptr, nullptr, &bx);
+}
+
+extern "C" int zm_rollout_linesearch_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                             const zm_inputbox_t* box, const double* x0, const double* l, const double* L,
+                                             const double* xPrev, const double* uPrev, const double* alphas, int n_alpha,
+                                             const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
+                                             int64_t batch, int T, void* stream) {
+    return zm_rollout_linesearch_box_list_f64(model, cost, track, box, x0, l, L, xPrev, uPrev, alphas, n_alpha, nullptr, 0, active, xTraj,
+                                              uTraj, J, alpha_idx, batch, T, stream);
 }
 
 // Solver-internal (ilqr_solve.hip): the 16-way line search in all-store mode -- every step size's rollout goes to the scratch blocks

@@ -12,6 +12,7 @@
 //  * "all-store" mode (FastArgs::scratch, used by the solvers once few trajectories are left and a launch lasts as long as its
 //    slowest wave's 2 x T dependent steps): EVERY lane stores its rollout into a scratch row [slot][step size], no second pass at
 //    all -- the accept step copies the winner's row.  16x the stores, half the chain.
+#include "input_box.h"
 #include "models.h"
 #include "quad_step.h"
 #include "track_cost.h"
@@ -178,11 +179,13 @@ __device__ __forceinline__ void ref_diff(double (&d)[K], const double (&z)[K], c
     }
 }
 
-template <int KIND, bool DIAG, bool ALL, bool TRK = false>
+// BOX: the inputs are clipped into the trajectory's bounds (eight more registers per lane; the clip lets a NaN through)
+template <int KIND, bool DIAG, bool ALL, bool TRK = false, bool BOX = false>
 // (no __restrict__ on the LDS tables: with it the loop-invariant LDS reads of Q, A, B ... are hoisted into registers --
 //  several hundred VGPRs -- instead of being re-read by broadcast every step)
 __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double* Qs, const double* Rs, const double* Qfs,
-                                                const double* As, const double* Bs, const TrackRef& tr = TrackRef{}) {
+                                                const double* As, const double* Bs, const TrackRef& tr = TrackRef{},
+                                                const BoxRef& bx = BoxRef{}) {
     const int lane = threadIdx.x;
     const int grp = lane >> 4, a = lane & 15;
     const long slot = (long)blockIdx.x * 4 + grp;
@@ -232,6 +235,14 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
             rst = tr.uk;
         }
     }
+    double blo[BOX ? RM : 1], bhi[BOX ? RM : 1];
+    if constexpr (BOX) {
+#pragma unroll
+        for (int i = 0; i < RM; ++i) {
+            blo[i] = bx.lb[t * bx.stride + i];
+            bhi[i] = bx.ub[t * bx.stride + i];
+        }
+    }
     const double* x0t = g.x0 + t * RN;
     double* xo = g.xTraj + t * (T + 1) * RN;
     double* uo = g.uTraj + t * T * RM;
@@ -279,6 +290,10 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
             double dx[RN];
             pol_dx(dx, x, neg1, cur);
             pol_controls(u, dx, al, one, cur);
+            if constexpr (BOX) {
+#pragma unroll
+                for (int i = 0; i < RM; ++i) u[i] = clip_nan(u[i], blo[i], bhi[i]);
+            }
             if constexpr (TRK) {   // the cost of (x - xr_k, u - ur_k): quad_form's / the all-store form's arithmetic on the differences
                 asm("s_nop 1" : "+v"(rcur));
                 double ex[RN], eu[RM];
@@ -452,10 +467,53 @@ __global__ __launch_bounds__(64) void rollout_ls_fast_track_kernel(const FastArg
     }
 }
 
+// The tracking kernel's two-pass form with input bounds (zm_inputbox_t); a zm_quadcost_t runs it with a null reference (tr.x == tr.u
+// == nullptr: the differences are the values themselves, bit for bit).
+template <int KIND, bool DIAG_ONLY>
+__global__ __launch_bounds__(64) void rollout_ls_fast_box_kernel(const FastArgs g, const TrackRef tr, const BoxRef bx) {
+    __shared__ double Qs[RN * RN], Rs[RM * RM], Qfs[RN * RN];
+    __shared__ double As[KIND == ZM_MODEL_LINEAR ? RN * RN : 1], Bs[KIND == ZM_MODEL_LINEAR ? RN * RM : 1];
+    const int lane = threadIdx.x;
+    bool offdiag = false;
+    for (int e = lane; e < RN * RN; e += 64) {
+        const double q = g.Q[e], qf = g.Qf[e];
+        Qs[e] = q;
+        Qfs[e] = qf;
+        offdiag |= (e / RN != e % RN) && (q != 0.0 || qf != 0.0);
+    }
+    for (int e = lane; e < RM * RM; e += 64) {
+        const double r = g.R[e];
+        Rs[e] = r;
+        offdiag |= (e / RM != e % RM) && (r != 0.0);
+    }
+    if constexpr (KIND == ZM_MODEL_LINEAR) {
+        for (int e = lane; e < RN * RN; e += 64) As[e] = g.A[e];
+        for (int e = lane; e < RN * RM; e += 64) Bs[e] = g.B[e];
+    }
+    __syncthreads();
+    if constexpr (DIAG_ONLY) {
+        rollout_ls_body<KIND, true, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+    } else {
+        if (__ballot(offdiag) == 0ull)
+            rollout_ls_body<KIND, true, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+        else
+            rollout_ls_body<KIND, false, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+    }
+}
+
 template <int KIND>
-static int launch_fast(const FastArgs& g, const bool diag_only, hipStream_t st, const TrackRef* track) {
+static int launch_fast(const FastArgs& g, const bool diag_only, hipStream_t st, const TrackRef* track, const BoxRef* box = nullptr) {
     const long nslot = g.list ? g.count : g.batch;
     const dim3 grid((unsigned)((nslot + 3) / 4)), block(64);
+    if (box) {
+        const TrackRef tr = track ? *track : TrackRef{};
+        if (diag_only)
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, true>), grid, block, 0, st, g, tr, *box);
+        else
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, false>), grid, block, 0, st, g, tr, *box);
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    }
     if (track) {
         if (g.scratch && diag_only)
             hipLaunchKernelGGL((rollout_ls_fast_track_kernel<KIND, true, true>), grid, block, 0, st, g, *track);
@@ -499,7 +557,7 @@ int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R
                           const double* x0, const double* l, const double* L, const double* xPrev, const double* uPrev,
                           const double* alphas, int n_alpha, const int* active, const int* list, int64_t count, double* xTraj,
                           double* uTraj, double* J, int* idx, int64_t batch, int T, hipStream_t st, double* scratch,
-                          const TrackRef* track) {
+                          const TrackRef* track, const BoxRef* box) {
     FastArgs g{md.A, md.B, md.dt, Q, R, Qf, x0, l, L, xPrev, uPrev, alphas, active, list, (long)count, xTraj, uTraj, J, idx,
                (long)batch, T, n_alpha, scratch, 0};
     // ZOPT_AMD_ROLLOUT_QUAD=0: everything in rollout_ls_fast_kernel (A/B; same results)
@@ -509,7 +567,8 @@ int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R
     }();
     // (the four-lanes-per-rollout kernels have no tracking form: a tracking cost stays in rollout_ls_fast_track_kernel, whose own
     //  second pass and all-store mode serve instead)
-    const bool quad = quad_on && !track && md.kind == ZM_MODEL_QUADCOPTER && diagonal == 1 && n_alpha == 16 && J && idx;
+    // (nor a form with input bounds: a box stays in rollout_ls_fast_box_kernel)
+    const bool quad = quad_on && !track && !box && md.kind == ZM_MODEL_QUADCOPTER && diagonal == 1 && n_alpha == 16 && J && idx;
     const QuadArgs qa{md.dt, Q, R, Qf, x0, l, L, xPrev, uPrev, alphas, active, list, (long)count, xTraj, uTraj, J, idx, (long)batch, T, scratch};
     // all-store line search with at most one wave per SIMD: one trajectory per wave, 4 lanes per step size (78 against 104 us per
     // launch; four-wave workgroups so that up to 1024 waves each get a SIMD).  With more trajectories its 4x as many waves no longer
@@ -522,8 +581,8 @@ int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R
     if (quad && scratch && count <= quad_all_max) return rollout_quad_all(qa, st);
     if (quad && !scratch) g.no_pass2 = 1;                              // two-pass line search: the second pass as its own, densely packed launch
     int rc;
-    if (md.kind == ZM_MODEL_QUADCOPTER) rc = launch_fast<ZM_MODEL_QUADCOPTER>(g, diagonal == 1, st, track);
-    else rc = launch_fast<ZM_MODEL_LINEAR>(g, diagonal == 1, st, track);
+    if (md.kind == ZM_MODEL_QUADCOPTER) rc = launch_fast<ZM_MODEL_QUADCOPTER>(g, diagonal == 1, st, track, box);
+    else rc = launch_fast<ZM_MODEL_LINEAR>(g, diagonal == 1, st, track, box);
     if (rc || !quad || scratch) return rc;
     return rollout_quad_reroll(qa, st);
 }

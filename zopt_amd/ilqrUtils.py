@@ -94,6 +94,53 @@ def backwardPass_ilqr(dynamics, cost, Vf):
     return AffinePolicy(arr.result_like(dl, template), arr.result_like(dL, template))
 
 
+def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
+    """Backwards pass of control-limited iLQR (Tassa, Mansard, Todorov 2014); an extension, the reference has no counterpart.
+
+    As `backwardPass_ilqr`, with bounds `u_lb <= u <= u_ub` on the inputs: per step `l_k` minimises the step's quadratic model over
+    `u_lb - uTraj_k <= l_k <= u_ub - uTraj_k` (a box-constrained QP), the rows of `L_k` of the clamped components are zero and the
+    other rows are `-Q_uu[F,F]^-1 Q_ux[F,:]`.
+
+    Arguments
+    ---------
+        dynamics, cost, Vf : as backwardPass_ilqr
+        uTraj : (..., N, m) inputs of the trajectory the expansions were taken along
+        u_lb, u_ub : scalars, (m,) or (..., m) with leading axes that broadcast to the batch; entries may be -inf / +inf
+
+    Returns
+    -------
+        AffinePolicy(l (..., N, m), L (..., N, m, n))
+    """
+    _, f_x, f_u = _fields(dynamics)[:3]
+    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
+    v, v_x, v_xx = _fields(Vf)
+    shp = _shape(f_u)
+    if len(shp) < 3:
+        raise ValueError("f_u must have shape (..., N, n, m)")
+    lead, (N, n, m) = shp[:-3], shp[-3:]
+    if n > _models.INPUTBOX_MAX_N or m > _models.INPUTBOX_MAX_M:
+        raise ValueError(f"backwardPass_ilqr_box: (n={n}, m={m}) not covered (need n <= 12, m <= 4)")
+    expect = {"f_x": (f_x, lead + (N, n, n)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
+              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
+              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n)), "uTraj": (uTraj, lead + (N, m))}
+    for name, (X, s) in expect.items():
+        if _shape(X) != s:
+            raise ValueError(f"{name} has shape {_shape(X)}, expected {s}")
+
+    box = _models.InputBox.for_shape(n, m, u_lb, u_ub).box_struct(tuple(lead))
+    dt = torch.float64
+    dev = [arr.to_device(X, dt) for X in (f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx, uTraj)]
+    batch = 1
+    for d in lead:
+        batch *= int(d)
+    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
+    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
+    rc = _lib.lib().zm_ilqr_backward_box_f64(*[t.data_ptr() for t in dev], ctypes.addressof(box), 0, dl.data_ptr(), dL.data_ptr(), None,
+                                             batch, N, n, m, ctypes.c_void_p(arr.stream_ptr(dev[0])))
+    _lib.check(rc, "backwardPass_ilqr_box")
+    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+
+
 def _ddp_large(n, m):
     """Shapes the one-tile DDP kernels (ilqr_backward.hip MODE 2, psd.hip's contracted-dynamics kernel) do not take."""
     return n > 12 or m > 4
@@ -211,6 +258,9 @@ _TRACE = None   # diagnostics: a list; while it is one, the fused drivers run zm
 
 def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     """Shared driver of trajectoryRollout / forwardPass2 on the rollout_linesearch kernel."""
+    box = dynFun if isinstance(dynFun, _models.InputBox) else None
+    if box is not None:
+        dynFun = box.model
     if _generic.is_callable_model(dynFun):
         return _rollout_generic(x0, dynFun, policy, trajPrev, alphas, costFun)
     if not hasattr(dynFun, "c_struct"):
@@ -242,8 +292,14 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     md = dynFun.c_struct()
     cs = (costFun.track_struct(lead, N) if tracking else costFun.c_struct()) if costFun is not None else None
     linesearch = _lib.lib().zm_rollout_linesearch_tracking_f64 if tracking else _lib.lib().zm_rollout_linesearch_f64
+    pcs = ctypes.addressof(cs) if cs is not None else None
+    head = (pcs,)
+    if box is not None:               # (model*, cost* | NULL, track* | NULL, box*, ...)
+        bs = box.box_struct(tuple(lead))
+        linesearch, head = _lib.lib().zm_rollout_linesearch_box_f64, (None if tracking else pcs, pcs if tracking else None,
+                                                                      ctypes.addressof(bs))
     rc = linesearch(
-        ctypes.addressof(md), ctypes.addressof(cs) if cs is not None else None, dx0.data_ptr(), dl.data_ptr(),
+        ctypes.addressof(md), *head, dx0.data_ptr(), dl.data_ptr(),
         dL.data_ptr(), dxp.data_ptr(), dup.data_ptr(), dal.data_ptr(), int(dal.numel()), None, xT.data_ptr(),
         uT.data_ptr(), J.data_ptr() if J is not None else None, None, batch, N, ctypes.c_void_p(arr.stream_ptr(dx0)))
     _lib.check(rc, "rollout")
@@ -511,6 +567,11 @@ def _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIte
 
 def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp):
     model = dynamics
+    box = model if isinstance(model, _models.InputBox) else None
+    if box is not None:
+        if ddp:
+            raise ValueError("differentialDynamicProgramming takes no InputBox: DDP with a box is not built (use iterativeLqr)")
+        model = box.model
     if _generic.is_callable_model(model):
         return _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp)
     if not hasattr(model, "c_struct"):
@@ -556,6 +617,12 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
                   converged.data_ptr(), ctypes.addressof(its), B, N, st)
         solve, solve_trace = ((lib.zm_ilqr_solve_tracking_f64, lib.zm_ilqr_solve_tracking_trace_f64) if tracking else
                               (lib.zm_ilqr_solve_f64, lib.zm_ilqr_solve_trace_f64))
+        if box is not None:           # (model*, cost* | NULL, track* | NULL, box*, x0, ..., iterations, qp_capped, batch, T, stream)
+            bs = box.box_struct(tuple(lead))
+            capped = torch.zeros(B, dtype=torch.int32, device=dev)
+            common = (pmd, None if tracking else pcs, pcs if tracking else None, ctypes.addressof(bs)) + common[2:17] + \
+                (capped.data_ptr(),) + common[17:]
+            solve, solve_trace = lib.zm_ilqr_solve_box_f64, lib.zm_ilqr_solve_box_trace_f64
         if _TRACE is None:
             rc = solve(*common)
         else:
@@ -567,6 +634,8 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
             _TRACE.append(("iterations", int(its.value)))
             _TRACE.append(("J_trace", Jtr[: int(its.value)].cpu().numpy()))
             _TRACE.append(("alpha_trace", atr[: int(its.value)].cpu().numpy()))
+            if box is not None:
+                _TRACE.append(("qp_capped", capped.cpu().numpy()))
     tmpl = uGuess
     fp32_in = (arr.is_torch(tmpl) and tmpl.dtype == torch.float32) or \
         (not arr.is_torch(tmpl) and np.asarray(tmpl).dtype == np.float32)

@@ -278,3 +278,84 @@ class Quadcopter:
         from .pytrees import AffineDynamics
         lin = AffineDynamics.from_function(QuadcopterRigidBody(float(dt)), x0, u0)
         return lin.f_x, lin.f_u
+
+
+class zm_inputbox_t(ctypes.Structure):
+    _fields_ = [("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p), ("stride", ctypes.c_int64)]
+
+
+INPUTBOX_MAX_N, INPUTBOX_MAX_M = 12, 4     # the fused drivers' shapes (zm::MAXN, zm::MAXM)
+
+
+class InputBox:
+    """A registered model with bounds on its inputs, `u_lb <= u <= u_ub` per component: control-limited iLQR (Tassa, Mansard, Todorov
+    2014).  An extension: the reference's iLQR is unconstrained (ilqrUtils.py:260-327).
+
+    u_lb, u_ub: scalars, (m,) or (..., m) with leading axes that broadcast to the batch of the call; an entry of -inf / +inf means no
+    bound on that side of that component, `u_lb == u_ub` fixes a component.  `u_lb > u_ub` and NaN are refused.
+
+    Accepted wherever a registered model is by `iterativeLqr`, `forwardPass2`, `trajectoryRollout` and the simulator: rollouts clip
+    `u_k = clip(alpha l_k + L_k (x_k - xPrev_k) + uPrev_k, u_lb, u_ub)`, the backward pass solves a box-constrained QP per step and
+    zeroes the feedback rows of the clamped inputs.  It is deliberately neither callable nor a device model itself: code that knows
+    nothing of the box (DDP, the expansions) refuses it instead of dropping the bounds."""
+
+    def __init__(self, model, u_lb, u_ub):
+        if isinstance(model, InputBox):
+            raise TypeError("InputBox: the model is an InputBox already")
+        if not hasattr(model, "c_struct"):
+            raise TypeError("InputBox wraps a registered device model (zopt_amd.models.*); the generic-callable path has no box: clip "
+                            "inside the torch callable there")
+        self.model, self.n, self.m = model, int(model.n), int(model.m)
+        if self.n > INPUTBOX_MAX_N or self.m > INPUTBOX_MAX_M:
+            raise ValueError(f"InputBox: (n={self.n}, m={self.m}) not covered -- the box kernels take n <= {INPUTBOX_MAX_N}, "
+                             f"m <= {INPUTBOX_MAX_M}")
+        self._set_bounds(u_lb, u_ub)
+
+    @classmethod
+    def for_shape(cls, n, m, u_lb, u_ub):
+        """the bounds alone, for array-level calls that have no model (ilqrUtils.backwardPass_ilqr_box)"""
+        self = cls.__new__(cls)
+        self.model, self.n, self.m = None, int(n), int(m)
+        self._set_bounds(u_lb, u_ub)
+        return self
+
+    def _set_bounds(self, u_lb, u_ub):
+        host = lambda b: np.asarray(b.detach().cpu().numpy() if arr.is_torch(b) else b, dtype=np.float64)       # noqa: E731
+        lb, ub = host(u_lb), host(u_ub)
+        for name, b in (("u_lb", lb), ("u_ub", ub)):
+            if b.ndim and b.shape[-1] != self.m:
+                raise ValueError(f"InputBox: {name} has shape {b.shape}, expected a scalar, ({self.m},) or (..., {self.m})")
+            if np.isnan(b).any():
+                raise ValueError(f"InputBox: {name} holds a NaN")
+        try:
+            shp = np.broadcast_shapes(lb.shape, ub.shape, (self.m,))
+        except ValueError:
+            raise ValueError(f"InputBox: u_lb {lb.shape} and u_ub {ub.shape} do not broadcast") from None
+        self.u_lb, self.u_ub = np.array(np.broadcast_to(lb, shp)), np.array(np.broadcast_to(ub, shp))
+        if (self.u_lb > self.u_ub).any():
+            raise ValueError("InputBox: u_lb > u_ub")
+        self._dev = {}
+
+    def clip(self, u):
+        """u clipped into the box (NumPy, host side)"""
+        return np.minimum(np.maximum(u, self.u_lb), self.u_ub)
+
+    def box_struct(self, lead):
+        """zm_inputbox_t for a call with batch axes `lead`: one shared row (stride 0) or a row per trajectory (stride m)"""
+        import torch
+        lead = tuple(int(d) for d in lead)
+        if lead not in self._dev:
+            if self.u_lb.ndim == 1:
+                rows, stride = (self.u_lb, self.u_ub), 0
+            else:
+                try:
+                    rows = tuple(np.array(np.broadcast_to(b, lead + (self.m,))) for b in (self.u_lb, self.u_ub))
+                except ValueError:
+                    raise ValueError(f"InputBox: leading axes {self.u_lb.shape[:-1]} of the bounds do not broadcast to the batch "
+                                     f"{lead}") from None
+                stride = self.m
+            self._dev[lead] = tuple(arr.to_device(np.ascontiguousarray(b), torch.float64) for b in rows) + (stride,)
+        lb, ub, stride = self._dev[lead]
+        st = zm_inputbox_t(lb.data_ptr(), ub.data_ptr(), stride)
+        st._owner = (self, lb, ub)      # raw device addresses: keep the arrays behind them alive with the struct
+        return st
