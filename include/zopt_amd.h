@@ -496,13 +496,15 @@ int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost
                                      int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
                                      int32_t* alpha_trace);
 
-/* ---- input box: iLQR with bounds u_lb <= u <= u_ub on the inputs (control-limited DDP: Tassa, Mansard, Todorov 2014) -------------
+/* ---- input box: iLQR and DDP with bounds u_lb <= u <= u_ub on the inputs (control-limited DDP: Tassa, Mansard, Todorov 2014) -------------
  * Every entry of this section is an extension; the reference has no counterpart (its iLQR is unconstrained, ilqrUtils.py:260-327).
  *   rollout / line search:  u_k = clip(alpha l_k + L_k (x_k - xPrev_k) + uPrev_k, lb, ub); the clip lets a NaN through.  With
  *                           infinite bounds the results are those of the unconstrained entries bit for bit.
  *   backward step:          l_k = argmin_d 1/2 d' sym(Q_uu) d + Q_u' d  over  lb - u_k <= d <= ub - u_k  (u_k: the current trajectory's
  *                           input); C = the components at a bound with a multiplier of the right sign (lb == ub: always), F the rest;
  *                           L_k[C,:] = 0, L_k[F,:] = -Q_uu[F,F]^-1 Q_ux[F,:];  v_x' = Q_x + Q_ux' l_k,  v_xx' = Q_xx - L_k' Q_uu L_k.
+ *   DDP backward step:      the same step after Q_xx, Q_ux, Q_uu have received the blocks of the PD-projected (1e-3)
+ *                           vf_zz = sum_i v_x[i] d2f_i/dz2, as in zm_ddp_backward_f64.
  * lb, ub: device pointers to m doubles per row, row t * stride belongs to trajectory t: stride 0 = one box for every trajectory,
  * stride m = a box per trajectory.  An entry may be -inf / +inf; lb <= ub is the caller's to ensure.  Shapes: n <= 12, m <= 4. */
 typedef struct zm_inputbox_t {
@@ -528,6 +530,24 @@ int zm_ilqr_backward_box_f64(const double* f_x, const double* f_u, const double*
                              const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* uTraj,
                              const zm_inputbox_t* box, int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T,
                              int n, int m, void* stream);
+/* zm_ddp_backward_list_f64 / zm_ddp_backward_f64 / zm_ddp_backward_pairs_list_f64 with the box: their arguments and rules (f_ux and
+ * f_uu may be NULL together; the pairs form needs a model that declares Hessian pairs) plus uTraj, box and qp_capped as above.  The
+ * three forms of second derivatives are contracted in the same summation order: equal operands give bitwise equal l, L.  Every
+ * argument is checked before anything is launched. */
+int zm_ddp_backward_box_list_f64(const double* f_x, const double* f_u, const double* f_xx, const double* f_ux, const double* f_uu,
+                                 const double* c_x, const double* c_u, const double* c_xx, const double* c_ux, const double* c_uu,
+                                 const double* vf_x, const double* vf_xx, const double* uTraj, const zm_inputbox_t* box,
+                                 const int32_t* list, int64_t count, const int32_t* active, int shared_hessian, double* l, double* L,
+                                 int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream);
+int zm_ddp_backward_box_f64(const double* f_x, const double* f_u, const double* f_xx, const double* f_ux, const double* f_uu,
+                            const double* c_x, const double* c_u, const double* c_xx, const double* c_ux, const double* c_uu,
+                            const double* vf_x, const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, int shared_hessian,
+                            double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream);
+int zm_ddp_backward_pairs_box_list_f64(const zm_model_t* model, const double* f_x, const double* f_u, const double* H, const double* c_x,
+                                       const double* c_u, const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                                       const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, const int32_t* list,
+                                       int64_t count, const int32_t* active, int shared_hessian, double* l, double* L,
+                                       int32_t* qp_capped, int64_t batch, int T, void* stream);
 /* zm_rollout_linesearch_f64 / _list_f64 with the box.  The cost is `cost` or `track` (exactly one; both NULL only for a plain
  * rollout, n_alpha == 1).  One lane per rollout, two passes. */
 int zm_rollout_linesearch_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -541,8 +561,9 @@ int zm_rollout_linesearch_box_list_f64(const zm_model_t* model, const zm_quadcos
                                        int64_t batch, int T, void* stream);
 /* zm_ilqr_solve_f64 / zm_ilqr_solve_trace_f64 with the box: the same loop on the box sweep and the box line search (full Jacobians,
  * alternating buffers; uGuess is clipped into the box by the initial rollout, every stored uTraj is feasible).  The cost is `cost`
- * or `track` (exactly one).  ddp = 1 is refused with ZM_EUNSUPPORTED.  qp_capped (optional): int32 per trajectory, set to the number
- * of capped QPs over the whole solve.  Workspace: zm_ilqr_solve_workspace_f64(model, batch, T, 0). */
+ * or `track` (exactly one).  ddp = 1: the DDP loop on the box DDP sweep (second derivatives as pairs where the model declares them,
+ * the full tensors otherwise).  qp_capped (optional): int32 per trajectory, set to the number of capped QPs over the whole solve.
+ * Workspace: zm_ilqr_solve_workspace_f64(model, batch, T, ddp). */
 int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track, const zm_inputbox_t* box,
                           const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every, double* workspace,
                           int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,

@@ -184,6 +184,16 @@ SYMBOLS = {
                                       [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "zm_ilqr_backward_box_f64": (ctypes.c_int, [_c_dp] * 11 + [ctypes.c_int] + [_c_dp] * 3 +
                                  [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box*, [list, count, active,] shared_hessian, l, L,
+    #  qp_capped, batch, T, n, m, stream)
+    "zm_ddp_backward_box_list_f64": (ctypes.c_int, [_c_dp] * 15 + [ctypes.c_int64, _c_dp, ctypes.c_int] + [_c_dp] * 3 +
+                                     [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ddp_backward_box_f64": (ctypes.c_int, [_c_dp] * 14 + [ctypes.c_int] + [_c_dp] * 3 +
+                                [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, f_x, f_u, H, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box*, list, count, active, shared_hessian, l, L, qp_capped,
+    #  batch, T, stream)
+    "zm_ddp_backward_pairs_box_list_f64": (ctypes.c_int, [_c_dp] * 14 + [ctypes.c_int64, _c_dp, ctypes.c_int] + [_c_dp] * 3 +
+                                           [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     # (model*, cost* | NULL, track* | NULL, box*, x0, l, L, xPrev, uPrev, alphas, n_alpha, [list, count,] active, xTraj, uTraj, J,
     #  alpha_idx, batch, T, stream)
     "zm_rollout_linesearch_box_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int] + [_c_dp] * 5 +

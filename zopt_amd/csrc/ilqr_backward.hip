@@ -36,7 +36,7 @@
 // K-step), V^T d a column reduction (2 shuffles) re-laid out through LDS; both are kept apart so that a
 // nonsymmetric V is treated exactly as the reference does.
 //
-// BOX (MODE 0 only; an extension, the reference has no counterpart) = the backward pass of control-limited DDP for bounds lb <= u <= ub
+// BOX (MODE 0 and MODE 2; an extension, the reference has no counterpart) = the backward pass of control-limited DDP for bounds lb <= u <= ub
 // on the inputs (Tassa, Mansard, Todorov 2014): per step, with u_k the current trajectory's input,
 //     l = argmin_d 1/2 d^T sym(Q_uu) d + Q_u^T d   over   lb - u_k <= d <= ub - u_k          (boxqp4.h, wave-uniform on registers)
 //     C = the components at a bound with a multiplier of the right sign, F the rest:  L[C,:] = 0,  L[F,:] = -Q_uu[F,F]^-1 Q_ux[F,:]
@@ -145,7 +145,7 @@ struct SweepLab {};
 
 __device__ __forceinline__ void ilqr_lds_sync() { wave_lds_sync(); }
 
-// BOX: what a step of the box-constrained sweep (ilqr_backward_box_t16_f64) carries besides the operands
+// BOX: what a step of a box-constrained sweep (ilqr_backward_box_t16_f64, ddp_backward_box_t16_f64) carries besides the operands
 struct BoxStep {
     const double* pu;      // u_k of the step (the current trajectory's input), walks back by m
     double lb[4], ub[4];   // the trajectory's bounds; -inf / +inf beyond m
@@ -154,8 +154,9 @@ struct BoxStep {
 
 // ZIN (MODE 2, the DMA kernel): the caller has contracted vf_zz = sum_i v_x[i] d2f_i/dz2 already (operands in its LDS ring) and
 // passes the tile in `zin`
-// BOX (MODE 0): l_k is the minimiser of the step's QP over lb - u_k <= d <= ub - u_k (boxqp4.h), the rows of L_k of its clamped
-// components are zero, the others solve the system whose clamped rows and columns are the identity's; v_x' = Q_x + Q_ux^T l_k
+// BOX (MODE 0 and 2): l_k is the minimiser of the step's QP over lb - u_k <= d <= ub - u_k (boxqp4.h), the rows of L_k of its clamped
+// components are zero, the others solve the system whose clamped rows and columns are the identity's; v_x' = Q_x + Q_ux^T l_k.
+// In MODE 2 Q_xx, Q_ux, Q_uu carry the projected vf_zz blocks; nothing else differs.
 template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false>
 __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], IlqrStepRegs<KS>& d, IlqrAddr<KS>& a,
                                           double* sm, const int g, const int c, const int ob0, const int ob1,
@@ -163,9 +164,9 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
                                           const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0}, SweepLab* lab = nullptr,
                                           BoxStep* bx = nullptr) {
     constexpr int NP = 4 * KS;
-    static_assert(!BOX || MODE == 0, "the box-constrained step is the iLQR one");
+    static_assert(!BOX || MODE != 1, "the box-constrained step is the iLQR or the DDP one");
     double uk[4] = {0.0, 0.0, 0.0, 0.0};
-    if constexpr (BOX) {   // in flight under the products of G; every lane reads the same row
+    if constexpr (BOX) {   // in flight under the products of G (MODE 2: and under the projection); every lane reads the same row
 #pragma unroll
         for (int i = 0; i < 4; ++i) uk[i] = bx->pu[i < m ? i : 0];
         bx->pu -= m;
@@ -381,6 +382,17 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
 #undef ZM_BOX_ARGS
 }
 
+// The hooks of the body header for the two kernels with input bounds (ilqr_backward_box_t16_f64, ddp_backward_box_t16_f64)
+#define ZM_BOX_SETUP                                                              \
+    bx.pu = uTraj + last * m;                                                     \
+    bx.capped = 0;                                                                \
+    for (int i = 0; i < 4; ++i) {                                                 \
+        bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();           \
+        bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();            \
+    }
+#define ZM_BOX_FLAGS , false, true
+#define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, &bx
+
 // The same kernel (MODE 0) with input bounds lb <= u <= ub: per step it also reads u_k of the current trajectory and runs the box-QP
 // before the gain solve.  Bounds: row traj * bstride of lb / ub (bstride 0: one box for every trajectory).  qp_capped (optional):
 // += the steps of the trajectory whose QP ended at its pass cap.
@@ -399,21 +411,40 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_box_t16_f64(
     double *const v_out = nullptr, *const vx_out = nullptr, *const vxx_out = nullptr;
     const PairTab ptab = PairTab{};
     BoxStep bx;
-#define ZM_BOX_SETUP                                                              \
-    bx.pu = uTraj + last * m;                                                     \
-    bx.capped = 0;                                                                \
-    for (int i = 0; i < 4; ++i) {                                                 \
-        bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();           \
-        bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();            \
-    }
-#define ZM_BOX_FLAGS , false, true
-#define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, &bx
 #include "ilqr_backward_t16_body.h"
+    if (qp_capped && lane == 0) qp_capped[traj] += bx.capped;
+}
+
+// Waves per SIMD the register budget is set for.  With two, the projection on top of the box step spills at KS = 2 (60 B of scratch)
+// and KS = 3 (220 B); with one, the unified register file holds everything (DESIGN 2.5 has the figures).  The sweep is latency-bound
+// on ~100 dependent matrix products per step: measured at n = 12, one wave without scratch is 6 - 12 % faster per solve than two with
+// it (profiles/ddp_box_bench.txt).  KS = 1 fits two waves without scratch.
+template <int KS>
+constexpr int DDP_BOX_WAVES = (KS == 1) ? 2 : 1;
+
+// The DDP sweep (MODE 2) with the same input bounds: per step the contraction and PD projection of vf_zz, then the box step above on
+// the augmented Q.  Second derivatives as ilqr_backward_t16_f64 takes them: the full tensors, f_ux = f_uu = nullptr (control-affine),
+// or the packed pairs Hpk / ptab.
+template <int KS>
+__global__ __launch_bounds__(64, DDP_BOX_WAVES<KS>) void ddp_backward_box_t16_f64(
+    const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
+    const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
+    const double* __restrict__ c_uu, const double* __restrict__ vf_x, const double* __restrict__ vf_xx,
+    const double* __restrict__ uTraj, const double* __restrict__ lb, const double* __restrict__ ub, const long bstride,
+    const double* __restrict__ f_xx, const double* __restrict__ f_ux, const double* __restrict__ f_uu, const long svx, const long svxx,
+    const int* __restrict__ active, const int shared_h, double* __restrict__ lout, double* __restrict__ Lout, int* __restrict__ qp_capped,
+    const int T, const int n, const int m, const TrajList tl, const double* __restrict__ Hpk, const PairTab ptab) {
+    constexpr int MODE = 2;
+    const double* const dvec = nullptr;
+    const double *const c_s = nullptr, *const vf_s = nullptr;
+    double *const v_out = nullptr, *const vx_out = nullptr, *const vxx_out = nullptr;
+    BoxStep bx;
+#include "ilqr_backward_t16_body.h"
+    if (qp_capped && lane == 0) qp_capped[traj] += bx.capped;
+}
 #undef ZM_BOX_SETUP
 #undef ZM_BOX_FLAGS
 #undef ZM_BOX_ARGS
-    if (qp_capped && lane == 0) qp_capped[traj] += bx.capped;
-}
 
 // Test entry of the box-QP (boxqp4.h): one problem per lane.  H (batch, m, m), g, lo, hi (batch, m) -> d (batch, m), the clamped set
 // as a bit mask, the passes taken (BOXQP_CAP where the cap was reached).
@@ -1048,6 +1079,77 @@ extern "C" int zm_ddp_backward_pairs_list_f64(const zm_model_t* model, const dou
     return zm::launch_ilqr<2>(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, nullptr, (long)n, (long)n * n, (const int*)active,
                               shared_hessian ? 1 : 0, l, L, batch, T, n, m, (hipStream_t)stream, z,
                               zm::ValueIO{nullptr, nullptr, nullptr, nullptr, nullptr}, tl);
+}
+
+// Extension; the reference has no counterpart: the DDP backward pass with input bounds (control-limited DDP with its second-order
+// dynamics terms).  One launcher behind the tensor and the pairs entries; every check has run before it.
+static int launch_ddp_box(const double* f_x, const double* f_u, const zm::DdpTensors& z, const double* c_x,
+                          const double* c_u, const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                          const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, const zm::TrajList tl, const int32_t* active,
+                          int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
+    const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const int sh = shared_hessian ? 1 : 0;
+#define ZM_LAUNCH_DDP_BOX(KS_)                                                                                                       \
+    hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,    \
+                       uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux, z.f_uu, (long)n, (long)n * n, (const int*)active, \
+                       sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab)
+    if (n <= 4) ZM_LAUNCH_DDP_BOX(1);
+    else if (n <= 8) ZM_LAUNCH_DDP_BOX(2);
+    else ZM_LAUNCH_DDP_BOX(3);
+#undef ZM_LAUNCH_DDP_BOX
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_ddp_backward_box_list_f64(const double* f_x, const double* f_u, const double* f_xx, const double* f_ux,
+                                            const double* f_uu, const double* c_x, const double* c_u, const double* c_xx,
+                                            const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx,
+                                            const double* uTraj, const zm_inputbox_t* box, const int32_t* list, int64_t count,
+                                            const int32_t* active, int shared_hessian, double* l, double* L, int32_t* qp_capped,
+                                            int64_t batch, int T, int n, int m, void* stream) {
+    if (batch == 0 || (list && count == 0)) return ZM_OK;
+    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_box_list_f64: bad list length");
+    if (!f_x || !f_u || !f_xx || (!f_ux != !f_uu) || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
+        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_box_list_f64: null pointer (f_ux and f_uu may be NULL together: identically zero)");
+    const int rc = zm_check_sweep_args("zm_ddp_backward_box_list_f64", batch, T, n, m);
+    if (rc) return rc;
+    if ((int64_t)n * n * n >= (int64_t)1 << 31) return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_box_list_f64: n too large");
+    if (const int rb = zm::box_check(box, m, "zm_ddp_backward_box_list_f64")) return rb;
+    return launch_ddp_box(f_x, f_u, zm::DdpTensors{f_xx, f_ux, f_uu}, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,
+                          uTraj, box, zm::TrajList{(const int*)list, (long)count}, active, shared_hessian, l, L, qp_capped, batch, T, n,
+                          m, stream);
+}
+
+extern "C" int zm_ddp_backward_box_f64(const double* f_x, const double* f_u, const double* f_xx, const double* f_ux,
+                                       const double* f_uu, const double* c_x, const double* c_u, const double* c_xx,
+                                       const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx,
+                                       const double* uTraj, const zm_inputbox_t* box, int shared_hessian, double* l, double* L,
+                                       int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
+    return zm_ddp_backward_box_list_f64(f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, nullptr, 0,
+                                        nullptr, shared_hessian, l, L, qp_capped, batch, T, n, m, stream);
+}
+
+extern "C" int zm_ddp_backward_pairs_box_list_f64(const zm_model_t* model, const double* f_x, const double* f_u, const double* H,
+                                                  const double* c_x, const double* c_u, const double* c_xx, const double* c_ux,
+                                                  const double* c_uu, const double* vf_x, const double* vf_xx, const double* uTraj,
+                                                  const zm_inputbox_t* box, const int32_t* list, int64_t count, const int32_t* active,
+                                                  int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T,
+                                                  void* stream) {
+    if (batch == 0 || (list && count == 0)) return ZM_OK;
+    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_box_list_f64: bad list length");
+    if (!model || !f_x || !f_u || !H || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
+        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_box_list_f64: null pointer");
+    const int n = model->n, m = model->m;
+    const int rc = zm_check_sweep_args("zm_ddp_backward_pairs_box_list_f64", batch, T, n, m);
+    if (rc) return rc;
+    const zm::PairTab pt = zm::model_pair_table(model->kind);
+    if (pt.n < 1)
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_pairs_box_list_f64: the model declares no Hessian pairs");
+    if (const int rb = zm::box_check(box, m, "zm_ddp_backward_pairs_box_list_f64")) return rb;
+    return launch_ddp_box(f_x, f_u, zm::DdpTensors{nullptr, nullptr, nullptr, H, pt}, c_x, c_u,
+                          c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, zm::TrajList{(const int*)list, (long)count}, active,
+                          shared_hessian, l, L, qp_capped, batch, T, n, m, stream);
 }
 
 extern "C" int zm_ddp_backward_f64(const double* f_x, const double* f_u, const double* f_xx, const double* f_ux,

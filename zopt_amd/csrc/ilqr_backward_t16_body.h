@@ -1,6 +1,7 @@
 // Body of the register-prefetch sweep kernel ilqr_backward_t16_f64 (ilqr_backward.hip).
-// A function BODY, not a header: #included verbatim inside ilqr_backward_t16_f64 and ilqr_backward_box_t16_f64, so that the kernel
-// that existed before the input box compiles from the very same tokens (same ISA; tools/isa_identity.py checks it).
+// A function BODY, not a header: #included verbatim inside ilqr_backward_t16_f64, ilqr_backward_box_t16_f64 and (MODE 2 with the box
+// hooks) ddp_backward_box_t16_f64, so that the kernel that existed before the input box compiles from the very same tokens (same ISA;
+// tools/isa_identity.py checks it).
 // The hooks ZM_BOX_SETUP (statements after the lane roles are known), ZM_BOX_FLAGS (further template arguments of ilqr_step) and
 // ZM_BOX_ARGS (its further arguments) expand to nothing in the kernel without a box.
     constexpr int NP = 4 * KS;

@@ -146,7 +146,7 @@ struct IlqrCost {
     const zm_trackcost_t* track;
     TrackRef ref;
     const TrackRef* ref_ptr() const { return track ? &ref : nullptr; }
-    // input bounds (zm_ilqr_solve_box_f64; nullptr: none): the sweep and the line search are then the box forms
+    // input bounds (zm_ilqr_solve_box_f64; nullptr: none): the sweep (iLQR or DDP) and the line search are then the box forms
     const zm_inputbox_t* box = nullptr;
     int32_t* qp_capped = nullptr;
 };
@@ -321,7 +321,6 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
     if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
     if (ck.box) {
-        if (ddp) return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: DDP has no box form (ddp must be 0)");
         if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
             return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);
         if (const int rb = zm::box_check(ck.box, m, "zm_ilqr_solve_box_f64")) return rb;
@@ -457,6 +456,22 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
                                             ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, (const int*)active, ws + w.l, L, batch, T,
                                             (hipStream_t)st, zm::TrajList{(const int*)list, (long)count}, sparse_h ? nhs : 0, hdense, nh);
             if (rc == ZM_EUNSUPPORTED) return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: packed sweep refused its operands");
+        } else if (ddp && ck.box) {
+            // DDP with input bounds: full Jacobians, the second derivatives as pairs where the model declares them, the register sweep
+            // with the box-QP per step on the current inputs
+            if (npairs > 0) {
+                rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
+                if (rc) return rc;
+                rc = zm_ddp_backward_pairs_box_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                        ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count,
+                                                        active, 1, ws + w.l, L, ck.qp_capped, batch, T, st);
+            } else {
+                rc = zm_quadratic_dynamics_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, f_ux, f_uu, batch, T, st);
+                if (rc) return rc;
+                rc = zm_ddp_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, f_ux, f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                  ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1,
+                                                  ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
+            }
         } else if (ddp && npairs > 0) {
             // packed second derivatives: 28 x 12 doubles per point for the quadcopter instead of the zero-filled (n,n,n) tensors
             // (2.7 KB instead of 13.8 KB written by the expansion and read back by the sweep, same arithmetic)
@@ -555,7 +570,7 @@ extern "C" int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trac
                                             xTraj, uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
 }
 
-// Extension; the reference has no counterpart: the iLQR loop with input bounds.
+// Extension; the reference has no counterpart: the iLQR (ddp = 0) or DDP (ddp = 1) loop with input bounds.
 extern "C" int zm_ilqr_solve_box_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
                                            const zm_inputbox_t* box, const double* x0, const double* uGuess, int ddp, int max_iter,
                                            double tol, int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork,

@@ -508,6 +508,61 @@ def backwardPass_ddp(dynamics, cost, Vf):
     return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
 
 
+def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
+    """Backwards pass of control-limited DDP (Tassa, Mansard, Todorov 2014) with the second-order dynamics terms; an extension, the
+    reference has no counterpart.
+
+    As `backwardPass_ddp` (per step `Q_xx`, `Q_ux`, `Q_uu` receive the blocks of the PD-projected `sum_i v_x[i] d2f_i/dz2`), with
+    the bounds of `backwardPass_ilqr_box`: `l_k` minimises the step's quadratic model over `u_lb - uTraj_k <= l_k <= u_ub - uTraj_k`,
+    the rows of `L_k` of the clamped components are zero.
+
+    Arguments
+    ---------
+        dynamics : QuadraticDynamics(f, f_x, f_u, f_xx, f_ux, f_uu) as backwardPass_ddp; f_ux and f_uu may both be None for dynamics
+                   affine in the controls (they are identically zero and are neither stored nor read)
+        cost, Vf : as backwardPass_ilqr
+        uTraj : (..., N, m) inputs of the trajectory the expansions were taken along
+        u_lb, u_ub : scalars, (m,) or (..., m) with leading axes that broadcast to the batch; entries may be -inf / +inf
+
+    Returns
+    -------
+        AffinePolicy(l (..., N, m), L (..., N, m, n))
+    """
+    _, f_x, f_u, f_xx, f_ux, f_uu = _fields(dynamics)
+    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
+    v, v_x, v_xx = _fields(Vf)
+    shp = _shape(f_u)
+    if len(shp) < 3:
+        raise ValueError("f_u must have shape (..., N, n, m)")
+    lead, (N, n, m) = shp[:-3], shp[-3:]
+    if n > _models.INPUTBOX_MAX_N or m > _models.INPUTBOX_MAX_M:
+        raise ValueError(f"backwardPass_ddp_box: (n={n}, m={m}) not covered (need n <= 12, m <= 4)")
+    affine = f_ux is None and f_uu is None
+    expect = {"f_x": (f_x, lead + (N, n, n)), "f_xx": (f_xx, lead + (N, n, n, n)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
+              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
+              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n)), "uTraj": (uTraj, lead + (N, m))}
+    if not affine:
+        if f_ux is None or f_uu is None:
+            raise ValueError("f_ux and f_uu are None together or not at all")
+        expect.update({"f_ux": (f_ux, lead + (N, n, m, n)), "f_uu": (f_uu, lead + (N, n, m, m))})
+    for name, (X, s_) in expect.items():
+        if _shape(X) != s_:
+            raise ValueError(f"{name} has shape {_shape(X)}, expected {s_}")
+
+    box = _models.InputBox.for_shape(n, m, u_lb, u_ub).box_struct(tuple(lead))
+    dt = torch.float64
+    dev = [None if X is None else arr.to_device(X, dt) for X in (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx, uTraj)]
+    batch = 1
+    for d in lead:
+        batch *= int(d)
+    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
+    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
+    rc = _lib.lib().zm_ddp_backward_box_f64(*[None if t is None else t.data_ptr() for t in dev], ctypes.addressof(box), 0, dl.data_ptr(), dL.data_ptr(), None,
+                                            batch, N, n, m, ctypes.c_void_p(arr.stream_ptr(dev[0])))
+    _lib.check(rc, "backwardPass_ddp_box")
+    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+
+
 def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
     """Iterative LQR algorithm (reference ilqrUtils.py:260-327), batched and device-resident.
 
@@ -538,7 +593,8 @@ def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, t
 def differentialDynamicProgramming(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
     """Differential dynamic programming algorithm (reference ilqrUtils.py:330-397): `iterativeLqr` with the second-order
     expansion of the dynamics (QuadraticDynamics.from_trajectory, :365) and `backwardPass_ddp` (:373).  Same arguments
-    and return values as `iterativeLqr`."""
+    and return values as `iterativeLqr`.  A `models.InputBox` around a quadcopter model is solved as by `iterativeLqr`, on
+    `backwardPass_ddp_box`; around a LinearModel it is refused (no second derivatives: `iterativeLqr` is the call)."""
     return _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp=True)
 
 
@@ -569,8 +625,9 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     model = dynamics
     box = model if isinstance(model, _models.InputBox) else None
     if box is not None:
-        if ddp:
-            raise ValueError("differentialDynamicProgramming takes no InputBox: DDP with a box is not built (use iterativeLqr)")
+        if ddp and isinstance(box.model, _models.LinearModel):   # (before anything touches the device)
+            raise ValueError("differentialDynamicProgramming takes no InputBox around a LinearModel: a linear model has no second "
+                             "derivatives, DDP is iLQR there (use iterativeLqr)")
         model = box.model
     if _generic.is_callable_model(model):
         return _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp)

@@ -294,10 +294,11 @@ class InputBox:
     u_lb, u_ub: scalars, (m,) or (..., m) with leading axes that broadcast to the batch of the call; an entry of -inf / +inf means no
     bound on that side of that component, `u_lb == u_ub` fixes a component.  `u_lb > u_ub` and NaN are refused.
 
-    Accepted wherever a registered model is by `iterativeLqr`, `forwardPass2`, `trajectoryRollout` and the simulator: rollouts clip
+    Accepted wherever a registered model is by `iterativeLqr`, `differentialDynamicProgramming` (quadcopter models), `forwardPass2`,
+    `trajectoryRollout` and the simulator: rollouts clip
     `u_k = clip(alpha l_k + L_k (x_k - xPrev_k) + uPrev_k, u_lb, u_ub)`, the backward pass solves a box-constrained QP per step and
     zeroes the feedback rows of the clamped inputs.  It is deliberately neither callable nor a device model itself: code that knows
-    nothing of the box (DDP, the expansions) refuses it instead of dropping the bounds."""
+    nothing of the box (the expansions, the generic-callable path) refuses it instead of dropping the bounds."""
 
     def __init__(self, model, u_lb, u_ub):
         if isinstance(model, InputBox):
