@@ -574,6 +574,92 @@ int zm_ilqr_solve_box_trace_f64(const zm_model_t* model, const zm_quadcost_t* co
                                 double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations, int32_t* qp_capped,
                                 int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace);
 
+/* ---- state box: iLQR with bounds x_lb <= x_k <= x_ub on the states, k = 1..T, by an augmented-Lagrangian (AL) outer loop around the
+ * fused iLQR (AL-iLQR: Howell, Jackson, Manchester 2019) --------------------------------------------------------------------------------
+ * Every entry of this section is an extension; the reference has no counterpart (its iLQR is unconstrained, ilqrUtils.py:260-327).
+ * Per trajectory t a penalty mu_t > 0 and multipliers lam_ub[k][i] >= 0, lam_lb[k][i] >= 0; row k = 0 is never constrained (x_0 is
+ * given).  For k = 1..T, i < n, with pos(s) = s > 0 ? s : 0 (a NaN gives 0):
+ *     s_ub = lam_ub + mu (x_i - ub_i),   s_lb = lam_lb + mu (lb_i - x_i)
+ *     psi  = (pos(s_ub)^2 - lam_ub^2 + pos(s_lb)^2 - lam_lb^2) / (2 mu),   g_i = pos(s_ub) - pos(s_lb),   h_i = mu ((s_ub > 0) + (s_lb > 0))
+ *   cost:        J_AL = J_cost + P, P = sum_{k=1..T} sum_i psi in an accumulator of its own (k, i ascending), added once at the end.
+ *                With infinite bounds and zero multipliers P is exactly 0.0.
+ *   expansion:   c_x[k] += g_k (1 <= k < T), v_x += g_T; the cost Hessian of step k is c_xx + diag h_k, the terminal one v_xx + diag h_T.
+ *   outer loop:  lam = 0, mu = mu0; per outer iteration an inner iLQR solve on J_AL over the trajectories that are not done (from the
+ *                stored inputs, policy (u, L = 0)), then viol_t = max(0, max(x - ub), max(lb - x)) over k >= 1 (NaN if a state is);
+ *                done = the inner solve converged and viol_t <= ctol -- nothing of a done trajectory is touched again; otherwise, if
+ *                another outer iteration follows, lam <- pos(s) and mu_t <- min(mu_t growth, mu_max).
+ * lb, ub: device pointers to n doubles per row, row t * stride belongs to trajectory t (stride 0: shared, n: per trajectory); an entry
+ * may be -inf / +inf, lb == ub is allowed.  lam_lb, lam_ub: (batch, T+1, n); mu: (batch).  Shapes: n <= 12, m <= 4. */
+typedef struct zm_statebox_t {
+    const double* lb;
+    const double* ub;
+    int64_t stride;
+    double* lam_lb;
+    double* lam_ub;
+    double* mu;
+} zm_statebox_t;
+
+/* zm_rollout_linesearch_box_f64 / _list_f64 on J_AL: `box` may be NULL (no input bounds); the cost is `cost` or `track` (exactly one).
+ * J <- J_AL, J_cost (optional) <- the cost without the penalty, both of the winner.  One lane per rollout, two passes. */
+int zm_rollout_linesearch_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                    const zm_inputbox_t* box, const zm_statebox_t* sbox, const double* x0, const double* l, const double* L,
+                                    const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* active,
+                                    double* xTraj, double* uTraj, double* J, double* J_cost, int32_t* alpha_idx, int64_t batch, int T,
+                                    void* stream);
+int zm_rollout_linesearch_state_list_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                         const zm_inputbox_t* box, const zm_statebox_t* sbox, const double* x0, const double* l,
+                                         const double* L, const double* xPrev, const double* uPrev, const double* alphas, int n_alpha,
+                                         const int32_t* list, int64_t count, const int32_t* active, double* xTraj, double* uTraj,
+                                         double* J, double* J_cost, int32_t* alpha_idx, int64_t batch, int T, void* stream);
+/* The penalty's part of the expansion along xTraj (batch, T+1, n), after the cost's: c_x (batch, T, n) rows 1..T-1 += g_k,
+ * v_x (batch, n) += g_T, h (batch, T+1, n) <- the diagonal addend (row 0 zero).  list (may be NULL) / active: as elsewhere; the rows
+ * of other trajectories are not touched. */
+int zm_state_penalty_expand_list_f64(const zm_statebox_t* sbox, const double* xTraj, const int32_t* list, int64_t count,
+                                     const int32_t* active, double* c_x, double* v_x, double* h, int64_t batch, int T, int n,
+                                     void* stream);
+/* zm_ilqr_backward_list_f64 / _box_list_f64 on the cost Hessians c_xx + diag h_k (k = 0..T-1) and v_xx + diag h_T, h (batch, T+1, n):
+ * every row is read, row 0 included (zm_state_penalty_expand_list_f64 writes zeros there; a caller's own h must do the same if step 0
+ * is to keep its Hessian).  box and uTraj may be NULL together (no input bounds).  The register-prefetch sweep only (n <= 12, m <= 4). */
+int zm_ilqr_backward_state_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
+                               const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* h,
+                               const double* uTraj, const zm_inputbox_t* box, int shared_hessian, double* l, double* L,
+                               int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream);
+int zm_ilqr_backward_state_list_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
+                                    const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* h,
+                                    const double* uTraj, const zm_inputbox_t* box, const int32_t* list, int64_t count,
+                                    const int32_t* active, int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch,
+                                    int T, int n, int m, void* stream);
+/* Between two inner solves, for every trajectory with active[t] != 0 (the others are not touched): violation[t] <- viol_t;
+ * done = converged[t] && viol_t <= ctol; converged[t] <- done, active[t] <- !done; where not done and `update` != 0: lam <- pos(s),
+ * mu_t <- min(mu_t growth, mu_max).  outer_count (optional, int32 per trajectory) += 1; remaining (optional, one int32) += the number
+ * of trajectories that are not done. */
+int zm_state_multiplier_update_f64(const zm_statebox_t* sbox, const double* xTraj, int32_t* active, int32_t* converged,
+                                   double* violation, int32_t* outer_count, int32_t* remaining, double ctol, double growth,
+                                   double mu_max, int update, int64_t batch, int T, int n, void* stream);
+/* Doubles of workspace zm_ilqr_solve_state_f64 needs (-1: cannot be sized); iwork as zm_ilqr_solve_f64 (2 batch + 2 int32). */
+int64_t zm_ilqr_solve_state_workspace_f64(const zm_model_t* model, int64_t batch, int T);
+/* The AL loop as one call (host code around the loop of zm_ilqr_solve_f64, nothing in between but launches).  The cost is `cost` or
+ * `track` (exactly one); `box` (optional) adds input bounds: rollouts clip, the backward step is the box-QP step.  ddp must be 0
+ * (ZM_EUNSUPPORTED otherwise).  sbox: the caller's bounds and its arrays for the multipliers and mu (outputs: started at 0 / mu0).
+ * Outputs per trajectory: J <- the cost WITHOUT the penalty of the returned trajectory, converged <- done, violation,
+ * outer_iterations (optional) <- the outer iterations it took part in, inner_iterations (optional, (outer, batch)) <- its iLQR
+ * iterations in each of them; iterations (host, optional) <- outer iterations run.  Every argument is checked before any launch.
+ * The trace form adds J_trace / alpha_trace ((outer * max_iter, batch): row j * max_iter + it <- J_AL after the acceptance step and
+ * the winning step index) and violation_trace / mu_trace ((outer, batch): after / during outer iteration j); each may be NULL. */
+int zm_ilqr_solve_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track, const zm_inputbox_t* box,
+                            const zm_statebox_t* sbox, double mu0, double growth, double mu_max, int outer, double ctol, const double* x0,
+                            const double* uGuess, int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                            int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
+                            int32_t* converged, double* violation, int32_t* outer_iterations, int32_t* inner_iterations,
+                            int32_t* iterations, int32_t* qp_capped, int64_t batch, int T, void* stream);
+int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                  const zm_inputbox_t* box, const zm_statebox_t* sbox, double mu0, double growth, double mu_max, int outer,
+                                  double ctol, const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every,
+                                  double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L,
+                                  double* J, int32_t* converged, double* violation, int32_t* outer_iterations,
+                                  int32_t* inner_iterations, int32_t* iterations, int32_t* qp_capped, int64_t batch, int T, void* stream,
+                                  double* J_trace, int32_t* alpha_trace, double* violation_trace, double* mu_trace);
+
 /* Same, with OSQP's over-relaxation `alpha` in (0, 2) (OSQP / cvxpy default 1.6, which is what the reference's
  * `prob.solve(**kwargs)` runs with, mpcUtils.py:77): the relaxed iterate alpha w + (1 - alpha) y_prev enters the projection and
  * the dual update; residuals are those of the unrelaxed iterate.  alpha = 1 is zm_mpc_solve_adaptive_f64. */

@@ -207,6 +207,35 @@ SYMBOLS = {
     "zm_ilqr_solve_box_trace_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
                                                                ctypes.c_int64] + [_c_dp] * 8 +
                                     [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
+    # state box (extension; the reference has no counterpart)
+    # (model*, cost* | NULL, track* | NULL, box* | NULL, sbox*, x0, l, L, xPrev, uPrev, alphas, n_alpha, [list, count,] active, xTraj,
+    #  uTraj, J, J_cost | NULL, alpha_idx, batch, T, stream)
+    "zm_rollout_linesearch_state_f64": (ctypes.c_int, [_c_dp] * 11 + [ctypes.c_int] + [_c_dp] * 6 +
+                                        [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_rollout_linesearch_state_list_f64": (ctypes.c_int, [_c_dp] * 11 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 6 +
+                                             [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (sbox*, xTraj, list | NULL, count, active | NULL, c_x, v_x, h, batch, T, n, stream)
+    "zm_state_penalty_expand_list_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64] + [_c_dp] * 4 +
+                                         [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, h, uTraj | NULL, box* | NULL, [list, count, active,] shared_hessian, l, L,
+    #  qp_capped, batch, T, n, m, stream)
+    "zm_ilqr_backward_state_f64": (ctypes.c_int, [_c_dp] * 12 + [ctypes.c_int] + [_c_dp] * 3 +
+                                   [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_backward_state_list_f64": (ctypes.c_int, [_c_dp] * 13 + [ctypes.c_int64, _c_dp, ctypes.c_int] + [_c_dp] * 3 +
+                                        [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # (sbox*, xTraj, active, converged, violation, outer_count | NULL, remaining | NULL, ctol, growth, mu_max, update, batch, T, n, stream)
+    "zm_state_multiplier_update_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_double] * 3 +
+                                       [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_solve_state_workspace_f64": (ctypes.c_int64, [_c_dp, ctypes.c_int64, ctypes.c_int]),
+    # (model*, cost* | NULL, track* | NULL, box* | NULL, sbox*, mu0, growth, mu_max, outer, ctol, x0, uGuess, ddp, max_iter, tol,
+    #  sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged, violation, outer_iterations | NULL,
+    #  inner_iterations | NULL, iterations (host), qp_capped | NULL, batch, T, stream[, J_trace, alpha_trace, violation_trace, mu_trace])
+    "zm_ilqr_solve_state_f64": (ctypes.c_int, [_c_dp] * 5 + [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_double] + [_c_dp] * 2 +
+                                [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] + [_c_dp] * 11 +
+                                [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_ilqr_solve_state_trace_f64": (ctypes.c_int, [_c_dp] * 5 + [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_double] + [_c_dp] * 2 +
+                                      [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] + [_c_dp] * 11 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p] + [_c_dp] * 4),
     "zm_model_nonlinear_mask": (ctypes.c_int, [_c_dp, _c_dp]),
     "zm_psd_project_f64": (ctypes.c_int, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "zm_condition_cost_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,

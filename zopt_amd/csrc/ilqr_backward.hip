@@ -60,6 +60,7 @@ struct IlqrStepRegs {
     double cv;      // [c_x ; c_u][c]  (column-indexed)
     double dc;      // MODE 1: d[c]       (column-indexed)
     double dr[KS];  // MODE 1: d[4s+g]    (row-indexed)
+    double hd;      // PEN: h_k[c] on the lanes of the Hessian's diagonal (row == c), 0 elsewhere
 };
 
 // optional compacted list of trajectory ids: block b works on list[b] (grid = count) instead of on trajectory b (grid = batch)
@@ -87,8 +88,17 @@ struct IlqrAddr {
     double cu_pad;
 };
 
-template <int KS, int MODE>
-__device__ __forceinline__ void ilqr_load_step(IlqrStepRegs<KS>& d, IlqrAddr<KS>& a) {
+// PEN: what a step of a sweep with a state-box penalty (ilqr_backward_pen_t16_f64, ilqr_backward_box_pen_t16_f64) carries besides the
+// operands: the diagonal addend h_k (batch, T+1, n) of the step's cost Hessian, one double per lane of the tile's diagonal
+struct PenStep {
+    const double* ph;   // the lane's entry of h_k (element 0 of the row off the diagonal), walks back by sh
+    int sh;
+    int hs;             // the K-step s whose tile element (4s+g, c) is the diagonal one; -1 off the diagonal
+    bool hv;
+};
+
+template <int KS, int MODE, bool PEN = false>
+__device__ __forceinline__ void ilqr_load_step(IlqrStepRegs<KS>& d, IlqrAddr<KS>& a, PenStep* pn = nullptr) {
     double f[KS], cc[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) f[s] = a.pF0[a.rowok[s] ? s * a.dF : 0];
@@ -107,6 +117,11 @@ __device__ __forceinline__ void ilqr_load_step(IlqrStepRegs<KS>& d, IlqrAddr<KS>
     }
     d.Cu = a.vCu ? cu : a.cu_pad;
     d.cv = a.vcv ? cv : 0.0;
+    if constexpr (PEN) {
+        const double hh = *pn->ph;
+        pn->ph -= pn->sh;
+        d.hd = pn->hv ? hh : 0.0;
+    }
     if constexpr (MODE == 1) {
         const double dc = *a.pdc;
         double dr[KS];
@@ -157,12 +172,13 @@ struct BoxStep {
 // BOX (MODE 0 and 2): l_k is the minimiser of the step's QP over lb - u_k <= d <= ub - u_k (boxqp4.h), the rows of L_k of its clamped
 // components are zero, the others solve the system whose clamped rows and columns are the identity's; v_x' = Q_x + Q_ux^T l_k.
 // In MODE 2 Q_xx, Q_ux, Q_uu carry the projected vf_zz blocks; nothing else differs.
-template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false>
+// PEN (MODE 0): the step's cost Hessian is c_xx + diag h_k, formed before anything is accumulated onto it.
+template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false, bool PEN = false>
 __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], IlqrStepRegs<KS>& d, IlqrAddr<KS>& a,
                                           double* sm, const int g, const int c, const int ob0, const int ob1,
                                           const int ob2, const int ob3, const int oqa, double* jA, const int n,
                                           const int m, const d4 zin = d4{0.0, 0.0, 0.0, 0.0}, SweepLab* lab = nullptr,
-                                          BoxStep* bx = nullptr) {
+                                          BoxStep* bx = nullptr, PenStep* pn = nullptr) {
     constexpr int NP = 4 * KS;
     static_assert(!BOX || MODE != 1, "the box-constrained step is the iLQR or the DDP one");
     double uk[4] = {0.0, 0.0, 0.0, 0.0};
@@ -214,7 +230,10 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
     // G = Y^T F + C0
     d4 gacc = zero4();
 #pragma unroll
-    for (int s = 0; s < KS; ++s) gacc[s] = d.C[s] + pz[s];
+    for (int s = 0; s < KS; ++s) {
+        if constexpr (PEN) gacc[s] = ((pn->hs == s) ? d.C[s] + d.hd : d.C[s]) + pz[s];
+        else gacc[s] = d.C[s] + pz[s];
+    }
     gacc[KS] = d.Cu + pz[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) gacc = mfma(y[s], d.F[s], gacc);
@@ -244,7 +263,7 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
     qp = sum_xor16(qp);     // over the four lane groups: gfx950 row / half-wave swaps instead of two ds_bpermute round trips
     qp = sum_xor32(qp);
     const double qv = d.cv + qp;
-    if constexpr (PREFETCH) ilqr_load_step<KS, MODE>(d, a);
+    if constexpr (PREFETCH) ilqr_load_step<KS, MODE, PEN>(d, a, pn);
 
     ZM_SWEEP_STAMP(lab, 2);   // projection (MODE 2), the six MFMAs of G, the vector terms
     // solve: tile + q row through LDS
@@ -376,6 +395,9 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
 #define ZM_BOX_SETUP
 #define ZM_BOX_FLAGS
 #define ZM_BOX_ARGS
+#define ZM_PEN_LOAD_FLAG
+#define ZM_PEN_LOAD_ARG
+#define ZM_PEN_TERMINAL
 #include "ilqr_backward_t16_body.h"
 #undef ZM_BOX_SETUP
 #undef ZM_BOX_FLAGS
@@ -445,6 +467,86 @@ __global__ __launch_bounds__(64, DDP_BOX_WAVES<KS>) void ddp_backward_box_t16_f6
 #undef ZM_BOX_SETUP
 #undef ZM_BOX_FLAGS
 #undef ZM_BOX_ARGS
+#undef ZM_PEN_LOAD_FLAG
+#undef ZM_PEN_LOAD_ARG
+#undef ZM_PEN_TERMINAL
+
+// The hooks of the body header for the two kernels with a state-box penalty: the second pair (ZM_PEN_LOAD_FLAG / ZM_PEN_LOAD_ARG) makes
+// the operand fetch read the lane's entry of h_k with the step's other operands (prefetched two steps ahead like them), the step adds
+// it to the loaded cost Hessian; ZM_PEN_TERMINAL adds h_T to the terminal V_xx.
+#define ZM_PEN_SETUP                                                              \
+    pn.hv = cA && ((c & 3) == g);                                                 \
+    pn.hs = pn.hv ? (c >> 2) : -1;                                                \
+    pn.sh = n;                                                                    \
+    pn.ph = hdiag + (traj * (long)(T + 1) + (T - 1)) * n + (pn.hv ? c : 0);
+#define ZM_PEN_LOAD_FLAG , true
+#define ZM_PEN_LOAD_ARG , &pn
+#define ZM_PEN_TERMINAL                                                                   \
+    {                                                                                     \
+        const double hT = hdiag[(traj * (long)(T + 1) + T) * n + (pn.hv ? c : 0)];        \
+        _Pragma("unroll") for (int s = 0; s < KS; ++s) Vxx[s] = (pn.hs == s) ? Vxx[s] + hT : Vxx[s]; \
+    }
+
+// ilqr_backward_t16_f64<KS, 0> on the cost Hessians c_xx + diag h_k (k < T) and v_xx + diag h_T: hdiag (batch, T+1, n).  Row 0 IS read
+// and added to step 0's c_xx like every other row (the penalty expansion writes zeros there: x_0 is never constrained).
+#define ZM_BOX_SETUP ZM_PEN_SETUP
+#define ZM_BOX_FLAGS , false, false, true
+#define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, nullptr, &pn
+template <int KS>
+__global__ __launch_bounds__(64, 2) void ilqr_backward_pen_t16_f64(
+    const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
+    const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
+    const double* __restrict__ c_uu, const double* __restrict__ vf_x, const double* __restrict__ vf_xx,
+    const double* __restrict__ hdiag, const long svx, const long svxx, const int* __restrict__ active, const int shared_h,
+    double* __restrict__ lout, double* __restrict__ Lout, const int T, const int n, const int m, const TrajList tl) {
+    constexpr int MODE = 0;
+    const double *const dvec = nullptr, *const f_xx = nullptr, *const f_ux = nullptr, *const f_uu = nullptr, *const Hpk = nullptr;
+    const double *const c_s = nullptr, *const vf_s = nullptr;
+    double *const v_out = nullptr, *const vx_out = nullptr, *const vxx_out = nullptr;
+    const PairTab ptab = PairTab{};
+    PenStep pn;
+#include "ilqr_backward_t16_body.h"
+}
+#undef ZM_BOX_SETUP
+#undef ZM_BOX_FLAGS
+#undef ZM_BOX_ARGS
+
+// ... and ilqr_backward_box_t16_f64 on the same Hessians
+#define ZM_BOX_SETUP                                                              \
+    bx.pu = uTraj + last * m;                                                     \
+    bx.capped = 0;                                                                \
+    for (int i = 0; i < 4; ++i) {                                                 \
+        bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();           \
+        bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();            \
+    }                                                                             \
+    ZM_PEN_SETUP
+#define ZM_BOX_FLAGS , false, true, true
+#define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, &bx, &pn
+template <int KS>
+__global__ __launch_bounds__(64, 2) void ilqr_backward_box_pen_t16_f64(
+    const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
+    const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
+    const double* __restrict__ c_uu, const double* __restrict__ vf_x, const double* __restrict__ vf_xx,
+    const double* __restrict__ hdiag, const double* __restrict__ uTraj, const double* __restrict__ lb, const double* __restrict__ ub,
+    const long bstride, const long svx, const long svxx, const int* __restrict__ active, const int shared_h, double* __restrict__ lout,
+    double* __restrict__ Lout, int* __restrict__ qp_capped, const int T, const int n, const int m, const TrajList tl) {
+    constexpr int MODE = 0;
+    const double *const dvec = nullptr, *const f_xx = nullptr, *const f_ux = nullptr, *const f_uu = nullptr, *const Hpk = nullptr;
+    const double *const c_s = nullptr, *const vf_s = nullptr;
+    double *const v_out = nullptr, *const vx_out = nullptr, *const vxx_out = nullptr;
+    const PairTab ptab = PairTab{};
+    BoxStep bx;
+    PenStep pn;
+#include "ilqr_backward_t16_body.h"
+    if (qp_capped && lane == 0) qp_capped[traj] += bx.capped;
+}
+#undef ZM_BOX_SETUP
+#undef ZM_BOX_FLAGS
+#undef ZM_BOX_ARGS
+#undef ZM_PEN_SETUP
+#undef ZM_PEN_LOAD_FLAG
+#undef ZM_PEN_LOAD_ARG
+#undef ZM_PEN_TERMINAL
 
 // Test entry of the box-QP (boxqp4.h): one problem per lane.  H (batch, m, m), g, lo, hi (batch, m) -> d (batch, m), the clamped set
 // as a bit mask, the passes taken (BOXQP_CAP where the cap was reached).
@@ -982,6 +1084,54 @@ extern "C" int zm_ilqr_backward_box_f64(const double* f_x, const double* f_u, co
                                         double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
     return zm_ilqr_backward_box_list_f64(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, nullptr, 0, nullptr,
                                          shared_hessian, l, L, qp_capped, batch, T, n, m, stream);
+}
+
+// Extension; the reference has no counterpart: the iLQR backward pass on the cost Hessians c_xx + diag h_k, v_xx + diag h_T (the
+// augmented-Lagrangian penalty of a state box), without (box == uTraj == NULL) or with input bounds.  Register path only.
+extern "C" int zm_ilqr_backward_state_list_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,
+                                               const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                                               const double* vf_xx, const double* h, const double* uTraj, const zm_inputbox_t* box,
+                                               const int32_t* list, int64_t count, const int32_t* active, int shared_hessian, double* l,
+                                               double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
+    if (batch == 0 || (list && count == 0)) return ZM_OK;
+    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: bad list length");
+    if (!f_x || !f_u || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !h || !l || !L)
+        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: null pointer");
+    if ((box != nullptr) != (uTraj != nullptr))
+        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: box and uTraj go together (both or neither)");
+    const int rc = zm_check_sweep_args("zm_ilqr_backward_state_f64", batch, T, n, m);
+    if (rc) return rc;
+    if (box)
+        if (const int rb = zm::box_check(box, m, "zm_ilqr_backward_state_f64")) return rb;
+    const zm::TrajList tl{(const int*)list, (long)count};
+    const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    const int sh = shared_hessian ? 1 : 0;
+#define ZM_LAUNCH_PEN(KS_)                                                                                                              \
+    do {                                                                                                                                \
+        if (box)                                                                                                                        \
+            hipLaunchKernelGGL((zm::ilqr_backward_box_pen_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,  \
+                               vf_xx, h, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L,  \
+                               (int*)qp_capped, T, n, m, tl);                                                                           \
+        else                                                                                                                            \
+            hipLaunchKernelGGL((zm::ilqr_backward_pen_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,      \
+                               vf_xx, h, (long)n, (long)n * n, (const int*)active, sh, l, L, T, n, m, tl);                               \
+    } while (0)
+    if (n <= 4) ZM_LAUNCH_PEN(1);
+    else if (n <= 8) ZM_LAUNCH_PEN(2);
+    else ZM_LAUNCH_PEN(3);
+#undef ZM_LAUNCH_PEN
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_ilqr_backward_state_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,
+                                          const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
+                                          const double* vf_xx, const double* h, const double* uTraj, const zm_inputbox_t* box,
+                                          int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m,
+                                          void* stream) {
+    return zm_ilqr_backward_state_list_f64(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, h, uTraj, box, nullptr, 0, nullptr,
+                                           shared_hessian, l, L, qp_capped, batch, T, n, m, stream);
 }
 
 extern "C" int zm_boxqp_f64(const double* H, const double* g, const double* lo, const double* hi, double* d_out, int32_t* clamped_out,

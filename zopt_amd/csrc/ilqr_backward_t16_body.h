@@ -4,6 +4,8 @@
 // tools/isa_identity.py checks it).
 // The hooks ZM_BOX_SETUP (statements after the lane roles are known), ZM_BOX_FLAGS (further template arguments of ilqr_step) and
 // ZM_BOX_ARGS (its further arguments) expand to nothing in the kernel without a box.
+// The hooks ZM_PEN_LOAD_FLAG / ZM_PEN_LOAD_ARG (the operand fetch also reads the lane's entry of the diagonal addend h_k) and
+// ZM_PEN_TERMINAL (h_T joins the terminal V_xx) expand to nothing in the kernels without a state-box penalty.
     constexpr int NP = 4 * KS;
     const int lane = threadIdx.x;
     const long traj = tl.list ? (long)tl.list[blockIdx.x] : (long)blockIdx.x;
@@ -135,6 +137,7 @@
         }
     }
 
+    ZM_PEN_TERMINAL
     if (g == 0) sm[80 + c] = cA ? (vf_x + traj * svx)[c] : 0.0;  // v_x (column-indexed), read by MODE 2's contraction
     ilqr_lds_sync();
     if constexpr (MODE == 2) {
@@ -146,8 +149,8 @@
         }
     } else {
     IlqrStepRegs<KS> d0, d1;
-    ilqr_load_step<KS, MODE>(d0, a);
-    if (T >= 2) ilqr_load_step<KS, MODE>(d1, a);
+    ilqr_load_step<KS, MODE ZM_PEN_LOAD_FLAG>(d0, a ZM_PEN_LOAD_ARG);
+    if (T >= 2) ilqr_load_step<KS, MODE ZM_PEN_LOAD_FLAG>(d1, a ZM_PEN_LOAD_ARG);
     int k = T - 1;
     while (k >= 3) {
         ilqr_step<KS, MODE, true ZM_BOX_FLAGS>(Vxx, vxr, d0, a, sm, g, c, ob0, ob1, ob2, ob3, oqa, jA, n, m ZM_BOX_ARGS);

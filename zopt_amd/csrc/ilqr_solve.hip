@@ -18,6 +18,7 @@
 #include "input_box.h"
 #include "models.h"
 #include "quad_derivs_gen.h"
+#include "state_box.h"
 #include "track_cost.h"
 #include "zm_common.h"
 
@@ -137,6 +138,23 @@ int ilqr_accept(const int32_t* list, int64_t count, double* J, const double* Jn,
 int ilqr_collect(const int32_t* where, double* xTraj, const double* xAlt, double* uTraj, const double* uAlt, int64_t batch, int T, int n,
                  int m, void* stream);
 
+// state_box.hip
+int ilqr_init_masked(const int32_t* mask, double* l, const double* uStart, double* L, double* xT2, double* uT2, double* alphas,
+                     int32_t* active, int32_t* converged, int32_t* where, int64_t batch, int T, int n, int m, hipStream_t st);
+int state_penalty_expand(const zm_statebox_t* sbox, const double* xTraj, const int32_t* list, int64_t count, const int32_t* active,
+                         double* c_x, double* v_x, double* h, int32_t* visits, int64_t batch, int T, int n, hipStream_t st);
+
+// One inner solve of the augmented-Lagrangian loop (zm_ilqr_solve_state_f64): the loop below on J_AL = cost + penalty of the state box.
+struct StatePen {
+    const zm_statebox_t* sbox;
+    double* h;                  // (batch, T+1, n) diagonal addend of the cost Hessians, written by the penalty expansion
+    double* Jcost;              // (batch) the cost without the penalty, written by the line search's store pass
+    int32_t* visits;            // (batch, optional) += 1 per iteration of the loop over the trajectory
+    const int32_t* init_mask;   // (batch) the trajectories this inner solve covers; the others are skipped by the init kernel, the
+                                // initial rollout and the loop
+    const double* uStart;       // (batch, T, m) the inputs it starts from
+};
+
 // The cost of a solve, as the loop sees it: the weights (the Hessians, the conditioning and the kernels' cost arithmetic read only
 // these) and, for a tracking cost (zm_trackcost_t), the reference that the line search's cost values and the expansion's gradients
 // are taken about.  One loop serves both; `track` == nullptr is the zm_quadcost_t path with exactly its launches.
@@ -149,12 +167,18 @@ struct IlqrCost {
     // input bounds (zm_ilqr_solve_box_f64; nullptr: none): the sweep (iLQR or DDP) and the line search are then the box forms
     const zm_inputbox_t* box = nullptr;
     int32_t* qp_capped = nullptr;
+    // state box (zm_ilqr_solve_state_f64; nullptr: none): penalty line search, penalty expansion, sweep with the diagonal addend
+    const StatePen* pen = nullptr;
 };
 // the line search of the loop: dense (list == nullptr) or over the id list
 static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const double* x0, const double* l, const double* L,
                            const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* list,
                            int64_t count, const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
                            int64_t batch, int T, void* stream) {
+    if (ck.pen)
+        return zm_rollout_linesearch_state_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.box, ck.pen->sbox, x0, l, L, xPrev,
+                                                    uPrev, alphas, n_alpha, list, count, active, xTraj, uTraj, J, ck.pen->Jcost,
+                                                    alpha_idx, batch, T, stream);
     if (ck.box)
         return zm_rollout_linesearch_box_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.box, x0, l, L, xPrev, uPrev, alphas,
                                                   n_alpha, list, count, active, xTraj, uTraj, J, alpha_idx, batch, T, stream);
@@ -324,8 +348,10 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
         if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
             return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);
         if (const int rb = zm::box_check(ck.box, m, "zm_ilqr_solve_box_f64")) return rb;
-        if (ck.qp_capped) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
+        if (ck.qp_capped && !ck.pen) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
     }
+    if (ck.pen && (ddp || n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_state_f64: iLQR with n<=12, m<=4 only (n=%d, m=%d, ddp=%d)", n, m, ddp);
     if (ck.track && model->kind == ZM_MODEL_LINEAR && (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_tracking_f64: (n=%d, m=%d) not covered (tracking cost: n<=12, m<=4)", n, m);
     uint32_t mask = 0;
@@ -351,7 +377,11 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
 
     // policy = (uGuess, 0); traj_prev = zeros; step sizes; masks                                     (ilqrUtils.py:293-294, :145)
     int32_t* where = (int32_t*)(ws + w.where);
-    {
+    if (ck.pen) {
+        const int ri = zm::ilqr_init_masked(ck.pen->init_mask, ws + w.l, ck.pen->uStart, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, active,
+                                            converged, where, batch, T, n, m, (hipStream_t)stream);
+        if (ri) return ri;
+    } else {
         const long nL = (long)batch * urow * n, nx = (long)batch * xrow, nl = (long)batch * urow;
         const long work = nL > nx ? nL : nx;
         const unsigned blocks = (unsigned)((work + 256L * 8 - 1) / (256L * 8) < 4096 ? (work + 256L * 8 - 1) / (256L * 8) : 4096);
@@ -359,8 +389,8 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
                            ws + w.uT2, ws + w.alphas, (int*)active, (int*)converged, (int*)where, (long)batch);
     }
     // initial rollout (alpha = 1) from the zero trajectory and its cost                                (:297-298)
-    int rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0, nullptr, xTraj, uTraj,
-                                 J, nullptr, batch, T, st);
+    int rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0,
+                                 ck.pen ? active : nullptr, xTraj, uTraj, J, nullptr, batch, T, st);
     if (rc) return rc;
     // trajectory-independent Hessians of the quadratic cost, PD-conditioned once                         (:309-313)
     rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.c_xx,
@@ -374,7 +404,7 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
     double* f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
     double* f_uu = (need_ux && npairs == 0) ? ws + w.f_uu : nullptr;
     // (a box solve: one-lane two-pass line search and full Jacobians only)
-    const bool can_all_store = !ck.box && w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
+    const bool can_all_store = !ck.box && !ck.pen && w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
     // Packed Jacobians (quadcopter): the expansion writes and the ring sweeps read only the structurally nonzero entries of
     // [f_x | f_u] -- 448 B (480 with wind) per point instead of 1 536 B.  ZOPT_AMD_JAC=full or ZOPT_AMD_ILQR_PATH=reg: the full matrices.
     static const bool packed_off = [] {
@@ -383,7 +413,7 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
         return (e && e[0] == 'f') || (r && r[0] == 'r');
     }();
     const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
-    const bool packed = !ck.box && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
+    const bool packed = !ck.box && !ck.pen && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
                         (!ddp || npairs == 28);
     const int njp = windy ? ((zm::QUAD_NJ_WIND + 1) & ~1) : ((zm::QUAD_NJ_STILL + 1) & ~1);
     const unsigned char* jpos = windy ? zm::QUAD_JPOS_WIND : zm::QUAD_JPOS_STILL;
@@ -444,6 +474,11 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
             count = c32;
             if (count == 0) break;
         }
+        if (ck.pen) {   // (behind the round trip: the list and its count are this iteration's)
+            rc = zm::state_penalty_expand(ck.pen->sbox, curX, list, count, active, ws + w.c_x, ws + w.v_x, ck.pen->h, ck.pen->visits, batch,
+                                          T, n, st);
+            if (rc) return rc;
+        }
         if (packed) {
             if (sparse_h) {
                 rc = zm::quad_hessian_sparse_list(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
@@ -486,6 +521,10 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
             rc = zm_ddp_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, f_ux, f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
                                           ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L,
                                           batch, T, n, m, st);
+        } else if (ck.pen) {
+            rc = zm_ilqr_backward_state_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
+                                                 ws + w.v_x, ws + w.v_xx, ck.pen->h, ck.box ? curU : nullptr, ck.box, list, count, active,
+                                                 1, ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
         } else if (ck.box) {
             rc = zm_ilqr_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
                                                ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1, ws + w.l, L, ck.qp_capped,
@@ -598,6 +637,112 @@ extern "C" int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_
                                      int64_t batch, int T, void* stream) {
     return zm_ilqr_solve_box_trace_f64(model, cost, track, box, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles,
                                        iwork, xTraj, uTraj, L, J, converged, iterations, qp_capped, batch, T, stream, nullptr, nullptr);
+}
+
+// Extension; the reference has no counterpart: iLQR with bounds on the states by an augmented-Lagrangian outer loop around the loop
+// above (AL-iLQR).  Host code: per outer iteration one inner solve over the trajectories that are not done, then the multiplier update.
+extern "C" int64_t zm_ilqr_solve_state_workspace_f64(const zm_model_t* model, int64_t batch, int T) {
+    const int64_t base = zm_ilqr_solve_workspace_f64(model, batch, T, 0);
+    if (base < 0) return -1;
+    // + h (batch, T+1, n) + J_AL (batch) + int32: the not-done mask (batch), the count of the trajectories that go on
+    return base + (((int64_t)batch * (T + 1) * model->n + 1) & ~(int64_t)1) + ((batch + 1) & ~(int64_t)1) + ((batch + 1) / 2 + 1) + 2;
+}
+
+extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                             const zm_inputbox_t* box, const zm_statebox_t* sbox, double mu0, double growth, double mu_max,
+                                             int outer, double ctol, const double* x0, const double* uGuess, int ddp, int max_iter,
+                                             double tol, int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork,
+                                             double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, double* violation,
+                                             int32_t* outer_iterations, int32_t* inner_iterations, int32_t* iterations,
+                                             int32_t* qp_capped, int64_t batch, int T, void* stream, double* J_trace,
+                                             int32_t* alpha_trace, double* violation_trace, double* mu_trace) {
+    const char* who = "zm_ilqr_solve_state_f64";
+    if (batch == 0) return ZM_OK;
+    if (!model || !sbox || !x0 || !uGuess || !workspace || !iwork || !xTraj || !uTraj || !L || !J || !converged || !violation)
+        return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "%s: pass exactly one of cost and track", who);
+    if (ddp != 0) return zm::set_error(ZM_EUNSUPPORTED, "%s: DDP with state bounds is not built (ddp must be 0)", who);
+    if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "%s: bad size", who);
+    if (!(mu0 > 0.0) || !(growth >= 1.0) || !(mu_max >= mu0) || outer < 1 || !(ctol >= 0.0))
+        return zm::set_error(ZM_EINVAL, "%s: need mu0 > 0, growth >= 1, mu_max >= mu0, outer >= 1, ctol >= 0", who);
+    const int n = model->n, m = model->m;
+    if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (state box: n<=12, m<=4)", who, n, m);
+    if (const int rc = zm::statebox_check(sbox, n, who)) return rc;
+    if (box)
+        if (const int rc = zm::box_check(box, m, who)) return rc;
+    // (what the kernels' own entry points would refuse later, behind this function's first launches)
+    if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
+    if (model->kind != ZM_MODEL_LINEAR && model->kind != ZM_MODEL_QUADCOPTER && model->kind != ZM_MODEL_QUADCOPTER_RB)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, model->kind);
+    if (model->kind == ZM_MODEL_LINEAR && (!model->A || !model->B)) return zm::set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
+    if (model->kind == ZM_MODEL_QUADCOPTER && (n != 12 || m != 4)) return zm::set_error(ZM_EINVAL, "%s: the quadcopter model is (12, 4)", who);
+    if (model->kind == ZM_MODEL_QUADCOPTER_RB && (n != 8 || m != 4)) return zm::set_error(ZM_EINVAL, "%s: the rigid-body model is (8, 4)", who);
+    if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31)) return zm::set_error(ZM_EUNSUPPORTED, "%s: T*n*n or batch too large", who);
+    zm::IlqrCost ck = quad_cost(cost);
+    if (track) {
+        if (const int rc = zm::track_check(track, who)) return rc;
+        ck = zm::IlqrCost{true, zm::track_weights(*track), track, zm::track_ref(*track)};
+    }
+    const int64_t base = zm_ilqr_solve_workspace_f64(model, batch, T, 0);
+    if (base < 0 || workspace_doubles < zm_ilqr_solve_state_workspace_f64(model, batch, T))
+        return zm::set_error(ZM_EINVAL, "%s: workspace of %lld doubles, %lld needed", who, (long long)workspace_doubles,
+                             (long long)zm_ilqr_solve_state_workspace_f64(model, batch, T));
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)batch * (T + 1) * n;
+    double* h = workspace + base;
+    double* Jal = h + ((rows + 1) & ~1L);
+    // the mask of the trajectories that are not done: the inner solve's own `active` mask (iwork) also drops what merely converged
+    int32_t* notdone = (int32_t*)(Jal + ((batch + 1) & ~(int64_t)1));
+    int32_t* remaining = notdone + ((batch + 1) & ~(int64_t)1);
+    const unsigned fb = (unsigned)((batch + 255) / 256);
+    hipLaunchKernelGGL(zm::fill_i32_kernel, dim3(fb), dim3(256), 0, st, (int*)notdone, (long)batch, 1);
+    hipLaunchKernelGGL(zm::fill_f64_kernel, dim3(fb), dim3(256), 0, st, sbox->mu, (long)batch, mu0);
+    ZM_HIP_CHECK(hipMemsetAsync(sbox->lam_lb, 0, sizeof(double) * rows, st));
+    ZM_HIP_CHECK(hipMemsetAsync(sbox->lam_ub, 0, sizeof(double) * rows, st));
+    ZM_HIP_CHECK(hipMemsetAsync(converged, 0, sizeof(int32_t) * batch, st));
+    if (outer_iterations) ZM_HIP_CHECK(hipMemsetAsync(outer_iterations, 0, sizeof(int32_t) * batch, st));
+    if (inner_iterations) ZM_HIP_CHECK(hipMemsetAsync(inner_iterations, 0, sizeof(int32_t) * batch * outer, st));
+    if (box && qp_capped) ZM_HIP_CHECK(hipMemsetAsync(qp_capped, 0, sizeof(int32_t) * batch, st));
+    ck.box = box;
+    ck.qp_capped = box ? qp_capped : nullptr;
+    int ran = 0;
+    for (int j = 0; j < outer; ++j) {
+        const zm::StatePen pen{sbox, h, J, inner_iterations ? inner_iterations + (long)j * batch : nullptr, notdone,
+                               j == 0 ? uGuess : uTraj};
+        ck.pen = &pen;
+        if (mu_trace) ZM_HIP_CHECK(hipMemcpyAsync(mu_trace + (long)j * batch, sbox->mu, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+        int rc = ilqr_solve_impl(model, ck, x0, uGuess, 0, max_iter, tol, sync_every, workspace, base, iwork, xTraj, uTraj, L, Jal, converged,
+                                 nullptr, batch, T, stream, J_trace ? J_trace + (long)j * max_iter * batch : nullptr,
+                                 alpha_trace ? alpha_trace + (long)j * max_iter * batch : nullptr);
+        if (rc) return rc;
+        ZM_HIP_CHECK(hipMemsetAsync(remaining, 0, sizeof(int32_t), st));
+        rc = zm_state_multiplier_update_f64(sbox, xTraj, notdone, converged, violation, outer_iterations, remaining, ctol, growth, mu_max,
+                                            j + 1 < outer ? 1 : 0, batch, T, n, stream);
+        if (rc) return rc;
+        if (violation_trace)
+            ZM_HIP_CHECK(hipMemcpyAsync(violation_trace + (long)j * batch, violation, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+        int32_t left = 0;
+        ZM_HIP_CHECK(hipMemcpyAsync(&left, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ZM_HIP_CHECK(hipStreamSynchronize(st));
+        ran = j + 1;
+        if (left == 0) break;
+    }
+    if (iterations) *iterations = ran;
+    return ZM_OK;
+}
+
+extern "C" int zm_ilqr_solve_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                       const zm_inputbox_t* box, const zm_statebox_t* sbox, double mu0, double growth, double mu_max,
+                                       int outer, double ctol, const double* x0, const double* uGuess, int ddp, int max_iter, double tol,
+                                       int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj,
+                                       double* uTraj, double* L, double* J, int32_t* converged, double* violation,
+                                       int32_t* outer_iterations, int32_t* inner_iterations, int32_t* iterations, int32_t* qp_capped,
+                                       int64_t batch, int T, void* stream) {
+    return zm_ilqr_solve_state_trace_f64(model, cost, track, box, sbox, mu0, growth, mu_max, outer, ctol, x0, uGuess, ddp, max_iter, tol,
+                                         sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged, violation,
+                                         outer_iterations, inner_iterations, iterations, qp_capped, batch, T, stream, nullptr, nullptr,
+                                         nullptr, nullptr);
 }
 
 extern "C" int zm_shutdown(void) { return zm::release_host_slots(); }

@@ -11,6 +11,7 @@
 // 8(mn + 2m + n) = 544 B per trajectory step.
 #include "input_box.h"
 #include "models.h"
+#include "state_box.h"
 #include "track_cost.h"
 #include "zm_common.h"
 
@@ -22,15 +23,28 @@ namespace zm {
 // TRK: tracking cost -- the cost of step k is that of (x_k - xr_k, u_k - ur_k), rows of trajectory `t` of `tr`
 // BOX: u_k is clipped into [lb, ub], the bounds of trajectory `t` of `bx` (the clip lets a NaN through); the cost may then be absent
 // (cs == nullptr) also in the TRK form
-template <bool STORE, bool TRK = false, bool BOX = false>
+// PEN: the augmented-Lagrangian penalty of the state box `pr` on the rows k = 1..T goes into an accumulator of its own (k ascending,
+// i ascending) and joins the cost once, at the end; *jcost (optional) <- the cost without it
+template <bool STORE, bool TRK = false, bool BOX = false, bool PEN = false>
 __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_quadcost_t* cs, const double alpha,
                                               const double* __restrict__ x0, const double* __restrict__ l,
                                               const double* __restrict__ L, const double* __restrict__ xPrev,
                                               const double* __restrict__ uPrev, double* __restrict__ xTraj,
                                               double* __restrict__ uTraj, const int T, const TrackRef& tr = TrackRef{},
-                                              const long t = 0, const BoxRef& bx = BoxRef{}) {
+                                              const long t = 0, const BoxRef& bx = BoxRef{}, const PenRef& pr = PenRef{},
+                                              double* jcost = nullptr) {
     const int n = md.n, m = md.m;
     double x[MAXN], u[MAXM], xn[MAXN];
+    double plo[PEN ? MAXN : 1], phi[PEN ? MAXN : 1];
+    double P = 0.0, pmu = 1.0;
+    if constexpr (PEN) {
+        pmu = pr.mu[t];
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) {
+            plo[i] = (i < n) ? pr.lb[t * pr.stride + i] : -__builtin_inf();
+            phi[i] = (i < n) ? pr.ub[t * pr.stride + i] : __builtin_inf();
+        }
+    }
     double blo[BOX ? MAXM : 1], bhi[BOX ? MAXM : 1];
     if constexpr (BOX) {
 #pragma unroll
@@ -76,6 +90,15 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
         } else {
             if (cs) J += running_cost(*cs, n, m, x, u);
         }
+        if constexpr (PEN) {
+            if (k >= 1) {
+                const double* ll = pr.lam_lb + (t * (T + 1) + k) * n;
+                const double* lu = pr.lam_ub + (t * (T + 1) + k) * n;
+#pragma unroll
+                for (int i = 0; i < MAXN; ++i)
+                    if (i < n) P += pen_psi(x[i], plo[i], phi[i], ll[i], lu[i], pmu);
+            }
+        }
         model_step<double>(md, x, u, xn);
 #pragma unroll
         for (int i = 0; i < MAXN; ++i) x[i] = xn[i];
@@ -97,12 +120,22 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
     } else {
         if (cs) J += terminal_cost(*cs, n, x);
     }
+    if constexpr (PEN) {
+        const double* ll = pr.lam_lb + (t * (T + 1) + T) * n;
+        const double* lu = pr.lam_ub + (t * (T + 1) + T) * n;
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i)
+            if (i < n) P += pen_psi(x[i], plo[i], phi[i], ll[i], lu[i], pmu);
+        if (jcost) *jcost = J;
+        J += P;
+    }
     return J;
 }
 
 // NA = lanes per trajectory (power of two <= 16 that holds n_alpha)
 #define ZM_TRK_FLAG
 #define ZM_TRK_ARGS
+#define ZM_PEN_STORE_ARGS
 template <int NA>
 __global__ __launch_bounds__(64) void rollout_linesearch_kernel(const zm_model_t md, const zm_quadcost_t cost,
                                                                 const bool has_cost, const double* __restrict__ x0,
@@ -118,9 +151,11 @@ __global__ __launch_bounds__(64) void rollout_linesearch_kernel(const zm_model_t
 }
 #undef ZM_TRK_FLAG
 #undef ZM_TRK_ARGS
+#undef ZM_PEN_STORE_ARGS
 // the same line search on the tracking cost (zm_trackcost_t): `cost` holds its weights, `tr` its reference
 #define ZM_TRK_FLAG , true
 #define ZM_TRK_ARGS , tr, t
+#define ZM_PEN_STORE_ARGS
 template <int NA>
 __global__ __launch_bounds__(64) void rollout_linesearch_track_kernel(const zm_model_t md, const zm_quadcost_t cost, const TrackRef tr,
                                                                       const double* __restrict__ x0, const double* __restrict__ l,
@@ -136,10 +171,12 @@ __global__ __launch_bounds__(64) void rollout_linesearch_track_kernel(const zm_m
 }
 #undef ZM_TRK_FLAG
 #undef ZM_TRK_ARGS
+#undef ZM_PEN_STORE_ARGS
 // the same line search with input bounds (zm_inputbox_t), on either cost: the tracking form, whose reference is null for a
 // zm_quadcost_t (the differences are then the values themselves, bit for bit)
 #define ZM_TRK_FLAG , true, true
 #define ZM_TRK_ARGS , tr, t, bx
+#define ZM_PEN_STORE_ARGS
 template <int NA>
 __global__ __launch_bounds__(64) void rollout_linesearch_box_kernel(const zm_model_t md, const zm_quadcost_t cost, const bool has_cost,
                                                                     const TrackRef tr, const BoxRef bx, const double* __restrict__ x0,
@@ -154,6 +191,29 @@ __global__ __launch_bounds__(64) void rollout_linesearch_box_kernel(const zm_mod
 }
 #undef ZM_TRK_FLAG
 #undef ZM_TRK_ARGS
+#undef ZM_PEN_STORE_ARGS
+// the same line search on the augmented-Lagrangian cost of a state box (zm_statebox_t), without (BOXED = false: infinite input bounds
+// are never read) or with input bounds; the store pass also writes the cost without the penalty (Jc_out, optional)
+#define ZM_TRK_FLAG , true, BOXED, true
+#define ZM_TRK_ARGS , tr, t, bx, pr
+#define ZM_PEN_STORE_ARGS , (Jc_out ? Jc_out + t : nullptr)
+template <int NA, bool BOXED>
+__global__ __launch_bounds__(64) void rollout_linesearch_pen_kernel(const zm_model_t md, const zm_quadcost_t cost, const TrackRef tr,
+                                                                    const BoxRef bx, const PenRef pr, const double* __restrict__ x0,
+                                                                    const double* __restrict__ l, const double* __restrict__ L,
+                                                                    const double* __restrict__ xPrev, const double* __restrict__ uPrev,
+                                                                    const double* __restrict__ alphas, const int n_alpha,
+                                                                    const int* __restrict__ active, const int* __restrict__ list,
+                                                                    const long count, double* __restrict__ xTraj,
+                                                                    double* __restrict__ uTraj, double* __restrict__ Jout,
+                                                                    double* __restrict__ Jc_out, int* __restrict__ idx_out,
+                                                                    const long batch, const int T) {
+    constexpr bool has_cost = true;
+#include "rollout_linesearch_body.h"
+}
+#undef ZM_TRK_FLAG
+#undef ZM_TRK_ARGS
+#undef ZM_PEN_STORE_ARGS
 
 // rollout_fast.hip: compile-time (n, m) = (12, 4), 16 step sizes
 int rollout_fast_dispatch(const zm_model_t& md, const double* Q, const double* R, const double* Qf, int diagonal, const double* x0,
@@ -339,6 +399,73 @@ extern "C" int zm_rollout_linesearch_box_f64(const zm_model_t* model, const zm_q
                                              int64_t batch, int T, void* stream) {
     return zm_rollout_linesearch_box_list_f64(model, cost, track, box, x0, l, L, xPrev, uPrev, alphas, n_alpha, nullptr, 0, active, xTraj,
                                               uTraj, J, alpha_idx, batch, T, stream);
+}
+
+// Extension; the reference has no counterpart: the line search on the augmented-Lagrangian cost of a state box, on a zm_quadcost_t or
+// a zm_trackcost_t, with or without input bounds.  One lane per rollout, two passes (the generic kernel's penalty form only).
+extern "C" int zm_rollout_linesearch_state_list_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                                    const zm_inputbox_t* box, const zm_statebox_t* sbox, const double* x0, const double* l,
+                                                    const double* L, const double* xPrev, const double* uPrev, const double* alphas,
+                                                    int n_alpha, const int32_t* list, int64_t count, const int32_t* active, double* xTraj,
+                                                    double* uTraj, double* J, double* J_cost, int32_t* alpha_idx, int64_t batch, int T,
+                                                    void* stream) {
+    const char* who = "zm_rollout_linesearch_state_f64";
+    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "%s: pass exactly one of cost and track", who);
+    if (track)
+        if (const int rc = zm::track_check(track, who)) return rc;
+    if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
+    if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj || !J) return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    if (batch < 0 || T < 1 || n_alpha < 1 || n_alpha > 16)
+        return zm::set_error(ZM_EINVAL, "%s: bad size batch=%lld T=%d n_alpha=%d", who, (long long)batch, T, n_alpha);
+    zm_model_t md = *model;
+    if (md.kind == ZM_MODEL_QUADCOPTER) {
+        md.n = 12;
+        md.m = 4;
+    } else if (md.kind == ZM_MODEL_QUADCOPTER_RB) {
+        md.n = 8;
+        md.m = 4;
+    } else if (md.kind == ZM_MODEL_LINEAR) {
+        if (!md.A || !md.B) return zm::set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
+    } else {
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, md.kind);
+    }
+    if (md.n < 1 || md.n > zm::MAXN || md.m < 1 || md.m > zm::MAXM)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (state box: n<=12, m<=4)", who, md.n, md.m);
+    if (box)
+        if (const int rc = zm::box_check(box, md.m, who)) return rc;
+    if (const int rc = zm::statebox_check(sbox, md.n, who)) return rc;
+    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "%s: bad list length", who);
+    if (batch == 0 || (list && count == 0)) return ZM_OK;
+    const zm_quadcost_t cs = track ? zm::track_weights(*track) : *cost;
+    const zm::TrackRef tr = track ? zm::track_ref(*track) : zm::TrackRef{};
+    const zm::BoxRef bx = box ? zm::box_ref(*box) : zm::BoxRef{};
+    const zm::PenRef pr = zm::pen_ref(*sbox);
+    const int64_t nslot = list ? count : batch;
+    hipStream_t st = (hipStream_t)stream;
+    const int* act = (const int*)active;
+#define ZM_LAUNCH_PEN(NA_, BOXED_, BLOCKS_)                                                                                               \
+    hipLaunchKernelGGL((zm::rollout_linesearch_pen_kernel<NA_, BOXED_>), dim3((unsigned)(BLOCKS_)), dim3(64), 0, st, md, cs, tr, bx, pr, x0, \
+                       l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, J_cost, (int*)alpha_idx, \
+                       (long)batch, T)
+    if (n_alpha == 1) {
+        if (box) ZM_LAUNCH_PEN(1, true, (nslot + 63) / 64);
+        else ZM_LAUNCH_PEN(1, false, (nslot + 63) / 64);
+    } else {
+        if (box) ZM_LAUNCH_PEN(16, true, (nslot + 3) / 4);
+        else ZM_LAUNCH_PEN(16, false, (nslot + 3) / 4);
+    }
+#undef ZM_LAUNCH_PEN
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
+extern "C" int zm_rollout_linesearch_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                               const zm_inputbox_t* box, const zm_statebox_t* sbox, const double* x0, const double* l,
+                                               const double* L, const double* xPrev, const double* uPrev, const double* alphas,
+                                               int n_alpha, const int32_t* active, double* xTraj, double* uTraj, double* J, double* J_cost,
+                                               int32_t* alpha_idx, int64_t batch, int T, void* stream) {
+    return zm_rollout_linesearch_state_list_f64(model, cost, track, box, sbox, x0, l, L, xPrev, uPrev, alphas, n_alpha, nullptr, 0, active,
+                                                xTraj, uTraj, J, J_cost, alpha_idx, batch, T, stream);
 }
 
 // Solver-internal (ilqr_solve.hip): the 16-way line search in all-store mode -- every step size's rollout goes to the scratch blocks

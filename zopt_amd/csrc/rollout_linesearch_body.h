@@ -2,7 +2,7 @@
 // A function BODY, not a header: #included verbatim inside rollout_linesearch_kernel and rollout_linesearch_track_kernel, so that the
 // kernel that existed before the tracking cost compiles from the very same tokens (same ISA; tools/isa_identity.py checks it).
 // The hooks ZM_TRK_FLAG / ZM_TRK_ARGS pass the tracking cost's reference on to rollout_one; they expand to nothing in the kernel
-// without a reference.
+// without a reference.  ZM_PEN_STORE_ARGS: further arguments of the store pass (the state box's plain-cost output); nothing elsewhere.
     constexpr int TPW = 64 / NA;  // trajectories per wave
     const int lane = threadIdx.x;
     const int a = lane % NA;
@@ -47,7 +47,7 @@
     const double abest = alphas[best];
     if (live) {
         if (a == 0) {
-            const double Jb = rollout_one<true ZM_TRK_FLAG>(md, cs, abest, x0t, lt, Lt, xpt, upt, xo, uo, T ZM_TRK_ARGS);
+            const double Jb = rollout_one<true ZM_TRK_FLAG>(md, cs, abest, x0t, lt, Lt, xpt, upt, xo, uo, T ZM_TRK_ARGS ZM_PEN_STORE_ARGS);
             if (Jout) Jout[t] = Jb;
             if (idx_out) idx_out[t] = best;
         }

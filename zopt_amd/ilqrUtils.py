@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -254,10 +255,30 @@ def riccatiStep_ddp(dynamics, cost, value):
 LINESEARCH_ALPHAS = 0.5 ** np.arange(16)   # reference ilqrUtils.py:145
 _TRACE = None   # diagnostics: a list; while it is one, the fused drivers run zm_ilqr_solve_trace_f64 and append ("iterations", its),
 #                 ("J_trace", (its, batch) costs after every iteration's acceptance), ("alpha_trace", (its, batch) winning step-size indices)
+#                 a StateBox solve (zm_ilqr_solve_state_trace_f64): "iterations" counts the outer iterations, J_trace / alpha_trace are
+#                 (outer, maxIter, batch) (J_AL; NaN / -1 where nothing ran), plus ("violation_trace", (outer, batch)), ("mu_trace", (outer,
+#                 batch)) and ("inner_trace", (outer, batch) iLQR iterations per outer iteration)
+
+
+class ConstraintInfo(NamedTuple):
+    """What `constrainedIterativeLqr` returns besides `iterativeLqr`'s four: per trajectory the largest violation of the state bounds
+    over k = 1..N, the final penalty, the multipliers (..., N+1, n) (row 0 zero), the outer iterations it took part in and its iLQR
+    iterations in each of them (..., outer)."""
+    violation: object
+    mu: object
+    lam_lb: object
+    lam_ub: object
+    outerIterations: object
+    innerIterations: object
 
 
 def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     """Shared driver of trajectoryRollout / forwardPass2 on the rollout_linesearch kernel."""
+    if isinstance(dynFun, _models.StateBox):
+        if costFun is not None:
+            raise ValueError("forwardPass2 takes no StateBox: its cost would silently omit the state box's penalty (the line search on "
+                             "the augmented-Lagrangian cost runs inside iterativeLqr / constrainedIterativeLqr)")
+        dynFun = dynFun.model         # the dynamics are unchanged; an inner InputBox still clips
     box = dynFun if isinstance(dynFun, _models.InputBox) else None
     if box is not None:
         dynFun = box.model
@@ -590,6 +611,18 @@ def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, t
     return _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp=False)
 
 
+def constrainedIterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
+    """`iterativeLqr` with bounds on the states: `dynamics` is a `models.StateBox` (around a registered model or an `InputBox`), solved
+    by an augmented-Lagrangian outer loop around the fused iLQR -- per outer iteration an iLQR solve (at most `maxIter` iterations,
+    `|J_AL - J_AL,new| <= tol`) on the cost plus the penalty of the state box, then the multiplier and penalty update; a trajectory is
+    done (`converged`) when its inner solve converged and its violation is <= the StateBox's `ctol`, and is not touched again.
+
+    Returns (traj, L, J, converged, info): `J` is the plain cost of the returned trajectory, `info` a `ConstraintInfo`."""
+    if not isinstance(dynamics, _models.StateBox):
+        raise TypeError("constrainedIterativeLqr: dynamics must be a zopt_amd.models.StateBox")
+    return _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp=False, info=True)
+
+
 def differentialDynamicProgramming(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
     """Differential dynamic programming algorithm (reference ilqrUtils.py:330-397): `iterativeLqr` with the second-order
     expansion of the dynamics (QuadraticDynamics.from_trajectory, :365) and `backwardPass_ddp` (:373).  Same arguments
@@ -621,8 +654,14 @@ def _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIte
     return Trajectory(xo, uo), Lo, Jo, co
 
 
-def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp):
+def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp, info=False):
     model = dynamics
+    sbox = model if isinstance(model, _models.StateBox) else None
+    if sbox is not None:
+        if ddp:                       # (before anything touches the device)
+            raise ValueError("differentialDynamicProgramming takes no StateBox: DDP with state bounds is the follow-up to the "
+                             "augmented-Lagrangian iLQR (use iterativeLqr / constrainedIterativeLqr)")
+        model = sbox.model
     box = model if isinstance(model, _models.InputBox) else None
     if box is not None:
         if ddp and isinstance(box.model, _models.LinearModel):   # (before anything touches the device)
@@ -680,14 +719,53 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
             common = (pmd, None if tracking else pcs, pcs if tracking else None, ctypes.addressof(bs)) + common[2:17] + \
                 (capped.data_ptr(),) + common[17:]
             solve, solve_trace = lib.zm_ilqr_solve_box_f64, lib.zm_ilqr_solve_box_trace_f64
-        if _TRACE is None:
+        if sbox is not None:          # (model*, cost* | NULL, track* | NULL, box* | NULL, sbox*, mu0, growth, mu_max, outer, ctol, x0, ...)
+            lam_lb = torch.empty((B, N + 1, n), dtype=dt, device=dev)
+            lam_ub = torch.empty((B, N + 1, n), dtype=dt, device=dev)
+            mu = torch.empty(B, dtype=dt, device=dev)
+            viol = torch.zeros(B, dtype=dt, device=dev)
+            outer_its = torch.zeros(B, dtype=torch.int32, device=dev)
+            inner_its = torch.zeros((sbox.outer, B), dtype=torch.int32, device=dev)
+            ss = sbox.statebox_struct(tuple(lead), lam_lb, lam_ub, mu)
+            nws = int(lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N))
+            if nws < 0:
+                raise ValueError("iterativeLqr: cannot size the workspace for this model")
+            ws = torch.empty(nws, dtype=dt, device=dev)
+            if box is None:
+                capped = torch.zeros(B, dtype=torch.int32, device=dev)
+            args = (pmd, None if tracking else pcs, pcs if tracking else None, ctypes.addressof(bs) if box is not None else None,
+                    ctypes.addressof(ss), sbox.mu0, sbox.growth, sbox.mu_max, sbox.outer, sbox.ctol, dx0.data_ptr(), dug.data_ptr(), 0,
+                    int(maxIter), float(tol), SYNC, ws.data_ptr(), nws, iwork.data_ptr(), xT.data_ptr(), uT.data_ptr(), L.data_ptr(),
+                    J.data_ptr(), converged.data_ptr(), viol.data_ptr(), outer_its.data_ptr(), inner_its.data_ptr(),
+                    ctypes.addressof(its), capped.data_ptr(), B, N, st)
+            if _TRACE is None:
+                rc = lib.zm_ilqr_solve_state_f64(*args)
+            else:
+                rows = sbox.outer * max(int(maxIter), 1)
+                Jtr = torch.full((rows, B), float("nan"), dtype=dt, device=dev)
+                atr = torch.full((rows, B), -1, dtype=torch.int32, device=dev)
+                vtr = torch.full((sbox.outer, B), float("nan"), dtype=dt, device=dev)
+                mtr = torch.full((sbox.outer, B), float("nan"), dtype=dt, device=dev)
+                rc = lib.zm_ilqr_solve_state_trace_f64(*args, Jtr.data_ptr(), atr.data_ptr(), vtr.data_ptr(), mtr.data_ptr())
+            _lib.check(rc, "iterativeLqr")
+            if _TRACE is not None:
+                o = int(its.value)
+                _TRACE.append(("iterations", o))
+                _TRACE.append(("J_trace", Jtr.reshape(sbox.outer, -1, B)[:o].cpu().numpy()))
+                _TRACE.append(("alpha_trace", atr.reshape(sbox.outer, -1, B)[:o].cpu().numpy()))
+                _TRACE.append(("violation_trace", vtr[:o].cpu().numpy()))
+                _TRACE.append(("mu_trace", mtr[:o].cpu().numpy()))
+                _TRACE.append(("inner_trace", inner_its[:o].cpu().numpy()))
+                if box is not None:
+                    _TRACE.append(("qp_capped", capped.cpu().numpy()))
+        elif _TRACE is None:
             rc = solve(*common)
         else:
             Jtr = torch.full((max(int(maxIter), 1), B), float("nan"), dtype=dt, device=dev)
             atr = torch.full((max(int(maxIter), 1), B), -1, dtype=torch.int32, device=dev)
             rc = solve_trace(*common, Jtr.data_ptr(), atr.data_ptr())
         _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
-        if _TRACE is not None:
+        if _TRACE is not None and sbox is None:
             _TRACE.append(("iterations", int(its.value)))
             _TRACE.append(("J_trace", Jtr[: int(its.value)].cpu().numpy()))
             _TRACE.append(("alpha_trace", atr[: int(its.value)].cpu().numpy()))
@@ -703,4 +781,16 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     co = arr.result_like(converged.bool().reshape(lead), tmpl)
     if not arr.is_torch(tmpl) and len(lead) == 0:
         Jo, co = float(Jo), bool(co)
+    if info:
+        if not B:
+            lam_lb = lam_ub = torch.zeros((0, N + 1, n), dtype=dt, device=dev)
+            mu = viol = torch.zeros(0, dtype=dt, device=dev)
+            outer_its, inner_its = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((sbox.outer, 0), dtype=torch.int32, device=dev)
+        fl = [viol.reshape(lead), mu.reshape(lead), lam_lb.reshape(lead + (N + 1, n)), lam_ub.reshape(lead + (N + 1, n))]
+        if fp32_in:
+            fl = [o.to(torch.float32) for o in fl]
+        res = [arr.result_like(o, tmpl) for o in fl]
+        res += [arr.result_like(outer_its.reshape(lead), tmpl),
+                arr.result_like(inner_its.transpose(0, 1).contiguous().reshape(lead + (sbox.outer,)), tmpl)]
+        return Trajectory(xo, uo), Lo, Jo, co, ConstraintInfo(*res)
     return Trajectory(xo, uo), Lo, Jo, co

@@ -303,6 +303,8 @@ class InputBox:
     def __init__(self, model, u_lb, u_ub):
         if isinstance(model, InputBox):
             raise TypeError("InputBox: the model is an InputBox already")
+        if isinstance(model, StateBox):
+            raise TypeError("InputBox: a StateBox is the outer wrapper -- write StateBox(InputBox(model, u_lb, u_ub), x_lb, x_ub)")
         if not hasattr(model, "c_struct"):
             raise TypeError("InputBox wraps a registered device model (zopt_amd.models.*); the generic-callable path has no box: clip "
                             "inside the torch callable there")
@@ -359,4 +361,81 @@ class InputBox:
         lb, ub, stride = self._dev[lead]
         st = zm_inputbox_t(lb.data_ptr(), ub.data_ptr(), stride)
         st._owner = (self, lb, ub)      # raw device addresses: keep the arrays behind them alive with the struct
+        return st
+
+
+class zm_statebox_t(ctypes.Structure):
+    _fields_ = [("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p), ("stride", ctypes.c_int64), ("lam_lb", ctypes.c_void_p),
+                ("lam_ub", ctypes.c_void_p), ("mu", ctypes.c_void_p)]
+
+
+STATEBOX_MAX_N, STATEBOX_MAX_M = 12, 4     # the fused drivers' shapes (zm::MAXN, zm::MAXM)
+
+
+class StateBox:
+    """A registered model (or an `InputBox` around one) with bounds on its states, `x_lb <= x_k <= x_ub` per component for
+    k = 1..N (x_0 is given): iLQR with an augmented-Lagrangian outer loop (AL-iLQR).  An extension: the reference's iLQR is
+    unconstrained (ilqrUtils.py:260-327).
+
+    x_lb, x_ub: scalars, (n,) or (..., n) with leading axes that broadcast to the batch of the call; an entry of -inf / +inf means no
+    bound on that side of that component, `x_lb == x_ub` pins a component.  `x_lb > x_ub` and NaN are refused.
+    mu0, growth, mu_max: the penalty starts at mu0 and grows by `growth` per outer iteration up to mu_max; outer: at most that many
+    outer iterations; ctol: a trajectory is done when its inner solve converged and its largest violation is <= ctol.
+
+    Accepted by `iterativeLqr` and `constrainedIterativeLqr`.  `trajectoryRollout` and the simulator unwrap it (the dynamics are
+    unchanged; an inner InputBox still clips); `forwardPass2` and `differentialDynamicProgramming` refuse it.  An InputBox around a
+    StateBox is a TypeError: the state box is the outer wrapper."""
+
+    def __init__(self, model, x_lb, x_ub, mu0=1.0, growth=10.0, mu_max=1e8, outer=10, ctol=1e-4):
+        if isinstance(model, StateBox):
+            raise TypeError("StateBox: the model is a StateBox already")
+        inner = model.model if isinstance(model, InputBox) else model
+        if not hasattr(inner, "c_struct"):
+            raise TypeError("StateBox wraps a registered device model (zopt_amd.models.*) or an InputBox around one; the "
+                            "generic-callable path has no state box")
+        self.model, self.n, self.m = model, int(inner.n), int(inner.m)
+        if self.n > STATEBOX_MAX_N or self.m > STATEBOX_MAX_M:
+            raise ValueError(f"StateBox: (n={self.n}, m={self.m}) not covered -- the state-box kernels take n <= {STATEBOX_MAX_N}, "
+                             f"m <= {STATEBOX_MAX_M}")
+        self.mu0, self.growth, self.mu_max, self.outer, self.ctol = float(mu0), float(growth), float(mu_max), int(outer), float(ctol)
+        if not self.mu0 > 0 or not self.growth >= 1 or not self.mu_max >= self.mu0 or self.outer < 1 or not self.ctol >= 0:
+            raise ValueError("StateBox: need mu0 > 0, growth >= 1, mu_max >= mu0, outer >= 1, ctol >= 0")
+        host = lambda b: np.asarray(b.detach().cpu().numpy() if arr.is_torch(b) else b, dtype=np.float64)       # noqa: E731
+        lb, ub = host(x_lb), host(x_ub)
+        for name, b in (("x_lb", lb), ("x_ub", ub)):
+            if b.ndim and b.shape[-1] != self.n:
+                raise ValueError(f"StateBox: {name} has shape {b.shape}, expected a scalar, ({self.n},) or (..., {self.n})")
+            if np.isnan(b).any():
+                raise ValueError(f"StateBox: {name} holds a NaN")
+        try:
+            shp = np.broadcast_shapes(lb.shape, ub.shape, (self.n,))
+        except ValueError:
+            raise ValueError(f"StateBox: x_lb {lb.shape} and x_ub {ub.shape} do not broadcast") from None
+        self.x_lb, self.x_ub = np.array(np.broadcast_to(lb, shp)), np.array(np.broadcast_to(ub, shp))
+        if (self.x_lb > self.x_ub).any():
+            raise ValueError("StateBox: x_lb > x_ub")
+        self._dev = {}
+
+    def bounds_rows(self, lead):
+        """(x_lb, x_ub, stride) as host arrays for a call with batch axes `lead`: one shared row (stride 0) or a row per trajectory
+        (stride n)"""
+        lead = tuple(int(d) for d in lead)
+        if self.x_lb.ndim == 1:
+            return self.x_lb, self.x_ub, 0
+        try:
+            lb, ub = (np.array(np.broadcast_to(b, lead + (self.n,))).reshape(-1, self.n) for b in (self.x_lb, self.x_ub))
+        except ValueError:
+            raise ValueError(f"StateBox: leading axes {self.x_lb.shape[:-1]} of the bounds do not broadcast to the batch {lead}") from None
+        return lb, ub, self.n
+
+    def statebox_struct(self, lead, lam_lb, lam_ub, mu):
+        """zm_statebox_t for a call with batch axes `lead` on the caller's device arrays for the multipliers and the penalty"""
+        import torch
+        lead = tuple(int(d) for d in lead)
+        if lead not in self._dev:
+            lb, ub, stride = self.bounds_rows(lead)
+            self._dev[lead] = tuple(arr.to_device(np.ascontiguousarray(b), torch.float64) for b in (lb, ub)) + (stride,)
+        lb, ub, stride = self._dev[lead]
+        st = zm_statebox_t(lb.data_ptr(), ub.data_ptr(), stride, lam_lb.data_ptr(), lam_ub.data_ptr(), mu.data_ptr())
+        st._owner = (self, lb, ub, lam_lb, lam_ub, mu)      # raw device addresses: keep the arrays behind them alive with the struct
         return st
