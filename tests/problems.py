@@ -467,6 +467,108 @@ def hard_affine(name: str, n: int, m: int, T: int, batch: int = 2):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# Hard time-varying problems for the finite-horizon Riccati sweep `discreteFiniteHorizonLqr` (lqr_backward_dma.hip, lqr_backward.hip,
+# lqr_tiled_core.h, lqr_backward_lds_f64.hip): each generator (batch, T, n, m, seed) -> (A, B, Q, R) starts from `random_time_varying` and
+# gives it ONE hard feature (tests/test_lqr_hard.py asserts that it has it).  Several of them are built to leave the kernels' fast m x m
+# solve: K1's cofactor solve behind its residual guard, the unpivoted elimination of the other kernels behind its growth check.
+def _pow2_span(k, decades):
+    """k powers of two spread evenly (in the exponent) over 10^-decades .. 10^decades; a single one is 1."""
+    e = np.round(np.linspace(-decades, decades, k) * np.log2(10.0)) if k > 1 else np.zeros(1)
+    return 2.0 ** e
+
+
+def lqr_units(n, m):
+    """The diagonals (D, E) of `lqr_input_units`' coordinate change x' = D x, u' = E u: powers of two over 1e-2 .. 1e2 and 1e-3 .. 1e3."""
+    return _pow2_span(n, 2), _pow2_span(m, 3)
+
+
+def lqr_mildly_unstable(batch, T, n, m, seed=0, rho=1.05):
+    """Every A_k scaled to the spectral radius rho (the problem that `lqr_input_units` writes in other units; rho = 1.3: `unstable`)."""
+    A, B, Q, R = random_time_varying(batch, T, n, m, seed)
+    return A * (rho / np.max(np.abs(np.linalg.eigvals(A)), axis=-1))[..., None, None], B, Q, R
+
+
+def lqr_input_units(batch, T, n, m, seed=0):
+    """`lqr_mildly_unstable` in the coordinates x' = D x, u' = E u of `lqr_units`: D A D^-1, D B E^-1, D^-1 Q D^-1, E^-1 R E^-1.  Suu' =
+    E^-1 Suu E^-1 is graded over twelve decades (its entries, not its condition after scaling), the gain is L' = E L D^-1: undoing the
+    units, E^-1 L' D, is exact."""
+    A, B, Q, R = lqr_mildly_unstable(batch, T, n, m, seed)
+    d, e = lqr_units(n, m)
+    return A * d[:, None] / d[None, :], B * d[:, None] / e[None, :], Q / (d[:, None] * d[None, :]), R / (e[:, None] * e[None, :])
+
+
+def lqr_dominant_input(batch, T, n, m, seed=0, r=1.0, every=1):
+    """B_k = u_k v_k^T of rank one and R_k scaled by r on the steps k = 0 mod `every` (plain elsewhere): B^T V B = (u^T V u) v v^T has
+    rank one and dominates Suu = r R + B^T V B, whose rows are then nearly parallel."""
+    A, B, Q, R = random_time_varying(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 1)
+    B1 = rng.standard_normal((batch, T, n, 1)) * rng.standard_normal((batch, T, 1, m))
+    hit = (np.arange(T) % every == 0)[None, :, None, None]
+    return A, np.where(hit, B1, B), Q, np.where(hit, r * R, R)
+
+
+def lqr_permuted_R(batch, T, n, m, seed=0):
+    """B scaled by 0.02 and R_k = (a cyclic column shift of I) + 0.01 noise, nonsymmetric: Suu ~ R_k is well conditioned (a perturbed
+    permutation), but its leading entry is ~0.01, so the elimination without row exchanges meets multipliers ~100 at the first column
+    (m = 1: no permutation exists, R = 1 + noise)."""
+    A, B, Q, _ = random_time_varying(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 2)
+    R = np.roll(np.eye(m), 1, axis=-1) + 0.01 * rng.standard_normal((batch, T, m, m))
+    return A, 0.02 * B, Q, R
+
+
+def lqr_nonsymmetric(batch, T, n, m, seed=0):
+    """O(1) antisymmetric parts in every Q_k and R_k: the reference's recursion does not symmetrise, so the kernels may not either."""
+    A, B, Q, R = random_time_varying(batch, T, n, m, seed)
+    rng = np.random.default_rng(seed + 3)
+    return A, B, Q + _antisym(rng, Q.shape, 0.5), R + _antisym(rng, R.shape, 0.5)
+
+
+def lqr_cheap(batch, T, n, m, seed=0, r=None):
+    """R_k scaled by r = 1e-8 on unstable dynamics (every A_k at the spectral radius 1.2, as `cheap_control`): Suu is dominated by B^T V B,
+    and a value update that subtracts (the Schur form) instead of the Joseph form loses digits along the horizon.  With more controls
+    than states B^T V B is singular and cond(Suu) ~ 1 / r: r = 1e-4 there keeps the problem well posed in fp64 (`sweep_cheap_control`)."""
+    r = (1e-8 if m <= n else 1e-4) if r is None else r
+    A, B, Q, R = lqr_mildly_unstable(batch, T, n, m, seed, rho=1.2)
+    return A, B, Q, r * R
+
+
+def lqr_expensive(batch, T, n, m, seed=0, r=1e8):
+    """R_k scaled by 1e8: Suu is dominated by R, the gains are ~1e-7."""
+    A, B, Q, R = random_time_varying(batch, T, n, m, seed)
+    return A, B, Q, r * R
+
+
+# name -> generator (batch, T, n, m, seed); "plain" is the yardstick family the bounds' floor comes from, not a hard one
+HARD_LQR = {
+    "plain": random_time_varying,
+    "input_units": lqr_input_units,
+    "dominant_input": lqr_dominant_input,
+    "dominant_input_1e-2": lambda batch, T, n, m, seed=0: lqr_dominant_input(batch, T, n, m, seed, r=1e-2),
+    "dominant_every_3": lambda batch, T, n, m, seed=0: lqr_dominant_input(batch, T, n, m, seed, r=1e-2, every=3),
+    "permuted_R": lqr_permuted_R,
+    "unstable": lambda batch, T, n, m, seed=0: lqr_mildly_unstable(batch, T, n, m, seed, rho=1.3),
+    "cheap": lqr_cheap,
+    "expensive": lqr_expensive,
+    "nonsymmetric": lqr_nonsymmetric,
+}
+
+
+# (family, n, m, T) -> seed offset, in thousands, of the cases whose first seed leaves a step of K1's model within a factor 8 of the guard's
+# threshold (tests/test_lqr_hard.py asserts the margins): there the GPU's rounding of Suu could decide the branch the other way
+LQR_SEED_BUMP = {("input_units", 12, 4, 7): 1, ("dominant_input_1e-2", 8, 4, 11): 1}
+
+
+def hard_lqr(name: str, n: int, m: int, T: int, batch: int = 5):
+    """The seeded batch of HARD_LQR[name] at (n, m, T) that the CPU property tests and the GPU tests both use."""
+    return HARD_LQR[name](batch, T, n, m, hard_lqr_seed(name, n, m, T))
+
+
+def hard_lqr_seed(name: str, n: int, m: int, T: int):
+    return 9000 + 97 * n + 13 * m + T + 1000 * LQR_SEED_BUMP.get((name, n, m, T), 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # Spectra that stress the PD projection V max(w, eps) V^T (ns16.h, psd_tiled.hip), shared by the stand-alone projection tests.
 ADVERSARIAL_SPECTRA = ("scaled_normal", "half_at_eps", "sixteen_decades", "rank_one", "dominant_pair", "hugging_eps", "zero_rows",
                        "all_pd")

@@ -72,7 +72,10 @@ def test_extra_leading_axes(lqr):
 
 
 def test_pivoting_paths(lqr):
-    """R with dominant off-diagonals forces row swaps in the m x m LU (partial pivoting, as getrf)."""
+    """R with dominant off-diagonals: a pivoted m x m LU (getrf) swaps rows on it, and an elimination without row exchanges would fail
+    its growth check.  K1 itself does neither here: its cofactor solve takes this matrix on the fast path (the CPU model's guard fires
+    on 0 of the 96 steps: tests/test_k1_solve_model.py, "permuted-dominant R").  The families that do reach K1's pivoted re-solve with
+    finite results, `input_units` and `dominant_input*`, are in tests/test_lqr_hard_gpu.py."""
     rng = np.random.default_rng(42)
     batch, T, n, m = 16, 6, 12, 4
     A, B, Q, R = problems.random_time_varying(batch, T, n, m, seed=77)

@@ -81,9 +81,11 @@ def _minor_rows(g, cc):
     return mr, mc
 
 
-def cofactor_solve(Suu, Sux):
+def cofactor_solve(Suu, Sux, details=False):
     """The product path on (..., 4, 4) and (..., 4, n).  Returns (L, admitted): L is the fast path's result wherever the guard
-    admits and the pivoted re-solve elsewhere."""
+    admits and the pivoted re-solve elsewhere.  details: (L, admitted, ratio, L_fast) with the guard's residual ratio
+    max|X - det I| / (TAU |det|) (the guard admits ratio <= 1; inf where det or 1/det is not finite) and the fast path's own result
+    everywhere, admitted or not."""
     Suu = np.asarray(Suu, np.float64)
     Sux = np.asarray(Sux, np.float64)
     # signed cofactors C[g][cc] (lane (g, c) with c & 3 = cc)
@@ -104,12 +106,17 @@ def cofactor_solve(Suu, Sux):
         L = X[..., :, :n] * r[..., None, None]
         eye = np.eye(4)
         res = np.abs(fma(-eye, det[..., None, None], X[..., :, n:]))
-        ok = (np.abs(det) <= _BIG) & (np.abs(r) <= _BIG) & np.all(res <= TAU * np.abs(det)[..., None, None], axis=(-2, -1))
+        finite = (np.abs(det) <= _BIG) & (np.abs(r) <= _BIG)
+        ok = finite & np.all(res <= TAU * np.abs(det)[..., None, None], axis=(-2, -1))
+        ratio = np.where(finite, np.max(res, axis=(-2, -1)) / (TAU * np.abs(det)), np.inf)
+    if details:
+        return _refit(L, ok, Suu, Sux), ok, np.where(np.isnan(ratio), np.inf, ratio), L
     return _refit(L, ok, Suu, Sux), ok
 
 
-def nopivot_solve(Suu, Sux):
-    """lu_solve4_nopivot on (..., 4, 4) and (..., 4, n), every right-hand side as in its own lane.  Returns (L, admitted)."""
+def nopivot_solve(Suu, Sux, details=False):
+    """lu_solve4_nopivot on (..., 4, 4) and (..., 4, n), every right-hand side as in its own lane.  Returns (L, admitted); details:
+    (L, admitted, L_fast) with the unpivoted result everywhere, whatever its check said."""
     S = np.asarray(Suu, np.float64)
     b = np.asarray(Sux, np.float64)
     lim = 4.0
@@ -138,6 +145,8 @@ def nopivot_solve(Suu, Sux):
         x0 = fma(-s(0, 3), x3, fma(-s(0, 2), x2, fma(-s(0, 1), x1, b[..., 0, :]))) * r0
     L = np.stack([x0, x1, x2, x3], axis=-2)
     okw = np.all(ok, axis=-1)                      # the wave-uniform vote over the right-hand sides
+    if details:
+        return _refit(L, okw, Suu, Sux), okw, L
     return _refit(L, okw, Suu, Sux), okw
 
 
