@@ -28,6 +28,21 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SYMBOLS) == names
 
 
+def test_solve_argument_names_follow_the_header():
+    """The fused drivers call a solve entry with [record[k] for k in _lib.SOLVE_ARGS[entry]]: those names are the header's parameter
+    names, one by one and in order, and as many as the ctypes signature has."""
+    hdr = open(os.path.join(ROOT, "include", "zopt_amd.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    entries = sorted(s for s in _lib.SYMBOLS if s.startswith("zm_ilqr_solve") and "workspace" not in s)
+    assert sorted(_lib.SOLVE_ARGS) == entries and len(entries) == 8
+    for name in entries:
+        decl = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
+        assert decl, f"{name}: no declaration in include/zopt_amd.h"
+        params = [re.search(r"(\w+)\s*$", p).group(1) for p in decl.group(1).split(",")]
+        assert _lib.SOLVE_ARGS[name] == params, name
+        assert len(_lib.SYMBOLS[name][1]) == len(params), name
+
+
 def test_version_and_support_matrix():
     lib = _lib.lib()
     assert lib.zm_version() >= 100

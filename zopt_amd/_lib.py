@@ -154,8 +154,7 @@ SYMBOLS = {
     "zm_ddp_backward_pairs_list_f64": (ctypes.c_int, [_c_dp] * 12 + [ctypes.c_int64, _c_dp, ctypes.c_int] + [_c_dp] * 2 +
                                        [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "zm_ilqr_solve_workspace_f64": (ctypes.c_int64, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
-    # (model*, cost*, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged,
-    #  iterations (host), batch, T, stream)
+    # the fused solves: their argument names are SOLVE_ARGS below (iterations: a host int32)
     "zm_ilqr_solve_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] +
                           [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "zm_shutdown": (ctypes.c_int, []),
@@ -200,8 +199,6 @@ SYMBOLS = {
                                       [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "zm_rollout_linesearch_box_list_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 5 +
                                            [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
-    # (model*, cost* | NULL, track* | NULL, box*, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
-    #  uTraj, L, J, converged, iterations (host), qp_capped | NULL, batch, T, stream[, J_trace, alpha_trace])
     "zm_ilqr_solve_box_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
                                                          ctypes.c_int64] + [_c_dp] * 8 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     "zm_ilqr_solve_box_trace_f64": (ctypes.c_int, [_c_dp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
@@ -227,9 +224,6 @@ SYMBOLS = {
     "zm_state_multiplier_update_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_double] * 3 +
                                        [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "zm_ilqr_solve_state_workspace_f64": (ctypes.c_int64, [_c_dp, ctypes.c_int64, ctypes.c_int]),
-    # (model*, cost* | NULL, track* | NULL, box* | NULL, sbox*, mu0, growth, mu_max, outer, ctol, x0, uGuess, ddp, max_iter, tol,
-    #  sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged, violation, outer_iterations | NULL,
-    #  inner_iterations | NULL, iterations (host), qp_capped | NULL, batch, T, stream[, J_trace, alpha_trace, violation_trace, mu_trace])
     "zm_ilqr_solve_state_f64": (ctypes.c_int, [_c_dp] * 5 + [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_double] + [_c_dp] * 2 +
                                 [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] + [_c_dp] * 11 +
                                 [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
@@ -240,6 +234,26 @@ SYMBOLS = {
     "zm_psd_project_f64": (ctypes.c_int, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "zm_condition_cost_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                           ctypes.c_void_p]),
+}
+
+
+# The ordered argument names of the eight fused-solve entries, spelled as include/zopt_amd.h spells its parameters (tests/test_abi.py
+# holds the two against each other): ilqrUtils fills one record keyed by these names and calls an entry with [record[k] for k in names].
+_SOLVE_CORE = "x0 uGuess ddp max_iter tol sync_every workspace workspace_doubles iwork xTraj uTraj L J converged"
+_SOLVE_PLAIN = f"model cost {_SOLVE_CORE} iterations batch T stream".split()
+_SOLVE_BOX = f"model cost track box {_SOLVE_CORE} iterations qp_capped batch T stream".split()
+_SOLVE_STATE = (f"model cost track box sbox mu0 growth mu_max outer ctol {_SOLVE_CORE} violation outer_iterations inner_iterations "
+                "iterations qp_capped batch T stream").split()
+_SOLVE_TRACE = ["J_trace", "alpha_trace"]
+SOLVE_ARGS = {
+    "zm_ilqr_solve_f64": _SOLVE_PLAIN,
+    "zm_ilqr_solve_trace_f64": _SOLVE_PLAIN + _SOLVE_TRACE,
+    "zm_ilqr_solve_tracking_f64": _SOLVE_PLAIN,           # `cost` is the zm_trackcost_t
+    "zm_ilqr_solve_tracking_trace_f64": _SOLVE_PLAIN + _SOLVE_TRACE,
+    "zm_ilqr_solve_box_f64": _SOLVE_BOX,                  # exactly one of `cost` and `track`
+    "zm_ilqr_solve_box_trace_f64": _SOLVE_BOX + _SOLVE_TRACE,
+    "zm_ilqr_solve_state_f64": _SOLVE_STATE,
+    "zm_ilqr_solve_state_trace_f64": _SOLVE_STATE + _SOLVE_TRACE + ["violation_trace", "mu_trace"],
 }
 
 

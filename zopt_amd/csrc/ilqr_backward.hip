@@ -49,6 +49,7 @@
 #include "zm_common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace zm {
 
@@ -982,6 +983,15 @@ struct ValueIO {   // optional scalar inputs / value-function outputs
     double *v_out, *vx_out, *vxx_out;
 };
 
+// The register-tile sweep kernels are instantiated per KS = ceil(n / 4) tile rows: calls f(ks) with ks an integral_constant, so that
+// a kernel family is written once as `[&](auto ks) { launch family<decltype(ks)::value> }`.
+template <typename F>
+static void with_ks(const int n, F&& f) {
+    if (n <= 4) f(std::integral_constant<int, 1>{});
+    else if (n <= 8) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 3>{});
+}
+
 template <int MODE>
 static int launch_ilqr(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
                        const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* d,
@@ -989,15 +999,10 @@ static int launch_ilqr(const double* f_x, const double* f_u, const double* c_x, 
                        hipStream_t st, DdpTensors z = DdpTensors{nullptr, nullptr, nullptr},
                        ValueIO v = ValueIO{nullptr, nullptr, nullptr, nullptr, nullptr}, TrajList tl = TrajList{nullptr, 0}) {
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
-    if (n <= 4)
-        hipLaunchKernelGGL((ilqr_backward_t16_f64<1, MODE>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,
+    with_ks(n, [&](auto ks) {
+        hipLaunchKernelGGL((ilqr_backward_t16_f64<decltype(ks)::value, MODE>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,
                            vf_xx, d, z.f_xx, z.f_ux, z.f_uu, svx, svxx, act, sh, l, L, T, n, m, v.c, v.vf, v.v_out, v.vx_out, v.vxx_out, tl, z.Hpk, z.ptab);
-    else if (n <= 8)
-        hipLaunchKernelGGL((ilqr_backward_t16_f64<2, MODE>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,
-                           vf_xx, d, z.f_xx, z.f_ux, z.f_uu, svx, svxx, act, sh, l, L, T, n, m, v.c, v.vf, v.v_out, v.vx_out, v.vxx_out, tl, z.Hpk, z.ptab);
-    else
-        hipLaunchKernelGGL((ilqr_backward_t16_f64<3, MODE>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,
-                           vf_xx, d, z.f_xx, z.f_ux, z.f_uu, svx, svxx, act, sh, l, L, T, n, m, v.c, v.vf, v.v_out, v.vx_out, v.vxx_out, tl, z.Hpk, z.ptab);
+    });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
@@ -1024,18 +1029,30 @@ static int zm_check_sweep_args(const char* who, int64_t batch, int T, int n, int
     return ZM_OK;
 }
 
+// What the list entries check first, in this order: nothing to do (*rc <- ZM_OK; pointers of empty arrays may be NULL), the list's
+// length, the operands (`operands`: the entry's own "all given"), the sizes.  true: the entry returns *rc.  `who_list` names the entry
+// in the list-length message, `who` in the others (for some entries the name of the dense form), as they always did.
+static bool sweep_prologue(int* rc, const char* who_list, const char* who, const int32_t* list, int64_t count, bool operands, int64_t batch,
+                           int T, int n, int m, bool tiled = false, const char* null_note = "") {
+    *rc = ZM_OK;
+    if (batch == 0 || (list && count == 0)) return true;
+    if (list && (count < 0 || count > batch)) *rc = zm::set_error(ZM_EINVAL, "%s: bad list length", who_list);
+    else if (!operands) *rc = zm::set_error(ZM_EINVAL, "%s: null pointer%s", who, null_note);
+    else *rc = zm_check_sweep_args(who, batch, T, n, m, tiled);
+    return *rc != ZM_OK;
+}
+static const char* const ZM_DDP_NULL_NOTE = " (f_ux and f_uu may be NULL together: identically zero)";
+
 extern "C" int zm_ilqr_backward_list_f64(const double* f_x, const double* f_u, const double* c_x, const double* c_u,
                                          const double* c_xx, const double* c_ux, const double* c_uu, const double* vf_x,
                                          const double* vf_xx, const int32_t* list, int64_t count, const int32_t* active,
                                          int shared_hessian, double* l, double* L, int64_t batch, int T, int n, int m,
                                          void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;   /* nothing to do (pointers of empty arrays may be NULL) */
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_list_f64: bad list length");
+    int rc;
+    if (sweep_prologue(&rc, "zm_ilqr_backward_list_f64", "zm_ilqr_backward_f64", list, count,
+                       f_x && f_u && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && l && L, batch, T, n, m, true))
+        return rc;
     const zm::TrajList tl{(const int*)list, (long)count};
-    if (!f_x || !f_u || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_f64: null pointer");
-    const int rc = zm_check_sweep_args("zm_ilqr_backward_f64", batch, T, n, m, true);
-    if (rc) return rc;
     if (n > 12 || m > 4)   // large states: fp64 MFMA tile sweep (sweep_tiled_f64.hip)
         return zm::sweep_tiled_f64_dispatch(0, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, nullptr, (long)n, (long)n * n,
                                             (const int*)active, shared_hessian ? 1 : 0, l, L, batch, T, n, m, (hipStream_t)stream,
@@ -1055,25 +1072,21 @@ extern "C" int zm_ilqr_backward_box_list_f64(const double* f_x, const double* f_
                                              const double* vf_xx, const double* uTraj, const zm_inputbox_t* box, const int32_t* list,
                                              int64_t count, const int32_t* active, int shared_hessian, double* l, double* L,
                                              int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_box_f64: bad list length");
-    if (!f_x || !f_u || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_box_f64: null pointer");
-    const int rc = zm_check_sweep_args("zm_ilqr_backward_box_f64", batch, T, n, m);
-    if (rc) return rc;
-    if (const int rb = zm::box_check(box, m, "zm_ilqr_backward_box_f64")) return rb;
+    const char* who = "zm_ilqr_backward_box_f64";
+    int rc;
+    if (sweep_prologue(&rc, who, who, list, count, f_x && f_u && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && uTraj && l && L,
+                       batch, T, n, m))
+        return rc;
+    if (const int rb = zm::box_check(box, m, who)) return rb;
     const zm::TrajList tl{(const int*)list, (long)count};
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
     hipStream_t st = (hipStream_t)stream;
     const int sh = shared_hessian ? 1 : 0;
-#define ZM_LAUNCH_BOX(KS_)                                                                                                          \
-    hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,   \
-                       uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L, (int*)qp_capped, \
-                       T, n, m, tl)
-    if (n <= 4) ZM_LAUNCH_BOX(1);
-    else if (n <= 8) ZM_LAUNCH_BOX(2);
-    else ZM_LAUNCH_BOX(3);
-#undef ZM_LAUNCH_BOX
+    zm::with_ks(n, [&](auto ks) {
+        hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu,
+                           vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L,
+                           (int*)qp_capped, T, n, m, tl);
+    });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
@@ -1093,34 +1106,27 @@ extern "C" int zm_ilqr_backward_state_list_f64(const double* f_x, const double* 
                                                const double* vf_xx, const double* h, const double* uTraj, const zm_inputbox_t* box,
                                                const int32_t* list, int64_t count, const int32_t* active, int shared_hessian, double* l,
                                                double* L, int32_t* qp_capped, int64_t batch, int T, int n, int m, void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: bad list length");
-    if (!f_x || !f_u || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !h || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: null pointer");
-    if ((box != nullptr) != (uTraj != nullptr))
-        return zm::set_error(ZM_EINVAL, "zm_ilqr_backward_state_f64: box and uTraj go together (both or neither)");
-    const int rc = zm_check_sweep_args("zm_ilqr_backward_state_f64", batch, T, n, m);
-    if (rc) return rc;
+    const char* who = "zm_ilqr_backward_state_f64";
+    int rc;
+    if (sweep_prologue(&rc, who, who, list, count, f_x && f_u && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && h && l && L, batch,
+                       T, n, m))
+        return rc;
+    if ((box != nullptr) != (uTraj != nullptr)) return zm::set_error(ZM_EINVAL, "%s: box and uTraj go together (both or neither)", who);
     if (box)
-        if (const int rb = zm::box_check(box, m, "zm_ilqr_backward_state_f64")) return rb;
+        if (const int rb = zm::box_check(box, m, who)) return rb;
     const zm::TrajList tl{(const int*)list, (long)count};
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
     hipStream_t st = (hipStream_t)stream;
     const int sh = shared_hessian ? 1 : 0;
-#define ZM_LAUNCH_PEN(KS_)                                                                                                              \
-    do {                                                                                                                                \
-        if (box)                                                                                                                        \
-            hipLaunchKernelGGL((zm::ilqr_backward_box_pen_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,  \
-                               vf_xx, h, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L,  \
-                               (int*)qp_capped, T, n, m, tl);                                                                           \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((zm::ilqr_backward_pen_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x,      \
-                               vf_xx, h, (long)n, (long)n * n, (const int*)active, sh, l, L, T, n, m, tl);                               \
-    } while (0)
-    if (n <= 4) ZM_LAUNCH_PEN(1);
-    else if (n <= 8) ZM_LAUNCH_PEN(2);
-    else ZM_LAUNCH_PEN(3);
-#undef ZM_LAUNCH_PEN
+    zm::with_ks(n, [&](auto ks) {
+        if (box)
+            hipLaunchKernelGGL((zm::ilqr_backward_box_pen_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux,
+                               c_uu, vf_x, vf_xx, h, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active,
+                               sh, l, L, (int*)qp_capped, T, n, m, tl);
+        else
+            hipLaunchKernelGGL((zm::ilqr_backward_pen_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux,
+                               c_uu, vf_x, vf_xx, h, (long)n, (long)n * n, (const int*)active, sh, l, L, T, n, m, tl);
+    });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
@@ -1190,14 +1196,12 @@ extern "C" int zm_ddp_backward_list_f64(const double* f_x, const double* f_u, co
                                         const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx,
                                         const int32_t* list, int64_t count, const int32_t* active, int shared_hessian,
                                         double* l, double* L, int64_t batch, int T, int n, int m, void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;   /* nothing to do (pointers of empty arrays may be NULL) */
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_list_f64: bad list length");
-    if (!f_x || !f_u || !f_xx || (!f_ux != !f_uu) || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_f64: null pointer (f_ux and f_uu may be NULL together: identically zero)");
-    const int rc = zm_check_sweep_args("zm_ddp_backward_f64", batch, T, n, m);
-    if (rc) return rc;
+    int rc;
+    if (sweep_prologue(&rc, "zm_ddp_backward_list_f64", "zm_ddp_backward_f64", list, count,
+                       f_x && f_u && f_xx && (!f_ux == !f_uu) && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && l && L, batch, T, n, m,
+                       false, ZM_DDP_NULL_NOTE))
+        return rc;
     if ((int64_t)n * n * n >= (int64_t)1 << 31) return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_f64: n too large");
-    if (batch == 0) return ZM_OK;
     return zm::launch_ilqr<2>(f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, nullptr, (long)n, (long)n * n,
                               (const int*)active, shared_hessian ? 1 : 0, l, L, batch, T, n, m, (hipStream_t)stream,
                               zm::DdpTensors{f_xx, f_ux, f_uu}, zm::ValueIO{nullptr, nullptr, nullptr, nullptr, nullptr},
@@ -1209,16 +1213,14 @@ extern "C" int zm_ddp_backward_pairs_list_f64(const zm_model_t* model, const dou
                                               const double* c_uu, const double* vf_x, const double* vf_xx, const int32_t* list,
                                               int64_t count, const int32_t* active, int shared_hessian, double* l, double* L,
                                               int64_t batch, int T, void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_list_f64: bad list length");
-    if (!model || !f_x || !f_u || !H || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_list_f64: null pointer");
-    const int n = model->n, m = model->m;
-    const int rc = zm_check_sweep_args("zm_ddp_backward_pairs_list_f64", batch, T, n, m);
-    if (rc) return rc;
+    const char* who = "zm_ddp_backward_pairs_list_f64";
+    const int n = model ? model->n : 0, m = model ? model->m : 0;
+    int rc;
+    if (sweep_prologue(&rc, who, who, list, count, model && f_x && f_u && H && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && l && L,
+                       batch, T, n, m))
+        return rc;
     const zm::PairTab pt = zm::model_pair_table(model->kind);
-    if (pt.n < 1)
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_pairs_list_f64: the model declares no Hessian pairs");
+    if (pt.n < 1) return zm::set_error(ZM_EUNSUPPORTED, "%s: the model declares no Hessian pairs", who);
     const zm::TrajList tl{(const int*)list, (long)count};
     {   // the LDS-ring kernel where it applies (quadcopter shapes, shared cost Hessians); the register kernel otherwise
         const int rd = zm::ddp_backward_dma_dispatch(f_x, f_u, H, pt, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx, (long)n, (const int*)active,
@@ -1240,14 +1242,11 @@ static int launch_ddp_box(const double* f_x, const double* f_u, const zm::DdpTen
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
     hipStream_t st = (hipStream_t)stream;
     const int sh = shared_hessian ? 1 : 0;
-#define ZM_LAUNCH_DDP_BOX(KS_)                                                                                                       \
-    hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<KS_>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,    \
-                       uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux, z.f_uu, (long)n, (long)n * n, (const int*)active, \
-                       sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab)
-    if (n <= 4) ZM_LAUNCH_DDP_BOX(1);
-    else if (n <= 8) ZM_LAUNCH_DDP_BOX(2);
-    else ZM_LAUNCH_DDP_BOX(3);
-#undef ZM_LAUNCH_DDP_BOX
+    zm::with_ks(n, [&](auto ks) {
+        hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu,
+                           vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux, z.f_uu, (long)n, (long)n * n,
+                           (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab);
+    });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }
@@ -1258,14 +1257,14 @@ extern "C" int zm_ddp_backward_box_list_f64(const double* f_x, const double* f_u
                                             const double* uTraj, const zm_inputbox_t* box, const int32_t* list, int64_t count,
                                             const int32_t* active, int shared_hessian, double* l, double* L, int32_t* qp_capped,
                                             int64_t batch, int T, int n, int m, void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_box_list_f64: bad list length");
-    if (!f_x || !f_u || !f_xx || (!f_ux != !f_uu) || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_box_list_f64: null pointer (f_ux and f_uu may be NULL together: identically zero)");
-    const int rc = zm_check_sweep_args("zm_ddp_backward_box_list_f64", batch, T, n, m);
-    if (rc) return rc;
-    if ((int64_t)n * n * n >= (int64_t)1 << 31) return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_box_list_f64: n too large");
-    if (const int rb = zm::box_check(box, m, "zm_ddp_backward_box_list_f64")) return rb;
+    const char* who = "zm_ddp_backward_box_list_f64";
+    int rc;
+    if (sweep_prologue(&rc, who, who, list, count,
+                       f_x && f_u && f_xx && (!f_ux == !f_uu) && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && uTraj && l && L, batch,
+                       T, n, m, false, ZM_DDP_NULL_NOTE))
+        return rc;
+    if ((int64_t)n * n * n >= (int64_t)1 << 31) return zm::set_error(ZM_EUNSUPPORTED, "%s: n too large", who);
+    if (const int rb = zm::box_check(box, m, who)) return rb;
     return launch_ddp_box(f_x, f_u, zm::DdpTensors{f_xx, f_ux, f_uu}, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,
                           uTraj, box, zm::TrajList{(const int*)list, (long)count}, active, shared_hessian, l, L, qp_capped, batch, T, n,
                           m, stream);
@@ -1286,17 +1285,15 @@ extern "C" int zm_ddp_backward_pairs_box_list_f64(const zm_model_t* model, const
                                                   const zm_inputbox_t* box, const int32_t* list, int64_t count, const int32_t* active,
                                                   int shared_hessian, double* l, double* L, int32_t* qp_capped, int64_t batch, int T,
                                                   void* stream) {
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_box_list_f64: bad list length");
-    if (!model || !f_x || !f_u || !H || !c_x || !c_u || !c_xx || !c_ux || !c_uu || !vf_x || !vf_xx || !uTraj || !l || !L)
-        return zm::set_error(ZM_EINVAL, "zm_ddp_backward_pairs_box_list_f64: null pointer");
-    const int n = model->n, m = model->m;
-    const int rc = zm_check_sweep_args("zm_ddp_backward_pairs_box_list_f64", batch, T, n, m);
-    if (rc) return rc;
+    const char* who = "zm_ddp_backward_pairs_box_list_f64";
+    const int n = model ? model->n : 0, m = model ? model->m : 0;
+    int rc;
+    if (sweep_prologue(&rc, who, who, list, count,
+                       model && f_x && f_u && H && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && uTraj && l && L, batch, T, n, m))
+        return rc;
     const zm::PairTab pt = zm::model_pair_table(model->kind);
-    if (pt.n < 1)
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_ddp_backward_pairs_box_list_f64: the model declares no Hessian pairs");
-    if (const int rb = zm::box_check(box, m, "zm_ddp_backward_pairs_box_list_f64")) return rb;
+    if (pt.n < 1) return zm::set_error(ZM_EUNSUPPORTED, "%s: the model declares no Hessian pairs", who);
+    if (const int rb = zm::box_check(box, m, who)) return rb;
     return launch_ddp_box(f_x, f_u, zm::DdpTensors{nullptr, nullptr, nullptr, H, pt}, c_x, c_u,
                           c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, zm::TrajList{(const int*)list, (long)count}, active,
                           shared_hessian, l, L, qp_capped, batch, T, n, m, stream);

@@ -155,15 +155,9 @@ struct StatePen {
     const double* uStart;       // (batch, T, m) the inputs it starts from
 };
 
-// The cost of a solve, as the loop sees it: the weights (the Hessians, the conditioning and the kernels' cost arithmetic read only
-// these) and, for a tracking cost (zm_trackcost_t), the reference that the line search's cost values and the expansion's gradients
-// are taken about.  One loop serves both; `track` == nullptr is the zm_quadcost_t path with exactly its launches.
-struct IlqrCost {
-    bool given;
-    zm_quadcost_t w;
-    const zm_trackcost_t* track;
-    TrackRef ref;
-    const TrackRef* ref_ptr() const { return track ? &ref : nullptr; }
+// The cost of a solve, as the loop sees it: the resolved cost (track_cost.h: one loop serves zm_quadcost_t and zm_trackcost_t) and
+// what the box and state entries add to it.
+struct IlqrCost : CostRef {
     // input bounds (zm_ilqr_solve_box_f64; nullptr: none): the sweep (iLQR or DDP) and the line search are then the box forms
     const zm_inputbox_t* box = nullptr;
     int32_t* qp_capped = nullptr;
@@ -227,6 +221,104 @@ static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_u
     w.scratch = take(w.tail_slots * (T + 1) * 256);
     w.total = o;
     return w;
+}
+
+// What the backward sweep of a solve runs on, decided once before the loop: the form of the Jacobians and of the second derivatives.
+struct SweepPlan {
+    int ddp, npairs;
+    bool packed, sparse_h;
+    double *f_ux, *f_uu;   // nullptr: identically zero (a model affine in its controls) or held as pairs -- neither written nor read
+    int njp;
+    const unsigned char* jpos;
+    PairTab ptab;
+    int nh, nhs;
+    const unsigned short* hdense;
+};
+static SweepPlan sweep_plan(const zm_model_t* model, const IlqrCost& ck, double* ws, const IlqrWs& w, int ddp, int need_ux, int npairs) {
+    // Packed Jacobians (quadcopter): the expansion writes and the ring sweeps read only the structurally nonzero entries of
+    // [f_x | f_u] -- 448 B (480 with wind) per point instead of 1 536 B.  ZOPT_AMD_JAC=full or ZOPT_AMD_ILQR_PATH=reg: the full matrices.
+    // (a box solve: full Jacobians only)
+    static const bool packed_off = [] {
+        const char* e = zm::lab_env("ZOPT_AMD_JAC");
+        const char* r = zm::fallback_env("ZOPT_AMD_ILQR_PATH");
+        return (e && e[0] == 'f') || (r && r[0] == 'r');
+    }();
+    // ... and the DDP path's second derivatives SPARSE (69 / 85 structurally nonzero entries of the 28 x 12 per point; ZOPT_AMD_HES=dense:
+    // the dense pair rows)
+    static const bool sparse_off = [] {
+        const char* e = zm::lab_env("ZOPT_AMD_HES");
+        return e && e[0] == 'd';
+    }();
+    const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
+    SweepPlan p;
+    p.ddp = ddp, p.npairs = npairs;
+    p.packed = !ck.box && !ck.pen && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
+               (!ddp || npairs == 28);
+    p.sparse_h = p.packed && ddp && !sparse_off;
+    p.f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
+    p.f_uu = (need_ux && npairs == 0) ? ws + w.f_uu : nullptr;
+    p.njp = windy ? ((QUAD_NJ_WIND + 1) & ~1) : ((QUAD_NJ_STILL + 1) & ~1);
+    p.jpos = windy ? QUAD_JPOS_WIND : QUAD_JPOS_STILL;
+    p.ptab = model_pair_table(model->kind);
+    p.nh = windy ? QUAD_NH_WIND : QUAD_NH_STILL, p.nhs = (p.nh + 1) & ~1;
+    p.hdense = windy ? QUAD_HDENSE_WIND : QUAD_HDENSE_STILL;
+    return p;
+}
+
+// The backward pass of one iteration over the listed trajectories (for DDP behind its second derivatives along curX, curU): the form
+// that the plan and the cost's box / penalty select.  l goes to the workspace, L to the caller's array.
+static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model_t* model, double* ws, const IlqrWs& w, const double* curX,
+                          const double* curU, const int32_t* list, int64_t count, const int32_t* active, double* L, int64_t batch, int T,
+                          hipStream_t st) {
+    const int n = model->n, m = model->m;
+    int rc = ZM_OK;
+    if (p.packed) {
+        if (p.sparse_h)
+            rc = quad_hessian_sparse_list(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
+        else if (p.ddp)
+            rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
+        if (rc) return rc;
+        rc = sweep_packed_jacobians(ws + w.f_x, p.njp, p.jpos, p.ddp ? ws + w.f_xx : nullptr, p.ptab, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                    ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, (const int*)active, ws + w.l, L, batch, T, st,
+                                    TrajList{(const int*)list, (long)count}, p.sparse_h ? p.nhs : 0, p.hdense, p.nh);
+        if (rc == ZM_EUNSUPPORTED) return set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: packed sweep refused its operands");
+        return rc;
+    }
+    if (p.ddp) {
+        // The second derivatives as pairs where the model declares them -- 28 x 12 doubles per point for the quadcopter instead of the
+        // zero-filled (n,n,n) tensors (2.7 KB instead of 13.8 KB written by the expansion and read back by the sweep, same arithmetic)
+        // -- and as the full tensors otherwise.  With input bounds: the register sweep with the box-QP per step on the current inputs.
+        if (p.npairs > 0) {
+            rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
+            if (rc) return rc;
+            if (ck.box)
+                return zm_ddp_backward_pairs_box_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                          ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count,
+                                                          active, 1, ws + w.l, L, ck.qp_capped, batch, T, st);
+            return zm_ddp_backward_pairs_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                  ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L,
+                                                  batch, T, st);
+        }
+        rc = zm_quadratic_dynamics_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, p.f_ux, p.f_uu, batch, T, st);
+        if (rc) return rc;
+        if (ck.box)
+            return zm_ddp_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, p.f_ux, p.f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1,
+                                                ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
+        return zm_ddp_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, p.f_ux, p.f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                        ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch,
+                                        T, n, m, st);
+    }
+    if (ck.pen)
+        return zm_ilqr_backward_state_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
+                                               ws + w.v_x, ws + w.v_xx, ck.pen->h, ck.box ? curU : nullptr, ck.box, list, count, active,
+                                               1, ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
+    if (ck.box)
+        return zm_ilqr_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
+                                             ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1, ws + w.l, L, ck.qp_capped,
+                                             batch, T, n, m, st);
+    return zm_ilqr_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, ws + w.v_x,
+                                     ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch, T, n, m, st);
 }
 
 // Pool of (pinned int32, event) pairs per device for the drivers' host round trips.
@@ -330,25 +422,43 @@ extern "C" int64_t zm_ilqr_solve_workspace_f64(const zm_model_t* model, int64_t 
     return zm::carve(model, batch, T, ddp, (mask >> model->n) != 0, npairs).total;
 }
 
-static zm::IlqrCost quad_cost(const zm_quadcost_t* c) {
-    return zm::IlqrCost{c != nullptr, c ? *c : zm_quadcost_t{nullptr, nullptr, nullptr, 0, 0}, nullptr, zm::TrackRef{}};
-}
+// One fused solve as its entry received it: every zm_ilqr_solve*_f64 entry fills this record and hands it to ilqr_solve_impl.
+struct SolveCall {
+    const zm_model_t* model;
+    zm::IlqrCost ck;
+    const double *x0, *uGuess;
+    int ddp, max_iter;
+    double tol;
+    int sync_every;
+    double* workspace;
+    int64_t workspace_doubles;
+    int32_t* iwork;
+    double *xTraj, *uTraj, *L, *J;
+    int32_t *converged, *iterations;
+    int64_t batch;
+    int T;
+    void* stream;
+    double* J_trace = nullptr;
+    int32_t* alpha_trace = nullptr;
+};
 
-static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, const double* x0, const double* uGuess,
-                           int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
-                           int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
-                           int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace) {
+static int ilqr_solve_impl(const SolveCall& c) {
+    const zm_model_t* const model = c.model;
+    const zm::IlqrCost& ck = c.ck;
+    const int64_t batch = c.batch;
+    const int T = c.T, ddp = c.ddp;
+    double *const xTraj = c.xTraj, *const uTraj = c.uTraj, *const L = c.L, *const J = c.J;
     if (batch == 0) return ZM_OK;
-    const zm_quadcost_t* cost = ck.given ? &ck.w : nullptr;   // the weights
-    if (!model || !cost || !x0 || !uGuess || !workspace || !iwork || !xTraj || !uTraj || !L || !J || !converged)
+    const zm_quadcost_t* cost = ck.weights();
+    if (!model || !cost || !c.x0 || !c.uGuess || !c.workspace || !c.iwork || !xTraj || !uTraj || !L || !J || !c.converged)
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: null pointer");
-    if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
+    if (batch < 0 || T < 1 || c.max_iter < 0 || c.sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
     if (ck.box) {
         if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
             return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);
         if (const int rb = zm::box_check(ck.box, m, "zm_ilqr_solve_box_f64")) return rb;
-        if (ck.qp_capped && !ck.pen) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
+        if (ck.qp_capped && !ck.pen) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)c.stream));
     }
     if (ck.pen && (ddp || n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_state_f64: iLQR with n<=12, m<=4 only (n=%d, m=%d, ddp=%d)", n, m, ddp);
@@ -364,32 +474,32 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
     }
     const int need_ux = (mask >> n) != 0;   // a model affine in its controls has f_ux = f_uu = 0: neither written nor read
     const zm::IlqrWs w = zm::carve(model, batch, T, ddp, need_ux, npairs);
-    if (workspace_doubles < w.total)
-        return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: workspace of %lld doubles, %lld needed", (long long)workspace_doubles,
+    if (c.workspace_doubles < w.total)
+        return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: workspace of %lld doubles, %lld needed", (long long)c.workspace_doubles,
                              (long long)w.total);
-    hipStream_t st = (hipStream_t)stream;
-    double* ws = workspace;
+    hipStream_t st = (hipStream_t)c.stream;
+    double* ws = c.workspace;
     // iwork (int32): active (batch) | list (batch) | count (2)
-    int32_t* active = iwork;
-    int32_t* list = iwork + batch;
-    int32_t* dcount = iwork + 2 * batch;
+    int32_t* active = c.iwork;
+    int32_t* list = c.iwork + batch;
+    int32_t* dcount = c.iwork + 2 * batch;
     const long xrow = (long)(T + 1) * n, urow = (long)T * m;
 
     // policy = (uGuess, 0); traj_prev = zeros; step sizes; masks                                     (ilqrUtils.py:293-294, :145)
     int32_t* where = (int32_t*)(ws + w.where);
     if (ck.pen) {
         const int ri = zm::ilqr_init_masked(ck.pen->init_mask, ws + w.l, ck.pen->uStart, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, active,
-                                            converged, where, batch, T, n, m, (hipStream_t)stream);
+                                            c.converged, where, batch, T, n, m, st);
         if (ri) return ri;
     } else {
         const long nL = (long)batch * urow * n, nx = (long)batch * xrow, nl = (long)batch * urow;
         const long work = nL > nx ? nL : nx;
         const unsigned blocks = (unsigned)((work + 256L * 8 - 1) / (256L * 8) < 4096 ? (work + 256L * 8 - 1) / (256L * 8) : 4096);
-        hipLaunchKernelGGL(zm::ilqr_init_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, ws + w.l, uGuess, nl, L, nL, ws + w.xT2, nx,
-                           ws + w.uT2, ws + w.alphas, (int*)active, (int*)converged, (int*)where, (long)batch);
+        hipLaunchKernelGGL(zm::ilqr_init_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, st, ws + w.l, c.uGuess, nl, L, nL, ws + w.xT2, nx,
+                           ws + w.uT2, ws + w.alphas, (int*)active, (int*)c.converged, (int*)where, (long)batch);
     }
     // initial rollout (alpha = 1) from the zero trajectory and its cost                                (:297-298)
-    int rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0,
+    int rc = zm::cost_linesearch(ck, model, c.x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0,
                                  ck.pen ? active : nullptr, xTraj, uTraj, J, nullptr, batch, T, st);
     if (rc) return rc;
     // trajectory-independent Hessians of the quadratic cost, PD-conditioned once                         (:309-313)
@@ -401,32 +511,9 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
     rc = zm_psd_project_f64(ws + w.v_xx, 1, n, 1e-3, st);
     if (rc) return rc;
 
-    double* f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
-    double* f_uu = (need_ux && npairs == 0) ? ws + w.f_uu : nullptr;
     // (a box solve: one-lane two-pass line search and full Jacobians only)
     const bool can_all_store = !ck.box && !ck.pen && w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
-    // Packed Jacobians (quadcopter): the expansion writes and the ring sweeps read only the structurally nonzero entries of
-    // [f_x | f_u] -- 448 B (480 with wind) per point instead of 1 536 B.  ZOPT_AMD_JAC=full or ZOPT_AMD_ILQR_PATH=reg: the full matrices.
-    static const bool packed_off = [] {
-        const char* e = zm::lab_env("ZOPT_AMD_JAC");
-        const char* r = zm::fallback_env("ZOPT_AMD_ILQR_PATH");
-        return (e && e[0] == 'f') || (r && r[0] == 'r');
-    }();
-    const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
-    const bool packed = !ck.box && !ck.pen && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
-                        (!ddp || npairs == 28);
-    const int njp = windy ? ((zm::QUAD_NJ_WIND + 1) & ~1) : ((zm::QUAD_NJ_STILL + 1) & ~1);
-    const unsigned char* jpos = windy ? zm::QUAD_JPOS_WIND : zm::QUAD_JPOS_STILL;
-    const zm::PairTab ptab = zm::model_pair_table(model->kind);
-    // ... and the DDP path's second derivatives SPARSE (69 / 85 structurally nonzero entries of the 28 x 12 per point; ZOPT_AMD_HES=dense:
-    // the dense pair rows)
-    static const bool sparse_off = [] {
-        const char* e = zm::lab_env("ZOPT_AMD_HES");
-        return e && e[0] == 'd';
-    }();
-    const bool sparse_h = packed && ddp && !sparse_off;
-    const int nh = windy ? zm::QUAD_NH_WIND : zm::QUAD_NH_STILL, nhs = (nh + 1) & ~1;
-    const unsigned short* hdense = windy ? zm::QUAD_HDENSE_WIND : zm::QUAD_HDENSE_STILL;
+    const zm::SweepPlan plan = zm::sweep_plan(model, ck, ws, w, ddp, need_ux, npairs);
     int32_t* widx = (int32_t*)(ws + w.idx);
     // pinned word + event for the active count, borrowed from a per-device pool for the duration of this call (a pinned allocation
     // per solve costs ~1 ms; an event belongs to the device that was current when it was created).  Concurrent solves on one device
@@ -449,13 +536,13 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
     double *curX = xTraj, *curU = uTraj, *altX = ws + w.xT2, *altU = ws + w.uT2;
     int it = 0;
     int64_t count = batch;
-    for (; it < max_iter; ++it) {                                                                        // (:301-303)
+    for (; it < c.max_iter; ++it) {                                                                      // (:301-303)
         // Every `sync_every` iterations: rebuild the id list on the device and learn how many trajectories are left.  The expansion
         // launch does not wait for that answer: it goes out behind the compaction with the PREVIOUS count (list entries past the new
         // count are ids of the previous list: inactive ones are skipped by the mask, a still-active one is merely expanded twice --
         // the same values into the same rows), and the host round trip (~45 us) passes while it runs.
         // (Measured: a longer interval once the active set is small does not pay -- a stale list costs the DDP tail 1-3 %.)
-        const bool sync_now = (it % sync_every == 0);
+        const bool sync_now = (it % c.sync_every == 0);
         unsigned seq = 0;
         if (sync_now) {
             seq = lease.next_seq();
@@ -465,7 +552,7 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
         }
         // expansions along the current trajectories: [f_x | f_u], c_x, c_u, v_x in one launch                  (:304-313)
         rc = zm::expand_list(model, cost, curX, curU, list, count, active, ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u,
-                             ws + w.v_x, batch, T, st, packed ? 1 : 0, ck.ref_ptr());
+                             ws + w.v_x, batch, T, st, plan.packed ? 1 : 0, ck.ref_ptr());
         if (rc) return rc;
         if (sync_now) {
             int32_t c32 = 0;
@@ -479,105 +566,55 @@ static int ilqr_solve_impl(const zm_model_t* model, const zm::IlqrCost& ck, cons
                                           T, n, st);
             if (rc) return rc;
         }
-        if (packed) {
-            if (sparse_h) {
-                rc = zm::quad_hessian_sparse_list(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
-                if (rc) return rc;
-            } else if (ddp) {
-                rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
-                if (rc) return rc;
-            }
-            rc = zm::sweep_packed_jacobians(ws + w.f_x, njp, jpos, ddp ? ws + w.f_xx : nullptr, ptab, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                            ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, (const int*)active, ws + w.l, L, batch, T,
-                                            (hipStream_t)st, zm::TrajList{(const int*)list, (long)count}, sparse_h ? nhs : 0, hdense, nh);
-            if (rc == ZM_EUNSUPPORTED) return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: packed sweep refused its operands");
-        } else if (ddp && ck.box) {
-            // DDP with input bounds: full Jacobians, the second derivatives as pairs where the model declares them, the register sweep
-            // with the box-QP per step on the current inputs
-            if (npairs > 0) {
-                rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
-                if (rc) return rc;
-                rc = zm_ddp_backward_pairs_box_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                                        ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count,
-                                                        active, 1, ws + w.l, L, ck.qp_capped, batch, T, st);
-            } else {
-                rc = zm_quadratic_dynamics_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, f_ux, f_uu, batch, T, st);
-                if (rc) return rc;
-                rc = zm_ddp_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, f_ux, f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                                  ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1,
-                                                  ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
-            }
-        } else if (ddp && npairs > 0) {
-            // packed second derivatives: 28 x 12 doubles per point for the quadcopter instead of the zero-filled (n,n,n) tensors
-            // (2.7 KB instead of 13.8 KB written by the expansion and read back by the sweep, same arithmetic)
-            rc = zm_quadratic_dynamics_pairs_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, batch, T, st);
-            if (rc) return rc;
-            rc = zm_ddp_backward_pairs_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                                ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l,
-                                                L, batch, T, st);
-        } else if (ddp) {
-            rc = zm_quadratic_dynamics_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, f_ux, f_uu, batch, T, st);
-            if (rc) return rc;
-            rc = zm_ddp_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, f_ux, f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                          ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L,
-                                          batch, T, n, m, st);
-        } else if (ck.pen) {
-            rc = zm_ilqr_backward_state_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
-                                                 ws + w.v_x, ws + w.v_xx, ck.pen->h, ck.box ? curU : nullptr, ck.box, list, count, active,
-                                                 1, ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
-        } else if (ck.box) {
-            rc = zm_ilqr_backward_box_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
-                                               ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1, ws + w.l, L, ck.qp_capped,
-                                               batch, T, n, m, st);
-        } else {
-            rc = zm_ilqr_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
-                                           ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch, T, n, m, st);
-        }
+        rc = zm::backward_sweep(plan, ck, model, ws, w, curX, curU, list, count, active, L, batch, T, st);
         if (rc) return rc;
         // 16-way line search (:116-150), then accept: converged = |J - J_new| <= tol, (traj, J) <- (traj_new, J_new) on the listed
         // rows (:316-320)
         if (can_all_store && count <= w.tail_slots) {
-            rc = zm::rollout_linesearch_all_store(model, cost, x0, ws + w.l, L, curX, curU, ws + w.alphas, list, count, active,
+            rc = zm::rollout_linesearch_all_store(model, cost, c.x0, ws + w.l, L, curX, curU, ws + w.alphas, list, count, active,
                                                   ws + w.scratch, ws + w.Jn, widx, batch, T, st, ck.ref_ptr());
             if (rc) return rc;
-            rc = zm::ilqr_accept(list, count, J, ws + w.Jn, curX, nullptr, curU, nullptr, converged, active, tol, batch, T, n, m, st,
+            rc = zm::ilqr_accept(list, count, J, ws + w.Jn, curX, nullptr, curU, nullptr, c.converged, active, c.tol, batch, T, n, m, st,
                                  ws + w.scratch, widx, swap_on ? where : nullptr, curX == xTraj ? 0 : 1);
         } else if (swap_on) {
-            rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, curX, curU, ws + w.alphas, 16, list, count, active, altX, altU, ws + w.Jn,
+            rc = zm::cost_linesearch(ck, model, c.x0, ws + w.l, L, curX, curU, ws + w.alphas, 16, list, count, active, altX, altU, ws + w.Jn,
                                      widx, batch, T, st);
             if (rc) return rc;
-            rc = zm::ilqr_accept(list, count, J, ws + w.Jn, altX, nullptr, altU, nullptr, converged, active, tol, batch, T, n, m, st,
+            rc = zm::ilqr_accept(list, count, J, ws + w.Jn, altX, nullptr, altU, nullptr, c.converged, active, c.tol, batch, T, n, m, st,
                                  nullptr, nullptr, where, altX == xTraj ? 0 : 1);
             std::swap(curX, altX);
             std::swap(curU, altU);
         } else {
-            rc = zm::cost_linesearch(ck, model, x0, ws + w.l, L, xTraj, uTraj, ws + w.alphas, 16, list, count, active, ws + w.xT2,
+            rc = zm::cost_linesearch(ck, model, c.x0, ws + w.l, L, xTraj, uTraj, ws + w.alphas, 16, list, count, active, ws + w.xT2,
                                      ws + w.uT2, ws + w.Jn, widx, batch, T, st);
             if (rc) return rc;
-            rc = zm_ilqr_accept_f64(list, count, J, ws + w.Jn, xTraj, ws + w.xT2, uTraj, ws + w.uT2, converged, active, tol, batch, T,
+            rc = zm_ilqr_accept_f64(list, count, J, ws + w.Jn, xTraj, ws + w.xT2, uTraj, ws + w.uT2, c.converged, active, c.tol, batch, T,
                                     n, m, st);
         }
         if (rc) return rc;
         // diagnostics (zm_ilqr_solve_trace_f64): row `it` <- every trajectory's cost after this iteration's acceptance step and the
         // line search's winning step-size index (meaningful for the trajectories that were active in this iteration)
-        if (J_trace) ZM_HIP_CHECK(hipMemcpyAsync(J_trace + (long)it * batch, J, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
-        if (alpha_trace)
-            ZM_HIP_CHECK(hipMemcpyAsync(alpha_trace + (long)it * batch, widx, sizeof(int32_t) * batch, hipMemcpyDeviceToDevice, st));
+        if (c.J_trace) ZM_HIP_CHECK(hipMemcpyAsync(c.J_trace + (long)it * batch, J, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+        if (c.alpha_trace)
+            ZM_HIP_CHECK(hipMemcpyAsync(c.alpha_trace + (long)it * batch, widx, sizeof(int32_t) * batch, hipMemcpyDeviceToDevice, st));
     }
     if (swap_on) {
         rc = zm::ilqr_collect(where, xTraj, ws + w.xT2, uTraj, ws + w.uT2, batch, T, n, m, st);
         if (rc) return rc;
     }
-    if (iterations) *iterations = it;
+    if (c.iterations) *c.iterations = it;
     return ZM_OK;
 }
 
-extern "C" int zm_ilqr_solve_f64(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* uGuess,
-                                 int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
-                                 int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
-                                 int32_t* iterations, int64_t batch, int T, void* stream) {
-    return ilqr_solve_impl(model, quad_cost(cost), x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
-                           uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
+// The eight entries: each resolves its cost argument(s), fills the record and runs the loop (the state entries: the AL loop around it).
+// The plain forms are the trace forms without a trace.
+static int solve_entry(SolveCall c, const zm_quadcost_t* cost, const zm_trackcost_t* track, zm::CostArg form, const char* who,
+                       const zm_inputbox_t* box = nullptr, int32_t* qp_capped = nullptr) {
+    if (c.batch == 0) return ZM_OK;
+    if (const int rc = zm::cost_resolve(cost, track, form, who, &c.ck)) return rc;
+    c.ck.box = box;
+    c.ck.qp_capped = qp_capped;
+    return ilqr_solve_impl(c);
 }
 
 extern "C" int zm_ilqr_solve_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* uGuess,
@@ -585,8 +622,17 @@ extern "C" int zm_ilqr_solve_trace_f64(const zm_model_t* model, const zm_quadcos
                                        int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
                                        int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
                                        int32_t* alpha_trace) {
-    return ilqr_solve_impl(model, quad_cost(cost), x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
-                           uTraj, L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace);
+    return solve_entry(SolveCall{model, {}, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj,
+                                 L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace},
+                       cost, nullptr, zm::CostArg::quad, "zm_ilqr_solve_f64");
+}
+
+extern "C" int zm_ilqr_solve_f64(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* uGuess,
+                                 int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
+                                 int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
+                                 int32_t* iterations, int64_t batch, int T, void* stream) {
+    return zm_ilqr_solve_trace_f64(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj,
+                                   uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
 }
 
 extern "C" int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess,
@@ -594,11 +640,9 @@ extern "C" int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const z
                                                 int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L,
                                                 double* J, int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream,
                                                 double* J_trace, int32_t* alpha_trace) {
-    if (batch == 0) return ZM_OK;
-    if (const int rc = zm::track_check(cost, "zm_ilqr_solve_tracking_f64")) return rc;
-    const zm::IlqrCost ck{true, zm::track_weights(*cost), cost, zm::track_ref(*cost)};
-    return ilqr_solve_impl(model, ck, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J,
-                           converged, iterations, batch, T, stream, J_trace, alpha_trace);
+    return solve_entry(SolveCall{model, {}, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj,
+                                 L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace},
+                       nullptr, cost, zm::CostArg::track, "zm_ilqr_solve_tracking_f64");
 }
 
 extern "C" int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* uGuess,
@@ -616,18 +660,10 @@ extern "C" int zm_ilqr_solve_box_trace_f64(const zm_model_t* model, const zm_qua
                                            double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations,
                                            int32_t* qp_capped, int64_t batch, int T, void* stream, double* J_trace,
                                            int32_t* alpha_trace) {
-    if (batch == 0) return ZM_OK;
-    if (!box) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_box_f64: null box");
-    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_box_f64: pass exactly one of cost and track");
-    zm::IlqrCost ck = quad_cost(cost);
-    if (track) {
-        if (const int rc = zm::track_check(track, "zm_ilqr_solve_box_f64")) return rc;
-        ck = zm::IlqrCost{true, zm::track_weights(*track), track, zm::track_ref(*track)};
-    }
-    ck.box = box;
-    ck.qp_capped = qp_capped;
-    return ilqr_solve_impl(model, ck, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J,
-                           converged, iterations, batch, T, stream, J_trace, alpha_trace);
+    if (batch != 0 && !box) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_box_f64: null box");
+    return solve_entry(SolveCall{model, {}, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj,
+                                 L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace},
+                       cost, track, zm::CostArg::exactly_one, "zm_ilqr_solve_box_f64", box, qp_capped);
 }
 
 extern "C" int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -641,11 +677,26 @@ extern "C" int zm_ilqr_solve_box_f64(const zm_model_t* model, const zm_quadcost_
 
 // Extension; the reference has no counterpart: iLQR with bounds on the states by an augmented-Lagrangian outer loop around the loop
 // above (AL-iLQR).  Host code: per outer iteration one inner solve over the trajectories that are not done, then the multiplier update.
+// What the state solve carves behind the inner solve's workspace (offsets in doubles from its start).
+struct StateWs {
+    int64_t base;       // the inner solve's own workspace (zm_ilqr_solve_workspace_f64, ddp = 0); -1: cannot be sized
+    int64_t h;          // (batch, T+1, n) diagonal addend of the cost Hessians
+    int64_t Jal;        // (batch) J_AL
+    int64_t notdone;    // int32 (batch): the trajectories that are not done
+    int64_t remaining;  // int32: how many of them go on
+    int64_t total;
+    StateWs(const zm_model_t* model, int64_t batch, int T) : base(zm_ilqr_solve_workspace_f64(model, batch, T, 0)) {
+        h = base;
+        Jal = h + (((int64_t)batch * (T + 1) * (model ? model->n : 0) + 1) & ~(int64_t)1);
+        notdone = Jal + ((batch + 1) & ~(int64_t)1);
+        remaining = notdone + (batch + 1) / 2;   // (behind the mask: int32 index (batch + 1) & ~1 of its piece)
+        total = remaining + 3;
+    }
+};
+
 extern "C" int64_t zm_ilqr_solve_state_workspace_f64(const zm_model_t* model, int64_t batch, int T) {
-    const int64_t base = zm_ilqr_solve_workspace_f64(model, batch, T, 0);
-    if (base < 0) return -1;
-    // + h (batch, T+1, n) + J_AL (batch) + int32: the not-done mask (batch), the count of the trajectories that go on
-    return base + (((int64_t)batch * (T + 1) * model->n + 1) & ~(int64_t)1) + ((batch + 1) & ~(int64_t)1) + ((batch + 1) / 2 + 1) + 2;
+    const StateWs s(model, batch, T);
+    return s.base < 0 ? -1 : s.total;
 }
 
 extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -658,9 +709,12 @@ extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_q
                                              int32_t* alpha_trace, double* violation_trace, double* mu_trace) {
     const char* who = "zm_ilqr_solve_state_f64";
     if (batch == 0) return ZM_OK;
+    // every argument is checked here, before the first launch (also what the kernels' own entry points would refuse behind it)
     if (!model || !sbox || !x0 || !uGuess || !workspace || !iwork || !xTraj || !uTraj || !L || !J || !converged || !violation)
         return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
-    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "%s: pass exactly one of cost and track", who);
+    SolveCall c{model, {}, x0, uGuess, 0, max_iter, tol, sync_every, workspace, 0, iwork, xTraj, uTraj, L, nullptr, converged, nullptr,
+                batch, T, stream};
+    if (const int rc = zm::cost_resolve(cost, track, zm::CostArg::exactly_one, who, &c.ck)) return rc;
     if (ddp != 0) return zm::set_error(ZM_EUNSUPPORTED, "%s: DDP with state bounds is not built (ddp must be 0)", who);
     if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "%s: bad size", who);
     if (!(mu0 > 0.0) || !(growth >= 1.0) || !(mu_max >= mu0) || outer < 1 || !(ctol >= 0.0))
@@ -671,30 +725,23 @@ extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_q
     if (const int rc = zm::statebox_check(sbox, n, who)) return rc;
     if (box)
         if (const int rc = zm::box_check(box, m, who)) return rc;
-    // (what the kernels' own entry points would refuse later, behind this function's first launches)
     if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
-    if (model->kind != ZM_MODEL_LINEAR && model->kind != ZM_MODEL_QUADCOPTER && model->kind != ZM_MODEL_QUADCOPTER_RB)
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, model->kind);
-    if (model->kind == ZM_MODEL_LINEAR && (!model->A || !model->B)) return zm::set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
-    if (model->kind == ZM_MODEL_QUADCOPTER && (n != 12 || m != 4)) return zm::set_error(ZM_EINVAL, "%s: the quadcopter model is (12, 4)", who);
-    if (model->kind == ZM_MODEL_QUADCOPTER_RB && (n != 8 || m != 4)) return zm::set_error(ZM_EINVAL, "%s: the rigid-body model is (8, 4)", who);
+    zm_model_t md;
+    if (const int rc = zm::model_check(model, who, &md)) return rc;
+    if (md.n != n || md.m != m)
+        return zm::set_error(ZM_EINVAL, "%s: the %s model is (%d, %d)", who, md.kind == ZM_MODEL_QUADCOPTER ? "quadcopter" : "rigid-body",
+                             md.n, md.m);
     if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31)) return zm::set_error(ZM_EUNSUPPORTED, "%s: T*n*n or batch too large", who);
-    zm::IlqrCost ck = quad_cost(cost);
-    if (track) {
-        if (const int rc = zm::track_check(track, who)) return rc;
-        ck = zm::IlqrCost{true, zm::track_weights(*track), track, zm::track_ref(*track)};
-    }
-    const int64_t base = zm_ilqr_solve_workspace_f64(model, batch, T, 0);
-    if (base < 0 || workspace_doubles < zm_ilqr_solve_state_workspace_f64(model, batch, T))
+    const StateWs sw(model, batch, T);
+    if (sw.base < 0 || workspace_doubles < sw.total)
         return zm::set_error(ZM_EINVAL, "%s: workspace of %lld doubles, %lld needed", who, (long long)workspace_doubles,
-                             (long long)zm_ilqr_solve_state_workspace_f64(model, batch, T));
+                             (long long)(sw.base < 0 ? -1 : sw.total));
     hipStream_t st = (hipStream_t)stream;
     const long rows = (long)batch * (T + 1) * n;
-    double* h = workspace + base;
-    double* Jal = h + ((rows + 1) & ~1L);
+    double* h = workspace + sw.h;
     // the mask of the trajectories that are not done: the inner solve's own `active` mask (iwork) also drops what merely converged
-    int32_t* notdone = (int32_t*)(Jal + ((batch + 1) & ~(int64_t)1));
-    int32_t* remaining = notdone + ((batch + 1) & ~(int64_t)1);
+    int32_t* notdone = (int32_t*)(workspace + sw.notdone);
+    int32_t* remaining = (int32_t*)(workspace + sw.remaining);
     const unsigned fb = (unsigned)((batch + 255) / 256);
     hipLaunchKernelGGL(zm::fill_i32_kernel, dim3(fb), dim3(256), 0, st, (int*)notdone, (long)batch, 1);
     hipLaunchKernelGGL(zm::fill_f64_kernel, dim3(fb), dim3(256), 0, st, sbox->mu, (long)batch, mu0);
@@ -704,17 +751,20 @@ extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_q
     if (outer_iterations) ZM_HIP_CHECK(hipMemsetAsync(outer_iterations, 0, sizeof(int32_t) * batch, st));
     if (inner_iterations) ZM_HIP_CHECK(hipMemsetAsync(inner_iterations, 0, sizeof(int32_t) * batch * outer, st));
     if (box && qp_capped) ZM_HIP_CHECK(hipMemsetAsync(qp_capped, 0, sizeof(int32_t) * batch, st));
-    ck.box = box;
-    ck.qp_capped = box ? qp_capped : nullptr;
+    // the inner solves: the loop above on J_AL (written to the workspace; the caller's J receives the cost without the penalty)
+    c.workspace_doubles = sw.base;
+    c.J = workspace + sw.Jal;
+    c.ck.box = box;
+    c.ck.qp_capped = box ? qp_capped : nullptr;
     int ran = 0;
     for (int j = 0; j < outer; ++j) {
         const zm::StatePen pen{sbox, h, J, inner_iterations ? inner_iterations + (long)j * batch : nullptr, notdone,
                                j == 0 ? uGuess : uTraj};
-        ck.pen = &pen;
+        c.ck.pen = &pen;
+        c.J_trace = J_trace ? J_trace + (long)j * max_iter * batch : nullptr;
+        c.alpha_trace = alpha_trace ? alpha_trace + (long)j * max_iter * batch : nullptr;
         if (mu_trace) ZM_HIP_CHECK(hipMemcpyAsync(mu_trace + (long)j * batch, sbox->mu, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
-        int rc = ilqr_solve_impl(model, ck, x0, uGuess, 0, max_iter, tol, sync_every, workspace, base, iwork, xTraj, uTraj, L, Jal, converged,
-                                 nullptr, batch, T, stream, J_trace ? J_trace + (long)j * max_iter * batch : nullptr,
-                                 alpha_trace ? alpha_trace + (long)j * max_iter * batch : nullptr);
+        int rc = ilqr_solve_impl(c);
         if (rc) return rc;
         ZM_HIP_CHECK(hipMemsetAsync(remaining, 0, sizeof(int32_t), st));
         rc = zm_state_multiplier_update_f64(sbox, xTraj, notdone, converged, violation, outer_iterations, remaining, ctol, growth, mu_max,

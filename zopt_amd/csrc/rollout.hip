@@ -230,39 +230,42 @@ int rollout_wide_dispatch(const zm_model_t& md, const zm_quadcost_t* cost, const
                           const int* list, long count, double* xTraj, double* uTraj, double* J, int* idx, long batch, int T,
                           hipStream_t st);   // rollout_wide.hip
 }
-static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0,
+// the penalty form (the *_state_* entry points): the state box, its optional input box and the cost-without-penalty output
+struct PenArgs {
+    const zm_statebox_t* sbox;
+    const zm_inputbox_t* box;
+    double* J_cost;
+};
+static const char* const ROLLOUT = "zm_rollout_linesearch_f64";   // the name the entries without a penalty report under
+static int rollout_impl(const char* who, const zm_model_t* model, const zm_quadcost_t* cost, const double* x0,
                                          const double* l, const double* L, const double* xPrev, const double* uPrev,
                                          const double* alphas, int n_alpha, const int32_t* active, const int32_t* list,
                                          int64_t count, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
                                          int64_t batch, int T, void* stream, double* scratch = nullptr,
-                                         const zm::TrackRef* track = nullptr, const zm::BoxRef* box = nullptr) {
+                                         const zm::TrackRef* track = nullptr, const zm::BoxRef* box = nullptr,
+                                         const PenArgs* pen = nullptr) {
     // box != nullptr: the inputs are clipped into it (the *_box_* entry points); one lane per rollout, two passes
     // track != nullptr: `cost` holds the weights of a zm_trackcost_t and *track its reference (the *_tracking_* entry points)
-    if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj)
-        return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: null pointer");
-    if (batch < 0 || T < 0 || n_alpha < 1 || n_alpha > 16)
-        return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: bad size batch=%lld T=%d n_alpha=%d", (long long)batch,
-                             T, n_alpha);
-    if (n_alpha > 1 && !cost) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: a line search needs a cost");
-    zm_model_t md = *model;
-    if (md.kind == ZM_MODEL_QUADCOPTER) {
-        md.n = 12;
-        md.m = 4;
-    } else if (md.kind == ZM_MODEL_QUADCOPTER_RB) {
-        md.n = 8;
-        md.m = 4;
-    } else if (md.kind == ZM_MODEL_LINEAR) {
-        if (!md.A || !md.B) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: linear model needs A, B");
-    } else {
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_rollout_linesearch_f64: unknown model kind %d", md.kind);
-    }
-    const bool wide = md.kind == ZM_MODEL_LINEAR && (md.n > zm::MAXN || md.m > zm::MAXM) && md.n >= 1 && md.m >= 1 && md.n <= 64 &&
-                      md.m <= 16;   // large linear models: one wave per rollout (rollout_wide.hip)
+    // pen != nullptr: the cost is the augmented-Lagrangian one of pen->sbox, with pen->box clipping the inputs (generic kernel only)
+    if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj || (pen && !J))
+        return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    if (batch < 0 || T < (pen ? 1 : 0) || n_alpha < 1 || n_alpha > 16)
+        return zm::set_error(ZM_EINVAL, "%s: bad size batch=%lld T=%d n_alpha=%d", who, (long long)batch, T, n_alpha);
+    if (n_alpha > 1 && !cost) return zm::set_error(ZM_EINVAL, "%s: a line search needs a cost", who);
+    zm_model_t md;
+    if (const int rc = zm::model_check(model, who, &md)) return rc;
+    const bool wide = !pen && md.kind == ZM_MODEL_LINEAR && (md.n > zm::MAXN || md.m > zm::MAXM) && md.n >= 1 && md.m >= 1 &&
+                      md.n <= 64 && md.m <= 16;   // large linear models: one wave per rollout (rollout_wide.hip)
     if (!wide && (md.n < 1 || md.n > zm::MAXN || md.m < 1 || md.m > zm::MAXM))
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_rollout_linesearch_f64: (n=%d, m=%d) not covered (n<=12, m<=4; linear models n<=64, m<=16)",
-                             md.n, md.m);
-    if (cost && (!cost->Q || !cost->R || !cost->Qf))
-        return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_f64: cost needs Q, R, Qf");
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (%s)", who, md.n, md.m,
+                             pen ? "state box: n<=12, m<=4" : "n<=12, m<=4; linear models n<=64, m<=16");
+    if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
+    if (pen) {
+        if (pen->box)
+            if (const int rc = zm::box_check(pen->box, md.m, who)) return rc;
+        if (const int rc = zm::statebox_check(pen->sbox, md.n, who)) return rc;
+        if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "%s: bad list length", who);
+    }
     if (batch == 0 || (list && count == 0)) return ZM_OK;
     if (count < 0 || count > batch) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch: bad list length");
     if (wide && track)
@@ -289,12 +292,30 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
     const bool windy = md.wind_ned[0] != 0.0 || md.wind_ned[1] != 0.0 || md.wind_ned[2] != 0.0;   // fast path: still air only
     // (one step size -- the solvers' initial rollout -- runs the same kernel with all 16 lanes of a group on that step size: 16x
     //  redundant, and still several times faster than the generic lane-per-trajectory kernel with its uncoalesced policy reads)
-    if (!force_generic && !windy && (n_alpha == 16 || n_alpha == 1) && md.n == 12 && md.m == 4 && cost && T >= 1)
+    if (!pen && !force_generic && !windy && (n_alpha == 16 || n_alpha == 1) && md.n == 12 && md.m == 4 && cost && T >= 1)
         return zm::rollout_fast_dispatch(md, cs.Q, cs.R, cs.Qf, cs.diagonal, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, count, xTraj,
                                          uTraj, J, (int*)alpha_idx, batch, T, st, scratch, track, box);
     if (scratch) return zm::set_error(ZM_EUNSUPPORTED, "rollout: all-store mode needs the fast path");
+    const zm::TrackRef tr = track ? *track : zm::TrackRef{};
+    if (pen) {
+        const zm::BoxRef bx = pen->box ? zm::box_ref(*pen->box) : zm::BoxRef{};
+        const zm::PenRef pr = zm::pen_ref(*pen->sbox);
+#define ZM_LAUNCH_PEN(NA_, BOXED_, BLOCKS_)                                                                                               \
+    hipLaunchKernelGGL((zm::rollout_linesearch_pen_kernel<NA_, BOXED_>), dim3((unsigned)(BLOCKS_)), dim3(64), 0, st, md, cs, tr, bx, pr, x0, \
+                       l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, pen->J_cost,             \
+                       (int*)alpha_idx, (long)batch, T)
+        if (n_alpha == 1) {
+            if (pen->box) ZM_LAUNCH_PEN(1, true, (nslot + 63) / 64);
+            else ZM_LAUNCH_PEN(1, false, (nslot + 63) / 64);
+        } else {
+            if (pen->box) ZM_LAUNCH_PEN(16, true, (nslot + 3) / 4);
+            else ZM_LAUNCH_PEN(16, false, (nslot + 3) / 4);
+        }
+#undef ZM_LAUNCH_PEN
+        ZM_HIP_CHECK(hipGetLastError());
+        return ZM_OK;
+    }
     if (box) {
-        const zm::TrackRef tr = track ? *track : zm::TrackRef{};
         if (n_alpha == 1)
             hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<1>), dim3((unsigned)((nslot + 63) / 64)), dim3(64), 0, st, md, cs, hc, tr,
                                *box, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J,
@@ -327,12 +348,14 @@ static int rollout_impl(const zm_model_t* model, const zm_quadcost_t* cost, cons
     return ZM_OK;
 }
 
+// The entries: each resolves its cost argument(s) (track_cost.h) and hands the line search to rollout_impl; the dense forms are the
+// list forms without a list.
 extern "C" int zm_rollout_linesearch_f64(const zm_model_t* model, const zm_quadcost_t* cost, const double* x0, const double* l,
                                          const double* L, const double* xPrev, const double* uPrev, const double* alphas,
                                          int n_alpha, const int32_t* active, double* xTraj, double* uTraj, double* J,
                                          int32_t* alpha_idx, int64_t batch, int T, void* stream) {
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, nullptr, 0, xTraj, uTraj, J, alpha_idx,
+    return rollout_impl(ROLLOUT, model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, nullptr, 0, xTraj, uTraj, J, alpha_idx,
                         batch, T, stream);
 }
 
@@ -343,7 +366,7 @@ extern "C" int zm_rollout_linesearch_list_f64(const zm_model_t* model, const zm_
                                               int64_t batch, int T, void* stream) {
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     if (!list) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_list_f64: null list");
-    return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx,
+    return rollout_impl(ROLLOUT, model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx,
                         batch, T, stream);
 }
 
@@ -352,12 +375,11 @@ extern "C" int zm_rollout_linesearch_tracking_list_f64(const zm_model_t* model, 
                                                        const double* alphas, int n_alpha, const int32_t* list, int64_t count,
                                                        const int32_t* active, double* xTraj, double* uTraj, double* J,
                                                        int32_t* alpha_idx, int64_t batch, int T, void* stream) {
-    if (const int rc = zm::track_check(cost, "zm_rollout_linesearch_tracking_f64")) return rc;
+    zm::CostRef ck;
+    if (const int rc = zm::cost_resolve(nullptr, cost, zm::CostArg::track, "zm_rollout_linesearch_tracking_f64", &ck)) return rc;
     if (batch == 0) return ZM_OK;
-    const zm_quadcost_t w = zm::track_weights(*cost);
-    const zm::TrackRef tr = zm::track_ref(*cost);
-    return rollout_impl(model, &w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
-                        stream, nullptr, &tr);
+    return rollout_impl(ROLLOUT, model, &ck.w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx,
+                        batch, T, stream, nullptr, &ck.ref);
 }
 
 extern "C" int zm_rollout_linesearch_tracking_f64(const zm_model_t* model, const zm_trackcost_t* cost, const double* x0, const double* l,
@@ -374,22 +396,15 @@ extern "C" int zm_rollout_linesearch_box_list_f64(const zm_model_t* model, const
                                                   const double* xPrev, const double* uPrev, const double* alphas, int n_alpha,
                                                   const int32_t* list, int64_t count, const int32_t* active, double* xTraj,
                                                   double* uTraj, double* J, int32_t* alpha_idx, int64_t batch, int T, void* stream) {
-    if (cost && track) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_box_f64: pass cost or track, not both");
-    if (track)
-        if (const int rc = zm::track_check(track, "zm_rollout_linesearch_box_f64")) return rc;
-    if (!model) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch_box_f64: null pointer");
-    const int mm = (model->kind == ZM_MODEL_QUADCOPTER || model->kind == ZM_MODEL_QUADCOPTER_RB) ? 4 : model->m;
-    if (const int rc = zm::box_check(box, mm, "zm_rollout_linesearch_box_f64")) return rc;
+    const char* who = "zm_rollout_linesearch_box_f64";
+    zm::CostRef ck;
+    if (const int rc = zm::cost_resolve(cost, track, zm::CostArg::at_most_one, who, &ck)) return rc;
+    if (!model) return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    if (const int rc = zm::box_check(box, zm::model_sized(*model).m, who)) return rc;
     if (batch == 0) return ZM_OK;
     const zm::BoxRef bx = zm::box_ref(*box);
-    if (track) {
-        const zm_quadcost_t w = zm::track_weights(*track);
-        const zm::TrackRef tr = zm::track_ref(*track);
-        return rollout_impl(model, &w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
-                            stream, nullptr, &tr, &bx);
-    }
-    return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch, T,
-                        stream, nullptr, nullptr, &bx);
+    return rollout_impl(ROLLOUT, model, ck.weights(), x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J,
+                        alpha_idx, batch, T, stream, nullptr, ck.ref_ptr(), &bx);
 }
 
 extern "C" int zm_rollout_linesearch_box_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -410,53 +425,11 @@ extern "C" int zm_rollout_linesearch_state_list_f64(const zm_model_t* model, con
                                                     double* uTraj, double* J, double* J_cost, int32_t* alpha_idx, int64_t batch, int T,
                                                     void* stream) {
     const char* who = "zm_rollout_linesearch_state_f64";
-    if ((cost != nullptr) == (track != nullptr)) return zm::set_error(ZM_EINVAL, "%s: pass exactly one of cost and track", who);
-    if (track)
-        if (const int rc = zm::track_check(track, who)) return rc;
-    if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
-    if (!model || !x0 || !l || !L || !xPrev || !uPrev || !alphas || !xTraj || !uTraj || !J) return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
-    if (batch < 0 || T < 1 || n_alpha < 1 || n_alpha > 16)
-        return zm::set_error(ZM_EINVAL, "%s: bad size batch=%lld T=%d n_alpha=%d", who, (long long)batch, T, n_alpha);
-    zm_model_t md = *model;
-    if (md.kind == ZM_MODEL_QUADCOPTER) {
-        md.n = 12;
-        md.m = 4;
-    } else if (md.kind == ZM_MODEL_QUADCOPTER_RB) {
-        md.n = 8;
-        md.m = 4;
-    } else if (md.kind == ZM_MODEL_LINEAR) {
-        if (!md.A || !md.B) return zm::set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
-    } else {
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, md.kind);
-    }
-    if (md.n < 1 || md.n > zm::MAXN || md.m < 1 || md.m > zm::MAXM)
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (state box: n<=12, m<=4)", who, md.n, md.m);
-    if (box)
-        if (const int rc = zm::box_check(box, md.m, who)) return rc;
-    if (const int rc = zm::statebox_check(sbox, md.n, who)) return rc;
-    if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "%s: bad list length", who);
-    if (batch == 0 || (list && count == 0)) return ZM_OK;
-    const zm_quadcost_t cs = track ? zm::track_weights(*track) : *cost;
-    const zm::TrackRef tr = track ? zm::track_ref(*track) : zm::TrackRef{};
-    const zm::BoxRef bx = box ? zm::box_ref(*box) : zm::BoxRef{};
-    const zm::PenRef pr = zm::pen_ref(*sbox);
-    const int64_t nslot = list ? count : batch;
-    hipStream_t st = (hipStream_t)stream;
-    const int* act = (const int*)active;
-#define ZM_LAUNCH_PEN(NA_, BOXED_, BLOCKS_)                                                                                               \
-    hipLaunchKernelGGL((zm::rollout_linesearch_pen_kernel<NA_, BOXED_>), dim3((unsigned)(BLOCKS_)), dim3(64), 0, st, md, cs, tr, bx, pr, x0, \
-                       l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, J_cost, (int*)alpha_idx, \
-                       (long)batch, T)
-    if (n_alpha == 1) {
-        if (box) ZM_LAUNCH_PEN(1, true, (nslot + 63) / 64);
-        else ZM_LAUNCH_PEN(1, false, (nslot + 63) / 64);
-    } else {
-        if (box) ZM_LAUNCH_PEN(16, true, (nslot + 3) / 4);
-        else ZM_LAUNCH_PEN(16, false, (nslot + 3) / 4);
-    }
-#undef ZM_LAUNCH_PEN
-    ZM_HIP_CHECK(hipGetLastError());
-    return ZM_OK;
+    zm::CostRef ck;
+    if (const int rc = zm::cost_resolve(cost, track, zm::CostArg::exactly_one, who, &ck)) return rc;
+    const PenArgs pen{sbox, box, J_cost};
+    return rollout_impl(who, model, &ck.w, x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J, alpha_idx, batch,
+                        T, stream, nullptr, ck.ref_ptr(), nullptr, &pen);
 }
 
 extern "C" int zm_rollout_linesearch_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -491,8 +464,8 @@ int rollout_linesearch_all_store(const zm_model_t* model, const zm_quadcost_t* c
                                  const int32_t* active, double* scratch, double* J, int32_t* alpha_idx, int64_t batch, int T,
                                  void* stream, const TrackRef* track) {
     // (xTraj / uTraj are not written in this mode; the non-null placeholders only pass the argument check)
-    return rollout_impl(model, cost, x0, l, L, xPrev, uPrev, alphas, 16, active, list, count, scratch, scratch, J, alpha_idx, batch, T,
-                        stream, scratch, track);
+    return rollout_impl(ROLLOUT, model, cost, x0, l, L, xPrev, uPrev, alphas, 16, active, list, count, scratch, scratch, J, alpha_idx, batch,
+                        T, stream, scratch, track);
 }
 }  // namespace zm
 

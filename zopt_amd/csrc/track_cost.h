@@ -34,6 +34,33 @@ inline int track_check(const zm_trackcost_t* c, const char* who) {
     return ZM_OK;
 }
 
+// The cost argument(s) of an entry, resolved (host): the weights (the Hessians, the conditioning and the kernels' cost arithmetic read
+// only these) and, for a zm_trackcost_t, the reference that cost values and gradients are taken about.  `track` == nullptr is the
+// zm_quadcost_t path with exactly its launches.
+struct CostRef {
+    bool given = false;
+    zm_quadcost_t w = zm_quadcost_t{nullptr, nullptr, nullptr, 0, 0};
+    const zm_trackcost_t* track = nullptr;
+    TrackRef ref = TrackRef{};
+    const zm_quadcost_t* weights() const { return given ? &w : nullptr; }
+    const TrackRef* ref_ptr() const { return track ? &ref : nullptr; }
+};
+// what an entry's parameter list takes: a zm_quadcost_t (may be missing: the entry's own null check answers), a zm_trackcost_t, or
+// the pair (cost, track) with at most / exactly one of the two given
+enum class CostArg { quad, track, at_most_one, exactly_one };
+inline int cost_resolve(const zm_quadcost_t* cost, const zm_trackcost_t* track, const CostArg form, const char* who, CostRef* out) {
+    if (form == CostArg::at_most_one && cost && track) return set_error(ZM_EINVAL, "%s: pass cost or track, not both", who);
+    if (form == CostArg::exactly_one && (cost != nullptr) == (track != nullptr))
+        return set_error(ZM_EINVAL, "%s: pass exactly one of cost and track", who);
+    if (track || form == CostArg::track) {
+        if (const int rc = track_check(track, who)) return rc;
+        out->given = true, out->w = track_weights(*track), out->track = track, out->ref = track_ref(*track);
+    } else if (cost) {
+        out->given = true, out->w = *cost;
+    }
+    return ZM_OK;
+}
+
 __device__ __forceinline__ const double* track_xrow(const TrackRef& r, const long t, const long k) {
     return r.x ? r.x + t * r.xt + k * r.xk : nullptr;
 }

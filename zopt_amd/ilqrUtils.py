@@ -51,6 +51,77 @@ def _shape(x):
     return tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
 
 
+def _batch(lead):
+    """Number of problems in the leading (batch) axes `lead`."""
+    b = 1
+    for d in lead:
+        b *= int(d)
+    return b
+
+
+def _is_fp32(x):
+    return x.dtype == torch.float32 if arr.is_torch(x) else np.asarray(x).dtype == np.float32
+
+
+def _check_shapes(table):
+    """`table`: (name, array, expected shape) rows; a row whose shape is None is an operand that is left out (NULL)."""
+    for name, X, s in table:
+        if s is not None and _shape(X) != s:
+            raise ValueError(f"{name} has shape {_shape(X)}, expected {s}")
+
+
+def _backward_pass(who, entry, dynamics, cost, Vf, ddp=False, boxed=None, cast_back=False):
+    """The four backwardPass_* functions: shape table, upload, outputs, the call of `entry` and the return.  `boxed`: (uTraj, u_lb, u_ub)
+    of the *_box forms.  Every sweep computes in fp64; `cast_back` hands an fp32 caller fp32 back -- backwardPass_ilqr does (as the fused
+    solves do), backwardPass_ilqr_box, backwardPass_ddp and backwardPass_ddp_box return fp64 whatever came in."""
+    dyn = _fields(dynamics)
+    f_x, f_u = dyn[1], dyn[2]
+    f_xx, f_ux, f_uu = dyn[3:6] if ddp else (None, None, None)
+    _, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
+    _, v_x, v_xx = _fields(Vf)
+    shp = _shape(f_u)
+    if len(shp) < 3:
+        raise ValueError("f_u must have shape (..., N, n, m)")
+    lead, (N, n, m) = shp[:-3], shp[-3:]
+    if boxed is not None and (n > _models.INPUTBOX_MAX_N or m > _models.INPUTBOX_MAX_M):
+        raise ValueError(f"{who}: (n={n}, m={m}) not covered (need n <= 12, m <= 4)")
+    # backwardPass_ddp_box alone takes dynamics affine in the controls: f_ux = f_uu = None (identically zero), neither stored nor read
+    affine = ddp and boxed is not None and f_ux is None and f_uu is None
+    if ddp and boxed is not None and not affine and (f_ux is None or f_uu is None):
+        raise ValueError("f_ux and f_uu are None together or not at all")
+    step = lead + (N,)
+    table = [("f_x", f_x, step + (n, n)), ("f_u", f_u, shp)]   # in the entries' argument order
+    if ddp:
+        table += [("f_xx", f_xx, step + (n, n, n))]
+        table += [("f_ux", None, None), ("f_uu", None, None)] if affine else [("f_ux", f_ux, step + (n, m, n)), ("f_uu", f_uu, step + (n, m, m))]
+    table += [("c_x", c_x, step + (n,)), ("c_u", c_u, step + (m,)), ("c_xx", c_xx, step + (n, n)), ("c_ux", c_ux, step + (m, n)),
+              ("c_uu", c_uu, step + (m, m)), ("v_x", v_x, lead + (n,)), ("v_xx", v_xx, lead + (n, n))]
+    if boxed is not None:
+        table += [("uTraj", boxed[0], step + (m,))]
+    _check_shapes(table)
+    box = _models.InputBox.for_shape(n, m, boxed[1], boxed[2]).box_struct(tuple(lead)) if boxed is not None else None
+    dt = torch.float64
+    dev = [None if s is None else arr.to_device(X, dt) for _, X, s in table]
+    batch = _batch(lead)
+    dl = torch.empty(step + (m,), dtype=dt, device=dev[0].device)
+    dL = torch.empty(step + (m, n), dtype=dt, device=dev[0].device)
+    if ddp and boxed is None and _ddp_large(n, m):
+        _ddp_backward_large(dev, dl, dL, batch, N, n, m)
+    else:
+        ptrs = [None if t is None else t.data_ptr() for t in dev]
+        if boxed is not None:         # (..., box*, shared_hessian, l, L, qp_capped, ...)
+            ptrs += [ctypes.addressof(box), 0, dl.data_ptr(), dL.data_ptr(), None]
+        elif ddp:                     # (..., active, shared_hessian, l, L, ...)
+            ptrs += [None, 0, dl.data_ptr(), dL.data_ptr()]
+        else:
+            ptrs += [dl.data_ptr(), dL.data_ptr()]
+        rc = getattr(_lib.lib(), entry)(*ptrs, batch, N, n, m, ctypes.c_void_p(arr.stream_ptr(dev[0])))
+        _lib.check(rc, who)
+    if cast_back and _is_fp32(f_x):
+        dl, dL = dl.to(torch.float32), dL.to(torch.float32)
+    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+
+
 def backwardPass_ilqr(dynamics, cost, Vf):
     """Backwards pass of the iLQR algorithm (reference ilqrUtils.py:176-181, step :153-173).
 
@@ -64,35 +135,7 @@ def backwardPass_ilqr(dynamics, cost, Vf):
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    _, f_x, f_u = _fields(dynamics)[:3]
-    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
-    v, v_x, v_xx = _fields(Vf)
-    shp = _shape(f_u)
-    if len(shp) < 3:
-        raise ValueError("f_u must have shape (..., N, n, m)")
-    lead, (N, n, m) = shp[:-3], shp[-3:]
-    expect = {"f_x": (f_x, lead + (N, n, n)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
-              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
-              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n))}
-    for name, (X, s) in expect.items():
-        if _shape(X) != s:
-            raise ValueError(f"{name} has shape {_shape(X)}, expected {s}")
-    template = f_x
-    dt = torch.float64
-    dev = [arr.to_device(X, dt) for X in (f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
-    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
-    rc = _lib.lib().zm_ilqr_backward_f64(*[t.data_ptr() for t in dev], dl.data_ptr(), dL.data_ptr(), batch, N, n, m,
-                                         ctypes.c_void_p(arr.stream_ptr(dev[0])))
-    _lib.check(rc, "backwardPass_ilqr")
-    fp32_in = (arr.is_torch(template) and template.dtype == torch.float32) or \
-        (not arr.is_torch(template) and np.asarray(template).dtype == np.float32)
-    if fp32_in:
-        dl, dL = dl.to(torch.float32), dL.to(torch.float32)
-    return AffinePolicy(arr.result_like(dl, template), arr.result_like(dL, template))
+    return _backward_pass("backwardPass_ilqr", "zm_ilqr_backward_f64", dynamics, cost, Vf, cast_back=True)
 
 
 def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
@@ -112,34 +155,7 @@ def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    _, f_x, f_u = _fields(dynamics)[:3]
-    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
-    v, v_x, v_xx = _fields(Vf)
-    shp = _shape(f_u)
-    if len(shp) < 3:
-        raise ValueError("f_u must have shape (..., N, n, m)")
-    lead, (N, n, m) = shp[:-3], shp[-3:]
-    if n > _models.INPUTBOX_MAX_N or m > _models.INPUTBOX_MAX_M:
-        raise ValueError(f"backwardPass_ilqr_box: (n={n}, m={m}) not covered (need n <= 12, m <= 4)")
-    expect = {"f_x": (f_x, lead + (N, n, n)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
-              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
-              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n)), "uTraj": (uTraj, lead + (N, m))}
-    for name, (X, s) in expect.items():
-        if _shape(X) != s:
-            raise ValueError(f"{name} has shape {_shape(X)}, expected {s}")
-
-    box = _models.InputBox.for_shape(n, m, u_lb, u_ub).box_struct(tuple(lead))
-    dt = torch.float64
-    dev = [arr.to_device(X, dt) for X in (f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx, uTraj)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
-    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
-    rc = _lib.lib().zm_ilqr_backward_box_f64(*[t.data_ptr() for t in dev], ctypes.addressof(box), 0, dl.data_ptr(), dL.data_ptr(), None,
-                                             batch, N, n, m, ctypes.c_void_p(arr.stream_ptr(dev[0])))
-    _lib.check(rc, "backwardPass_ilqr_box")
-    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+    return _backward_pass("backwardPass_ilqr_box", "zm_ilqr_backward_box_f64", dynamics, cost, Vf, boxed=(uTraj, u_lb, u_ub))
 
 
 def _ddp_large(n, m):
@@ -183,6 +199,24 @@ def _ddp_step_large(f_x, f_u, f_xx, f_ux, f_uu, c, c_x, c_u, c_xx, c_ux, c_uu, v
     return _riccati_value_call(f_x, f_u, c, c_x, c_u, c_xx + vf_xx, c_ux + vf_ux, c_uu + vf_uu, v, v_x, v_xx)
 
 
+def _ddp_backward_large(dev, dl, dL, batch, N, n, m):
+    """backwardPass_ddp beyond the one-tile DDP sweep (n <= 12, m <= 4): the recursion runs step by step from the host, per step a torch
+    contraction, the HIP PD projection of the stacked (n+m)^2 matrix and the HIP tile sweep for one step (three launches per time step:
+    a coverage path for the shapes the generic-callable drivers take, not a fast one).  `dev`: the uploaded operands in the order of
+    zm_ddp_backward_f64; fills dl, dL."""
+    if n > 48 or m > 16:
+        raise ValueError(f"backwardPass_ddp: (n={n}, m={m}) not covered (need n <= 48, m <= 16)")
+    nlead = dl.dim() - 2
+    fx, fu, fxx, fux, fuu, cx, cu, cxx, cux, cuu, vx, vxx = (t.reshape((batch,) + tuple(t.shape[nlead:])) for t in dev)
+    vv = torch.zeros(batch, dtype=dl.dtype, device=vx.device)
+    zc = torch.zeros(batch, dtype=dl.dtype, device=vx.device)
+    fl, fL = dl.reshape(batch, N, m), dL.reshape(batch, N, m, n)
+    for k in range(N - 1, -1, -1):
+        vv, vx, vxx, lk, Lk = _ddp_step_large(fx[:, k], fu[:, k], fxx[:, k].contiguous(), fux[:, k].contiguous(), fuu[:, k].contiguous(),
+                                              zc, cx[:, k], cu[:, k], cxx[:, k], cux[:, k], cuu[:, k], vv, vx, vxx)
+        fl[:, k], fL[:, k] = lk, Lk
+
+
 def _riccati_step(dynamics, cost, value, ddp):
     """One backward step with the value function returned (zm_riccati_value_f64, T = 1)."""
     dyn = _fields(dynamics)
@@ -193,26 +227,19 @@ def _riccati_step(dynamics, cost, value, ddp):
     if len(shp) < 2:
         raise ValueError("f_u must have shape (..., n, m)")
     lead, (n, m) = shp[:-2], shp[-2:]
-    expect = {"f_x": (f_x, lead + (n, n)), "c": (c, lead), "c_x": (c_x, lead + (n,)), "c_u": (c_u, lead + (m,)),
-              "c_xx": (c_xx, lead + (n, n)), "c_ux": (c_ux, lead + (m, n)), "c_uu": (c_uu, lead + (m, m)),
-              "v": (v, lead), "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n))}
+    table = [("f_x", f_x, lead + (n, n)), ("c", c, lead), ("c_x", c_x, lead + (n,)), ("c_u", c_u, lead + (m,)),
+             ("c_xx", c_xx, lead + (n, n)), ("c_ux", c_ux, lead + (m, n)), ("c_uu", c_uu, lead + (m, m)),
+             ("v", v, lead), ("v_x", v_x, lead + (n,)), ("v_xx", v_xx, lead + (n, n))]
     if ddp:
-        expect.update({"f_xx": (dyn[3], lead + (n, n, n)), "f_ux": (dyn[4], lead + (n, m, n)), "f_uu": (dyn[5], lead + (n, m, m))})
-    for name, (X, s_) in expect.items():
-        if _shape(X) != s_:
-            raise ValueError(f"{name} has shape {_shape(X)}, expected {s_}")
+        table += [("f_xx", dyn[3], lead + (n, n, n)), ("f_ux", dyn[4], lead + (n, m, n)), ("f_uu", dyn[5], lead + (n, m, m))]
+    _check_shapes(table)
     template = f_x
     dt = torch.float64
-    T = lambda X: arr.to_device(X, dt).contiguous()
-    df_x, df_u, dc, dc_x, dc_u, dc_xx, dc_ux, dc_uu, dv, dv_x, dv_xx = (T(X) for X in (f_x, f_u, c, c_x, c_u, c_xx, c_ux, c_uu, v,
-                                                                                         v_x, v_xx))
-    z = [T(X).data_ptr() for X in dyn[3:6]] if ddp else [None, None, None]
-    zk = [T(X) for X in dyn[3:6]] if ddp else []          # keep alive
-    if ddp:
-        z = [t.data_ptr() for t in zk]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
+    df_x, df_u, dc, dc_x, dc_u, dc_xx, dc_ux, dc_uu, dv, dv_x, dv_xx = (arr.to_device(X, dt) for X in (f_x, f_u, c, c_x, c_u, c_xx, c_ux,
+                                                                                                       c_uu, v, v_x, v_xx))
+    zk = [arr.to_device(X, dt) for X in dyn[3:6]] if ddp else []   # the second derivatives, uploaded once and held until the call is out
+    z = [t.data_ptr() for t in zk] if ddp else [None, None, None]
+    batch = _batch(lead)
     dev = df_x.device
     if ddp and _ddp_large(n, m):
         fl = lambda t, tail: t.reshape((batch,) + tail)
@@ -304,9 +331,7 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     dt = torch.float64
     dx0, dl, dL, dxp, dup = (arr.to_device(X, dt) for X in (x0, l, L, xPrev, uPrev))
     dal = arr.to_device(np.asarray(alphas, dtype=np.float64), dt)
-    batch = 1
-    for d in lead:
-        batch *= int(d)
+    batch = _batch(lead)
     xT = torch.empty(lead + (N + 1, n), dtype=dt, device=dx0.device)
     uT = torch.empty(lead + (N, m), dtype=dt, device=dx0.device)
     J = torch.empty(lead, dtype=dt, device=dx0.device) if costFun is not None else None
@@ -396,10 +421,7 @@ def ensurePositiveDefinite(a, eps=1e-3):
         raise ValueError("a must be (..., k, k)")
     k = shp[-1]
     d = arr.to_device(a, torch.float64).clone()
-    count = 1
-    for s_ in shp[:-2]:
-        count *= int(s_)
-    rc = _lib.lib().zm_psd_project_f64(d.data_ptr(), count, k, float(eps), ctypes.c_void_p(arr.stream_ptr(d)))
+    rc = _lib.lib().zm_psd_project_f64(d.data_ptr(), _batch(shp[:-2]), k, float(eps), ctypes.c_void_p(arr.stream_ptr(d)))
     _lib.check(rc, "ensurePositiveDefinite")
     return arr.result_like(d, a)
 
@@ -414,10 +436,7 @@ def conditionQuadraticCost(quadratic_cost):
     if _shape(c_xx) != lead + (n, n) or _shape(c_uu) != lead + (m, m):
         raise ValueError("inconsistent cost Hessian shapes")
     dxx, dux, duu = (arr.to_device(X, torch.float64).clone() for X in (c_xx, c_ux, c_uu))
-    count = 1
-    for s_ in lead:
-        count *= int(s_)
-    rc = _lib.lib().zm_condition_cost_f64(dxx.data_ptr(), dux.data_ptr(), duu.data_ptr(), count, n, m, 1e-3,
+    rc = _lib.lib().zm_condition_cost_f64(dxx.data_ptr(), dux.data_ptr(), duu.data_ptr(), _batch(lead), n, m, 1e-3,
                                           ctypes.c_void_p(arr.stream_ptr(dxx)))
     _lib.check(rc, "conditionQuadraticCost")
     return QuadraticCostFunction(c, c_x, c_u, arr.result_like(dxx, c_xx), arr.result_like(dux, c_ux),
@@ -444,9 +463,7 @@ def conditionQuadraticDynamics(quadratic_dynamics, v_x):
         raise ValueError("conditionQuadraticDynamics: inconsistent shapes")
     dt = torch.float64
     dxx, dux, duu, dvx = (arr.to_device(X, dt).contiguous() for X in (f_xx, f_ux, f_uu, v_x))
-    count = 1
-    for d in lead:
-        count *= int(d)
+    count = _batch(lead)
     if n + m > 16:      # beyond the one-tile kernel: torch contraction + the multi-tile HIP projection
         oxx, oux, ouu = _project_vf_zz(dvx.reshape(count, n), dxx.reshape(count, n, n, n), dux.reshape(count, n, m, n),
                                        duu.reshape(count, n, m, m))
@@ -487,46 +504,7 @@ def backwardPass_ddp(dynamics, cost, Vf):
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    _, f_x, f_u, f_xx, f_ux, f_uu = _fields(dynamics)
-    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
-    v, v_x, v_xx = _fields(Vf)
-    shp = _shape(f_u)
-    if len(shp) < 3:
-        raise ValueError("f_u must have shape (..., N, n, m)")
-    lead, (N, n, m) = shp[:-3], shp[-3:]
-    expect = {"f_x": (f_x, lead + (N, n, n)), "f_xx": (f_xx, lead + (N, n, n, n)), "f_ux": (f_ux, lead + (N, n, m, n)),
-              "f_uu": (f_uu, lead + (N, n, m, m)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
-              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
-              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n))}
-    for name, (X, s_) in expect.items():
-        if _shape(X) != s_:
-            raise ValueError(f"{name} has shape {_shape(X)}, expected {s_}")
-    dt = torch.float64
-    dev = [arr.to_device(X, dt) for X in (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
-    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
-    if _ddp_large(n, m):
-        # Beyond the one-tile DDP sweep (n <= 12, m <= 4) the recursion runs step by step from the host: per step a torch contraction,
-        # the HIP PD projection of the stacked (n+m)^2 matrix and the HIP tile sweep for one step (three launches per time step:
-        # a coverage path for the shapes the generic-callable drivers take, not a fast one).
-        if n > 48 or m > 16:
-            raise ValueError(f"backwardPass_ddp: (n={n}, m={m}) not covered (need n <= 48, m <= 16)")
-        fx, fu, fxx, fux, fuu, cx, cu, cxx, cux, cuu, vx, vxx = (t.reshape((batch,) + tuple(t.shape[len(lead):])) for t in dev)
-        vv = torch.zeros(batch, dtype=dt, device=vx.device)
-        zc = torch.zeros(batch, dtype=dt, device=vx.device)
-        fl, fL = dl.reshape(batch, N, m), dL.reshape(batch, N, m, n)
-        for k in range(N - 1, -1, -1):
-            vv, vx, vxx, lk, Lk = _ddp_step_large(fx[:, k], fu[:, k], fxx[:, k].contiguous(), fux[:, k].contiguous(), fuu[:, k].contiguous(),
-                                                  zc, cx[:, k], cu[:, k], cxx[:, k], cux[:, k], cuu[:, k], vv, vx, vxx)
-            fl[:, k], fL[:, k] = lk, Lk
-        return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
-    rc = _lib.lib().zm_ddp_backward_f64(*[t.data_ptr() for t in dev], None, 0, dl.data_ptr(), dL.data_ptr(), batch, N, n, m,
-                                        ctypes.c_void_p(arr.stream_ptr(dev[0])))
-    _lib.check(rc, "backwardPass_ddp")
-    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+    return _backward_pass("backwardPass_ddp", "zm_ddp_backward_f64", dynamics, cost, Vf, ddp=True)
 
 
 def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
@@ -549,39 +527,7 @@ def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    _, f_x, f_u, f_xx, f_ux, f_uu = _fields(dynamics)
-    c, c_x, c_u, c_xx, c_ux, c_uu = _fields(cost)
-    v, v_x, v_xx = _fields(Vf)
-    shp = _shape(f_u)
-    if len(shp) < 3:
-        raise ValueError("f_u must have shape (..., N, n, m)")
-    lead, (N, n, m) = shp[:-3], shp[-3:]
-    if n > _models.INPUTBOX_MAX_N or m > _models.INPUTBOX_MAX_M:
-        raise ValueError(f"backwardPass_ddp_box: (n={n}, m={m}) not covered (need n <= 12, m <= 4)")
-    affine = f_ux is None and f_uu is None
-    expect = {"f_x": (f_x, lead + (N, n, n)), "f_xx": (f_xx, lead + (N, n, n, n)), "c_x": (c_x, lead + (N, n)), "c_u": (c_u, lead + (N, m)),
-              "c_xx": (c_xx, lead + (N, n, n)), "c_ux": (c_ux, lead + (N, m, n)), "c_uu": (c_uu, lead + (N, m, m)),
-              "v_x": (v_x, lead + (n,)), "v_xx": (v_xx, lead + (n, n)), "uTraj": (uTraj, lead + (N, m))}
-    if not affine:
-        if f_ux is None or f_uu is None:
-            raise ValueError("f_ux and f_uu are None together or not at all")
-        expect.update({"f_ux": (f_ux, lead + (N, n, m, n)), "f_uu": (f_uu, lead + (N, n, m, m))})
-    for name, (X, s_) in expect.items():
-        if _shape(X) != s_:
-            raise ValueError(f"{name} has shape {_shape(X)}, expected {s_}")
-
-    box = _models.InputBox.for_shape(n, m, u_lb, u_ub).box_struct(tuple(lead))
-    dt = torch.float64
-    dev = [None if X is None else arr.to_device(X, dt) for X in (f_x, f_u, f_xx, f_ux, f_uu, c_x, c_u, c_xx, c_ux, c_uu, v_x, v_xx, uTraj)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dl = torch.empty(lead + (N, m), dtype=dt, device=dev[0].device)
-    dL = torch.empty(lead + (N, m, n), dtype=dt, device=dev[0].device)
-    rc = _lib.lib().zm_ddp_backward_box_f64(*[None if t is None else t.data_ptr() for t in dev], ctypes.addressof(box), 0, dl.data_ptr(), dL.data_ptr(), None,
-                                            batch, N, n, m, ctypes.c_void_p(arr.stream_ptr(dev[0])))
-    _lib.check(rc, "backwardPass_ddp_box")
-    return AffinePolicy(arr.result_like(dl, f_x), arr.result_like(dL, f_x))
+    return _backward_pass("backwardPass_ddp_box", "zm_ddp_backward_box_f64", dynamics, cost, Vf, ddp=True, boxed=(uTraj, u_lb, u_ub))
 
 
 def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
@@ -689,91 +635,76 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     if tracking and (cost.n != n or cost.m != m):
         raise ValueError(f"the TrackingCost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
     md, cs = model.c_struct(), (cost.track_struct(tuple(lead), N) if tracking else cost.c_struct())
-    pmd, pcs = ctypes.addressof(md), ctypes.addressof(cs)
+    i32 = torch.int32
     L = torch.empty((B, N, m, n), dtype=dt, device=dev)
     xT = torch.empty((B, N + 1, n), dtype=dt, device=dev)
     uT = torch.empty((B, N, m), dtype=dt, device=dev)
     J = torch.empty(B, dtype=dt, device=dev)
-    converged = torch.zeros(B, dtype=torch.int32, device=dev)
+    converged = torch.zeros(B, dtype=i32, device=dev)
+    if sbox is not None:              # what the augmented-Lagrangian loop returns besides (ConstraintInfo)
+        lam_lb = torch.empty((B, N + 1, n), dtype=dt, device=dev)
+        lam_ub = torch.empty((B, N + 1, n), dtype=dt, device=dev)
+        mu = torch.empty(B, dtype=dt, device=dev)
+        viol = torch.zeros(B, dtype=dt, device=dev)
+        outer_its = torch.zeros(B, dtype=i32, device=dev)
+        inner_its = torch.zeros((sbox.outer, B), dtype=i32, device=dev)
     if B:
         # The whole loop -- initial rollout (:293-298), per iteration expansions, PD-conditioned Hessians, backward pass, 16-way
         # line search, `converged = |J - J_new| <= tol` (:305-322) over the compacted list of still-active trajectories -- is ONE
         # call into the C ABI: the host side of the iteration runs in C++ (zopt_amd/csrc/ilqr_solve.hip), no Python between the
         # launches.  SYNC: host synchronisation (termination test + rebuild of the id list) every SYNC iterations; the results do
         # not depend on it (an iteration over a converged trajectory touches nothing).
-        SYNC = max(1, int(os.environ.get("ZOPT_AMD_ILQR_SYNC", "4")))
-        nws = int(lib.zm_ilqr_solve_workspace_f64(pmd, B, N, 1 if ddp else 0))
+        # One record serves the eight entries (_lib.SOLVE_ARGS names each one's arguments in order).  The plain and the tracking
+        # entries take their cost struct as `cost`; the box and state entries take exactly one of `cost` and `track`.
+        family = "state_" if sbox is not None else "box_" if box is not None else "tracking_" if tracking else ""
+        entry = f"zm_ilqr_solve_{family}{'trace_' if _TRACE is not None else ''}f64"
+        pmd, pcs = ctypes.addressof(md), ctypes.addressof(cs)
+        nws = int(lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N) if sbox is not None else
+                  lib.zm_ilqr_solve_workspace_f64(pmd, B, N, 1 if ddp else 0))
         if nws < 0:
             raise ValueError("iterativeLqr: cannot size the workspace for this model")
         ws = torch.empty(nws, dtype=dt, device=dev)
-        iwork = torch.empty(2 * B + 2, dtype=torch.int32, device=dev)
+        iwork = torch.empty(2 * B + 2, dtype=i32, device=dev)
         its = ctypes.c_int32(0)
-        common = (pmd, pcs, dx0.data_ptr(), dug.data_ptr(), 1 if ddp else 0, int(maxIter), float(tol), SYNC,
-                  ws.data_ptr(), nws, iwork.data_ptr(), xT.data_ptr(), uT.data_ptr(), L.data_ptr(), J.data_ptr(),
-                  converged.data_ptr(), ctypes.addressof(its), B, N, st)
-        solve, solve_trace = ((lib.zm_ilqr_solve_tracking_f64, lib.zm_ilqr_solve_tracking_trace_f64) if tracking else
-                              (lib.zm_ilqr_solve_f64, lib.zm_ilqr_solve_trace_f64))
-        if box is not None:           # (model*, cost* | NULL, track* | NULL, box*, x0, ..., iterations, qp_capped, batch, T, stream)
-            bs = box.box_struct(tuple(lead))
-            capped = torch.zeros(B, dtype=torch.int32, device=dev)
-            common = (pmd, None if tracking else pcs, pcs if tracking else None, ctypes.addressof(bs)) + common[2:17] + \
-                (capped.data_ptr(),) + common[17:]
-            solve, solve_trace = lib.zm_ilqr_solve_box_f64, lib.zm_ilqr_solve_box_trace_f64
-        if sbox is not None:          # (model*, cost* | NULL, track* | NULL, box* | NULL, sbox*, mu0, growth, mu_max, outer, ctol, x0, ...)
-            lam_lb = torch.empty((B, N + 1, n), dtype=dt, device=dev)
-            lam_ub = torch.empty((B, N + 1, n), dtype=dt, device=dev)
-            mu = torch.empty(B, dtype=dt, device=dev)
-            viol = torch.zeros(B, dtype=dt, device=dev)
-            outer_its = torch.zeros(B, dtype=torch.int32, device=dev)
-            inner_its = torch.zeros((sbox.outer, B), dtype=torch.int32, device=dev)
+        d = {"model": pmd, "cost": None if tracking and family in ("state_", "box_") else pcs, "track": pcs if tracking else None,
+             "x0": dx0.data_ptr(), "uGuess": dug.data_ptr(), "ddp": 1 if ddp else 0, "max_iter": int(maxIter), "tol": float(tol),
+             "sync_every": max(1, int(os.environ.get("ZOPT_AMD_ILQR_SYNC", "4"))), "workspace": ws.data_ptr(),
+             "workspace_doubles": nws, "iwork": iwork.data_ptr(), "xTraj": xT.data_ptr(), "uTraj": uT.data_ptr(), "L": L.data_ptr(),
+             "J": J.data_ptr(), "converged": converged.data_ptr(), "iterations": ctypes.addressof(its), "batch": B, "T": N, "stream": st}
+        if box is not None or sbox is not None:
+            bs = box.box_struct(tuple(lead)) if box is not None else None
+            capped = torch.zeros(B, dtype=i32, device=dev)
+            d.update(box=ctypes.addressof(bs) if box is not None else None, qp_capped=capped.data_ptr())
+        if sbox is not None:
             ss = sbox.statebox_struct(tuple(lead), lam_lb, lam_ub, mu)
-            nws = int(lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N))
-            if nws < 0:
-                raise ValueError("iterativeLqr: cannot size the workspace for this model")
-            ws = torch.empty(nws, dtype=dt, device=dev)
-            if box is None:
-                capped = torch.zeros(B, dtype=torch.int32, device=dev)
-            args = (pmd, None if tracking else pcs, pcs if tracking else None, ctypes.addressof(bs) if box is not None else None,
-                    ctypes.addressof(ss), sbox.mu0, sbox.growth, sbox.mu_max, sbox.outer, sbox.ctol, dx0.data_ptr(), dug.data_ptr(), 0,
-                    int(maxIter), float(tol), SYNC, ws.data_ptr(), nws, iwork.data_ptr(), xT.data_ptr(), uT.data_ptr(), L.data_ptr(),
-                    J.data_ptr(), converged.data_ptr(), viol.data_ptr(), outer_its.data_ptr(), inner_its.data_ptr(),
-                    ctypes.addressof(its), capped.data_ptr(), B, N, st)
-            if _TRACE is None:
-                rc = lib.zm_ilqr_solve_state_f64(*args)
-            else:
-                rows = sbox.outer * max(int(maxIter), 1)
-                Jtr = torch.full((rows, B), float("nan"), dtype=dt, device=dev)
-                atr = torch.full((rows, B), -1, dtype=torch.int32, device=dev)
-                vtr = torch.full((sbox.outer, B), float("nan"), dtype=dt, device=dev)
-                mtr = torch.full((sbox.outer, B), float("nan"), dtype=dt, device=dev)
-                rc = lib.zm_ilqr_solve_state_trace_f64(*args, Jtr.data_ptr(), atr.data_ptr(), vtr.data_ptr(), mtr.data_ptr())
-            _lib.check(rc, "iterativeLqr")
-            if _TRACE is not None:
-                o = int(its.value)
-                _TRACE.append(("iterations", o))
-                _TRACE.append(("J_trace", Jtr.reshape(sbox.outer, -1, B)[:o].cpu().numpy()))
-                _TRACE.append(("alpha_trace", atr.reshape(sbox.outer, -1, B)[:o].cpu().numpy()))
+            d.update(sbox=ctypes.addressof(ss), mu0=sbox.mu0, growth=sbox.growth, mu_max=sbox.mu_max, outer=sbox.outer, ctol=sbox.ctol,
+                     violation=viol.data_ptr(), outer_iterations=outer_its.data_ptr(), inner_iterations=inner_its.data_ptr())
+        if _TRACE is not None:        # (outer, maxIter, batch) rows for a state box, (maxIter, batch) otherwise
+            outer = sbox.outer if sbox is not None else 1
+            Jtr = torch.full((outer * max(int(maxIter), 1), B), float("nan"), dtype=dt, device=dev)
+            atr = torch.full((outer * max(int(maxIter), 1), B), -1, dtype=i32, device=dev)
+            d.update(J_trace=Jtr.data_ptr(), alpha_trace=atr.data_ptr())
+            if sbox is not None:
+                vtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
+                mtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
+                d.update(violation_trace=vtr.data_ptr(), mu_trace=mtr.data_ptr())
+        rc = getattr(lib, entry)(*[d[k] for k in _lib.SOLVE_ARGS[entry]])
+        _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
+        if _TRACE is not None:
+            o = int(its.value)        # iLQR / DDP iterations; outer iterations of a state-box solve
+            if sbox is not None:
+                Jtr, atr = Jtr.reshape(outer, -1, B), atr.reshape(outer, -1, B)
+            _TRACE.append(("iterations", o))
+            _TRACE.append(("J_trace", Jtr[:o].cpu().numpy()))
+            _TRACE.append(("alpha_trace", atr[:o].cpu().numpy()))
+            if sbox is not None:
                 _TRACE.append(("violation_trace", vtr[:o].cpu().numpy()))
                 _TRACE.append(("mu_trace", mtr[:o].cpu().numpy()))
                 _TRACE.append(("inner_trace", inner_its[:o].cpu().numpy()))
-                if box is not None:
-                    _TRACE.append(("qp_capped", capped.cpu().numpy()))
-        elif _TRACE is None:
-            rc = solve(*common)
-        else:
-            Jtr = torch.full((max(int(maxIter), 1), B), float("nan"), dtype=dt, device=dev)
-            atr = torch.full((max(int(maxIter), 1), B), -1, dtype=torch.int32, device=dev)
-            rc = solve_trace(*common, Jtr.data_ptr(), atr.data_ptr())
-        _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
-        if _TRACE is not None and sbox is None:
-            _TRACE.append(("iterations", int(its.value)))
-            _TRACE.append(("J_trace", Jtr[: int(its.value)].cpu().numpy()))
-            _TRACE.append(("alpha_trace", atr[: int(its.value)].cpu().numpy()))
             if box is not None:
                 _TRACE.append(("qp_capped", capped.cpu().numpy()))
     tmpl = uGuess
-    fp32_in = (arr.is_torch(tmpl) and tmpl.dtype == torch.float32) or \
-        (not arr.is_torch(tmpl) and np.asarray(tmpl).dtype == np.float32)
+    fp32_in = _is_fp32(tmpl)
     outs = [xT.reshape(lead + (N + 1, n)), uT.reshape(lead + (N, m)), L.reshape(lead + (N, m, n)), J.reshape(lead)]
     if fp32_in:
         outs = [o.to(torch.float32) for o in outs]
@@ -782,10 +713,6 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     if not arr.is_torch(tmpl) and len(lead) == 0:
         Jo, co = float(Jo), bool(co)
     if info:
-        if not B:
-            lam_lb = lam_ub = torch.zeros((0, N + 1, n), dtype=dt, device=dev)
-            mu = viol = torch.zeros(0, dtype=dt, device=dev)
-            outer_its, inner_its = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((sbox.outer, 0), dtype=torch.int32, device=dev)
         fl = [viol.reshape(lead), mu.reshape(lead), lam_lb.reshape(lead + (N + 1, n)), lam_ub.reshape(lead + (N + 1, n))]
         if fp32_in:
             fl = [o.to(torch.float32) for o in fl]
