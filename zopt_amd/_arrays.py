@@ -15,6 +15,22 @@ def is_torch(x) -> bool:
     return torch is not None and isinstance(x, torch.Tensor)
 
 
+def shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+
+
+def batch(lead):
+    """Number of problems in the leading (batch) axes `lead`."""
+    b = 1
+    for d in lead:
+        b *= int(d)
+    return b
+
+
+def is_fp32(x):
+    return x.dtype == torch.float32 if is_torch(x) else np.asarray(x).dtype == np.float32
+
+
 def require_gpu():
     if torch is None or not torch.cuda.is_available():
         raise ZoptAmdError("zopt_amd needs a ROCm GPU (torch.cuda.is_available() is False); no CPU fallback exists")

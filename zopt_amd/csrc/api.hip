@@ -40,7 +40,6 @@ extern "C" int zm_lqr_backward_host_f64(const double* A, const double* B, const 
     if (batch < 0 || T < 1 || n < 1 || m < 1) return zm::set_error(ZM_EINVAL, "zm_lqr_backward_host_f64: bad size");
     if (!zm_lqr_backward_supported(n, m, 8))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_lqr_backward_host_f64: (n=%d, m=%d) not covered", n, m);
-    if (batch == 0) return ZM_OK;
     const size_t steps = (size_t)batch * T;
     const size_t bA = steps * n * n * sizeof(double), bB = steps * n * m * sizeof(double);
     const size_t bR = steps * m * m * sizeof(double), bL = bB;

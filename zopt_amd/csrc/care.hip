@@ -602,9 +602,9 @@ __global__ __launch_bounds__(64) void riccati_ode_kernel(const double* __restric
 extern "C" int zm_care_f64(const double* A, const double* B, const double* Q, const double* R, double* K, double* P,
                            int32_t* info, int64_t batch, int n, int m, double tol, int max_iter, void* stream) {
     if (batch == 0) return ZM_OK;
-    if (!A || !B || !Q || !R || !K) return zm::set_error(ZM_EINVAL, "zm_care_f64: null pointer");
-    if (batch < 0 || n < 1 || m < 1 || max_iter < 1 || !(tol >= 0.0)) return zm::set_error(ZM_EINVAL, "zm_care_f64: bad argument");
-    if (n > 16 || m > 16) return zm::set_error(ZM_EUNSUPPORTED, "zm_care_f64: (n=%d, m=%d) not covered (need n<=16, m<=16)", n, m);
+    if (const int rc = zm::check_design_args("zm_care_f64", A && B && Q && R && K, batch >= 0 && n >= 1 && m >= 1 && max_iter >= 1 && tol >= 0.0,
+                                             n, m, 16, 16))
+        return rc;
     if (batch >= ((int64_t)1 << 31)) return zm::set_error(ZM_EUNSUPPORTED, "zm_care_f64: batch too large");
     hipLaunchKernelGGL(zm::care_sda_kernel, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, A, B, Q, R, K, P,
                        (int*)info, n, m, tol, max_iter);
@@ -616,11 +616,11 @@ extern "C" int zm_riccati_ode_f64(const double* A_s, const double* B_s, const do
                                   const double* Qf, double* V, int32_t* info, int64_t batch, int n, int m, int n_samples, int N,
                                   double T, double rtol, double atol, int max_steps, void* stream) {
     if (batch == 0) return ZM_OK;
-    if (!A_s || !B_s || !Rinv_s || !Q_s || !Qf || !V) return zm::set_error(ZM_EINVAL, "zm_riccati_ode_f64: null pointer");
-    if (batch < 0 || n < 1 || m < 1 || n_samples < 1 || N < 1 || max_steps < 1 || !(T > 0.0) || !(rtol >= 0.0) || !(atol >= 0.0) ||
-        !(rtol + atol > 0.0))
-        return zm::set_error(ZM_EINVAL, "zm_riccati_ode_f64: bad argument");
-    if (n > 16 || m > 16) return zm::set_error(ZM_EUNSUPPORTED, "zm_riccati_ode_f64: (n=%d, m=%d) not covered (need n<=16, m<=16)", n, m);
+    if (const int rc = zm::check_design_args("zm_riccati_ode_f64", A_s && B_s && Rinv_s && Q_s && Qf && V,
+                                             batch >= 0 && n >= 1 && m >= 1 && n_samples >= 1 && N >= 1 && max_steps >= 1 && T > 0.0 &&
+                                                 rtol >= 0.0 && atol >= 0.0 && rtol + atol > 0.0,
+                                             n, m, 16, 16))
+        return rc;
     if (batch >= ((int64_t)1 << 31) || (int64_t)n_samples * n * n >= ((int64_t)1 << 30) || (int64_t)N * n * n >= ((int64_t)1 << 30))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_riccati_ode_f64: batch / sample count too large");
     hipLaunchKernelGGL(zm::riccati_ode_kernel, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, A_s, B_s, Rinv_s, Q_s, Qf,

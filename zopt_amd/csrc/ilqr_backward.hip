@@ -43,12 +43,12 @@
 //     v_x' = Q_x + Q_ux^T l        v_xx' = Q_xx - L^T Q_uu L
 #include "boxqp4.h"
 #include "dma_ring.h"
+#include "lqr_dispatch.h"
 #include "models.h"
 #include "ns16.h"
 #include "tile16_f64.h"
 #include "zm_common.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace zm {
@@ -983,15 +983,6 @@ struct ValueIO {   // optional scalar inputs / value-function outputs
     double *v_out, *vx_out, *vxx_out;
 };
 
-// The register-tile sweep kernels are instantiated per KS = ceil(n / 4) tile rows: calls f(ks) with ks an integral_constant, so that
-// a kernel family is written once as `[&](auto ks) { launch family<decltype(ks)::value> }`.
-template <typename F>
-static void with_ks(const int n, F&& f) {
-    if (n <= 4) f(std::integral_constant<int, 1>{});
-    else if (n <= 8) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 3>{});
-}
-
 template <int MODE>
 static int launch_ilqr(const double* f_x, const double* f_u, const double* c_x, const double* c_u, const double* c_xx,
                        const double* c_ux, const double* c_uu, const double* vf_x, const double* vf_xx, const double* d,
@@ -1019,14 +1010,7 @@ int sweep_tiled_f64_dispatch(int mode, const double* f_x, const double* f_u, con
 
 // tiled: the entry point also has the large-state tile kernel (n <= 48, m <= 16) behind it
 static int zm_check_sweep_args(const char* who, int64_t batch, int T, int n, int m, bool tiled = false) {
-    if (batch < 0 || T < 1 || n < 1 || m < 1)
-        return zm::set_error(ZM_EINVAL, "%s: bad size batch=%lld T=%d n=%d m=%d", who, (long long)batch, T, n, m);
-    if (tiled ? (n > 48 || m > 16) : (n > 12 || m > 4))
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (need %s)", who, n, m,
-                             tiled ? "n<=48, m<=16" : "n<=12, m<=4");
-    if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31))
-        return zm::set_error(ZM_EUNSUPPORTED, "%s: T*n*n or batch too large", who);
-    return ZM_OK;
+    return zm::check_sweep_args(who, batch, T, n, m, tiled ? 48 : 12, tiled ? 16 : 4);
 }
 
 // What the list entries check first, in this order: nothing to do (*rc <- ZM_OK; pointers of empty arrays may be NULL), the list's
@@ -1175,9 +1159,7 @@ extern "C" int zm_lqr_backward_affine_f64(const double* A, const double* B, cons
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     if (!A || !B || !d || !Q || !R || !H || !q || !r || !L || !l)
         return zm::set_error(ZM_EINVAL, "zm_lqr_backward_affine_f64: null pointer");
-    const int rc = zm_check_sweep_args("zm_lqr_backward_affine_f64", batch, T, n, m, true);
-    if (rc) return rc;
-    if (batch == 0) return ZM_OK;
+    if (const int rc = zm_check_sweep_args("zm_lqr_backward_affine_f64", batch, T, n, m, true)) return rc;
     // carry (V, v) <- (Q[T-1], q[T-1])   (lqrUtils.py:261): terminal pointers into the last step, trajectory stride T*size
     const double* vf_xx = Q + (int64_t)(T - 1) * n * n;
     const double* vf_x = q + (int64_t)(T - 1) * n;

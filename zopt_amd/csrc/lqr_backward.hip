@@ -20,10 +20,9 @@
 // A_k, B_k, Q_k, R_k are read ONCE from HBM straight into their MFMA register layouts (every step's
 // matrices are whole 128-B lines: 1152/384/1152/128 B at n=12, m=4), two steps ahead of their use; V never
 // leaves registers; L_k is written once.  Algorithmic HBM traffic: 8*(2n^2 + 2nm + m^2) B per horizon step.
+#include "lqr_dispatch.h"
 #include "lqr_step_core.h"
 #include "zm_common.h"
-
-#include <cstdlib>
 
 namespace zm {
 
@@ -294,23 +293,21 @@ __global__ __launch_bounds__(64, 4) void dare_t16_f64(const double* __restrict__
     if (iters && lane == 0) iters[sys] = conv ? it : -it;
 }
 
-// lqr_backward_dma.hip: LDS-DMA staged fast path (even n, m; 16-B aligned pointers); ZM_EUNSUPPORTED otherwise.
-int lqr_backward_dma_dispatch(const double* A, const double* B, const double* Q, const double* R, double* L,
-                              int64_t batch, int T, int n, int m, hipStream_t stream);
+// ZOPT_AMD_LQR_PATH, read once per process: lds sends the shapes beyond the register kernels to the LDS coverage kernel instead of the
+// fp64 tile kernel, reg the ring's shapes to the register-prefetch kernel (the first letter decides, as it always did).
+enum class LqrPath { Default, Lds, Reg };
+static LqrPath lqr_path() {
+    static const LqrPath path = [] {
+        const char* e = fallback_env("ZOPT_AMD_LQR_PATH");
+        return !e ? LqrPath::Default : e[0] == 'l' ? LqrPath::Lds : e[0] == 'r' ? LqrPath::Reg : LqrPath::Default;
+    }();
+    return path;
+}
 
 }  // namespace zm
 
-namespace zm {
-int lqr_backward_lds_dispatch(const double* A, const double* B, const double* Q, const double* R, double* L, int64_t batch,
-                              int T, int n, int m, hipStream_t st);   // lqr_backward_lds_f64.hip
-int lqr_backward_tiled_f64_dispatch(const double* A, const double* B, const double* Q, const double* R, double* L, int64_t batch,
-                                    int T, int n, int m, hipStream_t st);   // lqr_backward_tiled_f64.hip (n <= 64)
-int lqr_dare_tiled_f64_dispatch(const double* A, const double* B, const double* Q, const double* R, double* L, double* P, int* iters,
-                                int64_t batch, int n, int m, double tol, int max_iter, hipStream_t st);
-}
-
 extern "C" int zm_lqr_backward_supported(int n, int m, int elem_size) {
-    if (n < 1 || m < 1 || n > 64 || m > 16) return 0;
+    if (n < 1 || m < 1 || n > zm::LQR_MAX_N || m > zm::LQR_MAX_M) return 0;
     return (elem_size == 8 || elem_size == 4) ? 1 : 0;
 }
 
@@ -318,33 +315,18 @@ extern "C" int zm_lqr_backward_f64(const double* A, const double* B, const doubl
                                    int64_t batch, int T, int n, int m, void* stream) {
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     if (!A || !B || !Q || !R || !L) return zm::set_error(ZM_EINVAL, "zm_lqr_backward_f64: null pointer");
-    if (batch < 0 || T < 1 || n < 1 || m < 1)
-        return zm::set_error(ZM_EINVAL, "zm_lqr_backward_f64: bad size batch=%lld T=%d n=%d m=%d", (long long)batch, T,
-                             n, m);
-    if (!zm_lqr_backward_supported(n, m, 8))
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_lqr_backward_f64: (n=%d, m=%d) not covered (need n<=64, m<=16)", n, m);
-    if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31))
-        return zm::set_error(ZM_EUNSUPPORTED, "zm_lqr_backward_f64: T*n*n or batch too large");
-    if (batch == 0) return ZM_OK;
+    if (const int rc = zm::check_sweep_args("zm_lqr_backward_f64", batch, T, n, m, zm::LQR_MAX_N, zm::LQR_MAX_M)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (n > 12 || m > 4) {
-        // medium sizes: fp64 MFMA tile kernel (n <= 48); beyond, or with ZOPT_AMD_LQR_PATH=lds: the LDS coverage kernel
-        static const bool force_lds = [] {
-            const char* e = zm::fallback_env("ZOPT_AMD_LQR_PATH");
-            return e && e[0] == 'l';
-        }();
-        if (!force_lds) {
+        // medium and large sizes: the fp64 MFMA tile kernel; with ZOPT_AMD_LQR_PATH=lds the LDS coverage kernel
+        if (zm::lqr_path() != zm::LqrPath::Lds) {
             const int rc = zm::lqr_backward_tiled_f64_dispatch(A, B, Q, R, L, batch, T, n, m, st);
             if (rc != ZM_EUNSUPPORTED) return rc;
         }
         return zm::lqr_backward_lds_dispatch(A, B, Q, R, L, batch, T, n, m, st);
     }
     // ZOPT_AMD_LQR_PATH=reg forces the register-prefetch kernel (A/B measurements); default: LDS-DMA when eligible.
-    static const bool force_reg = [] {
-        const char* e = zm::fallback_env("ZOPT_AMD_LQR_PATH");
-        return e && e[0] == 'r';
-    }();
-    if (!force_reg) {
+    if (zm::lqr_path() != zm::LqrPath::Reg) {
         const int rc = zm::lqr_backward_dma_dispatch(A, B, Q, R, L, batch, T, n, m, st);
         if (rc != ZM_EUNSUPPORTED) return rc;
     }
@@ -359,21 +341,16 @@ extern "C" int zm_lqr_backward_f64(const double* A, const double* B, const doubl
 extern "C" int zm_dare_f64(const double* A, const double* B, const double* Q, const double* R, double* L, double* P,
                            int32_t* iters, int64_t batch, int n, int m, double tol, int max_iter, void* stream) {
     if (batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
-    if (!A || !B || !Q || !R || !L) return zm::set_error(ZM_EINVAL, "zm_dare_f64: null pointer");
-    if (batch < 0 || n < 1 || m < 1 || max_iter < 1 || !(tol >= 0.0)) return zm::set_error(ZM_EINVAL, "zm_dare_f64: bad argument");
-    if (n > 64 || m > 16) return zm::set_error(ZM_EUNSUPPORTED, "zm_dare_f64: (n=%d, m=%d) not covered (need n<=64, m<=16)", n, m);
+    if (const int rc = zm::check_design_args("zm_dare_f64", A && B && Q && R && L, batch >= 0 && n >= 1 && m >= 1 && max_iter >= 1 && tol >= 0.0,
+                                             n, m, zm::LQR_MAX_N, zm::LQR_MAX_M))
+        return rc;
     if (batch >= ((int64_t)1 << 31)) return zm::set_error(ZM_EUNSUPPORTED, "zm_dare_f64: batch too large");
     if (n > 12 || m > 4)   // large states: the fp64 tile kernel's step on time-invariant operands
         return zm::lqr_dare_tiled_f64_dispatch(A, B, Q, R, L, P, (int*)iters, batch, n, m, tol, max_iter, (hipStream_t)stream);
-    if (batch == 0) return ZM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)batch), block(64);
-    if (n <= 4)
-        hipLaunchKernelGGL((zm::dare_t16_f64<1>), grid, block, 0, st, A, B, Q, R, L, P, (int*)iters, (long)batch, n, m, tol, max_iter);
-    else if (n <= 8)
-        hipLaunchKernelGGL((zm::dare_t16_f64<2>), grid, block, 0, st, A, B, Q, R, L, P, (int*)iters, (long)batch, n, m, tol, max_iter);
-    else
-        hipLaunchKernelGGL((zm::dare_t16_f64<3>), grid, block, 0, st, A, B, Q, R, L, P, (int*)iters, (long)batch, n, m, tol, max_iter);
+    zm::with_ks(n, [&](auto ks) {
+        hipLaunchKernelGGL((zm::dare_t16_f64<decltype(ks)::value>), dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, A, B, Q, R, L, P,
+                           (int*)iters, (long)batch, n, m, tol, max_iter);
+    });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
 }

@@ -4,8 +4,7 @@
 // cover:  V <- Q[T-1];  L_k = solve(R_k + B_k^T V B_k, B_k^T V A_k) (:168);  V = Q_k + L_k^T R_k L_k + Acl^T V Acl (:169).
 // Coverage kernel, not a tuned one: one 256-thread block per trajectory, V / A_k / V Acl resident in LDS (135 kB at
 // n = 64, m = 16), plain fp64 FMAs in the reference's own operation order, LU with partial pivoting by the first wave.
-#include <hip/hip_runtime.h>
-
+#include "lqr_dispatch.h"
 #include "zm_common.h"
 
 namespace zm {

@@ -47,6 +47,29 @@ inline int model_check(const zm_model_t* model, const char* who, zm_model_t* md)
     return ZM_OK;
 }
 
+// The sizes of a backward sweep, checked after "nothing to do" and the operands: who has T steps of an n x n matrix per trajectory and
+// covers n <= n_max, m <= m_max.
+inline int check_sweep_args(const char* who, int64_t batch, int T, int n, int m, int n_max, int m_max) {
+    if (batch < 0 || T < 1 || n < 1 || m < 1)
+        return set_error(ZM_EINVAL, "%s: bad size batch=%lld T=%d n=%d m=%d", who, (long long)batch, T, n, m);
+    if (n > n_max || m > m_max)
+        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (need n<=%d, m<=%d)", who, n, m, n_max, m_max);
+    if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31))
+        return set_error(ZM_EUNSUPPORTED, "%s: T*n*n or batch too large", who);
+    return ZM_OK;
+}
+
+// What the one-design-per-wave entries (DARE, CARE, Riccati ODE) check alike, in this order: the operands (`operands`: the entry's own
+// "all given"), the entry's own arguments (`arguments`: its own "all in range"), the shape.  The bound on the batch comes after it:
+// the ODE's covers its sample counts too and reads differently, so each entry keeps that line.
+inline int check_design_args(const char* who, bool operands, bool arguments, int n, int m, int n_max, int m_max) {
+    if (!operands) return set_error(ZM_EINVAL, "%s: null pointer", who);
+    if (!arguments) return set_error(ZM_EINVAL, "%s: bad argument", who);
+    if (n > n_max || m > m_max)
+        return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (need n<=%d, m<=%d)", who, n, m, n_max, m_max);
+    return ZM_OK;
+}
+
 #define ZM_HIP_CHECK(expr)                                                              \
     do {                                                                                \
         hipError_t _e = (expr);                                                         \

@@ -14,6 +14,7 @@ import numpy as np
 from . import _arrays as arr
 from . import _lib
 from . import models as _models
+from ._arrays import batch as _batch, is_fp32 as _is_fp32, shape as _shape
 from .pytrees import (AffineDynamics, AffinePolicy, QuadraticCostFunction, QuadraticDynamics,  # noqa: F401
                       QuadraticValueFunction, Trajectory)
 
@@ -45,22 +46,6 @@ _generic = _LazyGeneric()
 def _fields(t):
     """Fields of a (Named)tuple; the pytrees override __getitem__ (per-time-step slice), so use tuple.__iter__."""
     return list(tuple.__iter__(t)) if isinstance(t, tuple) else list(t)
-
-
-def _shape(x):
-    return tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
-
-
-def _batch(lead):
-    """Number of problems in the leading (batch) axes `lead`."""
-    b = 1
-    for d in lead:
-        b *= int(d)
-    return b
-
-
-def _is_fp32(x):
-    return x.dtype == torch.float32 if arr.is_torch(x) else np.asarray(x).dtype == np.float32
 
 
 def _check_shapes(table):

@@ -19,8 +19,52 @@ except Exception:  # pragma: no cover
     torch = None
 
 
-def _shape_error(msg):
-    raise ValueError(msg)
+def _check_operands(rows, lead, N=None):
+    """`rows`: (name, array, tail).  Without `N` an operand has exactly the shape lead + tail; with a horizon `N` it is time-indexed,
+    lead + (T,) + tail with T >= N (a longer one gets the carry step of `_carry_step`)."""
+    for name, X, tail in rows:
+        s, k = arr.shape(X), len(lead)
+        if N is None:
+            if s != lead + tail:
+                raise ValueError(f"{name} has shape {s}, expected {lead + tail}")
+        elif len(s) != k + 1 + len(tail) or s[:k] != lead or s[k + 1:] != tail or s[k] < N:
+            raise ValueError(f"{name} has shape {s}, expected {lead + ('>=N',) + tail} with N={N}")
+
+
+def _carry_step(dev, fills, ax, N):
+    """The reference scans the first N steps but starts from the carry (Q[-1], ...) of the WHOLE arrays (lqrUtils.py:172, :261).  The
+    kernels take the last step's cost as terminal value, so operands longer than N get one extra step along the time axis `ax` that
+    hands that carry to step N-1 and returns a zero gain: per operand `fills` names it -- "zero", "last" (the array's last step) or
+    "eye".  -> (operands, number of steps the kernel runs); the caller trims the extra step off the outputs (`_first_steps`)."""
+    if all(t.shape[ax] == N for t in dev):
+        return dev, N
+
+    def extra(t, fill):
+        if fill == "last":
+            return t.narrow(ax, t.shape[ax] - 1, 1)
+        if fill == "eye":
+            return torch.eye(t.shape[-1], dtype=t.dtype, device=t.device).expand(tuple(t.shape[:ax]) + (1,) + tuple(t.shape[-2:]))
+        return torch.zeros_like(t.narrow(ax, 0, 1))
+
+    return [torch.cat([t.narrow(ax, 0, N), extra(t, fill)], ax).contiguous() for t, fill in zip(dev, fills)], N + 1
+
+
+def _first_steps(outs, ax, N):
+    return [t if t.shape[ax] == N else t.narrow(ax, 0, N).contiguous() for t in outs]
+
+
+def _call(who, entry, batch, *args):
+    """The C entry `entry` on the current stream of its first operand's device, unless the batch is empty; a refusal raises as `who`."""
+    if batch:
+        ptrs = [a.data_ptr() if arr.is_torch(a) else a for a in args]
+        _lib.check(getattr(_lib.lib(), entry)(*ptrs, ctypes.c_void_p(arr.stream_ptr(args[0]))), who)
+
+
+def _like(template, *outs):
+    """The outputs in the caller's array family and precision: the entries compute in fp64, an fp32 caller gets fp32 back."""
+    if arr.is_fp32(template):
+        outs = [t.to(torch.float32) if t.is_floating_point() else t for t in outs]
+    return [arr.result_like(t, template) for t in outs]
 
 
 def discreteFiniteHorizonLqr(A, B, Q, R, N):
@@ -42,54 +86,24 @@ def discreteFiniteHorizonLqr(A, B, Q, R, N):
     -------
         L : (..., N, m, n) optimal gains `L[k]`
     """
-    shp = tuple(np.shape(B)) if not arr.is_torch(B) else tuple(B.shape)
+    shp = arr.shape(B)
     if len(shp) < 3:
-        _shape_error("B must have shape (..., N, n, m)")
-    n, m = shp[-2:]
-    lead = shp[:-3]
-    for name, X, tail in (("A", A, (n, n)), ("B", B, (n, m)), ("Q", Q, (n, n)), ("R", R, (m, m))):
-        s = tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        if s[-2:] != tail or len(s) < 3 or s[-3] < N or s[:-3] != lead:
-            _shape_error(f"{name} has shape {s}, expected {lead + ('>=N',) + tail} with N={N}")
+        raise ValueError("B must have shape (..., N, n, m)")
+    lead, (n, m) = shp[:-3], shp[-2:]
+    _check_operands((("A", A, (n, n)), ("B", B, (n, m)), ("Q", Q, (n, n)), ("R", R, (m, m))), lead, N)
     if N < 1:
-        _shape_error("N must be >= 1")
-    fp32_in = (arr.is_torch(A) and A.dtype == torch.float32) or (not arr.is_torch(A) and np.asarray(A).dtype == np.float32)
+        raise ValueError("N must be >= 1")
     # dtype follows the input arrays (quirk Q8).  fp32 inputs go to zm_lqr_backward_f32 as they are: the fast-path shapes (n in {8, 12},
     # m = 4) run K1 on fp32 storage with fp64 arithmetic, larger ones (n <= 64, m <= 16) the fp32 MFMA tile kernel; the remaining small
     # shapes are computed in fp64 on the tile-16 kernel and rounded once on output.
-    native32 = fp32_in and (n > 12 or m > 4 or ((n in (8, 12)) and m == 4))
+    native32 = arr.is_fp32(A) and (n > 12 or m > 4 or ((n in (8, 12)) and m == 4))
     dt = torch.float32 if native32 else torch.float64
-    dev = [arr.to_device(X, dt) for X in (A, B, Q, R)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    out_dt = torch.float32 if fp32_in else torch.float64
-    if batch == 0:
-        return arr.result_like(torch.empty(lead + (N, m, n), dtype=out_dt, device=dev[0].device), A)
-    # The reference scans xs = arange(N) over the first N steps but starts from V = Q[-1] of the WHOLE array
-    # (lqrUtils.py:172).  The kernel takes the last step's Q as terminal value, so over-long inputs get one extra step
-    # (A = 0, B = 0, Q = Q[-1], R = I): it returns L = 0 and hands V = Q[-1] to step N-1.
-    Tk = N
-    if any(x.shape[-3] != N for x in dev):
-        dA, dB, dQ, dR = dev
-        Tk = N + 1
-        eye = torch.eye(m, dtype=dt, device=dA.device).expand(lead + (1, m, m))
-        dA = torch.cat([dA[..., :N, :, :], torch.zeros_like(dA[..., :1, :, :])], dim=-3).contiguous()
-        dB = torch.cat([dB[..., :N, :, :], torch.zeros_like(dB[..., :1, :, :])], dim=-3).contiguous()
-        dQ = torch.cat([dQ[..., :N, :, :], dQ[..., -1:, :, :]], dim=-3).contiguous()
-        dR = torch.cat([dR[..., :N, :, :], eye], dim=-3).contiguous()
-    else:
-        dA, dB, dQ, dR = dev
-    dL = torch.empty(lead + (Tk, m, n), dtype=dt, device=dA.device)
-    fn = _lib.lib().zm_lqr_backward_f32 if native32 else _lib.lib().zm_lqr_backward_f64
-    rc = fn(dA.data_ptr(), dB.data_ptr(), dQ.data_ptr(), dR.data_ptr(), dL.data_ptr(), batch, Tk, n, m,
-            ctypes.c_void_p(arr.stream_ptr(dA)))
-    _lib.check(rc, "discreteFiniteHorizonLqr")
-    if Tk != N:
-        dL = dL[..., :N, :, :].contiguous()
-    if fp32_in and not native32:
-        dL = dL.to(torch.float32)
-    return arr.result_like(dL, A)
+    # the extra step of over-long inputs (A = 0, B = 0, Q = Q[-1], R = I) returns L = 0 and hands V = Q[-1] to step N-1
+    dev, Tk = _carry_step([arr.to_device(X, dt) for X in (A, B, Q, R)], ("zero", "zero", "last", "eye"), len(lead), N)
+    batch = arr.batch(lead)
+    dL = torch.empty(lead + (Tk, m, n), dtype=dt, device=dev[0].device)
+    _call("discreteFiniteHorizonLqr", "zm_lqr_backward_f32" if native32 else "zm_lqr_backward_f64", batch, *dev, dL, batch, Tk, n, m)
+    return _like(A, *_first_steps([dL], len(lead), N))[0]
 
 
 def discreteInfiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=200000, return_value=False):
@@ -116,27 +130,9 @@ def discreteInfiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=200000, return_val
         L : (..., m, n) optimal LQR gains `u = -L x`   (with `return_value=True`: (L, V, iterations), iterations < 0 where the
             cap ended the iteration before its stopping test was met)
     """
-    shp = tuple(B.shape) if hasattr(B, "shape") else tuple(np.shape(B))
-    if len(shp) < 2:
-        _shape_error("B must have shape (..., n, m)")
-    n, m = shp[-2:]
-    lead = shp[:-2]
-    for name, X, tail in (("A", A, (n, n)), ("B", B, (n, m)), ("Q", Q, (n, n)), ("R", R, (m, m))):
-        s_ = tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        if s_ != lead + tail:
-            _shape_error(f"{name} has shape {s_}, expected {lead + tail}")
-    dt = torch.float64
-    dA, dB, dQ, dR = [arr.to_device(X, dt) for X in (A, B, Q, R)]
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dL = torch.empty(lead + (m, n), dtype=dt, device=dA.device)
-    dP = torch.empty(lead + (n, n), dtype=dt, device=dA.device)
-    its = torch.empty(lead, dtype=torch.int32, device=dA.device)
-    rc = 0 if batch == 0 else _lib.lib().zm_dare_f64(dA.data_ptr(), dB.data_ptr(), dQ.data_ptr(), dR.data_ptr(), dL.data_ptr(), dP.data_ptr(),
-                                its.data_ptr(), batch, n, m, float(tol), int(maxIter), ctypes.c_void_p(arr.stream_ptr(dA)))
-    _lib.check(rc, "discreteInfiniteHorizonLqr")
-    if batch and not return_value:      # with return_value=True the caller receives `iterations` and judges convergence itself
+    def failed(its, dL, batch):
+        if return_value:      # the caller receives `iterations` and judges convergence itself
+            return
         # the kernel reports convergence explicitly (iters < 0: the cap ended the loop); a design that meets the tolerance exactly on
         # its last allowed iteration is converged
         bad = (its.reshape(-1) <= 0) | ~torch.isfinite(dL.reshape(batch, -1)).all(dim=1)
@@ -144,18 +140,40 @@ def discreteInfiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=200000, return_val
         if nbad:   # SciPy's solve_discrete_are raises LinAlgError('Failed to find a finite solution.') there (lqrUtils.py:202)
             raise np.linalg.LinAlgError(f"discreteInfiniteHorizonLqr: no converged finite solution for {nbad} of {batch} designs "
                                         f"within maxIter={int(maxIter)} (not stabilizable, or increase maxIter)")
-    fp32_in = (arr.is_torch(A) and A.dtype == torch.float32) or (not arr.is_torch(A) and np.asarray(A).dtype == np.float32)
-    if fp32_in:
-        dL, dP = dL.to(torch.float32), dP.to(torch.float32)
-    if return_value:
-        return arr.result_like(dL, A), arr.result_like(dP, A), arr.result_like(its, A)
-    return arr.result_like(dL, A)
+
+    return _riccati_design("discreteInfiniteHorizonLqr", "zm_dare_f64", A, B, Q, R, tol, maxIter, return_value, symmetric=False,
+                           status=torch.empty, failed=failed)
 
 
 def _check_symmetric(name, X):
     """scipy.linalg.solve_continuous_are rejects nonsymmetric q / r with a ValueError (its _are_validate_args)."""
     if X.numel() and float((X - X.transpose(-1, -2)).abs().max()) > 100 * np.finfo(np.float64).eps * max(float(X.abs().max()), 1.0):
-        _shape_error(f"Matrix {name} should be symmetric/hermitian.")
+        raise ValueError(f"Matrix {name} should be symmetric/hermitian.")
+
+
+def _riccati_design(who, entry, A, B, Q, R, tol, maxIter, return_value, symmetric, status, failed):
+    """The two algebraic Riccati designs: four operands of exact shape uploaded as fp64, a gain, a value and an int32 status per design
+    (`status`: how it is allocated), `entry(..., tol, maxIter)`, `failed(status, gain, batch)` raising LinAlgError where the entry's
+    status says so, the outputs in the caller's precision.  `symmetric`: Q and R must be symmetric, as SciPy's CARE solver demands."""
+    shp = arr.shape(B)
+    if len(shp) < 2:
+        raise ValueError("B must have shape (..., n, m)")
+    lead, (n, m) = shp[:-2], shp[-2:]
+    _check_operands((("A", A, (n, n)), ("B", B, (n, m)), ("Q", Q, (n, n)), ("R", R, (m, m))), lead)
+    dt = torch.float64
+    dA, dB, dQ, dR = [arr.to_device(X, dt) for X in (A, B, Q, R)]
+    if symmetric:
+        _check_symmetric("q", dQ)
+        _check_symmetric("r", dR)
+    batch = arr.batch(lead)
+    dK = torch.empty(lead + (m, n), dtype=dt, device=dA.device)
+    dP = torch.empty(lead + (n, n), dtype=dt, device=dA.device)
+    info = status(lead, dtype=torch.int32, device=dA.device)
+    _call(who, entry, batch, dA, dB, dQ, dR, dK, dP, info, batch, n, m, float(tol), int(maxIter))
+    if batch:
+        failed(info, dK, batch)
+    outs = _like(A, *((dK, dP, info) if return_value else (dK,)))
+    return tuple(outs) if return_value else outs[0]
 
 
 def infiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=60, return_value=False):
@@ -186,38 +204,13 @@ def infiniteHorizonLqr(A, B, Q, R, tol=1e-14, maxIter=60, return_value=False):
     -------
         K : (..., m, n) LQR gains   (with `return_value=True`: (K, P, doubling steps))
     """
-    shp = tuple(B.shape) if hasattr(B, "shape") else tuple(np.shape(B))
-    if len(shp) < 2:
-        _shape_error("B must have shape (..., n, m)")
-    n, m = shp[-2:]
-    lead = shp[:-2]
-    for name, X, tail in (("A", A, (n, n)), ("B", B, (n, m)), ("Q", Q, (n, n)), ("R", R, (m, m))):
-        s_ = tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        if s_ != lead + tail:
-            _shape_error(f"{name} has shape {s_}, expected {lead + tail}")
-    dt = torch.float64
-    dA, dB, dQ, dR = [arr.to_device(X, dt) for X in (A, B, Q, R)]
-    _check_symmetric("q", dQ)
-    _check_symmetric("r", dR)
-    batch = 1
-    for d in lead:
-        batch *= int(d)
-    dK = torch.empty(lead + (m, n), dtype=dt, device=dA.device)
-    dP = torch.empty(lead + (n, n), dtype=dt, device=dA.device)
-    info = torch.ones(lead, dtype=torch.int32, device=dA.device)
-    rc = 0 if batch == 0 else _lib.lib().zm_care_f64(dA.data_ptr(), dB.data_ptr(), dQ.data_ptr(), dR.data_ptr(), dK.data_ptr(),
-                                                     dP.data_ptr(), info.data_ptr(), batch, n, m, float(tol), int(maxIter),
-                                                     ctypes.c_void_p(arr.stream_ptr(dA)))
-    _lib.check(rc, "infiniteHorizonLqr")
-    if batch and int(info.min()) < 0:    # SciPy: LinAlgError('Failed to find a finite solution.')
-        raise np.linalg.LinAlgError("infiniteHorizonLqr: failed to find a finite stabilising solution "
-                                    f"({int((info < 0).sum())} of {batch} designs)")
-    fp32_in = (arr.is_torch(A) and A.dtype == torch.float32) or (not arr.is_torch(A) and np.asarray(A).dtype == np.float32)
-    if fp32_in:
-        dK, dP = dK.to(torch.float32), dP.to(torch.float32)
-    if return_value:
-        return arr.result_like(dK, A), arr.result_like(dP, A), arr.result_like(info, A)
-    return arr.result_like(dK, A)
+    def failed(info, dK, batch):
+        if int(info.min()) < 0:    # SciPy: LinAlgError('Failed to find a finite solution.')
+            raise np.linalg.LinAlgError("infiniteHorizonLqr: failed to find a finite stabilising solution "
+                                        f"({int((info < 0).sum())} of {batch} designs)")
+
+    return _riccati_design("infiniteHorizonLqr", "zm_care_f64", A, B, Q, R, tol, maxIter, return_value, symmetric=True,
+                           status=torch.ones, failed=failed)
 
 
 def infiniteHorizonIntegralLqr(A, B, Q, R, Qi, Ci):
@@ -240,15 +233,13 @@ def infiniteHorizonIntegralLqr(A, B, Q, R, Qi, Ci):
     dt = torch.float64
     dA, dB, dQ, dR, dQi, dCi = [arr.to_device(X, dt) for X in (A, B, Q, R, Qi, Ci)]
     if dB.dim() < 2 or dQi.dim() < 2:
-        _shape_error("B must have shape (..., n, m) and Qi (..., ni, ni)")
+        raise ValueError("B must have shape (..., n, m) and Qi (..., ni, ni)")
     n, m = dB.shape[-2:]
     ni = dQi.shape[-1]
     lead = tuple(dB.shape[:-2])
     if dCi.dim() == len(lead) + 1:       # np.block promotes a 1-D Ci to one row (:129)
         dCi = dCi.unsqueeze(-2)
-    for name, X, tail in (("A", dA, (n, n)), ("Q", dQ, (n, n)), ("R", dR, (m, m)), ("Qi", dQi, (ni, ni)), ("Ci", dCi, (ni, n))):
-        if tuple(X.shape) != lead + tail:
-            _shape_error(f"{name} has shape {tuple(X.shape)}, expected {lead + tail}")
+    _check_operands((("A", dA, (n, n)), ("Q", dQ, (n, n)), ("R", dR, (m, m)), ("Qi", dQi, (ni, ni)), ("Ci", dCi, (ni, n))), lead)
     z = lambda r, c: torch.zeros(lead + (r, c), dtype=dt, device=dA.device)
     Aw = torch.cat([torch.cat([z(ni, ni), dCi], -1), torch.cat([z(n, ni), dA], -1)], -2)
     Bw = torch.cat([z(ni, m), dB], -2)
@@ -314,10 +305,10 @@ def finiteHorizonLqr(A, B, Q, R_inv, Qf, T, N=50, n_samples=None, rtol=1.4e-8, a
     T = float(T)
     N = int(N)
     if not (T > 0.0) or N < 1:
-        _shape_error("T must be > 0 and N >= 1")
+        raise ValueError("T must be > 0 and N >= 1")
     ns0 = int(n_samples) if n_samples is not None else 8 * (N - 1) + 1
     if ns0 < 1:
-        _shape_error("n_samples must be >= 1")
+        raise ValueError("n_samples must be >= 1")
     dt = torch.float64
     dev = arr.to_device(Qf, dt).device
     dQf = arr.to_device(Qf, dt, dev).contiguous()
@@ -336,24 +327,17 @@ def finiteHorizonLqr(A, B, Q, R_inv, Qf, T, N=50, n_samples=None, rtol=1.4e-8, a
         stack = lambda v: torch.stack(v if len(v) == cnt else v * cnt, dim=-3).contiguous()
         dA, dB, dQ, dRi = stack(sA), stack(sB), stack(sQ), stack(sRi)
         if dB.dim() < 3:
-            _shape_error("B(t) must have shape (..., n, m)")
+            raise ValueError("B(t) must have shape (..., n, m)")
         n, m = dB.shape[-2:]
         lead = tuple(dB.shape[:-3])
-        for name, X, tail in (("A(t)", dA, (cnt, n, n)), ("Q(t)", dQ, (cnt, n, n)), ("R_inv(t)", dRi, (cnt, m, m))):
-            if tuple(X.shape) != lead + tail:
-                _shape_error(f"{name} has shape {tuple(X.shape[:-3]) + tuple(X.shape[-2:])}, expected {lead + tail[1:]}")
-        if tuple(dQf.shape) != lead + (n, n):
-            _shape_error(f"Qf has shape {tuple(dQf.shape)}, expected {lead + (n, n)}")
-        batch = 1
-        for d in lead:
-            batch *= int(d)
+        # every stack holds `cnt` samples along axis -3: the shapes of one sample are what is checked and reported
+        _check_operands((("A(t)", dA[..., 0, :, :], (n, n)), ("Q(t)", dQ[..., 0, :, :], (n, n)), ("R_inv(t)", dRi[..., 0, :, :], (m, m)),
+                         ("Qf", dQf, (n, n))), lead)
+        batch = arr.batch(lead)
         dV = torch.empty(lead + (N, n, n), dtype=dt, device=dev)
         info = torch.ones(lead, dtype=torch.int32, device=dev)
-        rc = 0 if batch == 0 else _lib.lib().zm_riccati_ode_f64(dA.data_ptr(), dB.data_ptr(), dRi.data_ptr(), dQ.data_ptr(),
-                                                                dQf.data_ptr(), dV.data_ptr(), info.data_ptr(), batch, n, m, cnt, N,
-                                                                T, float(rtol), float(atol), int(max_steps),
-                                                                ctypes.c_void_p(arr.stream_ptr(dQf)))
-        _lib.check(rc, "finiteHorizonLqr")
+        _call("finiteHorizonLqr", "zm_riccati_ode_f64", batch, dA, dB, dRi, dQ, dQf, dV, info, batch, n, m, cnt, N, T, float(rtol),
+              float(atol), int(max_steps))
         return dV, info, cnt
 
     ns = ns0
@@ -392,56 +376,24 @@ def bilinearAffineLqr(A, B, d, Q, R, H, q, r, q0, N):
         L : (..., N, m, n) optimal lqr gains `L[k]`
         l : (..., N, m) optimal lqr offsets `l[k]`          (law `u = -L x - l`, demos/bilinearLqrControl.py:14)
     """
-    shp = tuple(B.shape) if hasattr(B, "shape") else tuple(np.shape(B))
+    shp = arr.shape(B)
     if len(shp) < 3:
-        _shape_error("B must have shape (..., N, n, m)")
-    n, m = shp[-2:]
-    lead = shp[:-3]
+        raise ValueError("B must have shape (..., N, n, m)")
+    lead, (n, m) = shp[:-3], shp[-2:]
     spec = (("A", A, (n, n)), ("B", B, (n, m)), ("d", d, (n,)), ("Q", Q, (n, n)), ("R", R, (m, m)), ("H", H, (m, n)),
             ("q", q, (n,)), ("r", r, (m,)))
-    for name, X, tail in spec:
-        s_ = tuple(X.shape) if hasattr(X, "shape") else tuple(np.shape(X))
-        if s_[len(s_) - len(tail):] != tail or len(s_) != len(lead) + 1 + len(tail) or s_[:len(lead)] != lead or s_[len(lead)] < N:
-            _shape_error(f"{name} has shape {s_}, expected {lead + ('>=N',) + tail} with N={N}")
+    _check_operands(spec, lead, N)
     if N < 1:
-        _shape_error("N must be >= 1")
+        raise ValueError("N must be >= 1")
     dt = torch.float64
-    dev = [arr.to_device(X, dt) for name, X, tail in spec]
-    batch = 1
-    for s_ in lead:
-        batch *= int(s_)
-    fp32_in = (arr.is_torch(A) and A.dtype == torch.float32) or (not arr.is_torch(A) and np.asarray(A).dtype == np.float32)
-    if batch == 0:
-        odt = torch.float32 if fp32_in else dt
-        return (arr.result_like(torch.empty(lead + (N, m, n), dtype=odt, device=dev[0].device), A),
-                arr.result_like(torch.empty(lead + (N, m), dtype=odt, device=dev[0].device), A))
-    # Over-long inputs: the reference scans the first N steps from the carry (Q[-1], q[-1], q0[-1]) of the WHOLE arrays
-    # (lqrUtils.py:261).  One extra step (A = B = d = H = r = 0, Q = Q[-1], q = q[-1], R = I) reproduces that carry.
-    ax = len(lead)
-    Tk = N
-    if any(t.shape[ax] != N for t in dev):
-        Tk = N + 1
-        dA, dB, dd, dQ, dR, dH, dq, dr = dev
-        head = lambda t: t.narrow(ax, 0, N)
-        last = lambda t: t.narrow(ax, t.shape[ax] - 1, 1)
-        zero = lambda t: torch.zeros_like(t.narrow(ax, 0, 1))
-        eye = torch.eye(m, dtype=dt, device=dA.device).expand(lead + (1, m, m))
-        dev = [torch.cat([head(dA), zero(dA)], ax), torch.cat([head(dB), zero(dB)], ax), torch.cat([head(dd), zero(dd)], ax),
-               torch.cat([head(dQ), last(dQ)], ax), torch.cat([head(dR), eye], ax), torch.cat([head(dH), zero(dH)], ax),
-               torch.cat([head(dq), last(dq)], ax), torch.cat([head(dr), zero(dr)], ax)]
-        dev = [t.contiguous() for t in dev]
-    dA, dB, dd, dQ, dR, dH, dq, dr = dev
-    dL = torch.empty(lead + (Tk, m, n), dtype=dt, device=dA.device)
-    dl = torch.empty(lead + (Tk, m), dtype=dt, device=dA.device)
-    rc = _lib.lib().zm_lqr_backward_affine_f64(dA.data_ptr(), dB.data_ptr(), dd.data_ptr(), dQ.data_ptr(), dR.data_ptr(),
-                                               dH.data_ptr(), dq.data_ptr(), dr.data_ptr(), dL.data_ptr(), dl.data_ptr(),
-                                               batch, Tk, n, m, ctypes.c_void_p(arr.stream_ptr(dA)))
-    _lib.check(rc, "bilinearAffineLqr")
-    if Tk != N:
-        dL, dl = dL.narrow(ax, 0, N).contiguous(), dl.narrow(ax, 0, N).contiguous()
-    if fp32_in:
-        dL, dl = dL.to(torch.float32), dl.to(torch.float32)
-    return arr.result_like(dL, A), arr.result_like(dl, A)
+    # the extra step of over-long inputs (A = B = d = H = r = 0, Q = Q[-1], q = q[-1], R = I) reproduces the carry (Q[-1], q[-1])
+    dev, Tk = _carry_step([arr.to_device(X, dt) for name, X, tail in spec],
+                          ("zero", "zero", "zero", "last", "eye", "zero", "last", "zero"), len(lead), N)
+    batch = arr.batch(lead)
+    dL = torch.empty(lead + (Tk, m, n), dtype=dt, device=dev[0].device)
+    dl = torch.empty(lead + (Tk, m), dtype=dt, device=dev[0].device)
+    _call("bilinearAffineLqr", "zm_lqr_backward_affine_f64", batch, *dev, dL, dl, batch, Tk, n, m)
+    return tuple(_like(A, *_first_steps([dL, dl], len(lead), N)))
 
 
 def proportionalFeedbackController(x, x0, u0, K):

@@ -63,7 +63,7 @@ def simulateProportionalFeedback(dynFun, x0, K, xTrim, uTrim, N=None):
     -------
         Trajectory(xSim (..., N+1, n), uSim (..., N, m))
     """
-    lead = tuple(x0.shape[:-1]) if hasattr(x0, "shape") else np.shape(x0)[:-1]
+    lead = arr.shape(x0)[:-1]
     n, m = dynFun.n, dynFun.m
     kshape = tuple(K.shape)
     xp = torch if arr.is_torch(K) else np
