@@ -147,11 +147,38 @@ int zm_ilqr_backward_f64(const double* f_x, const double* f_u, const double* c_x
 #define ZM_MODEL_LINEAR 1     /* x+ = A x + B u, A (n,n), B (n,m) device pointers shared by the whole batch           */
 #define ZM_MODEL_QUADCOPTER 2 /* x+ = x + dt * Quadcopter.inertialDynamics(x,u)  (zopt/quadcopter.py:116-144), n=12, m=4; dt = 0: the derivative */
 #define ZM_MODEL_QUADCOPTER_RB 3 /* same with Quadcopter.rigidBodyDynamics (:70-113), n=8, m=4; wind_ned holds the BODY-frame wind */
-typedef struct zm_model_t {
-    int kind, n, m, reserved;
+/* ZM_MODEL_TRACED: x+ = f(x, u) or f(x, u, p) for a user-written straight-line expression, recorded once on the host (Python:
+ * zopt_amd.models.TracedModel) and evaluated by an interpreter inside the kernels on double, dual and hyper-dual numbers -- the part
+ * jax.jit / jax.jacobian / jax.hessian play for the reference's callables (zopt/ilqrUtils.py:260-269, pytrees.py:139-194).
+ *   tape:  ONE device buffer of 8-byte words: n_const fp64 constants, then n_instr 32-bit instruction words, then n 32-bit output
+ *          slot numbers.  An instruction is  op | a_is_const << 6 | b_is_const << 7 | dst << 8 | a << 16 | b << 24  with op in
+ *          0 add, 1 sub, 2 mul, 3 div, 4 neg, 5 sin, 6 cos, 7 tan, 8 sqrt, 9 mov (unary: a only); dst, a, b index the slot file, an
+ *          operand flagged as a constant the constant table.  Slots 0 .. n-1 hold x, n .. n+m-1 hold u, the next n_params hold p;
+ *          no instruction writes them, and none reads a slot before it is written (the recorder guarantees both; the host entry
+ *          points check the counts and pointers, not the words).
+ *   caps:  n <= 12, m <= 4, n_params <= 8, n_instr <= 1024, n + m + n_params <= n_slots <= 64, n_const <= 256.
+ *   params: (.., n_params) device doubles, row of trajectory t at params + t * param_stride (0: one row shared by the batch); NULL
+ *          when n_params == 0.  Per-problem constants: no derivative is taken with respect to them.
+ *   `reserved` holds the structural mask of zm_model_nonlinear_mask (the variables f is not affine in); no Hessian pairs are declared.
+ * Taken by zm_rollout_linesearch(_list)_f64, zm_linearize_dynamics(_list)_f64, zm_quadratic_dynamics(_list)_f64, zm_model_step_f64
+ * and zm_ilqr_solve(_trace)_f64 (ddp = 0 / 1); ZM_EUNSUPPORTED from the tracking, box, state, packed-pair and MPC entry points. */
+#define ZM_MODEL_TRACED 4
+#define ZM_TRACED_MAX_INSTR 1024
+#define ZM_TRACED_MAX_SLOTS 64
+#define ZM_TRACED_MAX_CONSTS 256
+#define ZM_TRACED_MAX_PARAMS 8
+typedef struct zm_traced_t {    /* 40 bytes, held in the bytes of zm_model_t's A, B and wind_ned (offset 24) when kind == ZM_MODEL_TRACED */
+    const void* tape;
+    const double* params;
+    int64_t param_stride;
+    int32_t n_instr, n_const;
+    int32_t n_slots, n_params;
+} zm_traced_t;
+typedef struct zm_model_t {     /* 64 bytes whatever the kind: every kernel takes the struct by value */
+    int kind, n, m, reserved;   /* reserved: 0; traced: the structural mask (bit i state i, bit n + j control j) */
     double dt;              /* quadcopter: Euler step (demos/iterativeLqr.py:23,35) */
-    const double* A;        /* linear: device pointers; else NULL */
-    const double* B;
+    const double* A;        /* linear: device pointers; else NULL.  traced: A, B and wind_ned are the storage of a zm_traced_t -- */
+    const double* B;        /*   fill it with memcpy(&model.A, &descriptor, sizeof(zm_traced_t)); the fields keep their declarations */
     double wind_ned[3];     /* quadcopter: constant wind in the north-east-down frame (quadcopter.py:117,138; the closed-loop
                                simulation of demos/iterativeLqr.py:48 uses (3,1,0)); zeros for the solvers */
 } zm_model_t;

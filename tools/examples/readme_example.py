@@ -12,3 +12,8 @@ Qt = torch.eye(2, dtype=torch.float64, device="cuda")
 dyn = lambda x, u: x + 0.1 * torch.stack([x[1], -torch.sin(x[0]) + u[0]])
 traj, L, J, converged = iterativeLqr(dyn, lambda x, u: x @ Qt @ x + u @ u, lambda x: 10 * x @ Qt @ x, np.array([3.0, 0.0]), np.zeros((50, 1)))
 print(J, converged, traj.xTraj.shape)
+# the same pendulum as a traced model: plain NumPy, recorded once, interpreted inside the fused HIP kernels
+pend = models.TracedModel(lambda x, u: x + 0.1 * np.array([x[1], -np.sin(x[0]) + u[0]]), 2, 1)
+pcost = models.QuadraticCost(np.eye(2), np.eye(1), 10 * np.eye(2))
+traj2, L2, J2, converged2 = iterativeLqr(pend, pcost, pcost, np.array([3.0, 0.0]), np.zeros((50, 1)))
+print(J2, converged2, abs(J2 - J) / abs(J))

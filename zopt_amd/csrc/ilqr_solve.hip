@@ -454,6 +454,9 @@ static int ilqr_solve_impl(const SolveCall& c) {
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: null pointer");
     if (batch < 0 || T < 1 || c.max_iter < 0 || c.sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
+    if (model->kind == ZM_MODEL_TRACED && (ck.track || ck.box || ck.pen))
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: a traced model takes a zm_quadcost_t and no bounds (tracking cost, input "
+                                              "box and state box on the tape interpreter are not built)");
     if (ck.box) {
         if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
             return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);

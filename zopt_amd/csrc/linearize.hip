@@ -12,6 +12,7 @@
 #include "models.h"
 #include "quad_derivs_gen.h"
 #include "track_cost.h"
+#include "traced.h"
 #include "zm_common.h"
 
 namespace zm {
@@ -354,6 +355,8 @@ static int zm_check_model(const zm_model_t* model, zm_model_t& md, const char* w
         md.m = 4;
     } else if (md.kind == ZM_MODEL_LINEAR) {
         if (!md.A || !md.B) return zm::set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
+    } else if (md.kind == ZM_MODEL_TRACED) {
+        return zm::traced_check(&md, who);
     } else {
         return zm::set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, md.kind);
     }
@@ -378,6 +381,9 @@ extern "C" int zm_linearize_dynamics_list_f64(const zm_model_t* model, const dou
     if (!xTraj || !uTraj || !f_x || !f_u) return zm::set_error(ZM_EINVAL, "zm_linearize_dynamics_f64: null pointer");
     if (batch < 0 || T < 1) return zm::set_error(ZM_EINVAL, "zm_linearize_dynamics_f64: bad size");
     if ((rc = zm_check_list("zm_linearize_dynamics_list_f64", list, count, batch))) return rc;
+    if (md.kind == ZM_MODEL_TRACED)   // the tape on dual numbers (traced.hip)
+        return zm::traced_linearize(md, xTraj, uTraj, (const int*)active, f, f_x, f_u, (long)batch, T, (const int*)list, (long)count,
+                                    (hipStream_t)stream);
     const long npts = (long)(list ? count : batch) * T;
     constexpr int GPB = 4 * zm::LIN_WAVES;   // 16-lane groups per workgroup
     const bool quad = md.kind == ZM_MODEL_QUADCOPTER;
@@ -515,6 +521,15 @@ int expand_list(const zm_model_t* model, const zm_quadcost_t* cost, const double
     if (!cost || !cost->Q || !cost->R || !cost->Qf || !xTraj || !uTraj || !list || !f_x || !f_u || !c_x || !c_u || !v_x)
         return set_error(ZM_EINVAL, "expand_list: null pointer");
     if (batch < 0 || T < 1 || count < 0 || count > batch) return set_error(ZM_EINVAL, "expand_list: bad size");
+    if (md.kind == ZM_MODEL_TRACED) {
+        // the tape on dual numbers, then c_x, c_u, v_x by the cost's own kernel (the same expressions as the fused form below)
+        if (track || packed) return set_error(ZM_EUNSUPPORTED, "expand_list: a traced model takes a zm_quadcost_t and full Jacobians");
+        rc = traced_linearize(md, xTraj, uTraj, (const int*)active, nullptr, f_x, f_u, (long)batch, T, (const int*)list, (long)count,
+                              (hipStream_t)stream);
+        if (rc) return rc;
+        return zm_quadratize_cost_list_f64(cost, md.n, md.m, xTraj, uTraj, list, count, active, nullptr, c_x, c_u, nullptr, v_x, nullptr,
+                                           nullptr, nullptr, nullptr, batch, T, stream);
+    }
     const long npts = (long)count * T;
     constexpr int GPB = 4 * LIN_WAVES;
     const bool quad = md.kind == ZM_MODEL_QUADCOPTER;
@@ -652,11 +667,14 @@ extern "C" int zm_quadratic_dynamics_list_f64(const zm_model_t* model, const dou
     int rc = zm_check_model(model, md, "zm_quadratic_dynamics_f64");
     if (rc) return rc;
     if (!xTraj || !uTraj || !f_xx || (!f_ux != !f_uu)) return zm::set_error(ZM_EINVAL, "zm_quadratic_dynamics_f64: null pointer");
-    if (!f_ux && (zm::model_nonlinear_mask(md) >> md.n) != 0u)
+    if (!f_ux && (zm::traced_or_registered_mask(md, zm::model_nonlinear_mask(md)) >> md.n) != 0u)
         return zm::set_error(ZM_EINVAL, "zm_quadratic_dynamics_f64: f_ux / f_uu may only be omitted for a model that is affine in its "
                                         "controls (zm_model_nonlinear_mask)");
     if (batch < 0 || T < 1) return zm::set_error(ZM_EINVAL, "zm_quadratic_dynamics_f64: bad size");
     if ((rc = zm_check_list("zm_quadratic_dynamics_list_f64", list, count, batch))) return rc;
+    if (md.kind == ZM_MODEL_TRACED)   // the tape on hyper-dual numbers over the pairs of its structural mask (traced.hip)
+        return zm::traced_quadratic(md, xTraj, uTraj, (const int*)active, f_xx, f_ux, f_uu, (long)batch, T, (const int*)list, (long)count,
+                                    (hipStream_t)stream);
     const long npts = (list ? (long)count : (long)batch) * T;
     if (md.kind == ZM_MODEL_QUADCOPTER)   // declares 28 pairs (model_hessian_pairs): two points per wave
         hipLaunchKernelGGL(zm::quadratic_dynamics_kernel<2>, dim3((unsigned)((npts + 1) / 2)), dim3(64), 0, (hipStream_t)stream, md,
@@ -947,7 +965,7 @@ extern "C" int zm_model_nonlinear_mask(const zm_model_t* model, uint32_t* mask) 
     const int rc = zm_check_model(model, md, "zm_model_nonlinear_mask");
     if (rc) return rc;
     if (!mask) return zm::set_error(ZM_EINVAL, "zm_model_nonlinear_mask: null pointer");
-    *mask = zm::model_nonlinear_mask(md);
+    *mask = zm::traced_or_registered_mask(md, zm::model_nonlinear_mask(md));
     return ZM_OK;
 }
 

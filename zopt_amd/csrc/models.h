@@ -94,6 +94,11 @@ __device__ __forceinline__ Hyper ztan(Hyper a) {
     return hyper_fn(a, t, q, 2.0 * t * q);
 }
 
+// square root on the three scalar types (the traced models' interpreter, tape_model.h): d sqrt = 1 / (2 sqrt), d2 sqrt = -1 / (4 x sqrt)
+__device__ __forceinline__ double zsqrt(double a) { return __builtin_sqrt(a); }
+__device__ __forceinline__ Dual zsqrt(Dual a) { const double r = __builtin_sqrt(a.v); return {r, a.d / (2.0 * r)}; }
+__device__ __forceinline__ Hyper zsqrt(Hyper a) { const double r = __builtin_sqrt(a.v), h = 0.5 / r; return hyper_fn(a, r, h, -0.5 * h / a.v); }
+
 // ---- quadcopter (zopt/quadcopter.py) ---------------------------------------------------------------------------
 // state [u,v,w,p,q,r,phi,theta,psi,x,y,z], control [thrust,mx,my,mz]; g = 9.807, mass = 2.5, I = eye(3) (:15-18).
 // rigidBodyDynamics (:70-113): 8 states [u,v,w,p,q,r,phi,theta], wind given in the BODY frame (the aero forces see uvw - wind, :64)

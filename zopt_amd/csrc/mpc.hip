@@ -27,6 +27,7 @@
 // is not certified within max_iter reports "user_limit".
 #include "mpc_common.h"
 #include "models.h"
+#include "traced.h"
 
 #include <cstdlib>
 #include <vector>
@@ -838,6 +839,9 @@ static int mpc_closed_loop(const MpcCall& a) {
 static int mpc_rti_check_model(const char* fn, const char* what, const zm_model_t* model, zm_model_t& md, int n, int m) {
     const int rc = check_model(model, md, fn);
     if (rc != ZM_OK) return rc;
+    if (md.kind == ZM_MODEL_TRACED)
+        return set_error(ZM_EUNSUPPORTED, "%s: the %s is a traced model; the real-time iteration on the tape interpreter is not built", fn,
+                         what);
     if (md.n != n || md.m != m)
         return set_error(ZM_EINVAL, "%s: the %s has (n=%d, m=%d), the problem (n=%d, m=%d)", fn, what, md.n, md.m, n, m);
     if (md.kind != ZM_MODEL_LINEAR && !(md.dt > 0.0)) return set_error(ZM_EINVAL, "%s: the %s needs a step dt > 0", fn, what);
@@ -1156,6 +1160,7 @@ extern "C" int zm_model_step_f64(const zm_model_t* model, const double* x, const
     if (rc != ZM_OK) return rc;
     if (!x || !u || !xNext) return zm::set_error(ZM_EINVAL, "%s: null pointer", fn);
     if (batch < 0 || (batch + 63) / 64 > 0x7fffffffL) return zm::set_error(ZM_EINVAL, "%s: bad size", fn);
+    if (md.kind == ZM_MODEL_TRACED) return zm::traced_step(md, x, u, xNext, (long)batch, (hipStream_t)stream);   // traced.hip
     hipLaunchKernelGGL(zm::mpc_rti_plant_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, md, x, (long)md.n, u,
                        (long)md.m, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, -1.0, xNext, md.n,
                        (double*)nullptr, 0, (long)batch);

@@ -13,6 +13,7 @@
 #include "models.h"
 #include "state_box.h"
 #include "track_cost.h"
+#include "traced.h"
 #include "zm_common.h"
 
 #include <cstdlib>
@@ -254,6 +255,16 @@ static int rollout_impl(const char* who, const zm_model_t* model, const zm_quadc
     if (n_alpha > 1 && !cost) return zm::set_error(ZM_EINVAL, "%s: a line search needs a cost", who);
     zm_model_t md;
     if (const int rc = zm::model_check(model, who, &md)) return rc;
+    if (md.kind == ZM_MODEL_TRACED) {   // the interpreter's kernels (traced.hip): plain cost, no bounds
+        if (track || box || pen || scratch)
+            return zm::set_error(ZM_EUNSUPPORTED, "%s: a traced model takes a zm_quadcost_t and no bounds (tracking cost, input box and "
+                                                  "state box on the tape interpreter are not built)", who);
+        if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
+        if (batch == 0 || (list && count == 0)) return ZM_OK;
+        if (count < 0 || count > batch) return zm::set_error(ZM_EINVAL, "zm_rollout_linesearch: bad list length");
+        return zm::traced_rollout(md, cost, x0, l, L, xPrev, uPrev, alphas, n_alpha, (const int*)active, (const int*)list, (long)count,
+                                  xTraj, uTraj, J, (int*)alpha_idx, (long)batch, T, (hipStream_t)stream);
+    }
     const bool wide = !pen && md.kind == ZM_MODEL_LINEAR && (md.n > zm::MAXN || md.m > zm::MAXM) && md.n >= 1 && md.m >= 1 &&
                       md.n <= 64 && md.m <= 16;   // large linear models: one wave per rollout (rollout_wide.hip)
     if (!wide && (md.n < 1 || md.n > zm::MAXN || md.m < 1 || md.m > zm::MAXM))

@@ -31,16 +31,20 @@ char* last_error_buf();
 int set_error(int code, const char* fmt, ...);
 
 // A registered model as the kernels take it: *md <- *model with (n, m) of its kind (a quadcopter's are fixed: (12, 4), rigid body
-// (8, 4); a linear model's are its own, and it needs A and B).  An unknown kind is refused.  `who`: the entry the message names.
+// (8, 4); a linear model's are its own, and it needs A and B; a traced model's are its own, and its descriptor is checked against the
+// interpreter's caps).  An unknown kind is refused.  `who`: the entry the message names.
 inline zm_model_t model_sized(zm_model_t md) {
     if (md.kind == ZM_MODEL_QUADCOPTER) md.n = 12, md.m = 4;
     if (md.kind == ZM_MODEL_QUADCOPTER_RB) md.n = 8, md.m = 4;
     return md;
 }
+int traced_check(const zm_model_t* model, const char* who);   // traced.hip: counts, pointers and mask of a ZM_MODEL_TRACED descriptor
 inline int model_check(const zm_model_t* model, const char* who, zm_model_t* md) {
     *md = model_sized(*model);
     if (md->kind == ZM_MODEL_LINEAR) {
         if (!md->A || !md->B) return set_error(ZM_EINVAL, "%s: linear model needs A, B", who);
+    } else if (md->kind == ZM_MODEL_TRACED) {
+        return traced_check(md, who);
     } else if (md->kind != ZM_MODEL_QUADCOPTER && md->kind != ZM_MODEL_QUADCOPTER_RB) {
         return set_error(ZM_EUNSUPPORTED, "%s: unknown model kind %d", who, md->kind);
     }

@@ -300,6 +300,8 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
         raise TypeError("dynFun must be a registered device model (zopt_amd.models.LinearModel / QuadcopterEuler) or a torch "
                         "callable f(x, u) -> x+ (generic path, zopt_amd/generic.py)")
     tracking = isinstance(costFun, _models.TrackingCost)
+    if tracking:
+        _models.refuse_traced(dynFun, "forwardPass2 with a TrackingCost", "the tracking line search on the tape interpreter is the follow-up")
     if costFun is not None and not tracking and not hasattr(costFun, "c_struct"):
         raise TypeError("costFun must be a registered zopt_amd.models.QuadraticCost or TrackingCost")
     l, L = _fields(policy)
@@ -320,7 +322,7 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     xT = torch.empty(lead + (N + 1, n), dtype=dt, device=dx0.device)
     uT = torch.empty(lead + (N, m), dtype=dt, device=dx0.device)
     J = torch.empty(lead, dtype=dt, device=dx0.device) if costFun is not None else None
-    md = dynFun.c_struct()
+    md = _models.model_struct(dynFun, lead)
     cs = (costFun.track_struct(lead, N) if tracking else costFun.c_struct()) if costFun is not None else None
     linesearch = _lib.lib().zm_rollout_linesearch_tracking_f64 if tracking else _lib.lib().zm_rollout_linesearch_f64
     pcs = ctypes.addressof(cs) if cs is not None else None
@@ -604,6 +606,9 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     if not hasattr(model, "c_struct"):
         raise TypeError("dynamics must be a registered device model (zopt_amd.models.*) or a torch callable f(x, u) -> x+")
     cost = _registered_cost(runningCost, terminalCost)
+    if isinstance(cost, _models.TrackingCost):                   # (before anything touches the device)
+        _models.refuse_traced(model, "iterativeLqr / differentialDynamicProgramming with a TrackingCost",
+                              "the tracking line search and expansion on the tape interpreter are the follow-up")
     n, m = model.n, model.m
     shp = _shape(uGuess)
     lead, (N, mm) = shp[:-2], shp[-2:]
@@ -619,7 +624,7 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     tracking = isinstance(cost, _models.TrackingCost)
     if tracking and (cost.n != n or cost.m != m):
         raise ValueError(f"the TrackingCost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
-    md, cs = model.c_struct(), (cost.track_struct(tuple(lead), N) if tracking else cost.c_struct())
+    md, cs = _models.model_struct(model, lead), (cost.track_struct(tuple(lead), N) if tracking else cost.c_struct())
     i32 = torch.int32
     L = torch.empty((B, N, m, n), dtype=dt, device=dev)
     xT = torch.empty((B, N + 1, n), dtype=dt, device=dev)

@@ -16,6 +16,7 @@ from . import _arrays as arr
 ZM_MODEL_LINEAR = 1
 ZM_MODEL_QUADCOPTER = 2
 ZM_MODEL_QUADCOPTER_RB = 3
+ZM_MODEL_TRACED = 4
 
 
 class zm_model_t(ctypes.Structure):
@@ -65,6 +66,94 @@ class QuadcopterEuler:
 
     def c_struct(self):
         return zm_model_t(ZM_MODEL_QUADCOPTER, 12, 4, 0, self.dt, None, None, (ctypes.c_double * 3)(*self.wind_ned))
+
+
+class zm_traced_model_t(ctypes.Structure):
+    """zm_model_t as ZM_MODEL_TRACED reads it: the same 64 bytes, the descriptor in place of A, B, wind_ned and the mask in `reserved`"""
+    _fields_ = [("kind", ctypes.c_int), ("n", ctypes.c_int), ("m", ctypes.c_int), ("mask", ctypes.c_int),
+                ("dt", ctypes.c_double), ("tape", ctypes.c_void_p), ("params", ctypes.c_void_p), ("param_stride", ctypes.c_int64),
+                ("n_instr", ctypes.c_int32), ("n_const", ctypes.c_int32), ("n_slots", ctypes.c_int32), ("n_params", ctypes.c_int32)]
+
+
+class TracedModel:
+    """x+ = f(x, u) or f(x, u, p) for a user-written `f`: the callable is recorded ONCE on NumPy object arrays of recording scalars
+    (zopt_amd/tape.py: `+ - * /`, unary minus, `** k`, np.sin / cos / tan / sqrt; no branches on the data) and the recording is
+    evaluated by an interpreter inside the rollout, line-search, expansion and plant kernels on double, dual and hyper-dual numbers --
+    the part jax.jit / jax.jacobian / jax.hessian play for the reference's callables (ilqrUtils.py:260-269).
+
+    n, m: state and control dimensions (n <= 12, m <= 4).  params: None, (np,) -- one row shared by the batch -- or (..., np) with
+    leading axes that broadcast to the batch of the call (as TrackingCost.xRef): per-problem constants, np <= 8; no derivative is
+    taken with respect to them.  At most 1024 instructions, 64 live slots (inputs included) and 256 constants: ValueError beyond.
+
+    Accepted wherever a registered model is by `iterativeLqr`, `differentialDynamicProgramming`, `forwardPass2`, `trajectoryRollout`,
+    the simulator, `AffineDynamics` / `QuadraticDynamics` `.from_function` / `.from_trajectory` and `mpcUtils.modelStep`, with a
+    `QuadraticCost`.  Not yet with a `TrackingCost`, inside an `InputBox` / `StateBox`, or in `ltvMpc.fromModel / relinearize /
+    realTimeIteration`: those refuse it.  Called with numeric arrays it evaluates `f`."""
+
+    def __init__(self, f, n, m, params=None):
+        from . import tape as _tape
+        if not callable(f):
+            raise TypeError("TracedModel: f must be a callable f(x, u) or f(x, u, p)")
+        self.f, self.n, self.m = f, int(n), int(m)
+        self.params = None
+        if params is not None:
+            self.params = params if arr.is_torch(params) else np.asarray(params, dtype=np.float64)
+            if len(self.params.shape) < 1 or self.params.shape[-1] < 1:
+                raise ValueError(f"TracedModel: params has shape {tuple(self.params.shape)}, expected (np,) or (..., np)")
+        self.n_params = 0 if self.params is None else int(self.params.shape[-1])
+        self.tape = _tape.record(f, self.n, self.m, self.n_params)
+        self._dev = {}
+
+    def __call__(self, x, u, p=None):
+        if self.n_params:
+            if p is None:
+                p = self.params.detach().cpu().numpy() if arr.is_torch(self.params) else self.params
+                if p.ndim != 1:
+                    raise ValueError("TracedModel: pass the parameter row p of this point (params has batch axes)")
+            return self.f(x, u, p)
+        return self.f(x, u)
+
+    def c_struct(self, lead=None):
+        """zm_model_t of kind ZM_MODEL_TRACED for a call with batch axes `lead` (None: a model without per-trajectory params)"""
+        import torch
+        from . import tape as _tape
+        t = self.tape
+        pdev, stride = None, 0
+        if self.n_params and lead is None and not all(int(d) == 1 for d in tuple(self.params.shape)[:-1]):
+            raise ValueError("TracedModel: params has batch axes; this call has no batch to match them with")   # (before the device)
+        if self.n_params:
+            shp = tuple(int(d) for d in self.params.shape)
+            if all(d == 1 for d in shp[:-1]):
+                key = "shared"
+                if key not in self._dev:
+                    self._dev[key] = arr.to_device(self.params, torch.float64).reshape(self.n_params).contiguous()
+            else:
+                key = tuple(int(d) for d in lead)
+                if key not in self._dev:
+                    full = key + (self.n_params,)
+                    if len(shp) > len(full) or any(a != 1 and a != b for a, b in zip(shp[::-1], full[::-1])):
+                        raise ValueError(f"TracedModel: leading axes {shp[:-1]} of params do not broadcast to the batch {key}")
+                    self._dev[key] = arr.to_device(self.params, torch.float64).expand(full).reshape(-1, self.n_params).contiguous()
+                stride = self.n_params
+            pdev = self._dev[key]
+        if "blob" not in self._dev:
+            self._dev["blob"] = arr.to_device(_tape.blob(t).view(np.float64), torch.float64)
+        blob = self._dev["blob"]
+        st = zm_traced_model_t(ZM_MODEL_TRACED, self.n, self.m, t.mask, 0.0, blob.data_ptr(), None if pdev is None else pdev.data_ptr(),
+                               stride, len(t.code), len(t.consts), t.n_slots, self.n_params)
+        st._owner = (self, blob, pdev)      # raw device addresses: keep the arrays behind them alive with the struct
+        return st
+
+
+def model_struct(model, lead):
+    """c_struct() of a registered model for a call with batch axes `lead` (a TracedModel's per-trajectory params need them)"""
+    return model.c_struct(tuple(lead)) if isinstance(model, TracedModel) else model.c_struct()
+
+
+def refuse_traced(model, who, follow_up):
+    """The combinations a TracedModel is not built for yet, refused before anything touches the device"""
+    if isinstance(model, TracedModel):
+        raise TypeError(f"{who}: a TracedModel is not supported here yet -- {follow_up}")
 
 
 class QuadraticCost:
@@ -305,6 +394,7 @@ class InputBox:
             raise TypeError("InputBox: the model is an InputBox already")
         if isinstance(model, StateBox):
             raise TypeError("InputBox: a StateBox is the outer wrapper -- write StateBox(InputBox(model, u_lb, u_ub), x_lb, x_ub)")
+        refuse_traced(model, "InputBox", "the box-QP line search and sweeps on the tape interpreter are the follow-up")
         if not hasattr(model, "c_struct"):
             raise TypeError("InputBox wraps a registered device model (zopt_amd.models.*); the generic-callable path has no box: clip "
                             "inside the torch callable there")
@@ -390,6 +480,7 @@ class StateBox:
         if isinstance(model, StateBox):
             raise TypeError("StateBox: the model is a StateBox already")
         inner = model.model if isinstance(model, InputBox) else model
+        refuse_traced(inner, "StateBox", "the augmented-Lagrangian line search on the tape interpreter is the follow-up")
         if not hasattr(inner, "c_struct"):
             raise TypeError("StateBox wraps a registered device model (zopt_amd.models.*) or an InputBox around one; the "
                             "generic-callable path has no state box")

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _arrays as arr
 from . import _lib
+from . import models as _models
 from .pytrees import Trajectory
 
 try:
@@ -958,7 +959,7 @@ def modelStep(model, x, u):
     dx = dx.expand(lead + (n,)).reshape(Bn, n).contiguous()
     du = du.expand(lead + (m,)).reshape(Bn, m).contiguous()
     out = torch.empty((Bn, n), dtype=torch.float64, device=dx.device)
-    cs = model.c_struct()
+    cs = _models.model_struct(model, lead)
     rc = _lib.lib().zm_model_step_f64(ctypes.addressof(cs), dx.data_ptr(), du.data_ptr(), out.data_ptr(), Bn,
                                       ctypes.c_void_p(arr.stream_ptr(dx)))
     _lib.check(rc, "modelStep")
@@ -1014,6 +1015,9 @@ def _model_shape(who, model, want=None, what="model"):
     n, m = getattr(model, "n", None), getattr(model, "m", None)
     if not callable(getattr(model, "c_struct", None)) or n is None or m is None:
         raise ValueError(f"{who}: the {what} must be a registered model (zopt_amd.models), got {type(model).__name__}")
+    if who.startswith("ltvMpc"):      # (before anything touches the device)
+        _models.refuse_traced(model, who, "the relinearisation and plant kernels of the real-time iteration on the tape interpreter "
+                                          "are the follow-up")
     n, m = int(n), int(m)
     if n < 1 or m < 1 or n > 12 or m > 4:
         raise ValueError(f"{who}: the {what} has (n={n}, m={m}), outside the kernels for stage-varying dynamics (n <= 12, m <= 4)")

@@ -46,7 +46,7 @@ def _expand(kind, fun, xTraj, uTraj):
             raise ValueError("xTraj / uTraj batch axes differ")
     B, dev = x.shape[0], x.device
     st = ctypes.c_void_p(arr.stream_ptr(x))
-    cs = fun.track_struct(lead, N, terminal=(kind == "terminal")) if tracking else fun.c_struct()
+    cs = fun.track_struct(lead, N, terminal=(kind == "terminal")) if tracking else _models.model_struct(fun, lead)
     pc = ctypes.addressof(cs)
     lib = _lib.lib()
     E = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
