@@ -6,10 +6,13 @@ array, bit for bit (NaN positions included, dtypes too).
     PYTHONPATH=<parent tree> python tools/ilqr_host_identity.py --out parent.npz
     PYTHONPATH=.             python tools/ilqr_host_identity.py --out branch.npz
     python tools/ilqr_host_identity.py --compare parent.npz branch.npz
+    ... --out x.npz --fallback                                     # the same cases on the product's fallback kernels
+    ZOPT_AMD_LIB=<another build of the library> ... --out x.npz    # two builds of the kernels under one host layer
     PYTHONPATH=<tree> python tools/ilqr_host_identity.py --time     # 200 back-to-back calls of the small linear solve per family: us per call
 """
 import argparse
 import json
+import os
 import sys
 import time
 
@@ -21,10 +24,9 @@ def _spd(rng, lead, k):
     return M @ np.swapaxes(M, -1, -2) / k + np.eye(k)
 
 
-def linear_case(rng):
-    """n=3, m=2, T=6, batch 5: a stable-ish linear model, costs about the origin and about a reference"""
+def linear_case(rng, n=3, m=2, T=6, B=5):
+    """n=3, m=2, T=6, batch 5 unless given: a stable-ish linear model, costs about the origin and about a reference"""
     from zopt_amd import models
-    n, m, T, B = 3, 2, 6, 5
     A = np.eye(n) + 0.1 * rng.standard_normal((n, n))
     Bm = rng.standard_normal((n, m))
     model = models.LinearModel(A, Bm)
@@ -137,7 +139,74 @@ def run_cases():
             step = lambda t: type(t)(*[a[:, 0] for a in tuple.__iter__(t)])   # noqa: E731  (one time step, batch axis kept)
             _put(out, f"{key}.riccatiStep_ilqr", ilqrUtils.riccatiStep_ilqr(step(aff), step(c), v))
             _put(out, f"{key}.riccatiStep_ddp", ilqrUtils.riccatiStep_ddp(step(d), step(c), v))
+    kernel_cases(out, rng)
     return out
+
+
+def kernel_cases(out, rng):
+    """Every instantiation of the sweep, line-search and expansion kernels (ilqr_backward.hip, rollout*.hip, linearize.hip, traced.hip)
+    at least once.  With --fallback the (12, 4) cases run the register-prefetch sweep and the generic line search instead of the
+    LDS-ring sweep and the fast line search."""
+    from zopt_amd import ilqrUtils, lqrUtils, models
+    from zopt_amd.pytrees import AffineDynamics, AffinePolicy, QuadraticCostFunction, Trajectory
+    # sweeps: K-steps 1, 2, 3; T = 1..5 are the five ways through the prefetch loop's tail
+    for n, m in ((3, 2), (6, 3), (12, 4)):
+        for T in (1, 2, 3, 4, 5):
+            dyn, cost, Vf, uT = sweep_operands(rng, (3,), T, n, m)
+            aff = AffineDynamics(*list(tuple.__iter__(dyn))[:3])
+            key = f"kernels.sweep.n{n}m{m}T{T}"
+            _put(out, f"{key}.ilqr", ilqrUtils.backwardPass_ilqr(aff, cost, Vf))
+            _put(out, f"{key}.affine", lqrUtils.bilinearAffineLqr(dyn.f_x, dyn.f_u, dyn.f, cost.c_xx, cost.c_uu, cost.c_ux, cost.c_x, cost.c_u,
+                                                                  cost.c, T))
+            _put(out, f"{key}.ilqr_box", ilqrUtils.backwardPass_ilqr_box(aff, cost, Vf, uT, -0.3, 0.4))
+            _put(out, f"{key}.ddp", ilqrUtils.backwardPass_ddp(dyn, cost, Vf))
+            _put(out, f"{key}.ddp_box", ilqrUtils.backwardPass_ddp_box(dyn, cost, Vf, uT, -0.3, 0.4))
+    # the penalty sweeps (with and without the input box) and the penalty line search: state-box solves at K-steps 2 and 3
+    for n, m in ((6, 3), (12, 4)):
+        costs, wrappers, x0, ug = linear_case(rng, n, m)
+        for wk in ("sbox", "sbox_ibox"):
+            _put(out, f"kernels.constrained.n{n}m{m}.{wk}", ilqrUtils.constrainedIterativeLqr(wrappers[wk], costs["quad"], costs["quad"], x0, ug, 10, 1e-6))
+    # line search: 1, 3 and 16 step sizes (1, 4 and 16 lanes per trajectory), 70 trajectories (no multiple of the 4, 16, 64 per wave),
+    # trajectory 7 starts at NaN (every cost NaN: the argmin's NaN branch)
+    B, T = 70, 6
+    for name, (n, m) in (("lin", (3, 2)), ("lin12", (12, 4)), ("quad", (12, 4)), ("traced", (3, 2))):
+        costs, wrappers, _, _ = linear_case(rng, n, m, B=B, T=T)
+        if name == "quad":
+            wrappers = {"none": models.QuadcopterEuler(0.1)}
+            wrappers["ibox"] = models.InputBox(wrappers["none"], -0.4, 0.5)
+        if name == "traced":
+            Am, Bm = np.eye(n) + 0.1 * rng.standard_normal((n, n)), rng.standard_normal((n, m))
+            step = lambda x, u: np.array([sum(Am[i, j] * x[j] for j in range(n)) + sum(Bm[i, j] * u[j] for j in range(m))   # noqa: E731
+                                          + 0.01 * np.sin(x[i]) for i in range(n)])
+            wrappers = {"none": models.TracedModel(step, n, m)}
+            costs = {"quad": costs["quad"]}
+        x0 = rng.standard_normal((B, n))
+        x0[7] = np.nan
+        pol = AffinePolicy(0.1 * rng.standard_normal((B, T, m)), 0.1 * rng.standard_normal((B, T, m, n)))
+        prev = Trajectory(0.2 * rng.standard_normal((B, T + 1, n)), 0.2 * rng.standard_normal((B, T, m)))
+        for wk in ("none", "ibox"):
+            for ck, cost in costs.items():
+                if wk in wrappers:
+                    for na, alphas in ((1, [0.5]), (3, [1.0, 0.5, 0.25]), (16, ilqrUtils.LINESEARCH_ALPHAS)):
+                        _put(out, f"kernels.linesearch.{name}.{wk}.{ck}.na{na}", ilqrUtils._rollout(x0, wrappers[wk], pol, prev, alphas, cost))
+    # expansions: a generic model and the quadcopter in still air and wind, with and without a reference; the solves above and below run
+    # the fused (cost) forms, the from_trajectory calls the plain ones
+    for name, model in (("lin", linear_case(rng)[1]["none"]), ("still", models.QuadcopterEuler(0.1)),
+                        ("wind", models.QuadcopterEuler(0.1, (1.0, -0.5, 0.2)))):
+        n, m, B, T = model.n, model.m, 3, 5
+        traj = Trajectory(0.3 * rng.standard_normal((B, T + 1, n)), 0.3 * rng.standard_normal((B, T, m)))
+        Q, R, Qf = _spd(rng, (), n), _spd(rng, (), m), _spd(rng, (), n)
+        costs = {"quad": models.QuadraticCost(Q, R, Qf), "diag": models.QuadraticCost(np.diag(np.diag(Q)), np.diag(np.diag(R)), np.diag(np.diag(Qf))),
+                 "track": models.TrackingCost(Q, R, Qf, 0.3 * rng.standard_normal((B, T + 1, n)), 0.1 * rng.standard_normal(m))}
+        _put(out, f"kernels.expand.{name}.affine", AffineDynamics.from_trajectory(model, traj))
+        for ck, cost in costs.items():
+            _put(out, f"kernels.expand.{name}.{ck}.cost", QuadraticCostFunction.from_trajectory(cost, traj))
+            if name != "lin":
+                x0 = np.zeros((B, 12))
+                x0[:, 9:12] = rng.uniform(-1, 1, (B, 3))
+                ug = np.tile(np.asarray(models.QuadcopterEuler.uTrim, dtype=np.float64), (B, T, 1)) + 0.05 * rng.standard_normal((B, T, 4))
+                _put(out, f"kernels.expand.{name}.{ck}.iterativeLqr", ilqrUtils.iterativeLqr(model, cost, cost, x0, ug, 4, 1e-4))
+                _put(out, f"kernels.expand.{name}.{ck}.ddp", ilqrUtils.differentialDynamicProgramming(model, cost, cost, x0, ug, 4, 1e-4))
 
 
 def compare(a_path, b_path):
@@ -182,7 +251,12 @@ def main():
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two such files")
     ap.add_argument("--time", action="store_true", help="the host-bound loop: us per call of the small linear solve, per family")
     ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--fallback", action="store_true", help="run the cases on the product's fallback kernels (ZOPT_AMD_ILQR_PATH=reg, "
+                                                            "ZOPT_AMD_ROLLOUT_PATH=generic): the (12, 4) shapes then reach the register-prefetch "
+                                                            "sweep and the generic line search")
     args = ap.parse_args()
+    if args.fallback:   # read once per process by the library
+        os.environ.update(ZOPT_AMD_ILQR_PATH="reg", ZOPT_AMD_ROLLOUT_PATH="generic")
     if args.compare:
         return compare(*args.compare)
     if args.time:

@@ -32,6 +32,13 @@ __device__ __forceinline__ QuadAtoms quad_atoms(const zm_model_t& md, const doub
     return a;
 }
 
+// a if FIRST, else b (two arrays of different lengths: the one not picked need not exist at full size)
+template <bool FIRST, class A, class B>
+__device__ __forceinline__ constexpr const auto& pick(const A& a, const B& b) {
+    if constexpr (FIRST) return a;
+    else return b;
+}
+
 // Optional fused cost expansion (the solvers' per-iteration call, zm::expand_list): the lane of variable j also writes
 // c_x[j] = ((Q + Q^T) x)[j] resp. c_u[j - n] = ((R + R^T) u)[j - n] of its point, and the lanes of a trajectory's last point the
 // terminal gradient v_x = (Qf + Qf^T) x_T -- the same expressions, in the same order, as quadratize_cost_kernel.
@@ -54,15 +61,149 @@ constexpr int LIN_WAVES = 4;
 // (quad_derivs_gen.h: 56 per point in still air, 59 (+1 pad) with wind; everything else is the identity's 0 or 1) -- 448 B per point
 // instead of 1 536 B; `f_u` is not written.  The solvers' sweeps read this form (ilqr_backward_dma_f64<..., NJP>).
 //
-// The kernel's body is linearize_dynamics_body.h, #included into the kernel below and into its tracking twin.
-// The tracking cost's hooks in the kernel bodies below (linearize_dynamics_body.h, expand_quad_points_body.h): what the cost gradients
-// are taken of -- the point itself, or its difference from the reference rows of trajectory id `traj` (formed first; the same
-// expressions then run on it).
-#define ZM_TRK_POINT(nn, mm)
-#define ZM_TRK_TERMINAL
-#define ZM_CX(i) xv[i]
-#define ZM_CU(i) uv[i]
-#define ZM_XT(i) xT[i]
+// TRK (COST): the cost gradients are taken of the point's difference from the reference rows of trajectory id `traj` (formed first;
+// the same expressions then run on it) instead of the point itself.
+template <bool COST, bool QUAD, bool WIND, bool PACKED, bool TRK>
+__device__ __forceinline__ void linearize_points(const zm_model_t& md, const double* __restrict__ xTraj, const double* __restrict__ uTraj,
+                                                 const int* __restrict__ active, double* __restrict__ f, double* __restrict__ f_x,
+                                                 double* __restrict__ f_u, const long batch, const int T, const int* __restrict__ list,
+                                                 const long count, const ExpandCost& ec, const TrackRef& tr) {
+    static_assert(COST || !TRK, "the reference belongs to the fused cost expansion");
+    // one point's [f_x (n, n) | f_u (n, m)] image per 16-lane group: the columns the lanes computed are transposed here so that the
+    // group stores whole 128-byte lines instead of column-strided 8-byte pieces
+    __shared__ double tile[4 * LIN_WAVES][MAXN * (MAXN + MAXM)];
+    const int lane = threadIdx.x;
+    const int j = lane & 15;                                   // seed direction / Jacobian column
+    const int q = lane >> 4;                                   // group of this workgroup
+    const long gi = (long)blockIdx.x * (4 * LIN_WAVES) + q;    // slot * T + k; slots are the listed trajectories, or all of them
+    const long nslot = list ? count : batch;
+    if (gi >= nslot * T) return;
+    const long slot = gi / T;
+    const int k = (int)(gi - slot * T);
+    const long traj = list ? (long)list[slot] : slot;
+    const int n = QUAD ? 12 : md.n, m = QUAD ? 4 : md.m;   // (compile-time in the quadcopter variant)
+    const long pt = traj * T + k;                              // point index
+    double xv[MAXN], uv[MAXM];
+    const double* xk = xTraj + (traj * (T + 1) + k) * n;
+    {   // the point's loads go out together with the mask's
+        const double* uk = uTraj + pt * m;
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) xv[i] = (i < n) ? xk[i] : 0.0;
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i) uv[i] = (i < m) ? uk[i] : 0.0;
+    }
+    if (active && active[traj] == 0) return;
+    // (the cost part first: its weight loads leave with the state's, ahead of the LDS exchange below -- a compiler barrier)
+    if constexpr (COST) {
+        const zm_quadcost_t& cs = ec.cs;
+        double ex[TRK ? MAXN : 1], eu[TRK ? MAXM : 1];   // the differences from the reference: only the tracking kernels have them
+        if constexpr (TRK) {
+            track_diff(ex, xv, track_xrow(tr, traj, k), n);
+            track_diff(eu, uv, track_urow(tr, traj, k), m);
+        }
+        const auto& cx = pick<TRK>(ex, xv);   // what the gradients are formed on
+        const auto& cu = pick<TRK>(eu, uv);
+        if (j < n) {
+            double g;
+            if (cs.diagonal == 1) {
+                double xj = 0.0;
+#pragma unroll
+                for (int i = 0; i < MAXN; ++i) xj = (i == j) ? cx[i] : xj;
+                g = (cs.Q[j * n + j] + cs.Q[j * n + j]) * xj;
+            } else {
+                g = 0.0;
+#pragma unroll
+                for (int i = 0; i < MAXN; ++i)
+                    if (i < n) g = __builtin_fma(cs.Q[j * n + i] + cs.Q[i * n + j], cx[i], g);
+            }
+            ec.c_x[pt * n + j] = g;
+            if (k == T - 1) {   // terminal gradient from x_T
+                const double* xT = xk + n;
+                const double* rT = TRK ? track_xrow(tr, traj, T) : nullptr;
+                const auto xt = [&](const int i) { return rT ? xT[i] - rT[i] : xT[i]; };
+                double gv;
+                if (cs.diagonal == 1) {
+                    gv = (cs.Qf[j * n + j] + cs.Qf[j * n + j]) * xt(j);
+                } else {
+                    gv = 0.0;
+                    for (int i = 0; i < n; ++i) gv = __builtin_fma(cs.Qf[j * n + i] + cs.Qf[i * n + j], xt(i), gv);
+                }
+                ec.v_x[traj * n + j] = gv;
+            }
+        } else if (j < n + m) {
+            const int ju = j - n;
+            double g;
+            if (cs.diagonal == 1) {
+                double uj = 0.0;
+#pragma unroll
+                for (int i = 0; i < MAXM; ++i) uj = (i == ju) ? cu[i] : uj;
+                g = (cs.R[ju * m + ju] + cs.R[ju * m + ju]) * uj;
+            } else {
+                g = 0.0;
+#pragma unroll
+                for (int i = 0; i < MAXM; ++i)
+                    if (i < m) g = __builtin_fma(cs.R[ju * m + i] + cs.R[i * m + ju], cu[i], g);
+            }
+            ec.c_u[pt * m + ju] = g;
+        }
+    }
+    if constexpr (PACKED) {
+        static_assert(QUAD, "packed Jacobians: the quadcopter's closed forms");
+        constexpr int NJ = WIND ? QUAD_NJ_WIND : QUAD_NJ_STILL, NJP = (NJ + 1) & ~1;
+        const QuadAtoms a = quad_atoms(md, xv, uv);
+        if (NJP != NJ && j == 0) tile[q][NJP - 1] = 0.0;
+        quad_jac_column_packed<WIND>(j, a, md.dt, tile[q]);
+        wave_lds_sync();
+        double* op = f_x + pt * NJP;
+        for (int e = j; e < NJP; e += 16) op[e] = tile[q][e];
+        return;
+    }
+    double col[MAXN];                                      // column j of [f_x | f_u] (lanes j >= n + m: unused)
+    if constexpr (QUAD) {
+        // closed-form column j of d xd / d z (generated, quad_derivs_gen.h): the trigonometric values once, a few operations
+        // per entry -- instead of the whole model on dual numbers per column.  x+ = x + dt xd  =>  column of [f_x | f_u] =
+        // e_j + dt d xd  (dt = 0: the derivative of xd itself, as model_step defines that case).
+        const QuadAtoms a = quad_atoms(md, xv, uv);
+        double o[12];
+        quad_jac_column<WIND>(j, a, o);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) col[i] = (md.dt == 0.0) ? o[i] : __builtin_fma(md.dt, o[i], (i == j) ? 1.0 : 0.0);
+        if (f && j == 0) {   // model_step's quadcopter branch, spelled out (the generic call drags the linear model's A, B loads
+                             // into this loop as invariants)
+            double xd[12];
+            quad_inertial_dynamics<double>(xv, uv, md.wind_ned, xd);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) f[pt * 12 + i] = (md.dt == 0.0) ? xd[i] : xv[i] + md.dt * xd[i];
+        }
+    } else {
+        Dual x[MAXN], u[MAXM], xn[MAXN];
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) x[i] = Dual{xv[i], (i == j) ? 1.0 : 0.0};
+#pragma unroll
+        for (int i = 0; i < MAXM; ++i) u[i] = Dual{uv[i], (n + i == j) ? 1.0 : 0.0};
+        model_step<Dual>(md, x, u, xn);
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i) col[i] = xn[i].d;
+        if (f && j == 0) {
+#pragma unroll
+            for (int i = 0; i < MAXN; ++i)
+                if (i < n) f[pt * n + i] = xn[i].v;
+        }
+    }
+    if (j < n + m) {
+        double* t = tile[q] + ((j < n) ? j : n * n + (j - n));
+        const int st = (j < n) ? n : m;
+#pragma unroll
+        for (int i = 0; i < MAXN; ++i)
+            if (i < n) t[i * st] = col[i];
+    }
+    wave_lds_sync();
+    double* ox = f_x + pt * n * n;
+    double* ou = f_u + pt * n * m;
+    for (int e = j; e < n * n; e += 16) ox[e] = tile[q][e];
+    for (int e = j; e < n * m; e += 16) ou[e] = tile[q][n * n + e];
+}
+
 template <bool COST, bool QUAD, bool WIND = false, bool PACKED = false>
 __global__ __launch_bounds__(64 * LIN_WAVES, 3) void linearize_dynamics_kernel(const zm_model_t md, const double* __restrict__ xTraj,
                                                                 const double* __restrict__ uTraj,
@@ -70,22 +211,8 @@ __global__ __launch_bounds__(64 * LIN_WAVES, 3) void linearize_dynamics_kernel(c
                                                                 double* __restrict__ f_x, double* __restrict__ f_u,
                                                                 const long batch, const int T,
                                                                 const int* __restrict__ list, const long count, const ExpandCost ec) {
-#include "linearize_dynamics_body.h"
+    linearize_points<COST, QUAD, WIND, PACKED, false>(md, xTraj, uTraj, active, f, f_x, f_u, batch, T, list, count, ec, TrackRef{});
 }
-#undef ZM_TRK_POINT
-#undef ZM_TRK_TERMINAL
-#undef ZM_CX
-#undef ZM_CU
-#undef ZM_XT
-#define ZM_TRK_POINT(nn, mm)                                \
-    decltype(xv) ex;                                        \
-    decltype(uv) eu;                                        \
-    track_diff(ex, xv, track_xrow(tr, traj, k), nn);        \
-    track_diff(eu, uv, track_urow(tr, traj, k), mm);
-#define ZM_TRK_TERMINAL const double* rT = track_xrow(tr, traj, T);
-#define ZM_CX(i) ex[i]
-#define ZM_CU(i) eu[i]
-#define ZM_XT(i) (rT ? xT[i] - rT[i] : xT[i])
 // the solvers' expansion (COST) with a tracking cost: ec.cs its weights, tr its reference
 template <bool QUAD, bool WIND = false, bool PACKED = false>
 __global__ __launch_bounds__(64 * LIN_WAVES, 3) void linearize_dynamics_track_kernel(const zm_model_t md, const double* __restrict__ xTraj,
@@ -95,14 +222,8 @@ __global__ __launch_bounds__(64 * LIN_WAVES, 3) void linearize_dynamics_track_ke
                                                                 const long batch, const int T,
                                                                 const int* __restrict__ list, const long count, const ExpandCost ec,
                                                                 const TrackRef tr) {
-    constexpr bool COST = true;
-#include "linearize_dynamics_body.h"
+    linearize_points<true, QUAD, WIND, PACKED, true>(md, xTraj, uTraj, active, f, f_x, f_u, batch, T, list, count, ec, tr);
 }
-#undef ZM_TRK_POINT
-#undef ZM_TRK_TERMINAL
-#undef ZM_CX
-#undef ZM_CU
-#undef ZM_XT
 
 // quadratic_dynamics: the unordered derivative pairs (a, b) that can be nonzero are spread over the lanes, each evaluated once on
 // hyper-dual numbers seeded e_a, e_b; every other entry is zero.  PPW points per wave: 2 when the model declares at most 32 pairs
@@ -296,8 +417,77 @@ __global__ __launch_bounds__(64 * LIN_WAVES) void quad_hessian_pairs16_kernel(co
 }
 
 // one thread per (trajectory, step) point plus one per trajectory for the terminal expansion
-#define ZM_TRK_DIFF_X
-#define ZM_TRK_DIFF_U
+// TRK: a tracking cost (cs its weights, tr its reference): x, u become the differences x_k - xr_k (x_T - xr_T), u_k - ur_k first
+template <bool TRK>
+__device__ __forceinline__ void quadratize_cost_point(const zm_quadcost_t& cs, const TrackRef& tr, const int n, const int m,
+                                                      const double* __restrict__ xTraj, const double* __restrict__ uTraj,
+                                                      const int* __restrict__ active, double* __restrict__ c, double* __restrict__ c_x,
+                                                      double* __restrict__ c_u, double* __restrict__ v, double* __restrict__ v_x,
+                                                      const long batch, const int T, const int* __restrict__ list, const long count) {
+    const long sid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nslot = list ? count : batch;
+    const long npts = nslot * T;
+    if (sid >= npts + nslot) return;
+    const bool terminal = sid >= npts;
+    const long slot = terminal ? (sid - npts) : (sid / T);
+    const long traj = list ? (long)list[slot] : slot;
+    if (active && active[traj] == 0) return;
+    const int k = terminal ? T : (int)(sid - slot * T);
+    const long id = traj * T + k;                              // point index (unused for the terminal expansion)
+    const double* xk = xTraj + (traj * (T + 1) + k) * n;
+    double x[MAXN], u[MAXM];
+#pragma unroll
+    for (int i = 0; i < MAXN; ++i) x[i] = (i < n) ? xk[i] : 0.0;
+    if constexpr (TRK) track_diff(x, x, track_xrow(tr, traj, k), n);
+    const double* Qm = terminal ? cs.Qf : cs.Q;
+    double* gx = terminal ? (v_x ? v_x + traj * n : nullptr) : (c_x ? c_x + id * n : nullptr);
+    if (gx) {
+        if (cs.diagonal == 1) {   // asserted diagonal weights: the n^2 - n vanishing terms of (Q + Q^T) x are not formed
+#pragma unroll
+            for (int jj = 0; jj < MAXN; ++jj)
+                if (jj < n) gx[jj] = (Qm[jj * n + jj] + Qm[jj * n + jj]) * x[jj];
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < MAXN; ++jj) {
+                if (jj < n) {
+                    double s = 0.0;   // ((Q + Q^T) x)[jj]
+#pragma unroll
+                    for (int i = 0; i < MAXN; ++i)
+                        if (i < n) s = __builtin_fma(Qm[jj * n + i] + Qm[i * n + jj], x[i], s);
+                    gx[jj] = s;
+                }
+            }
+        }
+    }
+    if (terminal) {
+        if (v) v[traj] = terminal_cost(cs, n, x);
+        return;
+    }
+    const double* uk = uTraj + id * m;
+#pragma unroll
+    for (int i = 0; i < MAXM; ++i) u[i] = (i < m) ? uk[i] : 0.0;
+    if constexpr (TRK) track_diff(u, u, track_urow(tr, traj, k), m);
+    if (c_u) {
+        if (cs.diagonal == 1) {
+#pragma unroll
+            for (int jj = 0; jj < MAXM; ++jj)
+                if (jj < m) c_u[id * m + jj] = (cs.R[jj * m + jj] + cs.R[jj * m + jj]) * u[jj];
+        } else {
+#pragma unroll
+            for (int jj = 0; jj < MAXM; ++jj) {
+                if (jj < m) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int i = 0; i < MAXM; ++i)
+                        if (i < m) s = __builtin_fma(cs.R[jj * m + i] + cs.R[i * m + jj], u[i], s);
+                    c_u[id * m + jj] = s;
+                }
+            }
+        }
+    }
+    if (c) c[id] = running_cost(cs, n, m, x, u);
+}
+
 __global__ __launch_bounds__(256) void quadratize_cost_kernel(const zm_quadcost_t cs, const int n, const int m,
                                                               const double* __restrict__ xTraj,
                                                               const double* __restrict__ uTraj,
@@ -306,13 +496,8 @@ __global__ __launch_bounds__(256) void quadratize_cost_kernel(const zm_quadcost_
                                                               double* __restrict__ v, double* __restrict__ v_x,
                                                               const long batch, const int T, const int* __restrict__ list,
                                                               const long count) {
-#include "quadratize_cost_body.h"
+    quadratize_cost_point<false>(cs, TrackRef{}, n, m, xTraj, uTraj, active, c, c_x, c_u, v, v_x, batch, T, list, count);
 }
-#undef ZM_TRK_DIFF_X
-#undef ZM_TRK_DIFF_U
-// ... of a tracking cost (cs its weights, tr its reference): x, u become the differences x_k - xr_k (x_T - xr_T), u_k - ur_k first
-#define ZM_TRK_DIFF_X track_diff(x, x, track_xrow(tr, traj, k), n);
-#define ZM_TRK_DIFF_U track_diff(u, u, track_urow(tr, traj, k), m);
 __global__ __launch_bounds__(256) void quadratize_cost_track_kernel(const zm_quadcost_t cs, const TrackRef tr, const int n, const int m,
                                                                     const double* __restrict__ xTraj,
                                                                     const double* __restrict__ uTraj,
@@ -321,10 +506,8 @@ __global__ __launch_bounds__(256) void quadratize_cost_track_kernel(const zm_qua
                                                                     double* __restrict__ v, double* __restrict__ v_x,
                                                                     const long batch, const int T, const int* __restrict__ list,
                                                                     const long count) {
-#include "quadratize_cost_body.h"
+    quadratize_cost_point<true>(cs, tr, n, m, xTraj, uTraj, active, c, c_x, c_u, v, v_x, batch, T, list, count);
 }
-#undef ZM_TRK_DIFF_X
-#undef ZM_TRK_DIFF_U
 
 __global__ __launch_bounds__(256) void cost_hessians_kernel(const zm_quadcost_t cs, const int n, const int m,
                                                             double* __restrict__ c_xx, double* __restrict__ c_ux,
@@ -438,33 +621,102 @@ constexpr int QP_WAVES = 4;
 // points) and two to four times as many waves overlap: expansion at the full batch 133-142 / 128-132 / 122-127 us for 64 / 32 / 16 rows.
 // 32: the wind forms carry twice the arithmetic.
 constexpr int QP_R = 32;
-#define ZM_TRK_POINT(nn, mm)
-#define ZM_TRK_TERMINAL
-#define ZM_CX(i) xv[i]
-#define ZM_CU(i) uv[i]
-#define ZM_XT(i) xT[i]
+// TRK: a tracking cost (ec.cs its weights, tr its reference), as linearize_points takes it
+template <bool WIND, bool TRK>
+__device__ __forceinline__ void expand_quad_points(const zm_model_t& md, const double* __restrict__ xTraj, const double* __restrict__ uTraj,
+                                                   const int* __restrict__ active, double* __restrict__ f_x, const int T,
+                                                   const int* __restrict__ list, const long nslot, const ExpandCost& ec, const int per,
+                                                   const int nchunk, const TrackRef& tr) {
+    constexpr int NJ = WIND ? QUAD_NJ_WIND : QUAD_NJ_STILL, NJP = (NJ + 1) & ~1;
+    constexpr int LD = NJP + 16 + 1;   // a point's row: packed Jacobians, c_x, c_u; odd, so that the lanes' rows start in different banks
+    extern __shared__ __attribute__((aligned(16))) double qp_lds[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double* tile = qp_lds + (long)wv * QP_R * LD;
+    const long chunk = (long)blockIdx.x * QP_WAVES + wv;
+    if (chunk >= nslot * nchunk) return;
+    const long slot = chunk / nchunk;
+    const int ch = (int)(chunk - slot * nchunk);
+    const long traj = list ? (long)list[slot] : slot;
+    if (active && active[traj] == 0) return;   // (whole wave)
+    const int k0 = ch * per;
+    const int np = (T - k0 < per) ? T - k0 : per;
+    const zm_quadcost_t& cs = ec.cs;
+    if (lane < np) {
+        const int k = k0 + lane;
+        const double* xk = xTraj + (traj * (T + 1) + k) * 12;
+        const double* uk = uTraj + (traj * T + k) * 4;
+        double xv[12], uv[4];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) xv[i] = xk[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) uv[i] = uk[i];
+        double* t = tile + lane * LD;
+        double ex[TRK ? 12 : 1], eu[TRK ? 4 : 1];   // the differences from the reference: only the tracking kernels have them
+        if constexpr (TRK) {
+            track_diff(ex, xv, track_xrow(tr, traj, k), 12);
+            track_diff(eu, uv, track_urow(tr, traj, k), 4);
+        }
+        const auto& cx = pick<TRK>(ex, xv);   // what the gradients are formed on
+        const auto& cu = pick<TRK>(eu, uv);
+        // cost gradients: the expressions of quadratize_cost_kernel / linearize_dynamics_kernel, in their order
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            double g;
+            if (cs.diagonal == 1) {
+                g = (cs.Q[j * 12 + j] + cs.Q[j * 12 + j]) * cx[j];
+            } else {
+                g = 0.0;
+#pragma unroll
+                for (int i = 0; i < 12; ++i) g = __builtin_fma(cs.Q[j * 12 + i] + cs.Q[i * 12 + j], cx[i], g);
+            }
+            t[NJP + j] = g;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double g;
+            if (cs.diagonal == 1) {
+                g = (cs.R[j * 4 + j] + cs.R[j * 4 + j]) * cu[j];
+            } else {
+                g = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) g = __builtin_fma(cs.R[j * 4 + i] + cs.R[i * 4 + j], cu[i], g);
+            }
+            t[NJP + 12 + j] = g;
+        }
+        const QuadAtoms a = quad_atoms(md, xv, uv);
+        if (NJP != NJ) t[NJP - 1] = 0.0;
+        quad_jac_all_packed<WIND>(a, md.dt, t);
+    }
+    if (k0 + np == T && lane < 12) {   // terminal gradient from x_T, one lane per component
+        const double* xT = xTraj + (traj * (T + 1) + T) * 12;
+        const int j = lane;
+        const double* rT = TRK ? track_xrow(tr, traj, T) : nullptr;
+        const auto xt = [&](const int i) { return rT ? xT[i] - rT[i] : xT[i]; };
+        double gv;
+        if (cs.diagonal == 1) {
+            gv = (cs.Qf[j * 12 + j] + cs.Qf[j * 12 + j]) * xt(j);
+        } else {
+            gv = 0.0;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) gv = __builtin_fma(cs.Qf[j * 12 + i] + cs.Qf[i * 12 + j], xt(i), gv);
+        }
+        ec.v_x[traj * 12 + j] = gv;
+    }
+    wave_lds_sync();
+    const long p0 = traj * T + k0;
+    tile_copy_out<NJP, 0, LD>(f_x + p0 * NJP, tile, np * NJP, lane);
+    tile_copy_out<12, NJP, LD>(ec.c_x + p0 * 12, tile, np * 12, lane);
+    tile_copy_out<4, NJP + 12, LD>(ec.c_u + p0 * 4, tile, np * 4, lane);
+}
+
 template <bool WIND>
 __global__ __launch_bounds__(64 * QP_WAVES) void expand_quad_points_kernel(const zm_model_t md, const double* __restrict__ xTraj,
                                                                            const double* __restrict__ uTraj,
                                                                            const int* __restrict__ active, double* __restrict__ f_x,
                                                                            const int T, const int* __restrict__ list, const long nslot,
                                                                            const ExpandCost ec, const int per, const int nchunk) {
-#include "expand_quad_points_body.h"
+    expand_quad_points<WIND, false>(md, xTraj, uTraj, active, f_x, T, list, nslot, ec, per, nchunk, TrackRef{});
 }
-#undef ZM_TRK_POINT
-#undef ZM_TRK_TERMINAL
-#undef ZM_CX
-#undef ZM_CU
-#undef ZM_XT
-#define ZM_TRK_POINT(nn, mm)                                \
-    decltype(xv) ex;                                        \
-    decltype(uv) eu;                                        \
-    track_diff(ex, xv, track_xrow(tr, traj, k), nn);        \
-    track_diff(eu, uv, track_urow(tr, traj, k), mm);
-#define ZM_TRK_TERMINAL const double* rT = track_xrow(tr, traj, T);
-#define ZM_CX(i) ex[i]
-#define ZM_CU(i) eu[i]
-#define ZM_XT(i) (rT ? xT[i] - rT[i] : xT[i])
 // ... with a tracking cost (ec.cs its weights, tr its reference)
 template <bool WIND>
 __global__ __launch_bounds__(64 * QP_WAVES) void expand_quad_points_track_kernel(const zm_model_t md, const double* __restrict__ xTraj,
@@ -473,13 +725,8 @@ __global__ __launch_bounds__(64 * QP_WAVES) void expand_quad_points_track_kernel
                                                                                  const int T, const int* __restrict__ list,
                                                                                  const long nslot, const ExpandCost ec, const int per,
                                                                                  const int nchunk, const TrackRef tr) {
-#include "expand_quad_points_body.h"
+    expand_quad_points<WIND, true>(md, xTraj, uTraj, active, f_x, T, list, nslot, ec, per, nchunk, tr);
 }
-#undef ZM_TRK_POINT
-#undef ZM_TRK_TERMINAL
-#undef ZM_CX
-#undef ZM_CU
-#undef ZM_XT
 
 template <bool WIND>
 static int launch_expand_quad_points(const zm_model_t& md, const double* xTraj, const double* uTraj, const int* active, double* f_x,

@@ -372,20 +372,7 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
     for (int pass = 0; pass < 2; ++pass) {
         const double J = rollout(al, store);
         if (pass == 1) break;
-        double key = live ? J : __builtin_inf();
-        int isn = (live && (J != J)) ? 1 : 0;
-        int who = a;
-#pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) {
-            const double ok = __shfl_xor(key, off);
-            const int on = __shfl_xor(isn, off);
-            const int ow = __shfl_xor(who, off);
-            const bool better = (on > isn) || (on == isn && ((on == 0 && ok < key) || ((on == 1 || ok == key) && ow < who)));
-            key = better ? ok : key;
-            isn = better ? on : isn;
-            who = better ? ow : who;
-        }
-        const int best = who;
+        const int best = argmin_nan_first<16>(live ? J : __builtin_inf(), a);
         const double Jbest = __shfl(J, (grp << 4) + best);
         if (live && a == 0) {
             if (g.J) g.J[t] = Jbest;

@@ -165,19 +165,7 @@ __global__ __launch_bounds__(256) void rollout_quad_all_kernel(const QuadArgs g)
         J += jf;
     }
     // argmin over the 16 step sizes with jnp.argmin semantics (NaN wins, first index on ties); the 4 lanes of a quad agree on J
-    double key = J;
-    int isn = (J != J) ? 1 : 0;
-    int who = a;
-#pragma unroll
-    for (int off = 32; off >= 4; off >>= 1) {
-        const double ok = __shfl_xor(key, off);
-        const int on = __shfl_xor(isn, off);
-        const int ow = __shfl_xor(who, off);
-        const bool better = (on > isn) || (on == isn && ((on == 0 && ok < key) || ((on == 1 || ok == key) && ow < who)));
-        key = better ? ok : key;
-        isn = better ? on : isn;
-        who = better ? ow : who;
-    }
+    const int who = argmin_nan_first<16, 4>(J, a);
     const double Jbest = __shfl(J, who * 4);
     if (lane == 0) {
         g.J[t] = Jbest;

@@ -3,8 +3,8 @@
 // here; ilqr_solve.hip reaches them through those entries).  No existing kernel includes the interpreter: their device code is what
 // it was.
 //
-//   traced_rollout_kernel     zopt/ilqrUtils.py:33-66, :116-150 -- one lane per (trajectory, step size), two passes, the argmin of
-//                             rollout_linesearch_body.h; S = double
+//   traced_rollout_kernel     zopt/ilqrUtils.py:33-66, :116-150 -- one lane per (trajectory, step size), two passes, the line search's
+//                             argmin (zm_common.h: argmin_nan_first); S = double
 //   traced_linearize_kernel   zopt/pytrees.py:139-153 -- 16 lanes per point, lane j seeds direction j; S = Dual
 //   traced_quadratic_kernel   zopt/pytrees.py:180-194 -- the pairs of the structural mask over the lanes of a point; S = Hyper
 //   traced_step_kernel        the plant step of mpcUtils.modelStep -- one lane per instance; S = double
@@ -89,7 +89,7 @@ __device__ __forceinline__ double traced_rollout_one(const zm_model_t& md, SLOTS
     return J;
 }
 
-// NA = lanes per trajectory (1 or 16); the frame and the argmin are rollout_linesearch_body.h's
+// NA = lanes per trajectory (1 or 16); the frame is rollout_linesearch_body.h's, the argmin the shared one (zm_common.h)
 template <int NA, bool LDS>
 __global__ __launch_bounds__(64) void traced_rollout_kernel(const zm_model_t md, const zm_quadcost_t cost, const bool has_cost,
                                                             const double* __restrict__ x0, const double* __restrict__ l,
@@ -124,21 +124,8 @@ __global__ __launch_bounds__(64) void traced_rollout_kernel(const zm_model_t md,
     int best = 0;
     if (NA > 1) {
         if (live) J = traced_rollout_one<false>(md, tf.f, prow, cs, alpha, x0t, lt, Lt, xpt, upt, nullptr, nullptr, T);
-        // argmin over the NA lanes of this trajectory with jnp.argmin semantics: a NaN cost beats every number
-        // (also -inf), the first index wins among equals.  Dead lanes carry (+inf, index NA).
-        double key = live ? J : __builtin_inf();
-        int isn = (live && (J != J)) ? 1 : 0;
-        int who = live ? a : NA;
-#pragma unroll
-        for (int off = NA / 2; off >= 1; off >>= 1) {
-            const double ok = __shfl_xor(key, off);
-            const int on = __shfl_xor(isn, off);
-            const int ow = __shfl_xor(who, off);
-            const bool better = (on > isn) || (on == isn && ((on == 0 && ok < key) || ((on == 1 || ok == key) && ow < who)));
-            key = better ? ok : key;
-            isn = better ? on : isn;
-            who = better ? ow : who;
-        }
+        // dead lanes carry (+inf, index NA)
+        const int who = argmin_nan_first<NA>(live ? J : __builtin_inf(), live ? a : NA);
         best = who < NA ? who : 0;
     }
     // lane 0 of the group re-rolls the winning step size (the same arithmetic) and stores

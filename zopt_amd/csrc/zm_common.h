@@ -149,4 +149,25 @@ __device__ __forceinline__ double sum_xor32(const double v) {
     return x + y;
 }
 
+// The line search's argmin over a group of W lanes (lane ids STRIDE apart) with jnp.argmin semantics: a NaN key beats every number
+// (also -inf), the first index wins among equals.  A lane brings its cost and its index; a dead lane brings +inf, and an index past
+// the live ones where a live +inf must beat it.  Every lane of the group returns the winner's index.
+// (The operands come by reference: by value, the scratch of one rollout_ls_fast_kernel instantiation grew from 28 to 36 bytes.)
+template <int W, int STRIDE = 1>
+__device__ __forceinline__ int argmin_nan_first(const double& cost, const int& index) {
+    double key = cost;
+    int isn = (key != key) ? 1 : 0, who = index;
+#pragma unroll
+    for (int off = W * STRIDE / 2; off >= STRIDE; off >>= 1) {
+        const double ok = __shfl_xor(key, off);
+        const int on = __shfl_xor(isn, off);
+        const int ow = __shfl_xor(who, off);
+        const bool better = (on > isn) || (on == isn && ((on == 0 && ok < key) || ((on == 1 || ok == key) && ow < who)));
+        key = better ? ok : key;
+        isn = better ? on : isn;
+        who = better ? ow : who;
+    }
+    return who;
+}
+
 }  // namespace zm
