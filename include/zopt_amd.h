@@ -918,6 +918,55 @@ int zm_mpc_rti_f64(const zm_model_t* model, const zm_model_t* plant, double* xPl
                    double* states, double* inputs, int32_t* status, int32_t* iters, double* resid, double* xPred, double* uPred,
                    int64_t batch, int N, int n_user, int m_user, int ns, int mc, void* stream);
 
+/* ---- Recorded cost functions (Python: zopt_amd.models.TracedCost): runningCost(x, u[, p]) and terminalCost(x[, p]) as two tapes of the
+ *      ZM_MODEL_TRACED interpreter with ONE output each -- the part the reference's cost callables play (zopt/ilqrUtils.py:260-269,
+ *      pytrees.py:27-55, :72-115).  Both tapes use the input slot layout [x | u | p]; the terminal tape leaves its control slots unread.
+ *      A tape is n_const fp64 constants, n_instr instruction words, then ONE 32-bit output slot number (zero padded to 8 bytes).
+ *      running_mask / terminal_mask: the variables the tape is not affine in (bit i state i, bit n + j control j): only pairs of those
+ *      have second derivatives.  params / param_stride / n_params of each tape: as zm_traced_t (normally the same rows for both).
+ *      Caps: those of zm_traced_t, 1 <= n <= 12, 1 <= m <= 4. */
+typedef struct zm_tracedcost_t {   /* 96 bytes */
+    zm_traced_t running;
+    zm_traced_t terminal;
+    int32_t n, m;
+    uint32_t running_mask, terminal_mask;
+} zm_tracedcost_t;
+
+/* zm_rollout_linesearch_list_f64 with a recorded cost in place of the zm_quadcost_t (list may be NULL: all trajectories; n_alpha is 1 or
+ * up to 16).  Per step: the policy, J += c(x_k, u_k, p) (k ascending, a plain add), the model step (a registered model with n <= 12,
+ * m <= 4, or a traced one); after the last step J += v(x_T, p).  A NaN cost wins the argmin, the first index wins among equals; the
+ * winner is rolled out again with the same arithmetic and stored.  The interpreter's value path has contraction off: the per-step
+ * costs equal a host build's bit for bit. */
+int zm_traced_cost_linesearch_list_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, const double* x0, const double* l,
+                                       const double* L, const double* xPrev, const double* uPrev, const double* alphas, int n_alpha,
+                                       const int32_t* list, int64_t count, const int32_t* active, double* xTraj, double* uTraj,
+                                       double* J, int32_t* alpha_idx, int64_t batch, int T, void* stream);
+/* Second-order expansion of a recorded cost along xTraj (batch,T+1,n), uTraj (batch,T,m): replaces QuadraticCostFunction.from_trajectory
+ * (zopt/pytrees.py:109-115), QuadraticValueFunction.fromTerminalCostFunction (:72-81) and CostFunction.__call__ (:40-55, through c, v).
+ * out: c (batch,T)  c_x (batch,T,n)  c_u (batch,T,m)  c_xx (batch,T,n,n)  c_ux (batch,T,m,n)  c_uu (batch,T,m,m)  v (batch)
+ *      v_x (batch,n)  v_xx (batch,n,n); any may be NULL and is then skipped (c_xx, c_ux, c_uu: all or none).  Values and gradients on
+ *      dual numbers (16 lanes per point, lane j owns entry j of [c_x | c_u]), Hessians on hyper-dual numbers over the unordered pairs of
+ *      the tape's mask, every other entry zero.  list (may be NULL) / active: as zm_linearize_dynamics_list_f64. */
+int zm_traced_cost_expand_list_f64(const zm_tracedcost_t* tcost, const double* xTraj, const double* uTraj, const int32_t* list,
+                                   int64_t count, const int32_t* active, double* c, double* c_x, double* c_u, double* c_xx, double* c_ux,
+                                   double* c_uu, double* v, double* v_x, double* v_xx, int64_t batch, int T, void* stream);
+/* The iLQR (ddp = 0) / DDP (ddp = 1) loop of zm_ilqr_solve_f64 with a recorded cost: the line search above, the model's own expansion
+ * with full Jacobians plus the cost expansion above, the PD projections of zm_condition_cost_f64 / zm_psd_project_f64 applied in every
+ * iteration to the per-point Hessians of the listed trajectories (zopt/ilqrUtils.py:309-313), and the list sweeps with
+ * shared_hessian = 0.  No packed Jacobians, no all-store line search, no ring sweep.  Arguments as zm_ilqr_solve_f64 /
+ * zm_ilqr_solve_trace_f64; the workspace is zm_ilqr_solve_workspace_f64's with the four shared Hessians replaced by per-point arrays of
+ * batch*T*(n*n + m*n + m*m) + batch*n*n doubles (each piece rounded up to an even count) and without the all-store block:
+ * zm_traced_cost_solve_workspace_f64 returns the total, -1 if it cannot. */
+int64_t zm_traced_cost_solve_workspace_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, int64_t batch, int T, int ddp);
+int zm_traced_cost_solve_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, const double* x0, const double* uGuess, int ddp,
+                             int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles, int32_t* iwork,
+                             double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, int32_t* iterations, int64_t batch,
+                             int T, void* stream);
+int zm_traced_cost_solve_trace_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, const double* x0, const double* uGuess, int ddp,
+                                   int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
+                                   int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
+                                   int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,20 @@ SYMBOLS = {
     "zm_psd_project_f64": (ctypes.c_int, [_c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     "zm_condition_cost_f64": (ctypes.c_int, [_c_dp] * 3 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                           ctypes.c_void_p]),
+    # recorded cost (zm_tracedcost_t* in place of zm_quadcost_t*)
+    # (model*, tcost*, x0, l, L, xPrev, uPrev, alphas, n_alpha, list | NULL, count, active, xTraj, uTraj, J, alpha_idx, batch, T, stream)
+    "zm_traced_cost_linesearch_list_f64": (ctypes.c_int, [_c_dp] * 8 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 5 +
+                                           [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (tcost*, xTraj, uTraj, list | NULL, count, active, c, c_x, c_u, c_xx, c_ux, c_uu, v, v_x, v_xx, batch, T, stream)
+    "zm_traced_cost_expand_list_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int64] + [_c_dp] * 10 +
+                                       [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, tcost*, batch, T, ddp); the solves: zm_ilqr_solve_f64's arguments (TRACED_COST_SOLVE_ARGS below)
+    "zm_traced_cost_solve_workspace_f64": (ctypes.c_int64, [_c_dp, _c_dp, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    "zm_traced_cost_solve_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                            ctypes.c_int64] + [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_traced_cost_solve_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
+                                                                  ctypes.c_int64] + [_c_dp] * 7 +
+                                       [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
 }
 
 
@@ -254,6 +268,15 @@ SOLVE_ARGS = {
     "zm_ilqr_solve_box_trace_f64": _SOLVE_BOX + _SOLVE_TRACE,
     "zm_ilqr_solve_state_f64": _SOLVE_STATE,
     "zm_ilqr_solve_state_trace_f64": _SOLVE_STATE + _SOLVE_TRACE + ["violation_trace", "mu_trace"],
+}
+
+
+# the solves with a recorded cost: the plain entries' names with `tcost` in place of `cost` (kept apart from SOLVE_ARGS, which lists the
+# zm_ilqr_solve* entries)
+_TRACED_COST_PLAIN = ["tcost" if k == "cost" else k for k in _SOLVE_PLAIN]
+TRACED_COST_SOLVE_ARGS = {
+    "zm_traced_cost_solve_f64": _TRACED_COST_PLAIN,
+    "zm_traced_cost_solve_trace_f64": _TRACED_COST_PLAIN + _SOLVE_TRACE,
 }
 
 

@@ -20,6 +20,7 @@
 #include "quad_derivs_gen.h"
 #include "state_box.h"
 #include "track_cost.h"
+#include "traced_cost.h"
 #include "zm_common.h"
 
 namespace zm {
@@ -163,12 +164,22 @@ struct IlqrCost : CostRef {
     int32_t* qp_capped = nullptr;
     // state box (zm_ilqr_solve_state_f64; nullptr: none): penalty line search, penalty expansion, sweep with the diagonal addend
     const StatePen* pen = nullptr;
+    // recorded cost (zm_traced_cost_solve_f64; nullptr: none): its own line search and expansion, per-point Hessians conditioned in
+    // every iteration, the list sweeps with shared_hessian = 0; there are then no weights, no box and no penalty
+    const zm_tracedcost_t* traced = nullptr;
 };
+// psd.hip: the projections of zm_condition_cost_f64 / zm_psd_project_f64 over the listed trajectories' per-point Hessians
+int condition_cost_listed(double* c_xx, double* c_ux, double* c_uu, const int* list, long count, int T, int n, int m, double eps,
+                          hipStream_t st);
+int psd_project_listed(double* A, const int* list, long count, int k, double eps, hipStream_t st);
 // the line search of the loop: dense (list == nullptr) or over the id list
 static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const double* x0, const double* l, const double* L,
                            const double* xPrev, const double* uPrev, const double* alphas, int n_alpha, const int32_t* list,
                            int64_t count, const int32_t* active, double* xTraj, double* uTraj, double* J, int32_t* alpha_idx,
                            int64_t batch, int T, void* stream) {
+    if (ck.traced)
+        return zm_traced_cost_linesearch_list_f64(model, ck.traced, x0, l, L, xPrev, uPrev, alphas, n_alpha, list, count, active, xTraj,
+                                                  uTraj, J, alpha_idx, batch, T, stream);
     if (ck.pen)
         return zm_rollout_linesearch_state_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.box, ck.pen->sbox, x0, l, L, xPrev,
                                                     uPrev, alphas, n_alpha, list, count, active, xTraj, uTraj, J, ck.pen->Jcost,
@@ -186,7 +197,9 @@ static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const do
                                      stream);
 }
 
-static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_ux, int npairs) {
+// per_point: the cost Hessians are (batch, T, ...) / (batch, n, n) arrays (a recorded cost) instead of one shared set, and there is no
+// all-store block: the workspace grows by batch*T*(n*n + m*n + m*m) + batch*n*n doubles less the shared set
+static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_ux, int npairs, bool per_point = false) {
     const long n = model->n, m = model->m;
     IlqrWs w;
     long o = 0;
@@ -204,10 +217,10 @@ static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_u
     w.c_x = take(b * T * n);
     w.c_u = take(b * T * m);
     w.v_x = take(b * n);
-    w.c_xx = take(n * n);
-    w.c_ux = take(m * n);
-    w.c_uu = take(m * m);
-    w.v_xx = take(n * n);
+    w.c_xx = take(per_point ? b * T * n * n : n * n);
+    w.c_ux = take(per_point ? b * T * m * n : m * n);
+    w.c_uu = take(per_point ? b * T * m * m : m * m);
+    w.v_xx = take(per_point ? b * n * n : n * n);
     w.alphas = take(16);
     // second derivatives: packed (pairs x n per point) when the model declares its nonzero pairs, else the full tensors
     w.f_xx = ddp ? take(npairs > 0 ? b * T * npairs * n : b * T * n * n * n) : 0;
@@ -217,7 +230,7 @@ static IlqrWs carve(const zm_model_t* model, long b, long T, int ddp, int need_u
     w.where = take((b + 1) / 2); // int32 per trajectory: 0 = newest rows in the caller's xTraj / uTraj, 1 = in xT2 / uT2
     // all-store blocks (16 step sizes x 16 doubles per step and slot: 423 MB at T = 100 for 2048 slots) only for the models whose line
     // search can run in that form -- a windy quadcopter, another model or the generic rollout path never touch them
-    w.tail_slots = rollout_all_store_model_ok(model) ? ilqr_tail_slots(b) : 0;
+    w.tail_slots = (!per_point && rollout_all_store_model_ok(model)) ? ilqr_tail_slots(b) : 0;
     w.scratch = take(w.tail_slots * (T + 1) * 256);
     w.total = o;
     return w;
@@ -252,8 +265,8 @@ static SweepPlan sweep_plan(const zm_model_t* model, const IlqrCost& ck, double*
     const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
     SweepPlan p;
     p.ddp = ddp, p.npairs = npairs;
-    p.packed = !ck.box && !ck.pen && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 && (((uintptr_t)ws) & 15) == 0 &&
-               (!ddp || npairs == 28);
+    p.packed = !ck.box && !ck.pen && !ck.traced && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 &&
+               (((uintptr_t)ws) & 15) == 0 && (!ddp || npairs == 28);
     p.sparse_h = p.packed && ddp && !sparse_off;
     p.f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
     p.f_uu = (need_ux && npairs == 0) ? ws + w.f_uu : nullptr;
@@ -271,6 +284,7 @@ static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model
                           const double* curU, const int32_t* list, int64_t count, const int32_t* active, double* L, int64_t batch, int T,
                           hipStream_t st) {
     const int n = model->n, m = model->m;
+    const int shared = ck.traced ? 0 : 1;   // shared_hessian of the plain sweeps: a recorded cost has per-point Hessians
     int rc = ZM_OK;
     if (p.packed) {
         if (p.sparse_h)
@@ -296,8 +310,8 @@ static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model
                                                           ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count,
                                                           active, 1, ws + w.l, L, ck.qp_capped, batch, T, st);
             return zm_ddp_backward_pairs_list_f64(model, ws + w.f_x, ws + w.f_u, ws + w.f_xx, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                                  ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L,
-                                                  batch, T, st);
+                                                  ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, shared,
+                                                  ws + w.l, L, batch, T, st);
         }
         rc = zm_quadratic_dynamics_list_f64(model, curX, curU, list, count, active, ws + w.f_xx, p.f_ux, p.f_uu, batch, T, st);
         if (rc) return rc;
@@ -306,8 +320,8 @@ static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model
                                                 ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1,
                                                 ws + w.l, L, ck.qp_capped, batch, T, n, m, st);
         return zm_ddp_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.f_xx, p.f_ux, p.f_uu, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
-                                        ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch,
-                                        T, n, m, st);
+                                        ws + w.c_ux, ws + w.c_uu, ws + w.v_x, ws + w.v_xx, list, count, active, shared, ws + w.l, L,
+                                        batch, T, n, m, st);
     }
     if (ck.pen)
         return zm_ilqr_backward_state_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu,
@@ -318,7 +332,7 @@ static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model
                                              ws + w.v_x, ws + w.v_xx, curU, ck.box, list, count, active, 1, ws + w.l, L, ck.qp_capped,
                                              batch, T, n, m, st);
     return zm_ilqr_backward_list_f64(ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, ws + w.v_x,
-                                     ws + w.v_xx, list, count, active, 1, ws + w.l, L, batch, T, n, m, st);
+                                     ws + w.v_xx, list, count, active, shared, ws + w.l, L, batch, T, n, m, st);
 }
 
 // Pool of (pinned int32, event) pairs per device for the drivers' host round trips.
@@ -450,10 +464,13 @@ static int ilqr_solve_impl(const SolveCall& c) {
     double *const xTraj = c.xTraj, *const uTraj = c.uTraj, *const L = c.L, *const J = c.J;
     if (batch == 0) return ZM_OK;
     const zm_quadcost_t* cost = ck.weights();
-    if (!model || !cost || !c.x0 || !c.uGuess || !c.workspace || !c.iwork || !xTraj || !uTraj || !L || !J || !c.converged)
+    if (!model || (!cost && !ck.traced) || !c.x0 || !c.uGuess || !c.workspace || !c.iwork || !xTraj || !uTraj || !L || !J || !c.converged)
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: null pointer");
     if (batch < 0 || T < 1 || c.max_iter < 0 || c.sync_every < 1) return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: bad size");
     const int n = model->n, m = model->m;
+    if (ck.traced && (cost || ck.track || ck.box || ck.pen || n != ck.traced->n || m != ck.traced->m))
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_traced_cost_solve_f64: a recorded cost of the model's (n, m) and nothing else (weights, "
+                                              "input box and state box next to a recorded cost are not built)");
     if (model->kind == ZM_MODEL_TRACED && (ck.track || ck.box || ck.pen))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: a traced model takes a zm_quadcost_t and no bounds (tracking cost, input "
                                               "box and state box on the tape interpreter are not built)");
@@ -476,7 +493,7 @@ static int ilqr_solve_impl(const SolveCall& c) {
         if (rc) return rc;
     }
     const int need_ux = (mask >> n) != 0;   // a model affine in its controls has f_ux = f_uu = 0: neither written nor read
-    const zm::IlqrWs w = zm::carve(model, batch, T, ddp, need_ux, npairs);
+    const zm::IlqrWs w = zm::carve(model, batch, T, ddp, need_ux, npairs, ck.traced != nullptr);
     if (c.workspace_doubles < w.total)
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: workspace of %lld doubles, %lld needed", (long long)c.workspace_doubles,
                              (long long)w.total);
@@ -506,13 +523,16 @@ static int ilqr_solve_impl(const SolveCall& c) {
                                  ck.pen ? active : nullptr, xTraj, uTraj, J, nullptr, batch, T, st);
     if (rc) return rc;
     // trajectory-independent Hessians of the quadratic cost, PD-conditioned once                         (:309-313)
-    rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.c_xx,
-                                ws + w.c_ux, ws + w.c_uu, ws + w.v_xx, 0, T, st);
-    if (rc) return rc;
-    rc = zm_condition_cost_f64(ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, 1, n, m, 1e-3, st);
-    if (rc) return rc;
-    rc = zm_psd_project_f64(ws + w.v_xx, 1, n, 1e-3, st);
-    if (rc) return rc;
+    // (a recorded cost: per-point Hessians, expanded and conditioned in every iteration below)
+    if (!ck.traced) {
+        rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.c_xx,
+                                    ws + w.c_ux, ws + w.c_uu, ws + w.v_xx, 0, T, st);
+        if (rc) return rc;
+        rc = zm_condition_cost_f64(ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, 1, n, m, 1e-3, st);
+        if (rc) return rc;
+        rc = zm_psd_project_f64(ws + w.v_xx, 1, n, 1e-3, st);
+        if (rc) return rc;
+    }
 
     // (a box solve: one-lane two-pass line search and full Jacobians only)
     const bool can_all_store = !ck.box && !ck.pen && w.tail_slots > 0 && zm::rollout_all_store_supported(model, cost, T);
@@ -554,8 +574,16 @@ static int ilqr_solve_impl(const SolveCall& c) {
             ZM_HIP_CHECK(hipEventRecord(count_ready, st));   // only waited for if the pinned word does not show up (wait_for_count)
         }
         // expansions along the current trajectories: [f_x | f_u], c_x, c_u, v_x in one launch                  (:304-313)
-        rc = zm::expand_list(model, cost, curX, curU, list, count, active, ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u,
-                             ws + w.v_x, batch, T, st, plan.packed ? 1 : 0, ck.ref_ptr());
+        // (a recorded cost: the model's own expansion with full Jacobians, then the cost's with its per-point Hessians)
+        if (ck.traced) {
+            rc = zm_linearize_dynamics_list_f64(model, curX, curU, list, count, active, nullptr, ws + w.f_x, ws + w.f_u, batch, T, st);
+            if (rc) return rc;
+            rc = zm_traced_cost_expand_list_f64(ck.traced, curX, curU, list, count, active, nullptr, ws + w.c_x, ws + w.c_u, ws + w.c_xx,
+                                                ws + w.c_ux, ws + w.c_uu, nullptr, ws + w.v_x, ws + w.v_xx, batch, T, st);
+        } else {
+            rc = zm::expand_list(model, cost, curX, curU, list, count, active, ws + w.f_x, ws + w.f_u, ws + w.c_x, ws + w.c_u,
+                                 ws + w.v_x, batch, T, st, plan.packed ? 1 : 0, ck.ref_ptr());
+        }
         if (rc) return rc;
         if (sync_now) {
             int32_t c32 = 0;
@@ -567,6 +595,12 @@ static int ilqr_solve_impl(const SolveCall& c) {
         if (ck.pen) {   // (behind the round trip: the list and its count are this iteration's)
             rc = zm::state_penalty_expand(ck.pen->sbox, curX, list, count, active, ws + w.c_x, ws + w.v_x, ck.pen->h, ck.pen->visits, batch,
                                           T, n, st);
+            if (rc) return rc;
+        }
+        if (ck.traced) {   // the PD projections of the listed trajectories' Hessians, per iteration                 (:312-313)
+            rc = zm::condition_cost_listed(ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, (const int*)list, (long)count, T, n, m, 1e-3, st);
+            if (rc) return rc;
+            rc = zm::psd_project_listed(ws + w.v_xx, (const int*)list, (long)count, n, 1e-3, st);
             if (rc) return rc;
         }
         rc = zm::backward_sweep(plan, ck, model, ws, w, curX, curU, list, count, active, L, batch, T, st);
@@ -654,6 +688,42 @@ extern "C" int zm_ilqr_solve_tracking_f64(const zm_model_t* model, const zm_trac
                                           int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream) {
     return zm_ilqr_solve_tracking_trace_f64(model, cost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork,
                                             xTraj, uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
+}
+
+// A recorded cost (zm_tracedcost_t; traced_cost.hip): the same loop with the cost's own line search and expansion and per-point Hessians.
+extern "C" int64_t zm_traced_cost_solve_workspace_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, int64_t batch, int T, int ddp) {
+    if (!model || !tcost || batch < 0 || T < 1) return -1;
+    uint32_t mask = 0;
+    int32_t npairs = 0;
+    if (ddp && (zm_model_nonlinear_mask(model, &mask) != ZM_OK || zm_model_hessian_pairs(model, nullptr, &npairs) != ZM_OK)) return -1;
+    return zm::carve(model, batch, T, ddp, (mask >> model->n) != 0, npairs, true).total;
+}
+
+extern "C" int zm_traced_cost_solve_trace_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, const double* x0, const double* uGuess,
+                                              int ddp, int max_iter, double tol, int sync_every, double* workspace,
+                                              int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J,
+                                              int32_t* converged, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
+                                              int32_t* alpha_trace) {
+    const char* who = "zm_traced_cost_solve_f64";
+    if (batch == 0) return ZM_OK;
+    if (!model) return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    if (const int rc = zm::tracedcost_check(tcost, who)) return rc;   // (host code: before anything touches the device)
+    zm_model_t md;
+    if (const int rc = zm::model_check(model, who, &md)) return rc;
+    if (md.n != tcost->n || md.m != tcost->m)
+        return zm::set_error(ZM_EINVAL, "%s: the cost is (n=%d, m=%d), the model (n=%d, m=%d)", who, tcost->n, tcost->m, md.n, md.m);
+    SolveCall c{model, {}, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj,
+                L, J, converged, iterations, batch, T, stream, J_trace, alpha_trace};
+    c.ck.traced = tcost;
+    return ilqr_solve_impl(c);
+}
+
+extern "C" int zm_traced_cost_solve_f64(const zm_model_t* model, const zm_tracedcost_t* tcost, const double* x0, const double* uGuess, int ddp,
+                                        int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
+                                        int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
+                                        int32_t* iterations, int64_t batch, int T, void* stream) {
+    return zm_traced_cost_solve_trace_f64(model, tcost, x0, uGuess, ddp, max_iter, tol, sync_every, workspace, workspace_doubles, iwork,
+                                          xTraj, uTraj, L, J, converged, iterations, batch, T, stream, nullptr, nullptr);
 }
 
 // Extension; the reference has no counterpart: the iLQR (ddp = 0) or DDP (ddp = 1) loop with input bounds.

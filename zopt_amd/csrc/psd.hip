@@ -51,6 +51,29 @@ __global__ __launch_bounds__(64) void psd_project_kernel(const Mat M, const int 
 int psd_project_tiled_plain(double* A, int64_t count, int k, double eps, hipStream_t st);
 int psd_project_tiled_cost(double* c_xx, double* c_ux, double* c_uu, int64_t count, int n, int m, double eps, hipStream_t st);
 
+// The launches of zm_condition_cost_f64 / zm_psd_project_f64 with the matrix index mapped through the id list of a solve: the stacked
+// Hessians of the T points of each listed trajectory (c_xx (batch,T,n,n), c_ux (batch,T,m,n), c_uu (batch,T,m,m)), resp. its one
+// terminal Hessian (A (batch,k,k)).  One tile: n + m <= 16, k <= 16 (the caller's shapes: n <= 12, m <= 4).
+int condition_cost_listed(double* c_xx, double* c_ux, double* c_uu, const int* list, long count, int T, int n, int m, double eps,
+                          hipStream_t st) {
+    if (count == 0) return ZM_OK;
+    if (!c_xx || !c_ux || !c_uu || !list) return set_error(ZM_EINVAL, "condition_cost_listed: null pointer");
+    if (count < 0 || T < 1 || n < 1 || m < 1 || n + m > PK || count * T >= (1L << 31)) return set_error(ZM_EINVAL, "condition_cost_listed: bad size");
+    hipLaunchKernelGGL((psd_project_kernel<Listed<StackedCost>>), dim3((unsigned)(count * T)), dim3(64), 0, st,
+                       Listed<StackedCost>{StackedCost{c_xx, c_ux, c_uu, n, m}, list, T}, n + m, eps, count * T);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+int psd_project_listed(double* A, const int* list, long count, int k, double eps, hipStream_t st) {
+    if (count == 0) return ZM_OK;
+    if (!A || !list) return set_error(ZM_EINVAL, "psd_project_listed: null pointer");
+    if (count < 0 || k < 1 || k > PK || count >= (1L << 31)) return set_error(ZM_EINVAL, "psd_project_listed: bad size");
+    hipLaunchKernelGGL((psd_project_kernel<Listed<PlainMat>>), dim3((unsigned)count), dim3(64), 0, st,
+                       Listed<PlainMat>{PlainMat{A, k}, list, 1}, k, eps, count);
+    ZM_HIP_CHECK(hipGetLastError());
+    return ZM_OK;
+}
+
 }  // namespace zm
 
 extern "C" int zm_psd_project_f64(double* A, int64_t count, int k, double eps, void* stream) {

@@ -31,6 +31,21 @@ struct StackedCost {  // [[c_xx, c_ux^T],[c_ux, c_uu]]   (ilqrUtils.py:230)
     }
 };
 
+// The matrices of the LISTED trajectories of a solve (per-point Hessians of a recorded cost: ilqr_solve.hip): matrix q of the launch is
+// matrix q % per of trajectory list[q / per] of the (batch, per, ...) arrays behind M.
+template <class Mat>
+struct Listed {
+    Mat M;
+    const int* list;
+    int per;
+    __device__ __forceinline__ long at(long q) const {
+        const long s = q / per;
+        return (long)list[s] * per + (q - s * per);
+    }
+    __device__ __forceinline__ double load(long q, int i, int j) const { return M.load(at(q), i, j); }
+    __device__ __forceinline__ void store(long q, int i, int j, double v) const { M.store(at(q), i, j, v); }
+};
+
 // vf_zz = sum_l v_x[l] * d2f_l/dz2, stacked as [[vf_xx, vf_ux^T],[vf_ux, vf_uu]]   (ilqrUtils.py:240-247); the projected blocks go
 // to separate outputs (:249)
 struct ContractedDynamics {

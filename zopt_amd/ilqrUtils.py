@@ -294,6 +294,9 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     box = dynFun if isinstance(dynFun, _models.InputBox) else None
     if box is not None:
         dynFun = box.model
+    traced_cost = _models.traced_cost_of(costFun)
+    if traced_cost is not None:       # (before anything touches the device)
+        _models.check_traced_cost(traced_cost, dynFun, "forwardPass2", box=box)
     if _generic.is_callable_model(dynFun):
         return _rollout_generic(x0, dynFun, policy, trajPrev, alphas, costFun)
     if not hasattr(dynFun, "c_struct"):
@@ -302,8 +305,8 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     tracking = isinstance(costFun, _models.TrackingCost)
     if tracking:
         _models.refuse_traced(dynFun, "forwardPass2 with a TrackingCost", "the tracking line search on the tape interpreter is the follow-up")
-    if costFun is not None and not tracking and not hasattr(costFun, "c_struct"):
-        raise TypeError("costFun must be a registered zopt_amd.models.QuadraticCost or TrackingCost")
+    if costFun is not None and not tracking and traced_cost is None and not hasattr(costFun, "c_struct"):
+        raise TypeError("costFun must be a registered zopt_amd.models.QuadraticCost, TrackingCost or TracedCost")
     l, L = _fields(policy)
     xPrev, uPrev = _fields(trajPrev)
     n, m = dynFun.n, dynFun.m
@@ -323,6 +326,14 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     uT = torch.empty(lead + (N, m), dtype=dt, device=dx0.device)
     J = torch.empty(lead, dtype=dt, device=dx0.device) if costFun is not None else None
     md = _models.model_struct(dynFun, lead)
+    if traced_cost is not None:       # the line search with the cost tape next to the model step (list == NULL: every trajectory)
+        cs = traced_cost.tcost_struct(tuple(lead))
+        rc = _lib.lib().zm_traced_cost_linesearch_list_f64(
+            ctypes.addressof(md), ctypes.addressof(cs), dx0.data_ptr(), dl.data_ptr(), dL.data_ptr(), dxp.data_ptr(), dup.data_ptr(),
+            dal.data_ptr(), int(dal.numel()), None, 0, None, xT.data_ptr(), uT.data_ptr(), J.data_ptr(), None, batch, N,
+            ctypes.c_void_p(arr.stream_ptr(dx0)))
+        _lib.check(rc, "rollout")
+        return Trajectory(arr.result_like(xT, L), arr.result_like(uT, L)), arr.result_like(J, L)
     cs = (costFun.track_struct(lead, N) if tracking else costFun.c_struct()) if costFun is not None else None
     linesearch = _lib.lib().zm_rollout_linesearch_tracking_f64 if tracking else _lib.lib().zm_rollout_linesearch_f64
     pcs = ctypes.addressof(cs) if cs is not None else None
@@ -343,6 +354,8 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
 def _torch_costs(runningCost, terminalCost):
     """torch callables (x, u) -> c, (x) -> cf from what the caller passed: torch callables as they are; a registered QuadraticCost (or
     its bound methods) as x'Qx + u'Ru, x'Qf x on device copies of its matrices"""
+    if _models.traced_cost_of(runningCost, terminalCost) is not None:
+        _models.check_traced_cost(_models.traced_cost_of(runningCost, terminalCost), None, "the generic torch-callable path")
     for c in (runningCost, getattr(runningCost, "__self__", None), terminalCost, getattr(terminalCost, "__self__", None)):
         if isinstance(c, _models.TrackingCost):
             raise TypeError("a TrackingCost cannot run on the generic-callable path: its callables carry no stage index, so a reference "
@@ -393,7 +406,8 @@ def trajectoryRollout(x0, dynFun, policy, trajPrev, alpha=1):
 
 def forwardPass2(x0, dynFun, costFun, policy, trajPrev):
     """Simplified iLQR forward pass (reference ilqrUtils.py:116-150): roll out the 16 step sizes 0.5**j and return the
-    trajectory of minimum cost and that cost.  `costFun` is a registered QuadraticCost."""
+    trajectory of minimum cost and that cost.  `costFun` is a registered QuadraticCost or TrackingCost, or a `models.TracedCost` (a
+    recorded cost function: its tape runs next to the model step inside the line-search kernel)."""
     traj, J = _rollout(x0, dynFun, policy, trajPrev, LINESEARCH_ALPHAS, costFun)
     if not arr.is_torch(J) and np.ndim(J) == 0:
         J = float(J)
@@ -467,14 +481,14 @@ def conditionQuadraticDynamics(quadratic_dynamics, v_x):
 
 def _registered_cost(runningCost, terminalCost):
     """Accepts a zopt_amd.models.QuadraticCost or TrackingCost handle (for both arguments) or its bound methods."""
-    kinds = (_models.QuadraticCost, _models.TrackingCost)
+    kinds = (_models.QuadraticCost, _models.TrackingCost, _models.TracedCost)
     for c in (runningCost, getattr(runningCost, "__self__", None)):
         if isinstance(c, kinds):
             other = terminalCost if isinstance(terminalCost, kinds) else getattr(terminalCost, "__self__", None)
             if other is not c:
                 raise TypeError(f"runningCost and terminalCost must come from the same {type(c).__name__}")
             return c
-    raise TypeError("runningCost / terminalCost must be a registered zopt_amd.models.QuadraticCost or TrackingCost (or its "
+    raise TypeError("runningCost / terminalCost must be a registered zopt_amd.models.QuadraticCost, TrackingCost or TracedCost (or its "
                     ".runningCost / .terminalCost methods); arbitrary Python callables cannot run inside a HIP kernel")
 
 
@@ -523,7 +537,9 @@ def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, t
     Arguments
     ---------
         dynamics : registered discrete model `xOut = f(x,u)` (zopt_amd.models.LinearModel / QuadcopterEuler)
-        runningCost, terminalCost : a registered zopt_amd.models.QuadraticCost (the handle, or its two methods)
+        runningCost, terminalCost : a registered zopt_amd.models.QuadraticCost or TrackingCost, or a zopt_amd.models.TracedCost --
+                   user-written cost callables, recorded once (the handle, or its two methods); a TracedCost's Hessians are per
+                   point, expanded and PD-conditioned in every iteration over the trajectories that have not converged
         x0 : (..., n) initial state(s)
         uGuess : (..., N, m) initial guess for the control trajectory
         maxIter : maximum number of iLQR iterations
@@ -601,11 +617,15 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
             raise ValueError("differentialDynamicProgramming takes no InputBox around a LinearModel: a linear model has no second "
                              "derivatives, DDP is iLQR there (use iterativeLqr)")
         model = box.model
+    if _models.traced_cost_of(runningCost, terminalCost) is not None:   # (before anything touches the device)
+        _models.check_traced_cost(_registered_cost(runningCost, terminalCost), model,
+                                  "differentialDynamicProgramming" if ddp else "iterativeLqr", box=box, sbox=sbox)
     if _generic.is_callable_model(model):
         return _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp)
     if not hasattr(model, "c_struct"):
         raise TypeError("dynamics must be a registered device model (zopt_amd.models.*) or a torch callable f(x, u) -> x+")
     cost = _registered_cost(runningCost, terminalCost)
+    traced_cost = isinstance(cost, _models.TracedCost)
     if isinstance(cost, _models.TrackingCost):                   # (before anything touches the device)
         _models.refuse_traced(model, "iterativeLqr / differentialDynamicProgramming with a TrackingCost",
                               "the tracking line search and expansion on the tape interpreter are the follow-up")
@@ -624,7 +644,8 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     tracking = isinstance(cost, _models.TrackingCost)
     if tracking and (cost.n != n or cost.m != m):
         raise ValueError(f"the TrackingCost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
-    md, cs = _models.model_struct(model, lead), (cost.track_struct(tuple(lead), N) if tracking else cost.c_struct())
+    md = _models.model_struct(model, lead)
+    cs = cost.tcost_struct(tuple(lead)) if traced_cost else cost.track_struct(tuple(lead), N) if tracking else cost.c_struct()
     i32 = torch.int32
     L = torch.empty((B, N, m, n), dtype=dt, device=dev)
     xT = torch.empty((B, N + 1, n), dtype=dt, device=dev)
@@ -648,8 +669,11 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         # entries take their cost struct as `cost`; the box and state entries take exactly one of `cost` and `track`.
         family = "state_" if sbox is not None else "box_" if box is not None else "tracking_" if tracking else ""
         entry = f"zm_ilqr_solve_{family}{'trace_' if _TRACE is not None else ''}f64"
+        if traced_cost:               # a recorded cost: the same loop behind its own entries (`tcost` in place of `cost`)
+            entry = f"zm_traced_cost_solve_{'trace_' if _TRACE is not None else ''}f64"
         pmd, pcs = ctypes.addressof(md), ctypes.addressof(cs)
         nws = int(lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N) if sbox is not None else
+                  lib.zm_traced_cost_solve_workspace_f64(pmd, pcs, B, N, 1 if ddp else 0) if traced_cost else
                   lib.zm_ilqr_solve_workspace_f64(pmd, B, N, 1 if ddp else 0))
         if nws < 0:
             raise ValueError("iterativeLqr: cannot size the workspace for this model")
@@ -657,6 +681,7 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         iwork = torch.empty(2 * B + 2, dtype=i32, device=dev)
         its = ctypes.c_int32(0)
         d = {"model": pmd, "cost": None if tracking and family in ("state_", "box_") else pcs, "track": pcs if tracking else None,
+             "tcost": pcs if traced_cost else None,
              "x0": dx0.data_ptr(), "uGuess": dug.data_ptr(), "ddp": 1 if ddp else 0, "max_iter": int(maxIter), "tol": float(tol),
              "sync_every": max(1, int(os.environ.get("ZOPT_AMD_ILQR_SYNC", "4"))), "workspace": ws.data_ptr(),
              "workspace_doubles": nws, "iwork": iwork.data_ptr(), "xTraj": xT.data_ptr(), "uTraj": uT.data_ptr(), "L": L.data_ptr(),
@@ -678,7 +703,7 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
                 vtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
                 mtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
                 d.update(violation_trace=vtr.data_ptr(), mu_trace=mtr.data_ptr())
-        rc = getattr(lib, entry)(*[d[k] for k in _lib.SOLVE_ARGS[entry]])
+        rc = getattr(lib, entry)(*[d[k] for k in (_lib.TRACED_COST_SOLVE_ARGS if traced_cost else _lib.SOLVE_ARGS)[entry]])
         _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
         if _TRACE is not None:
             o = int(its.value)        # iLQR / DDP iterations; outer iterations of a state-box solve

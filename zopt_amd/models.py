@@ -198,6 +198,144 @@ class QuadraticCost:
         return st
 
 
+class zm_traced_t(ctypes.Structure):
+    _fields_ = [("tape", ctypes.c_void_p), ("params", ctypes.c_void_p), ("param_stride", ctypes.c_int64), ("n_instr", ctypes.c_int32),
+                ("n_const", ctypes.c_int32), ("n_slots", ctypes.c_int32), ("n_params", ctypes.c_int32)]
+
+
+class zm_tracedcost_t(ctypes.Structure):
+    _fields_ = [("running", zm_traced_t), ("terminal", zm_traced_t), ("n", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("running_mask", ctypes.c_uint32), ("terminal_mask", ctypes.c_uint32)]
+
+
+class TracedCost:
+    """runningCost(x, u) / terminalCost(x) for user-written callables (optionally with a parameter row: runningCost(x, u, p),
+    terminalCost(x, p)), each returning a scalar: recorded ONCE by the recorder of `TracedModel` (zopt_amd/tape.py: `+ - * /`, unary
+    minus, `** k`, np.sin / cos / tan / sqrt, indexing, np.array, np.concatenate, `@`, np.cross; no branches on the data) and evaluated
+    by the tape interpreter inside the line-search and expansion kernels on double, dual and hyper-dual numbers -- the part the
+    reference's cost callables play (ilqrUtils.py:260-269; demos/iterativeLqr.py:35-36).
+
+    terminalCost=None is the reference's rule (pytrees.py:37): terminalCost(x) = runningCost(x, zeros(m)).  The result of a callable is a
+    recorded scalar, a 0-d array or an array of exactly one element (ValueError otherwise).  params: None, (np,) or (..., np) with
+    leading axes that broadcast to the batch of the call, as `TracedModel.params`: per-problem constants (a goal or an obstacle centre
+    per trajectory), np <= 8, no derivative is taken with respect to them.  Caps per tape: 1024 instructions, 64 live slots (inputs
+    included), 256 constants; n <= 12, m <= 4.
+
+    Accepted -- the handle for both cost arguments, or its two bound methods, as a `QuadraticCost` -- with a registered model
+    (`LinearModel` at n <= 12 and m <= 4, the quadcopters) or a `TracedModel` by `iterativeLqr`, `differentialDynamicProgramming`,
+    `forwardPass2`, `cost(traj)` / `cost(traj, k)`, `QuadraticCostFunction.from_trajectory / from_function` and
+    `QuadraticValueFunction.fromTerminalCostFunction`.  Refused (TypeError, before anything touches the device): together with an
+    `InputBox` or a `StateBox`, on the generic torch-callable path, and with a model of another (n, m)."""
+
+    def __init__(self, runningCost, terminalCost, n, m, params=None):
+        from . import tape as _tape
+        if not callable(runningCost) or not (terminalCost is None or callable(terminalCost)):
+            raise TypeError("TracedCost: runningCost must be a callable c(x, u) or c(x, u, p), terminalCost a callable v(x) or v(x, p) "
+                            "or None")
+        self.n, self.m = int(n), int(m)
+        self.params = None
+        if params is not None:
+            self.params = params if arr.is_torch(params) else np.asarray(params, dtype=np.float64)
+            if len(self.params.shape) < 1 or self.params.shape[-1] < 1:
+                raise ValueError(f"TracedCost: params has shape {tuple(self.params.shape)}, expected (np,) or (..., np)")
+        self.n_params = 0 if self.params is None else int(self.params.shape[-1])
+        self._running = runningCost
+        if terminalCost is None:      # pytrees.py:37
+            zeros = np.zeros(self.m)
+            terminalCost = (lambda x, p: runningCost(x, zeros, p)) if self.n_params else (lambda x: runningCost(x, zeros))
+        self._terminal = terminalCost
+        self.running_tape = _tape.record(self._running, self.n, self.m, self.n_params, n_out=1, who="TracedCost")
+        self.terminal_tape = _tape.record(self._terminal, self.n, self.m, self.n_params, n_out=1, controls=False, who="TracedCost")
+        self._dev = {}
+
+    def _row(self, p):
+        if p is None:
+            p = self.params.detach().cpu().numpy() if arr.is_torch(self.params) else self.params
+            if p.ndim != 1:
+                raise ValueError("TracedCost: pass the parameter row p of this point (params has batch axes)")
+        return p
+
+    def runningCost(self, x, u, p=None):
+        """the callable itself on numeric arrays"""
+        return self._running(x, u, self._row(p)) if self.n_params else self._running(x, u)
+
+    def terminalCost(self, x, p=None):
+        return self._terminal(x, self._row(p)) if self.n_params else self._terminal(x)
+
+    def __call__(self, traj, k=None):
+        """Cost of a trajectory, J = terminalCost(x_N) + sum_k runningCost(x_k, u_k) -- CostFunction.__call__ of the reference
+        (pytrees.py:40-55); with `k`, the running cost at step k only.  Leading batch axes allowed; evaluated on the GPU, the sum in
+        step order."""
+        from .pytrees import _traced_cost_values
+        xT = traj.xTraj if hasattr(traj, "xTraj") else traj[0]
+        uT = traj.uTraj if hasattr(traj, "uTraj") else traj[1]
+        c, v = _traced_cost_values(self, xT, uT)
+        if k is not None:
+            return c[..., k]
+        J = 0.0 + c[..., 0]                           # J = (((0 + c_0) + c_1) + ...) + v: the line search's order
+        for i in range(1, c.shape[-1]):
+            J = J + c[..., i]
+        J = J + v
+        return float(J) if (not hasattr(J, "device") and getattr(J, "ndim", 1) == 0) else J
+
+    def tcost_struct(self, lead=None):
+        """zm_tracedcost_t for a call with batch axes `lead` (None: a cost without per-trajectory params)"""
+        import torch
+        from . import tape as _tape
+        pdev, stride = None, 0
+        if self.n_params:
+            shp = tuple(int(d) for d in self.params.shape)
+            if all(d == 1 for d in shp[:-1]):
+                key = "shared"
+                if key not in self._dev:
+                    self._dev[key] = arr.to_device(self.params, torch.float64).reshape(self.n_params).contiguous()
+            else:
+                if lead is None:
+                    raise ValueError("TracedCost: params has batch axes; this call has no batch to match them with")
+                key = tuple(int(d) for d in lead)
+                if key not in self._dev:
+                    full = key + (self.n_params,)
+                    if len(shp) > len(full) or any(a != 1 and a != b for a, b in zip(shp[::-1], full[::-1])):
+                        raise ValueError(f"TracedCost: leading axes {shp[:-1]} of params do not broadcast to the batch {key}")
+                    self._dev[key] = arr.to_device(self.params, torch.float64).expand(full).reshape(-1, self.n_params).contiguous()
+                stride = self.n_params
+            pdev = self._dev[key]
+        if "blobs" not in self._dev:
+            self._dev["blobs"] = tuple(arr.to_device(_tape.blob(t).view(np.float64), torch.float64)
+                                       for t in (self.running_tape, self.terminal_tape))
+        blobs = self._dev["blobs"]
+        pp = None if pdev is None else pdev.data_ptr()
+        tapes = [zm_traced_t(b.data_ptr(), pp, stride, len(t.code), len(t.consts), t.n_slots, self.n_params)
+                 for b, t in zip(blobs, (self.running_tape, self.terminal_tape))]
+        st = zm_tracedcost_t(tapes[0], tapes[1], self.n, self.m, self.running_tape.mask, self.terminal_tape.mask)
+        st._owner = (self, blobs, pdev)      # raw device addresses: keep the arrays behind them alive with the struct
+        return st
+
+
+def traced_cost_of(runningCost, terminalCost=None):
+    """The TracedCost behind a cost argument (the handle or one of its bound methods), else None"""
+    for c in (runningCost, getattr(runningCost, "__self__", None), terminalCost, getattr(terminalCost, "__self__", None)):
+        if isinstance(c, TracedCost):
+            return c
+    return None
+
+
+def check_traced_cost(cost, model, who, box=None, sbox=None):
+    """What a TracedCost is not built for, refused with a TypeError before anything touches the device"""
+    if box is not None or sbox is not None:
+        raise TypeError(f"{who}: a TracedCost takes no InputBox / StateBox yet -- the clipped line search, the box-QP sweep and the "
+                        "augmented-Lagrangian penalty next to a recorded cost are the follow-up")
+    if not hasattr(model, "c_struct"):
+        raise TypeError(f"{who}: a TracedCost needs a registered device model or a TracedModel -- its callables are written on NumPy "
+                        "arrays, not torch, so the generic torch-callable path cannot differentiate them (write the dynamics as a "
+                        "models.TracedModel; a torch restatement of the cost on the generic path is the alternative)")
+    if (model.n, model.m) != (cost.n, cost.m):
+        raise TypeError(f"{who}: the TracedCost is (n={cost.n}, m={cost.m}), the model (n={model.n}, m={model.m}) -- record the cost for "
+                        "the model's shape")
+    if model.n > 12 or model.m > 4:
+        raise TypeError(f"{who}: a TracedCost covers n <= 12, m <= 4 (the tape interpreter's caps); larger linear models are the follow-up")
+
+
 class zm_trackcost_t(ctypes.Structure):
     _fields_ = [("Q", ctypes.c_void_p), ("R", ctypes.c_void_p), ("Qf", ctypes.c_void_p), ("diagonal", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("xRef", ctypes.c_void_p), ("uRef", ctypes.c_void_p),

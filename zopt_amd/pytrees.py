@@ -23,6 +23,8 @@ def _expand(kind, fun, xTraj, uTraj):
     from . import _lib
     from . import models as _models
     arr.require_gpu()
+    if kind in ("cost", "terminal") and _models.traced_cost_of(fun) is not None:
+        return _expand_traced_cost(kind, _models.traced_cost_of(fun), xTraj, uTraj)
     tracking = isinstance(fun, _models.TrackingCost) or isinstance(getattr(fun, "__self__", None), _models.TrackingCost)
     if tracking:
         # the tracking cost's expansion runs in its own kernels (zm_quadratize_cost_tracking_f64); the torch.func path below would
@@ -77,6 +79,55 @@ def _expand(kind, fun, xTraj, uTraj):
             outs = [v[:, None], v_x[:, None], v_xx.expand((B, 1, n, n)).contiguous()]
             outs = [o.reshape(lead + tuple(o.shape[1:])) for o in outs]
     return [arr.result_like(o, xTraj) for o in outs]
+
+
+def _expand_traced_cost(kind, cost, xTraj, uTraj, values_only=False):
+    """The expansions of a models.TracedCost (zm_traced_cost_expand_list_f64): 'cost' -> c, c_x, c_u and the PER-POINT c_xx, c_ux, c_uu
+    along the trajectory; 'terminal' -> v, v_x, v_xx at the last state, with the dummy time axis of _expand.  values_only: (c, v)."""
+    import torch
+    from . import _arrays as arr
+    from . import _lib
+    n, m = cost.n, cost.m
+    dt = torch.float64
+    x = arr.to_device(xTraj, dt)
+    if x.shape[-1] != n:
+        raise ValueError(f"xTraj has {x.shape[-1]} states, the TracedCost n = {n}")
+    lead = tuple(x.shape[:-2])
+    N = x.shape[-2] - 1
+    x = x.reshape(-1, N + 1, n).contiguous()
+    if uTraj is None:
+        u = torch.zeros((x.shape[0], max(N, 1), m), dtype=dt, device=x.device)
+    else:
+        u = arr.to_device(uTraj, dt).reshape(-1, N, m).contiguous()
+        if u.shape[0] != x.shape[0]:
+            raise ValueError("xTraj / uTraj batch axes differ")
+    B, dev = x.shape[0], x.device
+    cs = cost.tcost_struct(lead)
+    E = lambda *shape: torch.empty(shape, dtype=dt, device=dev)
+    P = lambda t: None if t is None else t.data_ptr()
+    c = c_x = c_u = c_xx = c_ux = c_uu = v = v_x = v_xx = None
+    if values_only:
+        c, v = E(B, N), E(B)
+    elif kind == "cost":
+        c, c_x, c_u, c_xx, c_ux, c_uu = E(B, N), E(B, N, n), E(B, N, m), E(B, N, n, n), E(B, N, m, n), E(B, N, m, m)
+    else:
+        v, v_x, v_xx = E(B), E(B, n), E(B, n, n)
+    _lib.check(_lib.lib().zm_traced_cost_expand_list_f64(ctypes.addressof(cs), x.data_ptr(), u.data_ptr(), None, 0, None, P(c), P(c_x),
+                                                         P(c_u), P(c_xx), P(c_ux), P(c_uu), P(v), P(v_x), P(v_xx), B, N,
+                                                         ctypes.c_void_p(arr.stream_ptr(x))), "TracedCost expansion")
+    if values_only:
+        outs = [c, v]
+    elif kind == "cost":
+        outs = [c, c_x, c_u, c_xx, c_ux, c_uu]
+    else:
+        outs = [v[:, None], v_x[:, None], v_xx[:, None]]
+    outs = [o.reshape(lead + tuple(o.shape[1:])) for o in outs]
+    return [arr.result_like(o, xTraj) for o in outs]
+
+
+def _traced_cost_values(cost, xTraj, uTraj):
+    """(c (..., N), v (...)) of a models.TracedCost along a trajectory"""
+    return _expand_traced_cost("cost", cost, xTraj, uTraj, values_only=True)
 
 
 def _expand_callable(kind, fun, xTraj, uTraj):

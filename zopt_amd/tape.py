@@ -13,6 +13,10 @@ stays an instruction: the value path is IEEE-faithful to the callable, NaN inclu
 The tape: 32-bit words  op | a_is_const << 6 | b_is_const << 7 | dst << 8 | a << 16 | b << 24  over a slot file; the inputs x, u, p
 are pinned in slots 0 .. n+m+np-1, temporaries are reused after their last use (lowest free slot first, in recording order), `outputs`
 names the n slots that hold x+ at the end.  An operand flagged as a constant indexes the fp64 constant table instead of the slot file.
+
+`models.TracedCost` records its two cost callables with the same recorder (`record(..., n_out=1)`: one output; `controls=False` for
+terminalCost(x[, p]), whose tape keeps the control slots reserved and unread so that both tapes share the layout x, u, p); the device
+side is zopt_amd/csrc/tape_cost.h.
 """
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ _BINARY = {"add": lambda a, b: a + b, "sub": lambda a, b: a - b, "mul": lambda a
 
 
 class Tape(NamedTuple):
-    """code (K,) uint32, consts (C,) float64, outputs (n,) slot numbers, n_slots (inputs included), n, m, n_params, mask"""
+    """code (K,) uint32, consts (C,) float64, outputs (n,) slot numbers ((1,) for a cost), n_slots (inputs included), n, m, n_params,
+    mask"""
     code: np.ndarray
     consts: np.ndarray
     outputs: tuple
@@ -188,22 +193,27 @@ def _fold(tr):
     return nodes, repl
 
 
-def record(f, n, m, n_params=0):
+def record(f, n, m, n_params=0, n_out=None, controls=True, who="TracedModel"):
     """Trace `f` once; returns the Tape.  ValueError for sizes outside the caps or a wrong output length, TypeError for what the
-    recorder refuses."""
+    recorder refuses.  n_out: how many values `f` returns (None: n, a dynamics function; 1: a cost, whose result may also be a
+    recorded scalar or a 0-d array).  controls=False: `f` is called as f(x) / f(x, p); the control slots n .. n+m-1 stay reserved, so
+    that the slot layout [x | u | p] is the same, and are never read.  who: the name the messages of this call carry."""
     n, m, n_params = int(n), int(m), int(n_params)
+    n_out = n if n_out is None else int(n_out)
     if not (1 <= n <= MAX_N and 1 <= m <= MAX_M and 0 <= n_params <= MAX_P):
-        raise ValueError(f"TracedModel: (n={n}, m={m}, params={n_params}) outside the interpreter's caps (1 <= n <= {MAX_N}, "
+        raise ValueError(f"{who}: (n={n}, m={m}, params={n_params}) outside the interpreter's caps (1 <= n <= {MAX_N}, "
                          f"1 <= m <= {MAX_M}, params <= {MAX_P})")
     tr = _Trace()
     n_in = n + m + n_params
     ins = [tr.input(s, (1 << s) if s < n + m else 0) for s in range(n_in)]
     obj = lambda lst: np.array(lst + [None], dtype=object)[:-1]                               # noqa: E731  (1-d, whatever it holds)
     x, u, p = obj(ins[:n]), obj(ins[n:n + m]), obj(ins[n + m:])
-    out = f(x, u, p) if n_params else f(x, u)
+    args = ((x, u) if controls else (x,)) + ((p,) if n_params else ())
+    out = f(*args)
     out = np.asarray(out, dtype=object).reshape(-1)
-    if out.shape[0] != n:
-        raise ValueError(f"TracedModel: the callable returned {out.shape[0]} values, the next state has n = {n}")
+    if out.shape[0] != n_out:
+        raise ValueError(f"{who}: the callable returned {out.shape[0]} values, " +
+                         (f"the next state has n = {n}" if n_out == n and who == "TracedModel" else f"expected {n_out}"))
     nodes, repl = _fold(tr)
     outs = []
     for v in out:
@@ -212,7 +222,7 @@ def record(f, n, m, n_params=0):
         else:
             c = _number(v)
             if c is None:
-                raise TypeError(f"TracedModel: the callable returned a {type(v).__name__}, expected recorded scalars or numbers")
+                raise TypeError(f"{who}: the callable returned a {type(v).__name__}, expected recorded scalars or numbers")
             outs.append(tr.const(c))
     # a constant output is moved into a slot of its own by one instruction
     for k, o in enumerate(outs):
@@ -293,11 +303,11 @@ def record(f, n, m, n_params=0):
         if top > 256:
             break
     if len(code) > MAX_INSTR or len(order) > MAX_INSTR:
-        raise ValueError(f"TracedModel: {len(order)} instructions, the interpreter takes {MAX_INSTR}")
+        raise ValueError(f"{who}: {len(order)} instructions, the interpreter takes {MAX_INSTR}")
     if top > MAX_SLOTS:
-        raise ValueError(f"TracedModel: more than {MAX_SLOTS} slots are live at once (inputs included)")
+        raise ValueError(f"{who}: more than {MAX_SLOTS} slots are live at once (inputs included)")
     if len(consts) > MAX_CONSTS:
-        raise ValueError(f"TracedModel: {len(consts)} constants, the interpreter takes {MAX_CONSTS}")
+        raise ValueError(f"{who}: {len(consts)} constants, the interpreter takes {MAX_CONSTS}")
     return Tape(np.array(code, dtype=np.uint32), np.array(consts, dtype=np.float64), tuple(slot[o[1]] for o in outs), top, n, m,
                 n_params, mask)
 
