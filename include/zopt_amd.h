@@ -772,6 +772,42 @@ int zm_mpc_closed_loop_f64(const double* A, const double* B, const double* Q, co
                            int32_t* status, int32_t* iters, double* xPred, double* uPred, int64_t batch, int N, int n, int m,
                            void* stream);
 
+/* Soft box constraints on lqrMpc's problem (extension): the QP of zopt/mpcUtils.py:48-59 (about a reference or not) in which a component
+ * i of the stacked [x ; u] with a finite l1_i >= 0 is not held inside its box (:55-58) but pays
+ *     l1_i d + l2_i d^2,   d = max(0, v - ub_i, lb_i - v),   for every x_k,i (k >= 1) / u_k,i,
+ * so a start, or a state a disturbance has led to, outside the box in such a component is solved from and flown back, where the hard
+ * problem is "infeasible" (Replaces: nothing in the reference, whose bounds are all hard; with every l1 = +inf these entries compute what
+ * zm_mpc_solve_relaxed_f64 / _batched_f64 / _tracking_f64 and zm_mpc_closed_loop_f64 compute, bit for bit).  l1_i = +inf is a hard
+ * component (l2_i must be 0 there).  soft_l1, soft_l2 (P,n+m), the stacked layout [x ; u], one row for the shared problem  [device];
+ * soft_l2 may be NULL (zeros).  The tables do not depend on the weights: zm_mpc_setup_f64 / zm_mpc_setup_batched_f64 set up.
+ * The ADMM differs from zm_mpc_solve_tracking_f64's where zm_mpc_solve_ltv_soft_f64 (below) differs from its hard form, and nowhere else:
+ * a soft component of x0 is not tested against the box; the y-update is the proximal map of the penalty, t = l1 / rho and
+ * a = rho / (rho + 2 l2) following the adaptive penalty; a soft component has the bounds -inf / +inf in the certificate's support term;
+ * the cycle guard is on when the reference term is nonzero or the instance's problem has a soft component.
+ * zm_mpc_solve_soft_f64: the arguments of zm_mpc_solve_tracking_f64 with soft_l1, soft_l2 after u_ub.  Q, R, Qf are read, and the
+ *     workspace has its fifth block, only when xRef or uRef is given (4 * batch * N * (n + m) doubles without a reference).
+ * zm_mpc_closed_loop_soft_f64: the arguments of zm_mpc_closed_loop_f64 with soft_l1, soft_l2 after u_ub.  The clip between the steps
+ *     applies to the HARD state components only: a soft component of states[s + 1] is xTraj_s[1] + disturbance[s], the plant's state.
+ *     A regulator run is one launch with the step loop inside, a tracking run the queue of launches, as there.
+ * 16 lanes per instance only: ZM_EUNSUPPORTED for (n, m) outside the compiled shapes with n + m <= 16 and for N > 75;
+ * ZOPT_AMD_MPC_PATH does not apply.  ZM_EINVAL for a NULL soft_l1 and for whatever the hard entries refuse; all but the map check before
+ * any launch. */
+int zm_mpc_solve_soft_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                          const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                          const double* x_ub, const double* u_lb, const double* u_ub, const double* soft_l1, const double* soft_l2,
+                          const double* x0, const double* xRef, const double* uRef, double rho, const double* rho_p,
+                          const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf, int max_iter,
+                          int warm_start, double* workspace, double* xTraj, double* uTraj, int32_t* status, int32_t* iters, double* resid,
+                          int64_t batch, int N, int n, int m, void* stream);
+int zm_mpc_closed_loop_soft_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                                const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                                const double* x_ub, const double* u_lb, const double* u_ub, const double* soft_l1, const double* soft_l2,
+                                const double* x0, const double* xRef, const double* uRef, int xref_rows, int uref_rows, double rho,
+                                const double* rho_p, const int32_t* problem, int64_t P, double eps_abs, double eps_rel,
+                                double eps_prim_inf, int max_iter, int warm_start, int steps, double clip_tol, const double* disturbance,
+                                double* workspace, double* states, double* inputs, int32_t* status, int32_t* iters, double* xPred,
+                                double* uPred, int64_t batch, int N, int n, int m, void* stream);
+
 /* Stage-varying dynamics (extension; what linearising a model about a TRAJECTORY gives): the QP of zopt/mpcUtils.py:48-59 with
  *     x_{k+1} = A_k x_k + B_k u_k + c_k,   k = 0 .. N-1,
  * per problem, under the cost, bounds, ADMM, termination and status codes of zm_mpc_solve_tracking_f64 in its per-problem form.

@@ -93,6 +93,16 @@ SYMBOLS = {
                                [_c_dp] * 7 + [ctypes.c_int] * 2 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] +
                                [ctypes.c_double] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] + [_c_dp] * 8 +
                                [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # zm_mpc_solve_tracking_f64's arguments with soft_l1 (P,n+m), soft_l2 (P,n+m) | NULL after u_ub
+    "zm_mpc_solve_soft_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                              [_c_dp] * 9 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] + [ctypes.c_double] * 3 +
+                              [ctypes.c_int] * 2 + [_c_dp] * 6 +
+                              [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    # zm_mpc_closed_loop_f64's arguments with soft_l1, soft_l2 | NULL after u_ub
+    "zm_mpc_closed_loop_soft_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] +
+                                    [_c_dp] * 9 + [ctypes.c_int] * 2 + [ctypes.c_double] + [_c_dp] * 2 + [ctypes.c_int64] +
+                                    [ctypes.c_double] * 3 + [ctypes.c_int] * 3 + [ctypes.c_double] + [_c_dp] * 8 +
+                                    [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     # (A (P,N,n,n), B (P,N,n,m), c (P,N,n) | NULL, Q, R, Qf, rho (P,L), P, L, N, n, m, K, Minv, D, ABt, stream)
     "zm_mpc_setup_ltv_f64": (ctypes.c_int, [_c_dp] * 7 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int] +
                              [_c_dp] * 4 + [ctypes.c_void_p]),

@@ -499,6 +499,35 @@ __global__ __launch_bounds__(256) void mpc_advance_kernel(const double* src, con
     }
 }
 
+// mpc_advance_kernel for a softened object (zm_mpc_closed_loop_soft_f64, the queue of launches): the same rule, but a state component
+// whose l1 (soft_l1 (P,n+m), the stacked layout; one row without a problem map) is finite is never clipped -- it stays the plant's state.
+// A sibling rather than one more parameter: mpc_advance_kernel keeps its arguments and its code.
+__global__ __launch_bounds__(256) void mpc_advance_soft_kernel(const double* src, const long src_stride, const double* dist,
+                                                               const double* x_lb, const double* x_ub, const double* soft_l1,
+                                                               const int* prob, const double clip_tol, double* dst, const double* usrc,
+                                                               const long usrc_stride, double* udst, const long batch, const int n,
+                                                               const int m) {
+    const int W = n + m;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= batch * W) return;
+    const int i = (int)(e % W);
+    const long b = e / W;
+    if (i < n) {
+        double v = src[b * src_stride + i];
+        if (dist) v += dist[b * n + i];
+        const long p = prob ? prob[b] : 0;
+        if (clip_tol >= 0.0 && !(soft_l1[p * W + i] < __builtin_inf())) {   // min(max(v, lo), hi): np.clip's order, a NaN passes through
+            const double lo = x_lb[p * n + i] + clip_tol, hi = x_ub[p * n + i] - clip_tol;
+            v = v < lo ? lo : v;
+            v = v > hi ? hi : v;
+        }
+        dst[b * n + i] = v;
+    } else if (usrc) {
+        const int j = i - n;
+        udst[b * m + j] = usrc[b * usrc_stride + j];
+    }
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // real-time-iteration run (zm_mpc_rti_f64): the kernels between two solves (the expansion is linearize.hip's)
 // ----------------------------------------------------------------------------------------------------------------
@@ -597,7 +626,8 @@ struct MpcCall {
     // zm_mpc_solve_ltv_stage_f64: Q, R hold Qs (P,N,n,n), Rs (P,N,m,m) and Qf stays NULL; x_lb, x_ub hold the box of x_0 (P,n) and
     // u_lb, u_ub the stacked lo, hi (P,N,n+m) -- the slots the kernel takes them in (mpc_common.h: mpc_wave_ltv_dispatch)
     bool stage;
-    // zm_mpc_solve_ltv_soft_f64: the stage form with penalty weights (P,n+m) on the box; soft_l2 may be NULL (zeros)
+    // zm_mpc_solve_ltv_soft_f64: the stage form with penalty weights (P,n+m) on the box; soft_l2 may be NULL (zeros).
+    // zm_mpc_solve_soft_f64, zm_mpc_closed_loop_soft_f64: `soft` without `stage` -- lqrMpc's data with the weights, (1,n+m) without a map
     bool soft;
     const double *soft_l1, *soft_l2;
     void* stream;
@@ -746,8 +776,11 @@ static bool mpc_force_lane() {
 
 // One solve launch.  Default: 16 lanes per instance with the iterates in LDS (mpc_wave.hip); ZOPT_AMD_MPC_PATH=lane forces the
 // lane-per-instance kernel below, which also takes the shapes and the horizons that do not fit LDS.  It runs every problem at its
-// level0 table (fixed penalty).  `t` holds the whole tables (every level).
-static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, int n, int m, hipStream_t st) {
+// level0 table (fixed penalty).  `t` holds the whole tables (every level).  sf != nullptr: soft box constraints -- the 16-lane kernel that
+// takes the weights, whatever ZOPT_AMD_MPC_PATH says (there is no lane-per-instance kernel for them).
+static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, const MpcSoft* sf, int n, int m,
+                       hipStream_t st) {
+    if (sf) return mpc_wave_soft_dispatch(t, g, pb, trk, *sf, n, m, st);   // (its shape and horizon were checked: mpc_ltv_check_shape)
     if (!mpc_force_lane()) {
         const int rc = mpc_wave_dispatch(t, g, pb, trk, n, m, st);
         if (rc != ZM_EUNSUPPORTED) return rc;
@@ -768,11 +801,12 @@ static int mpc_enqueue(const char* fn, MpcTabs t, const MpcArgs& g, const MpcPro
 //                              there is (mpc_wave.hip), so what it does not take is refused before anything is launched
 //   zm_mpc_solve_ltv_stage_f64: the same with a.stage -- weights and box per stage, the sibling kernels for the linear term and the solve
 //   zm_mpc_solve_ltv_soft_f64: the stage entry with a.soft -- penalty weights on the box, the solve kernel that takes them
+//   zm_mpc_solve_soft_f64    : the tracking entry with a.soft (tracking only with a reference); 16 lanes per instance only, as ltv
 static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv) {
     if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     int rc = mpc_check_args(a, per_problem, tracking, a.xTraj && a.uTraj && a.status && (!ltv || (a.c && a.D && a.ABt)) && (!a.soft || a.soft_l1));
     if (rc != ZM_OK) return rc;
-    if (ltv && (rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
+    if ((ltv || a.soft) && (rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
     hipStream_t st = (hipStream_t)a.stream;
     if ((rc = mpc_check_map(a, false, st)) != ZM_OK) return rc;
     const MpcLayout lay = mpc_layout(a, tracking);
@@ -781,8 +815,9 @@ static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv
     const MpcArgs g = mpc_args(a, mpc_warm(a), a.xTraj, a.uTraj);
     const MpcProb pb{(const int*)a.problem, a.rho_p};
     const MpcTrack trk{lay.gbuf};
-    if (!ltv) return mpc_enqueue(a.fn, t, g, a.problem ? &pb : nullptr, tracking ? &trk : nullptr, a.n, a.m, st);
-    rc = a.soft ? mpc_wave_ltv_soft_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, MpcSoft{a.soft_l1, a.soft_l2}, a.n, a.m, st)
+    const MpcSoft sf{a.soft_l1, a.soft_l2};
+    if (!ltv) return mpc_enqueue(a.fn, t, g, a.problem ? &pb : nullptr, tracking ? &trk : nullptr, a.soft ? &sf : nullptr, a.n, a.m, st);
+    rc = a.soft ? mpc_wave_ltv_soft_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, sf, a.n, a.m, st)
                 : mpc_wave_ltv_dispatch(t, g, pb, trk, MpcLtv{a.c, a.D, a.ABt}, a.stage, a.n, a.m, st);
     if (rc == ZM_EUNSUPPORTED)
         return set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not among the shapes of the 16-lanes-per-instance kernels", a.fn, a.n, a.m);
@@ -794,13 +829,16 @@ static int mpc_solve(const MpcCall& a, bool per_problem, bool tracking, bool ltv
 //       (mpc_wave.hip: mpc_closed_loop_wave_kernel);
 //   (b) everything else -- tracking, (24, 8), horizons beyond LDS, ZOPT_AMD_MPC_PATH=lane: a loop that enqueues, per step, the launches
 //       of a single solve and mpc_advance_kernel, with no host synchronisation in between.
+// zm_mpc_closed_loop_soft_f64 (a.soft): the same two forms with the kernels that take the weights -- (a) mpc_closed_loop_wave_soft_kernel,
+// (b), for tracking runs, the soft solve kernel and mpc_advance_soft_kernel; the shapes and horizons beyond the 16-lane kernels are refused.
 static int mpc_closed_loop(const MpcCall& a) {
     if (a.batch == 0) return ZM_OK;   /* empty batch: nothing to do (pointers of empty arrays may be NULL) */
     const bool tracking = a.xRef || a.uRef;
     const int N = a.N, n = a.n, m = a.m;
-    int rc = mpc_check_args(a, false, tracking, a.states && a.inputs && a.status && a.iters);
+    int rc = mpc_check_args(a, false, tracking, a.states && a.inputs && a.status && a.iters && (!a.soft || a.soft_l1));
     if (rc != ZM_OK) return rc;
     if ((rc = mpc_check_run(a, n >= 1 && m >= 1)) != ZM_OK) return rc;
+    if (a.soft && (rc = mpc_ltv_check_shape(a)) != ZM_OK) return rc;
     const long ablocks = blocks256((long)a.batch * ((long)n + m));   // of mpc_advance_kernel
     if (ablocks > 0x7fffffffL) return set_error(ZM_EINVAL, "%s: batch x (n + m) too large", a.fn);
     hipStream_t st = (hipStream_t)a.stream;
@@ -812,14 +850,21 @@ static int mpc_closed_loop(const MpcCall& a) {
     const MpcArgs g = mpc_args(a, 0, lay.xroll, lay.uroll);
     const MpcProb pbv{(const int*)a.problem, a.rho_p};
     const MpcProb* pb = a.problem ? &pbv : nullptr;
+    const MpcSoft sfv{a.soft_l1, a.soft_l2};
+    const MpcSoft* sf = a.soft ? &sfv : nullptr;
+    if (!tracking && sf) return mpc_wave_closed_loop_soft_dispatch(t, g, pb, lp, sfv, n, m, st);
     if (!tracking && !mpc_force_lane()) {
         rc = mpc_wave_closed_loop_dispatch(t, g, pb, lp, n, m, st);
         if (rc != ZM_EUNSUPPORTED) return rc;
     }
     const MpcTrack trkv{lay.gbuf};
     const auto advance = [&](const double* src, long src_stride, const double* dist, double* dst, const double* usrc, double* udst) -> int {
-        hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, a.x_lb, a.x_ub,
-                           (const int*)a.problem, a.clip_tol, dst, usrc, (long)N * m, udst, (long)a.batch, n, m);
+        if (sf)
+            hipLaunchKernelGGL(mpc_advance_soft_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, a.x_lb, a.x_ub,
+                               a.soft_l1, (const int*)a.problem, a.clip_tol, dst, usrc, (long)N * m, udst, (long)a.batch, n, m);
+        else
+            hipLaunchKernelGGL(mpc_advance_kernel, dim3((unsigned)ablocks), dim3(256), 0, st, src, src_stride, dist, a.x_lb, a.x_ub,
+                               (const int*)a.problem, a.clip_tol, dst, usrc, (long)N * m, udst, (long)a.batch, n, m);
         ZM_HIP_CHECK(hipGetLastError());
         return ZM_OK;
     };
@@ -827,7 +872,7 @@ static int mpc_closed_loop(const MpcCall& a) {
     for (int s = 0; s < a.steps && rc == ZM_OK; ++s) {
         if (tracking && (rc = mpc_track_linear(a, lay, s, st)) != ZM_OK) break;
         const MpcArgs gs = mpc_step_args(g, lp, n, s);
-        rc = mpc_enqueue(a.fn, t, gs, pb, tracking ? &trkv : nullptr, n, m, st);
+        rc = mpc_enqueue(a.fn, t, gs, pb, tracking ? &trkv : nullptr, sf, n, m, st);
         if (rc != ZM_OK) break;
         rc = advance(gs.xTraj + n, (long)(N + 1) * n, a.disturbance ? a.disturbance + (long)s * a.batch * n : nullptr,
                      a.states + (long)(s + 1) * a.batch * n, gs.uTraj, a.inputs + (long)s * a.batch * m);
@@ -1035,6 +1080,26 @@ extern "C" int zm_mpc_solve_tracking_f64(const double* A, const double* B, const
     return zm::mpc_solve(a, false, true, false);
 }
 
+// soft box constraints on lqrMpc's data: the tracking entry with the penalty weights; tracking only with a reference
+extern "C" int zm_mpc_solve_soft_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf, const double* K,
+                                     const double* Minv, int n_levels, int level0, double rho_step, double alpha, const double* x_lb,
+                                     const double* x_ub, const double* u_lb, const double* u_ub, const double* soft_l1,
+                                     const double* soft_l2, const double* x0, const double* xRef, const double* uRef, double rho,
+                                     const double* rho_p, const int32_t* problem, int64_t P, double eps_abs, double eps_rel,
+                                     double eps_prim_inf, int max_iter, int warm_start, double* workspace, double* xTraj, double* uTraj,
+                                     int32_t* status, int32_t* iters, double* resid, int64_t batch, int N, int n, int m, void* stream) {
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_solve_soft_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.workspace = workspace, a.xTraj = xTraj, a.uTraj = uTraj, a.status = status, a.iters = iters, a.resid = resid;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.rho = rho, a.rho_p = rho_p, a.problem = problem, a.P = P;
+    a.soft = true, a.soft_l1 = soft_l1, a.soft_l2 = soft_l2;
+    return zm::mpc_solve(a, false, xRef || uRef, false);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // stage-varying dynamics: x+ = A_k x + B_k u + c_k per problem (16 lanes per instance only)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1145,6 +1210,30 @@ extern "C" int zm_mpc_closed_loop_f64(const double* A, const double* B, const do
     a.workspace = workspace, a.states = states, a.inputs = inputs, a.status = status, a.iters = iters, a.xPred = xPred, a.uPred = uPred;
     a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
     a.rho = rho, a.P = P;
+    return zm::mpc_closed_loop(a);
+}
+
+// the same run of a softened object: the weights, and a clip that leaves the soft state components alone
+extern "C" int zm_mpc_closed_loop_soft_f64(const double* A, const double* B, const double* Q, const double* R, const double* Qf,
+                                           const double* K, const double* Minv, int n_levels, int level0, double rho_step, double alpha,
+                                           const double* x_lb, const double* x_ub, const double* u_lb, const double* u_ub,
+                                           const double* soft_l1, const double* soft_l2, const double* x0, const double* xRef,
+                                           const double* uRef, int xref_rows, int uref_rows, double rho, const double* rho_p,
+                                           const int32_t* problem, int64_t P, double eps_abs, double eps_rel, double eps_prim_inf,
+                                           int max_iter, int warm_start, int steps, double clip_tol, const double* disturbance,
+                                           double* workspace, double* states, double* inputs, int32_t* status, int32_t* iters,
+                                           double* xPred, double* uPred, int64_t batch, int N, int n, int m, void* stream) {
+    zm::MpcCall a{};
+    a.fn = "zm_mpc_closed_loop_soft_f64";
+    a.A = A, a.B = B, a.K = K, a.Minv = Minv, a.x_lb = x_lb, a.x_ub = x_ub, a.u_lb = u_lb, a.u_ub = u_ub;
+    a.n_levels = n_levels, a.level0 = level0, a.rho_step = rho_step, a.alpha = alpha, a.x0 = x0;
+    a.eps_abs = eps_abs, a.eps_rel = eps_rel, a.eps_prim_inf = eps_prim_inf, a.max_iter = max_iter, a.warm_start = warm_start;
+    a.Q = Q, a.R = R, a.Qf = Qf, a.xRef = xRef, a.uRef = uRef, a.xref_rows = xref_rows, a.uref_rows = uref_rows;
+    a.rho_p = rho_p, a.problem = problem, a.steps = steps, a.clip_tol = clip_tol, a.disturbance = disturbance;
+    a.workspace = workspace, a.states = states, a.inputs = inputs, a.status = status, a.iters = iters, a.xPred = xPred, a.uPred = uPred;
+    a.batch = batch, a.N = N, a.n = n, a.m = m, a.stream = stream;
+    a.rho = rho, a.P = P;
+    a.soft = true, a.soft_l1 = soft_l1, a.soft_l2 = soft_l2;
     return zm::mpc_closed_loop(a);
 }
 

@@ -55,6 +55,7 @@ struct MpcLtv {
 
 // soft box constraints (zm_mpc_solve_ltv_soft_f64): the penalty weights l1, l2 (P,n+m) of every problem's stacked component [x ; u];
 // l1 = +inf is a hard component, l2 may be nullptr (zeros).  Its own kernel argument, after MpcLtv: the kernels without it keep theirs.
+// zm_mpc_solve_soft_f64, zm_mpc_closed_loop_soft_f64: the same rows for lqrMpc's kernels, (1,n+m) without per-problem data.
 struct MpcSoft {
     const double *l1, *l2;
 };
@@ -129,6 +130,14 @@ int mpc_wave_ltv_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb,
 // mpc_wave.hip: the stage form of the above (stage_box) with soft box constraints, weights sf (mpc_solve_wave_ltv_soft_kernel)
 int mpc_wave_ltv_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb& pb, const MpcTrack& trk, const MpcLtv& lv,
                                const MpcSoft& sf, int n, int m, hipStream_t st);
+// mpc_wave.hip: lqrMpc's solve with soft box constraints, weights sf (P,n+m), one row without per-problem data
+// (mpc_solve_wave_soft_kernel); pb, trk: either may be nullptr.  ZM_EUNSUPPORTED as above; there is no other kernel to take what does not fit.
+int mpc_wave_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, const MpcSoft& sf, int n, int m,
+                           hipStream_t st);
+// mpc_wave.hip: the closed-loop run of a softened regulator as ONE launch (mpc_closed_loop_wave_soft_kernel): mpc_wave_closed_loop_dispatch
+// with the weights; the clip between the steps leaves the soft state components alone
+int mpc_wave_closed_loop_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, const MpcSoft& sf, int n,
+                                       int m, hipStream_t st);
 
 // linearize.hip (where the model expansions live): the argument check of the entry points that take a registered model, and the launch
 // of mpc_rti_relinearize_kernel -- the expansion of `md` about every stage of the plans xPlan (batch,N+1,n), uPlan (batch,N,m), written

@@ -4,6 +4,8 @@
 // it).  The per-problem kernel reaches it with its parameters already offset to its problem (see there).
 // The ZM_TRK_* hooks are the reference-tracking variant (mpc_wave.hip: mpc_solve_wave_track_kernel); they expand to nothing in the
 // kernels without a reference.
+// The ZM_SOFT_* hooks are the soft-box variant (mpc_wave.hip: mpc_solve_wave_soft_kernel, mpc_closed_loop_wave_soft_kernel); in every other
+// kernel they expand to nothing, or to the tokens that stood in their place before there were hooks.
     static_assert(NS + MC <= 16, "the stacked index must fit the 16 lanes of a group");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     constexpr int W = NS + MC;
@@ -38,9 +40,10 @@
     }
     const double inf = __builtin_inf();
     const double lo = sx ? x_lb[ix] : (su ? u_lb[iu] : -inf), hi = sx ? x_ub[ix] : (su ? u_ub[iu] : inf);
+    ZM_SOFT_SETUP
     const double x0 = sx ? g.x0[inst * NS + ix] : 0.0;
     // x_0 = x0 is box-constrained too (mpcUtils.py:56,58): group-wide AND over the state lanes
-    const double viol = (sx && !(x0 >= lo && x0 <= hi)) ? 1.0 : 0.0;
+    const double viol = (sx ZM_SOFT_X0 && !(x0 >= lo && x0 <= hi)) ? 1.0 : 0.0;
     const bool x0_in = row_max(viol) == 0.0;
 
     // per-instance block of the caller's workspace: [y (N,W) | lam (N,W) | kf (N,MC), ok flag, spare | unused]
@@ -54,6 +57,7 @@
             rho = g.rho * pow(g.rho_step, (double)(lvl - g.level0));
         }
     }
+    ZM_SOFT_RHO
     for (int k = 0; k < N; ++k) {
         const int ks = (g.warm == 2 && k + 1 < N) ? k + 1 : k;    // shifted warm start: iterate k <- iterate k+1
         const double wy = warm ? wsi[(long)ks * W + iw] : 0.0, wl = warm ? wsi[(long)N * W + (long)ks * W + iw] : 0.0;
@@ -169,14 +173,14 @@
                 const double lold = t.lam, yold = t.y;
                 const double wh = __builtin_fma(alpha, w, om_alpha * yold);   // relaxed iterate (alpha = 1: w exactly)
                 double yn = wh + lold;
-                yn = yn < lo ? lo : (yn > hi ? hi : yn);
+                ZM_SOFT_PROJECT(yn)
                 const double r = w - yn, dl = wh - yn, ln = lold + dl;        // primal residual; dual step
                 yw[k * WS_STAGE] = (done || !sw) ? yold : yn;
                 lw[k * WS_STAGE] = (done || !sw) ? lold : ln;
                 if (chk) rw[k * WS_STAGE] = sw ? dl : 0.0;
                 if (sw) {
                     if (chk) {
-                        sup += (dl > 0.0) ? dl * hi : ((dl < 0.0) ? dl * lo : 0.0);
+                        sup += (dl > 0.0) ? dl * ZM_SOFT_SUP_HI : ((dl < 0.0) ? dl * ZM_SOFT_SUP_LO : 0.0);
                         amax(ndl, dl);
                     }
                     amax(nrp, r);
@@ -251,6 +255,7 @@
                 for (int k = 0; k < N; ++k) lw[k * WS_STAGE] *= sc;
                 rho = rnew;
                 lvl = nl_;
+                ZM_SOFT_RHO
             }
         }
         // ---- primal infeasibility certificate (mpc.hip header): adjoint sweep over r = w - y

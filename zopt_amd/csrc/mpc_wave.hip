@@ -87,6 +87,14 @@ constexpr int WS_STAGE = 64;
 #define ZM_TRK_LOAD(k, t)
 #define ZM_TRK_ED(ed, dual)
 #define ZM_TRK_LEVEL(nl)
+// The hooks of the soft-box variant (below, after the tracking kernels): nothing, or the tokens the body had before it had them.
+#define ZM_SOFT_SETUP
+#define ZM_SOFT_X0
+#define ZM_SOFT_RHO
+#define ZM_SOFT_GUARD
+#define ZM_SOFT_PROJECT(yn) yn = yn < lo ? lo : (yn > hi ? hi : yn);
+#define ZM_SOFT_SUP_LO lo
+#define ZM_SOFT_SUP_HI hi
 
 // Lane roles (round 3): the STACKED index [x ; u] on the 16 lanes of a group -- lane i < NS owns state component i, lane NS + j owns
 // control component j (NS + MC <= 16 for every compiled shape).  A mat-vec over the state lanes then serves both blocks of its result in
@@ -133,6 +141,7 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_batched_kernel(const double
 // fence between the steps orders them (a wait for the outstanding stores, no cache maintenance); none of these words is reached through a
 // `const __restrict__` parameter.  Idle groups of the last block shadow the last instance and store nothing here either; they keep
 // looping with their wave.  PB: per-problem data, the entry block of mpc_solve_wave_batched_kernel.
+// (mpc_closed_loop_wave_soft_kernel, below, is a COPY of this frame with a per-lane clip: a fix here belongs there too.)
 template <int NS, int MC, bool PB>
 __global__ __launch_bounds__(64) void mpc_closed_loop_wave_kernel(const double* __restrict__ A, const double* __restrict__ B,
                                                                   const double* __restrict__ Ktab, const double* __restrict__ Mtab,
@@ -233,7 +242,7 @@ __global__ __launch_bounds__(64) void mpc_closed_loop_wave_kernel(const double* 
 // regulator's, move for move, as zm_mpc_solve_tracking_f64 promises.
 constexpr int ZM_TRK_REVERSALS = 3;
 #define ZM_TRK_LEVEL(nl)                                                                  \
-    if (gnorm > 0.0) {                                                                    \
+    if (gnorm > 0.0 ZM_SOFT_GUARD) {                                                      \
         const int mv = nl - lvl;                                                          \
         if (trk_locked) {                                                                 \
             nl = lvl;                                                                     \
@@ -260,6 +269,149 @@ __global__ __launch_bounds__(64) void mpc_solve_wave_track_kernel(const double* 
     }
 #include "mpc_solve_wave_body.h"
 }
+
+// Soft box constraints (zm_mpc_solve_soft_f64, zm_mpc_closed_loop_soft_f64): the same body with the penalty weights of the lane's
+// component, sf.l1, sf.l2 (P,n+m) in the stacked layout [x ; u] (one row without per-problem data; l2 may be NULL: zeros).  A component
+// with a finite l1 pays l1 d + l2 d^2 for its distance d from its box instead of being held inside it; l1 = +inf is a hard component, and
+// a lane outside every role carries l1 = +inf, l2 = 0.  What differs from the tracking kernel, each through a ZM_SOFT_* hook:
+//     x0 test:     a soft state component of x0 is not tested against the box
+//     projection:  the proximal map of the penalty with t = l1 / rho, a = rho / (rho + 2 l2) at the penalty the iteration runs at (set at
+//                  entry, after a warm start has restored a level, and after every level move).  The branches are tested in the order of
+//                  the clip (lo first) and written with selects, as ZM_LTV_PROJECT is: l1 = +inf gives t = +inf, e = -inf and y = the
+//                  bound bit for bit, a bound of -0.0 included
+//     certificate: the support term takes -inf / +inf for a soft component, whose y ranges over the whole line
+//     cycle guard: on when the reference term is nonzero or any component of the instance's problem is soft (uniform over the 16-lane
+//                  group, not over the wave)
+// ONE kernel for shared and per-problem data (pb.prob NULL or not: a group-uniform pointer offset at entry) and for solves with and without
+// a reference (trk.g NULL or not).  Without a reference the lane's g is -0.0, the one value with x + g == x for every x, zeros of either
+// sign included: the sums keep the bits of the kernels without a reference.  With every l1 = +inf the solve is the pinned kernels' own.
+#undef ZM_TRK_SETUP
+#undef ZM_SOFT_SETUP
+#undef ZM_SOFT_X0
+#undef ZM_SOFT_RHO
+#undef ZM_SOFT_GUARD
+#undef ZM_SOFT_PROJECT
+#undef ZM_SOFT_SUP_LO
+#undef ZM_SOFT_SUP_HI
+#define ZM_TRK_SETUP                                                                                      \
+    const double* gw = trk.g ? trk.g + inst * ((long)N * W) + iw : nullptr; /* + k * W */                 \
+    double gnorm = 0.0;                                                                                   \
+    if (gw) {                                                                                             \
+        for (int k = 0; k < N; ++k) {                                                                     \
+            const double gk = gw[(long)k * W];                                                            \
+            if (sw) amax(gnorm, gk);                                                                      \
+        }                                                                                                 \
+    }                                                                                                     \
+    gnorm = row_max(gnorm);                                                                               \
+    int trk_last = 0, trk_rev = 0; /* the last level move; consecutive reversals of it */                 \
+    bool trk_locked = false;                                                                              \
+    auto load_g = [&](int k, Tab& t) {                                                                    \
+        k = k < 0 ? 0 : (k >= N ? N - 1 : k);                                                             \
+        t.g = gw ? gw[(long)k * W] : -0.0;                                                                \
+    };
+#define ZM_SOFT_SETUP                                                                                     \
+    const double l1 = sw ? soft_l1[iw] : inf, l2 = (sw && soft_l2) ? soft_l2[iw] : 0.0;                   \
+    const bool soft = l1 < inf;                                                                           \
+    const bool any_soft = row_max(soft ? 1.0 : 0.0) > 0.0; /* uniform over the group: its problem's */    \
+    double prox_t = inf, prox_a = 1.0;                     /* t = l1 / rho, a = rho / (rho + 2 l2) */
+#define ZM_SOFT_X0 &&!soft
+#define ZM_SOFT_RHO      \
+    prox_t = l1 / rho;   \
+    prox_a = rho / (rho + 2.0 * l2);
+#define ZM_SOFT_GUARD || any_soft
+#define ZM_SOFT_PROJECT(yn)                                \
+    if (yn < lo) {                                         \
+        const double e = prox_a * ((lo - yn) - prox_t);    \
+        yn = (e > 0.0) ? lo - e : lo;                      \
+    } else if (yn > hi) {                                  \
+        const double e = prox_a * ((yn - hi) - prox_t);    \
+        yn = (e > 0.0) ? hi + e : hi;                      \
+    }
+#define ZM_SOFT_SUP_LO (soft ? -inf : lo)
+#define ZM_SOFT_SUP_HI (soft ? inf : hi)
+// the group's problem: the entry block of the per-problem kernels, and its row of the weights
+#define ZM_SOFT_ENTER_PROBLEM(inst)                    \
+    const double *soft_l1 = sf.l1, *soft_l2 = sf.l2;   \
+    if (pb.prob) {                                     \
+        ZM_MPC_ENTER_PROBLEM(inst)                     \
+        soft_l1 += p * (NS + MC);                      \
+        if (soft_l2) soft_l2 += p * (NS + MC);         \
+    }
+template <int NS, int MC>
+__global__ __launch_bounds__(64) void mpc_solve_wave_soft_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                                 const double* __restrict__ Ktab, const double* __restrict__ Mtab,
+                                                                 const double* __restrict__ x_lb, const double* __restrict__ x_ub,
+                                                                 const double* __restrict__ u_lb, const double* __restrict__ u_ub,
+                                                                 const MpcArgs g_all, const MpcProb pb, const MpcTrack trk, const MpcSoft sf) {
+    MpcArgs g = g_all;
+    const long inst_raw_ = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
+    ZM_SOFT_ENTER_PROBLEM(inst_raw_ < g.batch ? inst_raw_ : g.batch - 1)
+#include "mpc_solve_wave_body.h"
+}
+
+// The closed-loop run of a softened regulator (zm_mpc_closed_loop_soft_f64): the frame of mpc_closed_loop_wave_kernel -- see there for the
+// step loop, the fences between the steps and the idle groups -- around the body with the soft hooks, without a reference (trk.g NULL: the
+// cycle guard rests on the soft components alone).  One thing differs in the frame: the clip into [x_lb + clip_tol, x_ub - clip_tol]
+// applies to the HARD state components only.  A soft component of the state is never moved, so states[s + 1] is the plant's own state
+// xTraj_s[1] + w_s there, and the solve from it pays for its distance from the box.
+template <int NS, int MC>
+__global__ __launch_bounds__(64) void mpc_closed_loop_wave_soft_kernel(const double* __restrict__ A, const double* __restrict__ B,
+                                                                       const double* __restrict__ Ktab, const double* __restrict__ Mtab,
+                                                                       const double* __restrict__ x_lb, const double* __restrict__ x_ub,
+                                                                       const double* __restrict__ u_lb, const double* __restrict__ u_ub,
+                                                                       const MpcArgs g_all, const MpcProb pb, const MpcLoop lp,
+                                                                       const MpcSoft sf) {
+    MpcArgs g_run = g_all;
+    const MpcTrack trk{nullptr};
+    const long o_batch = g_all.batch;
+    const int o_li = threadIdx.x & 15;
+    const long o_raw = (long)blockIdx.x * 4 + (threadIdx.x >> 4);
+    const bool o_live = o_raw < o_batch;
+    const long o_inst = o_live ? o_raw : o_batch - 1;
+    MpcArgs& g = g_run;
+    ZM_SOFT_ENTER_PROBLEM(o_inst)
+    const bool o_sx = o_li < NS, o_su = (o_li >= NS) && (o_li < NS + MC);
+    const int o_ix = o_sx ? o_li : 0, o_iu = o_su ? o_li - NS : 0;
+    const bool o_clip = lp.clip_tol >= 0.0 && !(o_sx && soft_l1[o_ix] < __builtin_inf());   // (per lane: a soft component is not clipped)
+    const double c_lo = x_lb[o_ix] + lp.clip_tol, c_hi = x_ub[o_ix] - lp.clip_tol;
+    const auto into_box = [&](double v) {   // min(max(v, lo), hi): np.clip's order, a NaN passes through
+        if (o_clip) {
+            v = v < c_lo ? c_lo : v;
+            v = v > c_hi ? c_hi : v;
+        }
+        return v;
+    };
+    const long slab_x = o_batch * NS, slab_u = o_batch * MC;
+    if (o_live && o_sx) lp.states[o_inst * NS + o_ix] = into_box(lp.x0[o_inst * NS + o_ix]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll 1
+    for (int s = 0; s < lp.steps; ++s) {
+        MpcArgs g = g_run;
+        g.x0 = lp.states + s * slab_x;
+        g.xTraj = lp.xPred + s * lp.xpred_step;
+        g.uTraj = lp.uPred + s * lp.upred_step;
+        g.status = lp.status + s * o_batch;
+        g.iters = lp.iters + s * o_batch;
+        g.resid = nullptr;
+        g.warm = s ? lp.warm : 0;
+        {
+#include "mpc_solve_wave_body.h"
+        }
+        if (o_live) {
+            if (o_sx) {
+                double xn = g.xTraj[(o_inst * (g.N + 1) + 1) * NS + o_ix];
+                if (lp.dist) xn += lp.dist[s * slab_x + o_inst * NS + o_ix];
+                lp.states[(s + 1) * slab_x + o_inst * NS + o_ix] = into_box(xn);
+            }
+            if (o_su) lp.inputs[s * slab_u + o_inst * MC + o_iu] = g.uTraj[(o_inst * g.N) * MC + o_iu];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+// (the ltv kernels below take none of these hooks)
+#undef ZM_SOFT_ENTER_PROBLEM
 
 // stage-varying dynamics (zm_mpc_solve_ltv_f64): mpc_solve_wave_ltv_kernel, in this translation unit with the kernels it borrows from.
 // The hooks of mpc_solve_wave_ltv.h for one box per problem: the lane's bounds are read once and stay in lo / hi.
@@ -392,6 +544,21 @@ int mpc_wave_ltv_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb
                                const MpcSoft& sf, int n, int m, hipStream_t st) {
     return for_wave_shape(n, m, [&](auto ns, auto mc) {
         return launch_wave(mpc_solve_wave_ltv_soft_kernel<ns.value, mc.value>, t, g, st, pb, trk, lv, sf);
+    });
+}
+
+// pb, trk: either may be nullptr (shared data; no reference) -- the one kernel takes both as possibly-NULL arrays
+int mpc_wave_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcTrack* trk, const MpcSoft& sf, int n, int m,
+                           hipStream_t st) {
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        return launch_wave(mpc_solve_wave_soft_kernel<ns.value, mc.value>, t, g, st, pb ? *pb : MpcProb{}, trk ? *trk : MpcTrack{}, sf);
+    });
+}
+
+int mpc_wave_closed_loop_soft_dispatch(const MpcTabs& t, const MpcArgs& g, const MpcProb* pb, const MpcLoop& lp, const MpcSoft& sf, int n,
+                                       int m, hipStream_t st) {
+    return for_wave_shape(n, m, [&](auto ns, auto mc) {
+        return launch_wave(mpc_closed_loop_wave_soft_kernel<ns.value, mc.value>, t, g, st, pb ? *pb : MpcProb{}, lp, sf);
     });
 }
 

@@ -2,7 +2,8 @@
 
 Same constructor and ``solve`` signature as the reference (mpcUtils.py:14-26, 61-81).  New: ``x0`` may carry leading
 batch axes -- every initial state is an independent QP instance solved by one GPU lane; `solve` takes references to track (keywords
-xRef, uRef); `simulate` runs the whole receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) on the device in one call.
+xRef, uRef); `simulate` runs the whole receding-horizon loop of the reference's demo (demos/lqrMpc.py:40-47) on the device in one call;
+`soften` makes chosen bounds soft (a penalty l1 d + l2 d^2 on the distance d from the box), in `solve` and in `simulate`.
 `ltvMpc` (extension) is the same QP with stage-varying dynamics x+ = A_k x + B_k u + c_k, a linearisation about a trajectory.
 The plotting / animation helpers
 of the reference module (mpcUtils.py:84-202) are presentation code and not part of this package.
@@ -93,10 +94,76 @@ class lqrMpc():
 
     _LTV = False                     # ltvMpc (below) shares `solve` and overrides this
     stage_varying = frozenset()      # ltvMpc: the names among Q, R and the four bounds that carry a stage axis
-    _soft = None                     # ltvMpc: the penalty weights of soft box constraints, as given (None: every bound is hard)
+    _soft = None                     # the penalty weights of soft box constraints, as given (None: every bound is hard): soften(), ltvMpc
     _stage_entry = False             # ltvMpc: the data is kept in stage form and goes through the stage entry points
 
     N_LEVELS, RHO_STEP = 7, 5.0      # adaptive penalty: rho * 5^(l - 3), l = 0..6  (OSQP changes rho only by factors >= 5)
+
+    _SOFT = ("x_soft_l1", "x_soft_l2", "u_soft_l1", "u_soft_l2")
+    N_MAX = 75   # the 16-lanes-per-instance kernels: 4 instances x N stages x 64 doubles of LDS <= 150 KiB
+
+    def soften(self, x_soft_l1=None, x_soft_l2=None, u_soft_l1=None, u_soft_l2=None):
+        """
+        Soft box constraints (extension; zm_mpc_solve_soft_f64, zm_mpc_closed_loop_soft_f64).  Returns self:
+
+            prob = lqrMpc(A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub).soften(x_soft_l1=l1)
+
+        x_soft_l1, x_soft_l2 (n,), u_soft_l1, u_soft_l2 (m,) -- or (..., n) / (..., m) with leading axes that broadcast to the problem
+        shape `P` of an object with per-problem data -- are penalty weights per component, constant over the stages, with ltvMpc's
+        meaning and checks: with d the distance of a component of x_k (k >= 1) or u_k from its box the cost gains l1 d + l2 d^2 and the
+        bounds of that component no longer constrain it; l1 = +inf (the default of a weight never given) keeps the component hard, and
+        l2 must be 0 there.  `solve` then solves from an x0 outside the box in a soft component, where a hard one is "infeasible" as
+        before; `simulate` does not clip the soft state components (see there).  With an l1 above the hard problem's multipliers the
+        hard solution comes back whenever there is one; with every l1 = +inf the results are those of the object before `soften`, bit
+        for bit.
+
+        A later call replaces the weights it names and keeps the others.  Nothing is launched: the tables depend on the problem and the
+        penalty only and stay, and so does the warm-start workspace (as after ltvMpc.update with new weights).
+
+        A softened object runs on the 16-lanes-per-instance kernels alone: ValueError, before anything touches a device, if the compiled
+        shape has n + m > 16 (the (24, 8) embedding) or N > 75.  ZOPT_AMD_MPC_PATH does not apply to it.
+        """
+        if self.n + self.m > 16:
+            raise ValueError(f"lqrMpc.soften: (n={self._n_user}, m={self._m_user}) runs in the ({self.n}, {self.m}) kernels, beyond the "
+                             f"16-lanes-per-instance kernels that take soft weights (n <= 12, m <= 4)")
+        if self.N > self.N_MAX:
+            raise ValueError(f"lqrMpc.soften: N={self.N} beyond the horizons whose iterates fit LDS (N <= {self.N_MAX}), which the kernels "
+                             f"that take soft weights need")
+        new = {k: X for k, X in zip(self._SOFT, (x_soft_l1, x_soft_l2, u_soft_l1, u_soft_l2)) if X is not None}
+        given = {**(self._soft or dict.fromkeys(self._SOFT)), **new}
+        l1, l2 = self._soft_stacked("lqrMpc.soften", given)
+        self._soft, self.soft_l1, self.soft_l2 = given, l1, l2
+        if self._dev is not None and "soft_l1" in self._dev:
+            for k, X in (("soft_l1", l1), ("soft_l2", l2)):
+                self._dev[k].copy_(arr.to_device(X.reshape(self._dev[k].shape), torch.float64, self._dev[k].device))
+        return self
+
+    def _soft_stacked(self, who, given):
+        """(l1, l2), each P + (n + m,) in the kernels' stacked layout [x ; u] of the compiled shape, from the four weights as given (None:
+        l1 = +inf, l2 = 0).  A padded component is hard: l1 = +inf, l2 = 0."""
+        P = () if self.P is None else self.P   # (lqrMpc without per-problem data: one row)
+        l1, l2 = np.full(P + (self.n + self.m,), np.inf), np.zeros(P + (self.n + self.m,))
+        for name, at, k in (("x_soft_l1", 0, self._n_user), ("x_soft_l2", 0, self._n_user), ("u_soft_l1", self.n, self._m_user),
+                            ("u_soft_l2", self.n, self._m_user)):
+            if given[name] is None:
+                continue
+            w = _host_f64(given[name])
+            try:
+                ok = w.ndim >= 1 and w.shape[-1] == k and np.broadcast_shapes(w.shape[:-1], P) == P
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ValueError(f"{who}: {name} has shape {w.shape}, expected (..., {k}) with leading axes that broadcast to the problem "
+                                 f"shape {P}")
+            if np.any(np.isnan(w)) or np.any(w < 0):
+                raise ValueError(f"{who}: {name} has a negative or NaN entry: a penalty weight is >= 0 (l1 = +inf: a hard component)")
+            if name.endswith("l2") and not np.all(np.isfinite(w)):
+                raise ValueError(f"{who}: {name} has a non-finite entry: the quadratic weight is finite (a hard component is l1 = +inf)")
+            (l1 if name.endswith("l1") else l2)[..., at:at + k] = w
+        if np.any((l2 > 0) & np.isinf(l1)):
+            raise ValueError(f"{who}: a quadratic weight l2 > 0 on a component whose l1 is +inf (hard): give that component a finite l1 "
+                             f"(0 for a purely quadratic penalty)")
+        return l1, l2
 
     def _device_problem_batched(self, rho, adaptive):
         """Device copies of the per-problem data and their tables: ONE setup launch for every (problem, penalty level)."""
@@ -178,9 +245,13 @@ class lqrMpc():
         """(device data, (K, Minv, n_levels, level0, rho per problem | None, ...), number of problems -- 0: the one shared problem)"""
         if self.P is None:
             d, tabs = self._device_problem(rho, adaptive)
-            return d, tabs + (None,), 0
-        d, tabs = self._device_problem_batched(rho, adaptive)
-        return d, tabs, int(np.prod(self.P))
+            tabs, Pn = tabs + (None,), 0
+        else:
+            d, tabs = self._device_problem_batched(rho, adaptive)
+            Pn = int(np.prod(self.P))
+        if self._soft is not None and "soft_l1" not in d:   # (a softened lqrMpc: the weights beside the data, one row per problem)
+            d.update({k: arr.to_device(getattr(self, k).reshape(max(Pn, 1), -1), torch.float64, d["A"].device) for k in ("soft_l1", "soft_l2")})
+        return d, tabs, Pn
 
     def _batch_shape(self, x0, arrays, suffix="", plural=True, own=False, plan=None):
         """The batch shape `lead` that x0 (..., n) and the per-instance `arrays` -- (name, X | None, (rows, user width), padded width)
@@ -291,7 +362,7 @@ class lqrMpc():
         rho_key = rho if self.P is None else rho.tobytes()
 
         # 4. one row per instance and the instance -> problem map
-        dev, dx0, (dxr, dur), prob = self._device_rows(lead, Bn, d, tracking, x0, refs)
+        dev, dx0, (dxr, dur), prob = self._device_rows(lead, Bn, d, tracking or self._soft is not None, x0, refs)
 
         # 5. workspace (y, lam, kf, rv; tracking: a fifth block for the linear term of the cost) and the warm start from it.  A plain solve
         # is keyed on the number of instances, the others on the batch shape, tracking as a kind of its own.
@@ -326,6 +397,9 @@ class lqrMpc():
             else:
                 rc = _lib.lib().zm_mpc_solve_ltv_f64(*_ptrs(d, "A B c", ABt), *_ptrs(d, "Q R Qf", K, Mi, D), *opts,
                                                       *_ptrs(d, "", dxr, dur, drho, prob), Pn, *out)
+        elif self._soft is not None:   # (soften: the tracking entry's arguments with the weights behind the box; a reference or none)
+            rc = _lib.lib().zm_mpc_solve_soft_f64(*_ptrs(d, "A B Q R Qf", K, Mi), *opts, *_ptrs(d, "", dxr, dur),
+                                                   rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, *out)
         elif tracking:
             rc = _lib.lib().zm_mpc_solve_tracking_f64(*_ptrs(d, "A B Q R Qf", K, Mi), *opts, *_ptrs(d, "", dxr, dur),
                                                        rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, *out)
@@ -353,7 +427,7 @@ class lqrMpc():
 
             x = x0
             for s in range(steps):
-                if clip_tol is not None: x = clip(x, x_lb + clip_tol, x_ub - clip_tol)
+                if clip_tol is not None: x = clip(x, x_lb + clip_tol, x_ub - clip_tol)      # (after `soften`: the hard components only)
                 xTraj[s] = x
                 u, traj, status[s] = self.solve(x, warm_start=(False if s == 0 else W), window s of the references, **solver_opts)
                 uTraj[s] = u;  iterations[s] = self.last_iterations
@@ -361,7 +435,9 @@ class lqrMpc():
             xTraj[steps] = clip(x, ...) if clip_tol is not None else x
 
         with the results that loop gives, whatever the status of a step (a step that is not "optimal" still leaves a rollout, and the step
-        after it starts cold).  A regulator run is one launch of a kernel that has the step loop inside (a wave goes on to its next step
+        after it starts cold).  After `soften`, `clip` moves the HARD state components only: a component with a finite x_soft_l1 is never
+        clipped, so xTraj[s + 1] is the plant's state there, outside the box if a disturbance has pushed it out, and the solve from it
+        brings it back.  A regulator run is one launch of a kernel that has the step loop inside (a wave goes on to its next step
         as soon as its own four instances are through); tracking runs, (n, m) beyond the 16-lane kernels and horizons beyond LDS are a
         queue of launches without a host round trip.  `simulate` has its own workspace: a `solve` after it (warm start, `last_iterations`,
         `last_residuals`) behaves as if it had not happened.
@@ -401,16 +477,19 @@ class lqrMpc():
         d, (K, Mi, n_levels, level0, drho, *_), Pn = self._problem_on_device(rho, adaptive)
 
         # 3. one row per instance (the disturbance step-major) and the instance -> problem map; device placement as in `solve`
-        dev, dx0, (dw, dxr, dur), prob = self._device_rows(lead, Bn, d, tracking, x0, per)
+        dev, dx0, (dw, dxr, dur), prob = self._device_rows(lead, Bn, d, tracking or self._soft is not None, x0, per)
         dw = None if dw is None else dw.transpose(0, 1).contiguous()
 
         # 4. outputs (step-major on the device) and the run's own workspace
         xs, us, st, its, xp, up, ws = _run_buffers(S, Bn, N, n, m, dev, return_predictions, tracking)
 
-        # 5. the C call
+        # 5. the C call (after `soften`: the sibling entry, the weights behind the box)
         if Bn > 0:
-            rc = _lib.lib().zm_mpc_closed_loop_f64(
-                *_ptrs(d, "A B Q R Qf", K, Mi), n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, "x_lb x_ub u_lb u_ub", dx0, dxr, dur),
+            run, box = _lib.lib().zm_mpc_closed_loop_f64, "x_lb x_ub u_lb u_ub"
+            if self._soft is not None:
+                run, box = _lib.lib().zm_mpc_closed_loop_soft_f64, box + " soft_l1 soft_l2"
+            rc = run(
+                *_ptrs(d, "A B Q R Qf", K, Mi), n_levels, level0, self.RHO_STEP, alpha, *_ptrs(d, box, dx0, dxr, dur),
                 S + N, S + N - 1, rho if self.P is None else 0.0, *_ptrs(d, "", drho, prob), Pn, eps_abs, eps_rel, eps_pinf, max_iter, warm,
                 S, clip, *_ptrs(d, "", dw, ws, xs, us, st, its, xp, up), Bn, N, n, m, ctypes.c_void_p(arr.stream_ptr(dx0)))
             _lib.check(rc, "lqrMpc.simulate")
@@ -458,11 +537,7 @@ class ltvMpc(lqrMpc):
 
     _LTV = True
     _COMPILED = tuple(s for s in lqrMpc._COMPILED if s[0] + s[1] <= 16)
-    N_MAX = 75   # 4 instances x N stages x 64 doubles of LDS <= 150 KiB
-
     _STAGED = {"Q": 1, "R": 0, "x_lb": 1, "x_ub": 1, "u_lb": 0, "u_ub": 0}   # what may vary by stage: rows beyond N of its stage axis
-
-    _SOFT = ("x_soft_l1", "x_soft_l2", "u_soft_l1", "u_soft_l2")
 
     def __init__(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf=None, c=None, stage_varying=(), x_soft_l1=None, x_soft_l2=None,
                  u_soft_l1=None, u_soft_l2=None):
@@ -527,33 +602,6 @@ class ltvMpc(lqrMpc):
         self._soft = dict(zip(self._SOFT, weights))
         self.soft_l1, self.soft_l2 = self._soft_stacked("ltvMpc", self._soft)
         self._stage_entry = True
-
-    def _soft_stacked(self, who, given):
-        """(l1, l2), each P + (n + m,) in the kernels' stacked layout [x ; u] of the compiled shape, from the four weights as given (None:
-        l1 = +inf, l2 = 0).  A padded component is hard: l1 = +inf, l2 = 0."""
-        P = self.P
-        l1, l2 = np.full(P + (self.n + self.m,), np.inf), np.zeros(P + (self.n + self.m,))
-        for name, at, k in (("x_soft_l1", 0, self._n_user), ("x_soft_l2", 0, self._n_user), ("u_soft_l1", self.n, self._m_user),
-                            ("u_soft_l2", self.n, self._m_user)):
-            if given[name] is None:
-                continue
-            w = _host_f64(given[name])
-            try:
-                ok = w.ndim >= 1 and w.shape[-1] == k and np.broadcast_shapes(w.shape[:-1], P) == P
-            except ValueError:
-                ok = False
-            if not ok:
-                raise ValueError(f"{who}: {name} has shape {w.shape}, expected (..., {k}) with leading axes that broadcast to the problem "
-                                 f"shape {P}")
-            if np.any(np.isnan(w)) or np.any(w < 0):
-                raise ValueError(f"{who}: {name} has a negative or NaN entry: a penalty weight is >= 0 (l1 = +inf: a hard component)")
-            if name.endswith("l2") and not np.all(np.isfinite(w)):
-                raise ValueError(f"{who}: {name} has a non-finite entry: the quadratic weight is finite (a hard component is l1 = +inf)")
-            (l1 if name.endswith("l1") else l2)[..., at:at + k] = w
-        if np.any((l2 > 0) & np.isinf(l1)):
-            raise ValueError(f"{who}: a quadratic weight l2 > 0 on a component whose l1 is +inf (hard): give that component a finite l1 "
-                             f"(0 for a purely quadratic penalty)")
-        return l1, l2
 
     def _init_stage_varying(self, A, B, Q, R, N, x_lb, x_ub, u_lb, u_ub, Qf, c):
         """The constructor with a non-empty `stage_varying`: the same checks, per stage where an array has a stage axis."""
@@ -736,6 +784,10 @@ class ltvMpc(lqrMpc):
                 d["lo" if name == "u_lb" else "hi"][:, :, ns:ns + m].copy_(t.expand((Pn, N, m)))
         if "Q" in new or "R" in new:
             self._tables = {}
+
+    def soften(self, *args, **kwargs):
+        raise TypeError("ltvMpc.soften: ltvMpc takes its soft weights as constructor arguments (x_soft_l1, x_soft_l2, u_soft_l1, "
+                        "u_soft_l2) and new ones through update(x_soft_l1=..., ...)")
 
     def simulate(self, *args, **kwargs):
         raise NotImplementedError("ltvMpc.simulate: a moving window needs new tables at every step; loop over update() and solve(), or -- "
