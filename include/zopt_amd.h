@@ -533,11 +533,21 @@ int zm_ilqr_solve_tracking_trace_f64(const zm_model_t* model, const zm_trackcost
  *   DDP backward step:      the same step after Q_xx, Q_ux, Q_uu have received the blocks of the PD-projected (1e-3)
  *                           vf_zz = sum_i v_x[i] d2f_i/dz2, as in zm_ddp_backward_f64.
  * lb, ub: device pointers to m doubles per row, row t * stride belongs to trajectory t: stride 0 = one box for every trajectory,
- * stride m = a box per trajectory.  An entry may be -inf / +inf; lb <= ub is the caller's to ensure.  Shapes: n <= 12, m <= 4. */
+ * stride m = a box per trajectory.  An entry may be -inf / +inf; lb <= ub is the caller's to ensure.  Shapes: n <= 12, m <= 4.
+ * Stage-varying bounds (step_stride): the bounds of trajectory t at step k (the box of u_k, k = 0..T-1) are the m doubles at
+ *     lb + t * stride + k * step_stride,   ub + t * stride + k * step_stride.
+ *   step_stride == 0: one box for the whole horizon (the layout above; a struct built from three fields leaves it zero),
+ *                     stride is 0 or m;
+ *   step_stride == m: a row per step, (T, m) per trajectory; stride is 0 (one schedule for every trajectory) or T * m (a schedule
+ *                     per trajectory), T the horizon of the call.
+ * Every other (stride, step_stride) pair is ZM_EINVAL, from host code before anything is launched.  Every *_box_* entry takes both
+ * forms; the *_state_* entries (state box around an input box) take step_stride == 0 only (ZM_EUNSUPPORTED otherwise).  With the same
+ * row repeated over the steps the stage form gives the results of the constant form bit for bit. */
 typedef struct zm_inputbox_t {
     const double* lb;
     const double* ub;
     int64_t stride;
+    int64_t step_stride;
 } zm_inputbox_t;
 
 /* The box-QP of the backward step, batched, one problem per lane (test entry of the device routine the sweep runs wave-uniform):

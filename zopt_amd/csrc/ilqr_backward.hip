@@ -166,6 +166,9 @@ struct BoxStep {
     const double* pu;      // u_k of the step (the current trajectory's input), walks back by m
     double lb[4], ub[4];   // the trajectory's bounds; -inf / +inf beyond m
     int capped;            // steps of this trajectory whose QP ended at its pass cap
+    // STG (stage-varying bounds): lb / ub above are not held; row k of the trajectory's schedule is read with u_k
+    const double* plb;     // lb_k, ub_k of the step, walk back by m
+    const double* pub;
 };
 
 // ZIN (MODE 2, the DMA kernel): the caller has contracted vf_zz = sum_i v_x[i] d2f_i/dz2 already (operands in its LDS ring) and
@@ -174,7 +177,9 @@ struct BoxStep {
 // components are zero, the others solve the system whose clamped rows and columns are the identity's; v_x' = Q_x + Q_ux^T l_k.
 // In MODE 2 Q_xx, Q_ux, Q_uu carry the projected vf_zz blocks; nothing else differs.
 // PEN (MODE 0): the step's cost Hessian is c_xx + diag h_k, formed before anything is accumulated onto it.
-template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false, bool PEN = false>
+// STG (with BOX): the bounds are those of the step, lo = lb_k - u_k, hi = ub_k - u_k: row k is fetched with u_k at the head of the step
+// (every lane the same row) and is in flight under the same products; nothing of the bounds is held across steps.
+template <int KS, int MODE, bool PREFETCH, bool ZIN = false, bool BOX = false, bool PEN = false, bool STG = false>
 __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], IlqrStepRegs<KS>& d, IlqrAddr<KS>& a,
                                           double* sm, const int g, const int c, const int ob0, const int ob1,
                                           const int ob2, const int ob3, const int oqa, double* jA, const int n,
@@ -182,11 +187,22 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
                                           BoxStep* bx = nullptr, PenStep* pn = nullptr) {
     constexpr int NP = 4 * KS;
     static_assert(!BOX || MODE != 1, "the box-constrained step is the iLQR or the DDP one");
+    static_assert(!STG || (BOX && !PEN), "stage-varying bounds: the box step without a state-box penalty");
     double uk[4] = {0.0, 0.0, 0.0, 0.0};
+    double lbk[STG ? 4 : 1], ubk[STG ? 4 : 1];
     if constexpr (BOX) {   // in flight under the products of G (MODE 2: and under the projection); every lane reads the same row
 #pragma unroll
         for (int i = 0; i < 4; ++i) uk[i] = bx->pu[i < m ? i : 0];
         bx->pu -= m;
+    }
+    if constexpr (STG) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            lbk[i] = bx->plb[i < m ? i : 0];
+            ubk[i] = bx->pub[i < m ? i : 0];
+        }
+        bx->plb -= m;
+        bx->pub -= m;
     }
     // MODE 2: vf_zz = sum_i v_x[i] * d2f_i/dz2, PD-projected, as extra accumulator init
     d4 pz = zero4();
@@ -298,8 +314,13 @@ __device__ __forceinline__ void ilqr_step(double (&Vxx)[KS], double (&vxr)[KS], 
         double lo[4], hi[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            lo[i] = bx->lb[i] - uk[i];
-            hi[i] = bx->ub[i] - uk[i];
+            if constexpr (STG) {
+                lo[i] = (i < m ? lbk[i] : -__builtin_inf()) - uk[i];
+                hi[i] = (i < m ? ubk[i] : __builtin_inf()) - uk[i];
+            } else {
+                lo[i] = bx->lb[i] - uk[i];
+                hi[i] = bx->ub[i] - uk[i];
+            }
         }
         bool capped;
         boxqp4(S, gq, lo, hi, dq, cl, capped);
@@ -406,20 +427,28 @@ __global__ __launch_bounds__(64, 2) void ilqr_backward_t16_f64(
 }
 
 // The hooks of the body header for the two kernels with input bounds (ilqr_backward_box_t16_f64, ddp_backward_box_t16_f64)
+// (STG: the bounds are a row per step, m doubles apart -- the one step stride zm_inputbox_t takes, so the kernels keep the constant
+//  form's argument list; the sweep starts at row T - 1 and walks back)
 #define ZM_BOX_SETUP                                                              \
     bx.pu = uTraj + last * m;                                                     \
     bx.capped = 0;                                                                \
-    for (int i = 0; i < 4; ++i) {                                                 \
-        bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();           \
-        bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();            \
+    if constexpr (STG) {                                                          \
+        bx.plb = lb + traj * bstride + (long)(T - 1) * m;                         \
+        bx.pub = ub + traj * bstride + (long)(T - 1) * m;                         \
+    } else {                                                                      \
+        for (int i = 0; i < 4; ++i) {                                             \
+            bx.lb[i] = (i < m) ? lb[traj * bstride + i] : -__builtin_inf();       \
+            bx.ub[i] = (i < m) ? ub[traj * bstride + i] : __builtin_inf();        \
+        }                                                                         \
     }
-#define ZM_BOX_FLAGS , false, true
+#define ZM_BOX_FLAGS , false, true, false, STG
 #define ZM_BOX_ARGS , d4{0.0, 0.0, 0.0, 0.0}, nullptr, &bx
 
 // The same kernel (MODE 0) with input bounds lb <= u <= ub: per step it also reads u_k of the current trajectory and runs the box-QP
 // before the gain solve.  Bounds: row traj * bstride of lb / ub (bstride 0: one box for every trajectory).  qp_capped (optional):
-// += the steps of the trajectory whose QP ended at its pass cap.
-template <int KS>
+// += the steps of the trajectory whose QP ended at its pass cap.  STG: stage-varying bounds, row traj * bstride + k * m at step k
+// (zm_inputbox_t.step_stride == m); the constant form is the kernel's other instantiation.
+template <int KS, bool STG>
 __global__ __launch_bounds__(64, 2) void ilqr_backward_box_t16_f64(
     const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
     const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
@@ -447,8 +476,8 @@ constexpr int DDP_BOX_WAVES = (KS == 1) ? 2 : 1;
 
 // The DDP sweep (MODE 2) with the same input bounds: per step the contraction and PD projection of vf_zz, then the box step above on
 // the augmented Q.  Second derivatives as ilqr_backward_t16_f64 takes them: the full tensors, f_ux = f_uu = nullptr (control-affine),
-// or the packed pairs Hpk / ptab.
-template <int KS>
+// or the packed pairs Hpk / ptab.  STG: as ilqr_backward_box_t16_f64.
+template <int KS, bool STG>
 __global__ __launch_bounds__(64, DDP_BOX_WAVES<KS>) void ddp_backward_box_t16_f64(
     const double* __restrict__ f_x, const double* __restrict__ f_u, const double* __restrict__ c_x,
     const double* __restrict__ c_u, const double* __restrict__ c_xx, const double* __restrict__ c_ux,
@@ -1061,15 +1090,20 @@ extern "C" int zm_ilqr_backward_box_list_f64(const double* f_x, const double* f_
     if (sweep_prologue(&rc, who, who, list, count, f_x && f_u && c_x && c_u && c_xx && c_ux && c_uu && vf_x && vf_xx && uTraj && l && L,
                        batch, T, n, m))
         return rc;
-    if (const int rb = zm::box_check(box, m, who)) return rb;
+    if (const int rb = zm::box_check(box, m, T, who)) return rb;
     const zm::TrajList tl{(const int*)list, (long)count};
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
     hipStream_t st = (hipStream_t)stream;
     const int sh = shared_hessian ? 1 : 0;
     zm::with_ks(n, [&](auto ks) {
-        hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu,
-                           vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n, (const int*)active, sh, l, L,
-                           (int*)qp_capped, T, n, m, tl);
+        if (box->step_stride != 0)
+            hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<decltype(ks)::value, true>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx,
+                               c_ux, c_uu, vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, (long)n,
+                               (long)n * n, (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl);
+        else
+            hipLaunchKernelGGL((zm::ilqr_backward_box_t16_f64<decltype(ks)::value, false>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx,
+                               c_ux, c_uu, vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, (long)n, (long)n * n,
+                               (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl);
     });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
@@ -1097,7 +1131,7 @@ extern "C" int zm_ilqr_backward_state_list_f64(const double* f_x, const double* 
         return rc;
     if ((box != nullptr) != (uTraj != nullptr)) return zm::set_error(ZM_EINVAL, "%s: box and uTraj go together (both or neither)", who);
     if (box)
-        if (const int rb = zm::box_check(box, m, who)) return rb;
+        if (const int rb = zm::box_check_constant(box, m, T, who)) return rb;
     const zm::TrajList tl{(const int*)list, (long)count};
     const dim3 grid((unsigned)(tl.list ? tl.count : batch)), block(64);
     hipStream_t st = (hipStream_t)stream;
@@ -1225,9 +1259,14 @@ static int launch_ddp_box(const double* f_x, const double* f_u, const zm::DdpTen
     hipStream_t st = (hipStream_t)stream;
     const int sh = shared_hessian ? 1 : 0;
     zm::with_ks(n, [&](auto ks) {
-        hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<decltype(ks)::value>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx, c_ux, c_uu,
-                           vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux, z.f_uu, (long)n, (long)n * n,
-                           (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab);
+        if (box->step_stride != 0)
+            hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<decltype(ks)::value, true>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx,
+                               c_ux, c_uu, vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux,
+                               z.f_uu, (long)n, (long)n * n, (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab);
+        else
+            hipLaunchKernelGGL((zm::ddp_backward_box_t16_f64<decltype(ks)::value, false>), grid, block, 0, st, f_x, f_u, c_x, c_u, c_xx,
+                               c_ux, c_uu, vf_x, vf_xx, uTraj, box->lb, box->ub, (long)box->stride, z.f_xx, z.f_ux, z.f_uu, (long)n,
+                               (long)n * n, (const int*)active, sh, l, L, (int*)qp_capped, T, n, m, tl, z.Hpk, z.ptab);
     });
     ZM_HIP_CHECK(hipGetLastError());
     return ZM_OK;
@@ -1246,7 +1285,7 @@ extern "C" int zm_ddp_backward_box_list_f64(const double* f_x, const double* f_u
                        T, n, m, false, ZM_DDP_NULL_NOTE))
         return rc;
     if ((int64_t)n * n * n >= (int64_t)1 << 31) return zm::set_error(ZM_EUNSUPPORTED, "%s: n too large", who);
-    if (const int rb = zm::box_check(box, m, who)) return rb;
+    if (const int rb = zm::box_check(box, m, T, who)) return rb;
     return launch_ddp_box(f_x, f_u, zm::DdpTensors{f_xx, f_ux, f_uu}, c_x, c_u, c_xx, c_ux, c_uu, vf_x, vf_xx,
                           uTraj, box, zm::TrajList{(const int*)list, (long)count}, active, shared_hessian, l, L, qp_capped, batch, T, n,
                           m, stream);
@@ -1275,7 +1314,7 @@ extern "C" int zm_ddp_backward_pairs_box_list_f64(const zm_model_t* model, const
         return rc;
     const zm::PairTab pt = zm::model_pair_table(model->kind);
     if (pt.n < 1) return zm::set_error(ZM_EUNSUPPORTED, "%s: the model declares no Hessian pairs", who);
-    if (const int rb = zm::box_check(box, m, who)) return rb;
+    if (const int rb = zm::box_check(box, m, T, who)) return rb;
     return launch_ddp_box(f_x, f_u, zm::DdpTensors{nullptr, nullptr, nullptr, H, pt}, c_x, c_u,
                           c_xx, c_ux, c_uu, vf_x, vf_xx, uTraj, box, zm::TrajList{(const int*)list, (long)count}, active,
                           shared_hessian, l, L, qp_capped, batch, T, n, m, stream);

@@ -477,7 +477,7 @@ static int ilqr_solve_impl(const SolveCall& c) {
     if (ck.box) {
         if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
             return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_box_f64: (n=%d, m=%d) not covered (input box: n<=12, m<=4)", n, m);
-        if (const int rb = zm::box_check(ck.box, m, "zm_ilqr_solve_box_f64")) return rb;
+        if (const int rb = zm::box_check(ck.box, m, T, "zm_ilqr_solve_box_f64")) return rb;
         if (ck.qp_capped && !ck.pen) ZM_HIP_CHECK(hipMemsetAsync(ck.qp_capped, 0, sizeof(int32_t) * batch, (hipStream_t)c.stream));
     }
     if (ck.pen && (ddp || n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
@@ -797,7 +797,7 @@ extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_q
         return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (state box: n<=12, m<=4)", who, n, m);
     if (const int rc = zm::statebox_check(sbox, n, who)) return rc;
     if (box)
-        if (const int rc = zm::box_check(box, m, who)) return rc;
+        if (const int rc = zm::box_check_constant(box, m, T, who)) return rc;
     if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
     zm_model_t md;
     if (const int rc = zm::model_check(model, who, &md)) return rc;

@@ -24,9 +24,11 @@ namespace zm {
 // TRK: tracking cost -- the cost of step k is that of (x_k - xr_k, u_k - ur_k), rows of trajectory `t` of `tr`
 // BOX: u_k is clipped into [lb, ub], the bounds of trajectory `t` of `bx` (the clip lets a NaN through); the cost may then be absent
 // (cs == nullptr) also in the TRK form
+// STG (with BOX): the bounds change along the horizon -- step k clips into row k of the trajectory's schedule (bx.step doubles apart),
+// read inside the step loop with the step's policy data; the constant form loads its one row before the loop
 // PEN: the augmented-Lagrangian penalty of the state box `pr` on the rows k = 1..T goes into an accumulator of its own (k ascending,
 // i ascending) and joins the cost once, at the end; *jcost (optional) <- the cost without it
-template <bool STORE, bool TRK = false, bool BOX = false, bool PEN = false>
+template <bool STORE, bool TRK = false, bool BOX = false, bool PEN = false, bool STG = false>
 __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_quadcost_t* cs, const double alpha,
                                               const double* __restrict__ x0, const double* __restrict__ l,
                                               const double* __restrict__ L, const double* __restrict__ xPrev,
@@ -47,7 +49,8 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
         }
     }
     double blo[BOX ? MAXM : 1], bhi[BOX ? MAXM : 1];
-    if constexpr (BOX) {
+    static_assert(!STG || (BOX && !PEN), "stage-varying bounds: the box form without a state-box penalty");
+    if constexpr (BOX && !STG) {
 #pragma unroll
         for (int i = 0; i < MAXM; ++i) {
             blo[i] = (i < m) ? bx.lb[t * bx.stride + i] : -__builtin_inf();
@@ -65,6 +68,13 @@ __device__ __forceinline__ double rollout_one(const zm_model_t& md, const zm_qua
     for (int k = 0; k < T; ++k) {
         const double* Lk = L + (long)k * m * n;
         const double* xp = xPrev + (long)k * n;
+        if constexpr (STG) {   // row k of the schedule: independent of x, in flight under the policy product
+#pragma unroll
+            for (int i = 0; i < MAXM; ++i) {
+                blo[i] = (i < m) ? bx.lb[t * bx.stride + (long)k * bx.step + i] : -__builtin_inf();
+                bhi[i] = (i < m) ? bx.ub[t * bx.stride + (long)k * bx.step + i] : __builtin_inf();
+            }
+        }
         double dx[MAXN];
 #pragma unroll
         for (int j = 0; j < MAXN; ++j) dx[j] = (j < n) ? (x[j] - xp[j]) : 0.0;
@@ -175,10 +185,11 @@ __global__ __launch_bounds__(64) void rollout_linesearch_track_kernel(const zm_m
 #undef ZM_PEN_STORE_ARGS
 // the same line search with input bounds (zm_inputbox_t), on either cost: the tracking form, whose reference is null for a
 // zm_quadcost_t (the differences are then the values themselves, bit for bit)
-#define ZM_TRK_FLAG , true, true
+// STG: the bounds are a row per step (zm_inputbox_t.step_stride == m); the constant form is the kernel's other instantiation
+#define ZM_TRK_FLAG , true, true, false, STG
 #define ZM_TRK_ARGS , tr, t, bx
 #define ZM_PEN_STORE_ARGS
-template <int NA>
+template <int NA, bool STG>
 __global__ __launch_bounds__(64) void rollout_linesearch_box_kernel(const zm_model_t md, const zm_quadcost_t cost, const bool has_cost,
                                                                     const TrackRef tr, const BoxRef bx, const double* __restrict__ x0,
                                                                     const double* __restrict__ l, const double* __restrict__ L,
@@ -273,7 +284,7 @@ static int rollout_impl(const char* who, const zm_model_t* model, const zm_quadc
     if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
     if (pen) {
         if (pen->box)
-            if (const int rc = zm::box_check(pen->box, md.m, who)) return rc;
+            if (const int rc = zm::box_check_constant(pen->box, md.m, T, who)) return rc;
         if (const int rc = zm::statebox_check(pen->sbox, md.n, who)) return rc;
         if (list && (count < 0 || count > batch)) return zm::set_error(ZM_EINVAL, "%s: bad list length", who);
     }
@@ -327,14 +338,19 @@ static int rollout_impl(const char* who, const zm_model_t* model, const zm_quadc
         return ZM_OK;
     }
     if (box) {
-        if (n_alpha == 1)
-            hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<1>), dim3((unsigned)((nslot + 63) / 64)), dim3(64), 0, st, md, cs, hc, tr,
-                               *box, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J,
-                               (int*)alpha_idx, (long)batch, T);
-        else
-            hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<16>), dim3((unsigned)((nslot + 3) / 4)), dim3(64), 0, st, md, cs, hc, tr,
-                               *box, x0, l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J,
-                               (int*)alpha_idx, (long)batch, T);
+#define ZM_LAUNCH_BOX(NA_, STG_, BLOCKS_)                                                                                                 \
+    hipLaunchKernelGGL((zm::rollout_linesearch_box_kernel<NA_, STG_>), dim3((unsigned)(BLOCKS_)), dim3(64), 0, st, md, cs, hc, tr, *box, x0, \
+                       l, L, xPrev, uPrev, alphas, n_alpha, act, (const int*)list, (long)count, xTraj, uTraj, J, (int*)alpha_idx,          \
+                       (long)batch, T)
+        const bool stg = box->step != 0;
+        if (n_alpha == 1) {
+            if (stg) ZM_LAUNCH_BOX(1, true, (nslot + 63) / 64);
+            else ZM_LAUNCH_BOX(1, false, (nslot + 63) / 64);
+        } else {
+            if (stg) ZM_LAUNCH_BOX(16, true, (nslot + 3) / 4);
+            else ZM_LAUNCH_BOX(16, false, (nslot + 3) / 4);
+        }
+#undef ZM_LAUNCH_BOX
         ZM_HIP_CHECK(hipGetLastError());
         return ZM_OK;
     }
@@ -411,7 +427,7 @@ extern "C" int zm_rollout_linesearch_box_list_f64(const zm_model_t* model, const
     zm::CostRef ck;
     if (const int rc = zm::cost_resolve(cost, track, zm::CostArg::at_most_one, who, &ck)) return rc;
     if (!model) return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
-    if (const int rc = zm::box_check(box, zm::model_sized(*model).m, who)) return rc;
+    if (const int rc = zm::box_check(box, zm::model_sized(*model).m, T, who)) return rc;
     if (batch == 0) return ZM_OK;
     const zm::BoxRef bx = zm::box_ref(*box);
     return rollout_impl(ROLLOUT, model, ck.weights(), x0, l, L, xPrev, uPrev, alphas, n_alpha, active, list, count, xTraj, uTraj, J,

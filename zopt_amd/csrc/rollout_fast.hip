@@ -19,6 +19,7 @@
 #include "zm_common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace zm {
 
@@ -179,8 +180,29 @@ __device__ __forceinline__ void ref_diff(double (&d)[K], const double (&z)[K], c
     }
 }
 
+// Stage-varying bounds (STG): a step's row [lb_k | ub_k] is 2 RM = 8 doubles.  It travels like the reference row: one more rotating
+// register, loaded by the group with one coalesced load per step (lanes 0..3 from lb's row k, 4..7 from ub's; lanes 8..15 repeat
+// them), three steps ahead, and read by DPP broadcasts -- no load on the step's chain.  The broadcast is fma(bound, 1, -0.0): the bound
+// itself, bit for bit (-0.0 is the additive identity of every double, -0.0, the infinities and subnormals included).
+// b <- bounds element E of the row held in r
+template <int E>
+__device__ __forceinline__ double box_bcast(const double one, const double& r) {
+    double b = -0.0;
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(b) : "v"(r), "v"(one), "i"(E));
+    return b;
+}
+// u[i] <- clip(u[i], lb_k[i], ub_k[i]) from the row held in r
+template <int I = 0>
+__device__ __forceinline__ void box_clip_row(double (&u)[RM], const double one, const double& r) {
+    if constexpr (I < RM) {
+        u[I] = clip_nan(u[I], box_bcast<I>(one, r), box_bcast<RM + I>(one, r));
+        box_clip_row<I + 1>(u, one, r);
+    }
+}
+
 // BOX: the inputs are clipped into the trajectory's bounds (eight more registers per lane; the clip lets a NaN through)
-template <int KIND, bool DIAG, bool ALL, bool TRK = false, bool BOX = false>
+// STG (with BOX): into the bounds of the step, see above (four rotating registers in place of the eight)
+template <int KIND, bool DIAG, bool ALL, bool TRK = false, bool BOX = false, bool STG = false>
 // (no __restrict__ on the LDS tables: with it the loop-invariant LDS reads of Q, A, B ... are hoisted into registers --
 //  several hundred VGPRs -- instead of being re-read by broadcast every step)
 __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double* Qs, const double* Rs, const double* Qfs,
@@ -236,13 +258,17 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
         }
     }
     double blo[BOX ? RM : 1], bhi[BOX ? RM : 1];
-    if constexpr (BOX) {
+    static_assert(!STG || BOX, "stage-varying bounds are a form of the box kernel");
+    if constexpr (BOX && !STG) {
 #pragma unroll
         for (int i = 0; i < RM; ++i) {
             blo[i] = bx.lb[t * bx.stride + i];
             bhi[i] = bx.ub[t * bx.stride + i];
         }
     }
+    // this lane's element of the bounds rows of trajectory t (STG): lb's on lanes 0..3 (and 8..11), ub's on 4..7 (and 12..15)
+    const double* bp = nullptr;
+    if constexpr (STG) bp = ((a & RM) ? bx.ub : bx.lb) + t * bx.stride + (a & (RM - 1));
     const double* x0t = g.x0 + t * RN;
     double* xo = g.xTraj + t * (T + 1) * RN;
     double* uo = g.uTraj + t * T * RM;
@@ -281,8 +307,19 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
         auto fetch_ref = [&](double& r, const int k) {
             if constexpr (TRK) r = (rp && (a < RN || k < T)) ? rp[(long)k * rst] : 0.0;
         };
-        auto body = [&](PolRegs& cur, PolRegs& ahead, double& rcur, double& rahead, const int k) {
+        // bounds row k (k = 0..T-1)
+        auto fetch_box = [&](double& r, const int k) {
+            if constexpr (STG) r = bp[(long)k * bx.step];
+        };
+        // (STG) the bounds rows rotate with the policy sets: brow[k & 3] holds row k; the step's slot is a compile-time argument
+        // (an empty tag: the four registers are named statically, nothing is indexed at run time)
+        double brow[STG ? 4 : 1];
+        auto body = [&](PolRegs& cur, PolRegs& ahead, double& rcur, double& rahead, const int k, auto slot) {
+            constexpr int bslot = STG ? decltype(slot)::value : 0;
             if (k + 3 < T) fetch(ahead, k + 3);
+            if constexpr (STG) {
+                if (k + 3 < T) fetch_box(brow[(bslot + 3) & 3], k + 3);
+            }
             if constexpr (TRK) {
                 if (k + 3 <= T) fetch_ref(rahead, k + 3);
             }
@@ -290,7 +327,10 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
             double dx[RN];
             pol_dx(dx, x, neg1, cur);
             pol_controls(u, dx, al, one, cur);
-            if constexpr (BOX) {
+            if constexpr (STG) {
+                asm("s_nop 1" : "+v"(brow[bslot]));
+                box_clip_row(u, one, brow[bslot]);
+            } else if constexpr (BOX) {
 #pragma unroll
                 for (int i = 0; i < RM; ++i) u[i] = clip_nan(u[i], blo[i], bhi[i]);
             }
@@ -342,16 +382,21 @@ __device__ __forceinline__ void rollout_ls_body(const FastArgs& g, const double*
         fetch(pa, 0);
         if (T > 1) fetch(pb, 1);
         if (T > 2) fetch(pc, 2);
+        if constexpr (STG) {
+            fetch_box(brow[0], 0);
+            if (T > 1) fetch_box(brow[1], 1);
+            if (T > 2) fetch_box(brow[2], 2);
+        }
         if constexpr (TRK) {
             fetch_ref(ra, 0);
             fetch_ref(rb, 1);               // (T >= 1: row 1 exists, the terminal one at the least)
             if (T > 1) fetch_ref(rc, 2);
         }
         for (int k = 0; k < T; k += 4) {   // rotating sets: no copies
-            body(pa, pd, ra, rd_, k);
-            if (k + 1 < T) body(pb, pa, rb, ra, k + 1);
-            if (k + 2 < T) body(pc, pb, rc, rb, k + 2);
-            if (k + 3 < T) body(pd, pc, rd_, rc, k + 3);
+            body(pa, pd, ra, rd_, k, std::integral_constant<int, 0>{});
+            if (k + 1 < T) body(pb, pa, rb, ra, k + 1, std::integral_constant<int, 1>{});
+            if (k + 2 < T) body(pc, pb, rc, rb, k + 2, std::integral_constant<int, 2>{});
+            if (k + 3 < T) body(pd, pc, rd_, rc, k + 3, std::integral_constant<int, 3>{});
         }
         if constexpr (TRK) {   // the terminal row sits in set T mod 4
             double rT = (T & 3) == 0 ? ra : (T & 3) == 1 ? rb : (T & 3) == 2 ? rc : rd_;
@@ -456,7 +501,8 @@ __global__ __launch_bounds__(64) void rollout_ls_fast_track_kernel(const FastArg
 
 // The tracking kernel's two-pass form with input bounds (zm_inputbox_t); a zm_quadcost_t runs it with a null reference (tr.x == tr.u
 // == nullptr: the differences are the values themselves, bit for bit).
-template <int KIND, bool DIAG_ONLY>
+// STG: the bounds are a row per step (zm_inputbox_t.step_stride == m); the constant form is the kernel's other instantiation.
+template <int KIND, bool DIAG_ONLY, bool STG>
 __global__ __launch_bounds__(64) void rollout_ls_fast_box_kernel(const FastArgs g, const TrackRef tr, const BoxRef bx) {
     __shared__ double Qs[RN * RN], Rs[RM * RM], Qfs[RN * RN];
     __shared__ double As[KIND == ZM_MODEL_LINEAR ? RN * RN : 1], Bs[KIND == ZM_MODEL_LINEAR ? RN * RM : 1];
@@ -479,12 +525,12 @@ __global__ __launch_bounds__(64) void rollout_ls_fast_box_kernel(const FastArgs 
     }
     __syncthreads();
     if constexpr (DIAG_ONLY) {
-        rollout_ls_body<KIND, true, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+        rollout_ls_body<KIND, true, false, true, true, STG>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
     } else {
         if (__ballot(offdiag) == 0ull)
-            rollout_ls_body<KIND, true, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+            rollout_ls_body<KIND, true, false, true, true, STG>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
         else
-            rollout_ls_body<KIND, false, false, true, true>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
+            rollout_ls_body<KIND, false, false, true, true, STG>(g, Qs, Rs, Qfs, As, Bs, tr, bx);
     }
 }
 
@@ -494,10 +540,15 @@ static int launch_fast(const FastArgs& g, const bool diag_only, hipStream_t st, 
     const dim3 grid((unsigned)((nslot + 3) / 4)), block(64);
     if (box) {
         const TrackRef tr = track ? *track : TrackRef{};
-        if (diag_only)
-            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, true>), grid, block, 0, st, g, tr, *box);
+        const bool stg = box->step != 0;
+        if (diag_only && stg)
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, true, true>), grid, block, 0, st, g, tr, *box);
+        else if (diag_only)
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, true, false>), grid, block, 0, st, g, tr, *box);
+        else if (stg)
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, false, true>), grid, block, 0, st, g, tr, *box);
         else
-            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, false>), grid, block, 0, st, g, tr, *box);
+            hipLaunchKernelGGL((rollout_ls_fast_box_kernel<KIND, false, false>), grid, block, 0, st, g, tr, *box);
         ZM_HIP_CHECK(hipGetLastError());
         return ZM_OK;
     }

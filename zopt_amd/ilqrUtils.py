@@ -55,9 +55,9 @@ def _check_shapes(table):
             raise ValueError(f"{name} has shape {_shape(X)}, expected {s}")
 
 
-def _backward_pass(who, entry, dynamics, cost, Vf, ddp=False, boxed=None, cast_back=False):
+def _backward_pass(who, entry, dynamics, cost, Vf, ddp=False, boxed=None, cast_back=False, stage_varying=False):
     """The four backwardPass_* functions: shape table, upload, outputs, the call of `entry` and the return.  `boxed`: (uTraj, u_lb, u_ub)
-    of the *_box forms.  Every sweep computes in fp64; `cast_back` hands an fp32 caller fp32 back -- backwardPass_ilqr does (as the fused
+    of the *_box forms (`stage_varying`: the bounds carry a step axis, models.InputBox).  Every sweep computes in fp64; `cast_back` hands an fp32 caller fp32 back -- backwardPass_ilqr does (as the fused
     solves do), backwardPass_ilqr_box, backwardPass_ddp and backwardPass_ddp_box return fp64 whatever came in."""
     dyn = _fields(dynamics)
     f_x, f_u = dyn[1], dyn[2]
@@ -84,7 +84,7 @@ def _backward_pass(who, entry, dynamics, cost, Vf, ddp=False, boxed=None, cast_b
     if boxed is not None:
         table += [("uTraj", boxed[0], step + (m,))]
     _check_shapes(table)
-    box = _models.InputBox.for_shape(n, m, boxed[1], boxed[2]).box_struct(tuple(lead)) if boxed is not None else None
+    box = _models.InputBox.for_shape(n, m, boxed[1], boxed[2], stage_varying).box_struct(tuple(lead), N) if boxed is not None else None
     dt = torch.float64
     dev = [None if s is None else arr.to_device(X, dt) for _, X, s in table]
     batch = _batch(lead)
@@ -123,7 +123,7 @@ def backwardPass_ilqr(dynamics, cost, Vf):
     return _backward_pass("backwardPass_ilqr", "zm_ilqr_backward_f64", dynamics, cost, Vf, cast_back=True)
 
 
-def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
+def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub, stage_varying=False):
     """Backwards pass of control-limited iLQR (Tassa, Mansard, Todorov 2014); an extension, the reference has no counterpart.
 
     As `backwardPass_ilqr`, with bounds `u_lb <= u <= u_ub` on the inputs: per step `l_k` minimises the step's quadratic model over
@@ -135,12 +135,14 @@ def backwardPass_ilqr_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
         dynamics, cost, Vf : as backwardPass_ilqr
         uTraj : (..., N, m) inputs of the trajectory the expansions were taken along
         u_lb, u_ub : scalars, (m,) or (..., m) with leading axes that broadcast to the batch; entries may be -inf / +inf
+        stage_varying : the bounds are (N, m) or (..., N, m) (or a scalar next to such an array): step k uses row k
 
     Returns
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    return _backward_pass("backwardPass_ilqr_box", "zm_ilqr_backward_box_f64", dynamics, cost, Vf, boxed=(uTraj, u_lb, u_ub))
+    return _backward_pass("backwardPass_ilqr_box", "zm_ilqr_backward_box_f64", dynamics, cost, Vf, boxed=(uTraj, u_lb, u_ub),
+                          stage_varying=stage_varying)
 
 
 def _ddp_large(n, m):
@@ -314,6 +316,8 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     lead, (N, mm, nn) = shp[:-3], shp[-3:]
     if (mm, nn) != (m, n):
         raise ValueError(f"policy.L has shape {shp}, model is (n={n}, m={m})")
+    if box is not None:
+        box.check_horizon(N)          # (before anything touches the device)
     for name, X, s in (("x0", x0, lead + (n,)), ("policy.l", l, lead + (N, m)), ("xPrev", xPrev, lead + (N + 1, n)),
                        ("uPrev", uPrev, lead + (N, m))):
         if _shape(X) != s:
@@ -339,7 +343,7 @@ def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     pcs = ctypes.addressof(cs) if cs is not None else None
     head = (pcs,)
     if box is not None:               # (model*, cost* | NULL, track* | NULL, box*, ...)
-        bs = box.box_struct(tuple(lead))
+        bs = box.box_struct(tuple(lead), N)
         linesearch, head = _lib.lib().zm_rollout_linesearch_box_f64, (None if tracking else pcs, pcs if tracking else None,
                                                                       ctypes.addressof(bs))
     rc = linesearch(
@@ -508,7 +512,7 @@ def backwardPass_ddp(dynamics, cost, Vf):
     return _backward_pass("backwardPass_ddp", "zm_ddp_backward_f64", dynamics, cost, Vf, ddp=True)
 
 
-def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
+def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub, stage_varying=False):
     """Backwards pass of control-limited DDP (Tassa, Mansard, Todorov 2014) with the second-order dynamics terms; an extension, the
     reference has no counterpart.
 
@@ -528,7 +532,8 @@ def backwardPass_ddp_box(dynamics, cost, Vf, uTraj, u_lb, u_ub):
     -------
         AffinePolicy(l (..., N, m), L (..., N, m, n))
     """
-    return _backward_pass("backwardPass_ddp_box", "zm_ddp_backward_box_f64", dynamics, cost, Vf, ddp=True, boxed=(uTraj, u_lb, u_ub))
+    return _backward_pass("backwardPass_ddp_box", "zm_ddp_backward_box_f64", dynamics, cost, Vf, ddp=True, boxed=(uTraj, u_lb, u_ub),
+                          stage_varying=stage_varying)
 
 
 def iterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, maxIter=100, tol=1e-3):
@@ -634,6 +639,8 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     lead, (N, mm) = shp[:-2], shp[-2:]
     if mm != m or _shape(x0) != lead + (n,):
         raise ValueError(f"x0 {_shape(x0)} / uGuess {shp} do not match the model (n={n}, m={m})")
+    if box is not None:
+        box.check_horizon(N)          # (before anything touches the device)
     dt = torch.float64
     lib = _lib.lib()
     dx0 = arr.to_device(x0, dt).reshape(-1, n).contiguous()
@@ -687,7 +694,7 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
              "workspace_doubles": nws, "iwork": iwork.data_ptr(), "xTraj": xT.data_ptr(), "uTraj": uT.data_ptr(), "L": L.data_ptr(),
              "J": J.data_ptr(), "converged": converged.data_ptr(), "iterations": ctypes.addressof(its), "batch": B, "T": N, "stream": st}
         if box is not None or sbox is not None:
-            bs = box.box_struct(tuple(lead)) if box is not None else None
+            bs = box.box_struct(tuple(lead), N) if box is not None else None
             capped = torch.zeros(B, dtype=i32, device=dev)
             d.update(box=ctypes.addressof(bs) if box is not None else None, qp_capped=capped.data_ptr())
         if sbox is not None:

@@ -508,7 +508,8 @@ class Quadcopter:
 
 
 class zm_inputbox_t(ctypes.Structure):
-    _fields_ = [("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p), ("stride", ctypes.c_int64)]
+    # (step_stride trails: a struct built from three fields leaves it zero, the constant form)
+    _fields_ = [("lb", ctypes.c_void_p), ("ub", ctypes.c_void_p), ("stride", ctypes.c_int64), ("step_stride", ctypes.c_int64)]
 
 
 INPUTBOX_MAX_N, INPUTBOX_MAX_M = 12, 4     # the fused drivers' shapes (zm::MAXN, zm::MAXM)
@@ -521,13 +522,18 @@ class InputBox:
     u_lb, u_ub: scalars, (m,) or (..., m) with leading axes that broadcast to the batch of the call; an entry of -inf / +inf means no
     bound on that side of that component, `u_lb == u_ub` fixes a component.  `u_lb > u_ub` and NaN are refused.
 
+    stage_varying=True: the bounds change along the horizon.  Each bound is (N, m) or (..., N, m) -- row k is the box of `u_k`, N the
+    horizon of every call the box is used in, the leading axes broadcast to the batch -- or a scalar (the other bound then carries the
+    step axis).  Rows with `u_lb == u_ub` pin inputs that are committed already (delay compensation), a row of zeros is a cut-off.
+    A call with another horizon is a ValueError; a `StateBox` around a stage-varying box is a TypeError (the follow-up).
+
     Accepted wherever a registered model is by `iterativeLqr`, `differentialDynamicProgramming` (quadcopter models), `forwardPass2`,
     `trajectoryRollout` and the simulator: rollouts clip
     `u_k = clip(alpha l_k + L_k (x_k - xPrev_k) + uPrev_k, u_lb, u_ub)`, the backward pass solves a box-constrained QP per step and
     zeroes the feedback rows of the clamped inputs.  It is deliberately neither callable nor a device model itself: code that knows
     nothing of the box (the expansions, the generic-callable path) refuses it instead of dropping the bounds."""
 
-    def __init__(self, model, u_lb, u_ub):
+    def __init__(self, model, u_lb, u_ub, stage_varying=False):
         if isinstance(model, InputBox):
             raise TypeError("InputBox: the model is an InputBox already")
         if isinstance(model, StateBox):
@@ -540,19 +546,22 @@ class InputBox:
         if self.n > INPUTBOX_MAX_N or self.m > INPUTBOX_MAX_M:
             raise ValueError(f"InputBox: (n={self.n}, m={self.m}) not covered -- the box kernels take n <= {INPUTBOX_MAX_N}, "
                              f"m <= {INPUTBOX_MAX_M}")
-        self._set_bounds(u_lb, u_ub)
+        self._set_bounds(u_lb, u_ub, stage_varying)
 
     @classmethod
-    def for_shape(cls, n, m, u_lb, u_ub):
+    def for_shape(cls, n, m, u_lb, u_ub, stage_varying=False):
         """the bounds alone, for array-level calls that have no model (ilqrUtils.backwardPass_ilqr_box)"""
         self = cls.__new__(cls)
         self.model, self.n, self.m = None, int(n), int(m)
-        self._set_bounds(u_lb, u_ub)
+        self._set_bounds(u_lb, u_ub, stage_varying)
         return self
 
-    def _set_bounds(self, u_lb, u_ub):
+    def _set_bounds(self, u_lb, u_ub, stage_varying=False):
         host = lambda b: np.asarray(b.detach().cpu().numpy() if arr.is_torch(b) else b, dtype=np.float64)       # noqa: E731
         lb, ub = host(u_lb), host(u_ub)
+        self.stage_varying = bool(stage_varying)
+        if self.stage_varying:
+            return self._set_stage_bounds(lb, ub)
         for name, b in (("u_lb", lb), ("u_ub", ub)):
             if b.ndim and b.shape[-1] != self.m:
                 raise ValueError(f"InputBox: {name} has shape {b.shape}, expected a scalar, ({self.m},) or (..., {self.m})")
@@ -567,14 +576,62 @@ class InputBox:
             raise ValueError("InputBox: u_lb > u_ub")
         self._dev = {}
 
+    def _set_stage_bounds(self, lb, ub):
+        """stage_varying=True: u_lb, u_ub (N, m) or (..., N, m), or a scalar next to such an array"""
+        for name, b in (("u_lb", lb), ("u_ub", ub)):
+            if b.ndim and (b.ndim < 2 or b.shape[-1] != self.m):
+                raise ValueError(f"InputBox: stage-varying {name} has shape {b.shape}, expected a scalar, (N, {self.m}) or (..., N, {self.m})")
+            if np.isnan(b).any():
+                raise ValueError(f"InputBox: {name} holds a NaN")
+        if lb.ndim == 0 and ub.ndim == 0:
+            raise ValueError("InputBox: stage-varying bounds need a step axis -- u_lb or u_ub of shape (N, m) or (..., N, m)")
+        if lb.ndim and ub.ndim and lb.shape[-2] != ub.shape[-2]:
+            raise ValueError(f"InputBox: u_lb has {lb.shape[-2]} steps and u_ub {ub.shape[-2]}")
+        try:
+            shp = np.broadcast_shapes(lb.shape, ub.shape)
+        except ValueError:
+            raise ValueError(f"InputBox: u_lb {lb.shape} and u_ub {ub.shape} do not broadcast") from None
+        if shp[-2] < 1:
+            raise ValueError("InputBox: stage-varying bounds need at least one step")
+        self.u_lb, self.u_ub = np.array(np.broadcast_to(lb, shp)), np.array(np.broadcast_to(ub, shp))
+        self.steps = int(shp[-2])
+        bad = self.u_lb > self.u_ub
+        if bad.any():
+            raise ValueError(f"InputBox: u_lb > u_ub at step {int(np.argwhere(bad)[0][-2])}")
+        self._dev = {}
+
     def clip(self, u):
-        """u clipped into the box (NumPy, host side)"""
+        """u clipped into the box (NumPy, host side); stage-varying bounds: u (..., N, m), row k into the box of step k"""
         return np.minimum(np.maximum(u, self.u_lb), self.u_ub)
 
-    def box_struct(self, lead):
-        """zm_inputbox_t for a call with batch axes `lead`: one shared row (stride 0) or a row per trajectory (stride m)"""
+    def check_horizon(self, T):
+        """stage-varying bounds: the call's horizon is the bounds' step axis (checked by the drivers before anything touches the device)"""
+        if self.stage_varying and (T is None or int(T) != self.steps):
+            raise ValueError(f"InputBox: the stage-varying bounds have {self.steps} steps, the call has a horizon of {T}")
+
+    def box_struct(self, lead, T=None):
+        """zm_inputbox_t for a call with batch axes `lead` and horizon `T`: one shared row (stride 0) or a row per trajectory (stride m);
+        stage-varying bounds: (T, m) rows, one schedule shared (stride 0) or one per trajectory (stride T m), step_stride m.  The device
+        copy is made once per `lead` and kept."""
         import torch
         lead = tuple(int(d) for d in lead)
+        self.check_horizon(T)
+        if self.stage_varying:
+            if lead not in self._dev:
+                if self.u_lb.ndim == 2:
+                    rows, stride = (self.u_lb, self.u_ub), 0
+                else:
+                    try:
+                        rows = tuple(np.array(np.broadcast_to(b, lead + (self.steps, self.m))) for b in (self.u_lb, self.u_ub))
+                    except ValueError:
+                        raise ValueError(f"InputBox: leading axes {self.u_lb.shape[:-2]} of the bounds do not broadcast to the batch "
+                                         f"{lead}") from None
+                    stride = self.steps * self.m
+                self._dev[lead] = tuple(arr.to_device(np.ascontiguousarray(b), torch.float64) for b in rows) + (stride,)
+            lb, ub, stride = self._dev[lead]
+            st = zm_inputbox_t(lb.data_ptr(), ub.data_ptr(), stride, self.m)
+            st._owner = (self, lb, ub)
+            return st
         if lead not in self._dev:
             if self.u_lb.ndim == 1:
                 rows, stride = (self.u_lb, self.u_ub), 0
@@ -618,6 +675,9 @@ class StateBox:
         if isinstance(model, StateBox):
             raise TypeError("StateBox: the model is a StateBox already")
         inner = model.model if isinstance(model, InputBox) else model
+        if isinstance(model, InputBox) and model.stage_varying:
+            raise TypeError("StateBox: a stage-varying InputBox inside a StateBox is the follow-up -- the penalty line search and sweep "
+                            "take one input box for the whole horizon")
         refuse_traced(inner, "StateBox", "the augmented-Lagrangian line search on the tape interpreter is the follow-up")
         if not hasattr(inner, "c_struct"):
             raise TypeError("StateBox wraps a registered device model (zopt_amd.models.*) or an InputBox around one; the "
