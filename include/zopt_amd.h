@@ -1013,6 +1013,71 @@ int zm_traced_cost_solve_trace_f64(const zm_model_t* model, const zm_tracedcost_
                                    int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged,
                                    int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace, int32_t* alpha_trace);
 
+/* ---- Recorded inequality constraints (Python: zopt_amd.models.TracedConstraint): g(x, u[, p]) <= 0 with n_con values on (x_k, u_k),
+ *      k = 0 .. T-1, and terminal(x[, p]) <= 0 with n_con_terminal values on x_T, as two tapes of the ZM_MODEL_TRACED interpreter with
+ *      SEVERAL outputs each.  Extends zm_tracedcost_t (the same slot layout [x | u | p], the same blob with n_con resp. n_con_terminal
+ *      output slot numbers behind the instruction words) and zm_statebox_t (the same augmented Lagrangian on g in place of the box
+ *      distances):  s_i = lam_i + mu g_i,  pos(s) = s > 0 ? s : 0 (a NaN gives 0),  psi = sum_i (pos(s_i)^2 - lam_i^2) / (2 mu),
+ *      gradient G^T pos(s) with G = dg/d(x, u), Gauss-Newton Hessian mu G^T diag(s_i > 0) G (no second derivatives of g).
+ *      A tape with no outputs (n_con == 0 resp. n_con_terminal == 0) is absent: its tape pointer is not read.  At least one is present.
+ *      lam (batch, T, n_con), lam_terminal (batch, n_con_terminal), mu (batch): the caller's device arrays, as lam_lb / lam_ub / mu of
+ *      zm_statebox_t.  Caps: those of zm_traced_t, 1 <= n <= 12, 1 <= m <= 4, n_con <= 8, n_con_terminal <= 8. */
+#define ZM_TRACEDCON_MAX 8
+typedef struct zm_tracedcon_t {   /* 120 bytes */
+    zm_traced_t stage;
+    zm_traced_t terminal;
+    int32_t n, m, n_con, n_con_terminal;
+    double* lam;
+    double* lam_terminal;
+    double* mu;
+} zm_tracedcon_t;
+
+/* g along given trajectories: g (batch, T, n_con) <- g(x_k, u_k, p), g_terminal (batch, n_con_terminal) <- terminal(x_T, p); either
+ * may be NULL.  The interpreter's value path: bits equal to a host build's.  lam, lam_terminal and mu are not read. */
+int zm_traced_con_values_f64(const zm_tracedcon_t* con, const double* xTraj, const double* uTraj, double* g, double* g_terminal,
+                             int64_t batch, int T, void* stream);
+/* zm_rollout_linesearch_state_list_f64 on the constraint's penalty: the cost is `cost` or `track` (exactly one; a traced model takes
+ * `cost` only).  Per step: the policy, the cost, the stage tape with psi accumulated into an accumulator of its own (k ascending, i
+ * ascending, terminal rows last), the model step; the penalty joins the cost once, at the end.  J <- cost + penalty, J_cost
+ * (optional) <- the cost without it, written by the store pass.  n_alpha is 1 or 16. */
+int zm_traced_con_linesearch_list_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                      const zm_tracedcon_t* con, const double* x0, const double* l, const double* L, const double* xPrev,
+                                      const double* uPrev, const double* alphas, int n_alpha, const int32_t* list, int64_t count,
+                                      const int32_t* active, double* xTraj, double* uTraj, double* J, double* J_cost, int32_t* alpha_idx,
+                                      int64_t batch, int T, void* stream);
+/* zm_state_penalty_expand_list_f64 for the recorded constraint: behind the cost expansion, per listed active trajectory
+ * c_x[k] += G_x^T pos(s), c_u[k] += G_u^T pos(s), v_x += G_T^T pos(s_T), and the per-point Hessians
+ * [c_xx c_ux^T; c_ux c_uu][k] <- the shared (conditioned) set sc_xx (n,n), sc_ux (m,n), sc_uu (m,m) + mu G^T diag(s > 0) G,
+ * v_xx (batch,n,n) <- sv_xx (n,n) + the same of the terminal rows.  16 lanes per point: lane j runs the tape on dual numbers seeded
+ * e_j and owns entry j of the gradient and row j of the Hessian.  Rows of trajectories not listed or not active are not touched. */
+int zm_traced_con_expand_list_f64(const zm_tracedcon_t* con, const double* xTraj, const double* uTraj, const int32_t* list, int64_t count,
+                                  const int32_t* active, const double* sc_xx, const double* sc_ux, const double* sc_uu,
+                                  const double* sv_xx, double* c_x, double* c_u, double* v_x, double* c_xx, double* c_ux, double* c_uu,
+                                  double* v_xx, int64_t batch, int T, void* stream);
+/* zm_state_multiplier_update_f64 for the recorded constraint: viol_t = max over the rows and i of pos(g_i), NaN if any g is NaN; the
+ * done test, the masks, the counters and the update lam <- pos(lam + mu g), mu <- min(mu growth, mu_max) as there. */
+int zm_traced_con_multiplier_update_f64(const zm_tracedcon_t* con, const double* xTraj, const double* uTraj, int32_t* active,
+                                        int32_t* converged, double* violation, int32_t* outer_count, int32_t* remaining, double ctol,
+                                        double growth, double mu_max, int update, int64_t batch, int T, void* stream);
+/* zm_ilqr_solve_state_f64 with the recorded constraint in place of the state box: the same outer loop around the loop of
+ * zm_ilqr_solve_f64 with the line search, the expansion and the multiplier update above, per-point Hessians (the workspace of
+ * zm_traced_cost_solve_workspace_f64 plus one shared conditioned set) and the list sweeps with shared_hessian = 0.  ddp must be 0.
+ * Every argument is checked before any launch.  Outputs and traces as zm_ilqr_solve_state_f64 / zm_ilqr_solve_state_trace_f64. */
+int64_t zm_traced_con_solve_workspace_f64(const zm_model_t* model, int64_t batch, int T);
+int zm_traced_con_solve_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track, const zm_tracedcon_t* con,
+                            double mu0, double growth, double mu_max, int outer, double ctol, const double* x0, const double* uGuess,
+                            int ddp, int max_iter, double tol, int sync_every, double* workspace, int64_t workspace_doubles,
+                            int32_t* iwork, double* xTraj, double* uTraj, double* L, double* J, int32_t* converged, double* violation,
+                            int32_t* outer_iterations, int32_t* inner_iterations, int32_t* iterations, int64_t batch, int T,
+                            void* stream);
+int zm_traced_con_solve_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                  const zm_tracedcon_t* con, double mu0, double growth, double mu_max, int outer, double ctol,
+                                  const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every,
+                                  double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L,
+                                  double* J, int32_t* converged, double* violation, int32_t* outer_iterations,
+                                  int32_t* inner_iterations, int32_t* iterations, int64_t batch, int T, void* stream, double* J_trace,
+                                  int32_t* alpha_trace, double* violation_trace, double* mu_trace);
+
 #ifdef __cplusplus
 }
 #endif

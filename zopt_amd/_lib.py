@@ -258,6 +258,26 @@ SYMBOLS = {
     "zm_traced_cost_solve_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp,
                                                                   ctypes.c_int64] + [_c_dp] * 7 +
                                        [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, _c_dp, _c_dp]),
+    # recorded constraints (zm_tracedcon_t*): what the state-box entries are for a zm_statebox_t*
+    # (con*, xTraj, uTraj, g | NULL, g_terminal | NULL, batch, T, stream)
+    "zm_traced_con_values_f64": (ctypes.c_int, [_c_dp] * 5 + [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (model*, cost* | NULL, track* | NULL, con*, x0, l, L, xPrev, uPrev, alphas, n_alpha, list | NULL, count, active, xTraj, uTraj, J,
+    #  J_cost | NULL, alpha_idx, batch, T, stream)
+    "zm_traced_con_linesearch_list_f64": (ctypes.c_int, [_c_dp] * 10 + [ctypes.c_int] + [_c_dp] + [ctypes.c_int64] + [_c_dp] * 6 +
+                                          [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (con*, xTraj, uTraj, list | NULL, count, active, sc_xx, sc_ux, sc_uu, sv_xx, c_x, c_u, v_x, c_xx, c_ux, c_uu, v_xx, batch, T, stream)
+    "zm_traced_con_expand_list_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_int64] + [_c_dp] * 12 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    # (con*, xTraj, uTraj, active, converged, violation, outer_count | NULL, remaining | NULL, ctol, growth, mu_max, update, batch, T, stream)
+    "zm_traced_con_multiplier_update_f64": (ctypes.c_int, [_c_dp] * 8 + [ctypes.c_double] * 3 +
+                                            [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_traced_con_solve_workspace_f64": (ctypes.c_int64, [_c_dp, ctypes.c_int64, ctypes.c_int]),
+    "zm_traced_con_solve_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_double] + [_c_dp] * 2 +
+                                [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] + [_c_dp] * 10 +
+                                [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    "zm_traced_con_solve_trace_f64": (ctypes.c_int, [_c_dp] * 4 + [ctypes.c_double] * 3 + [ctypes.c_int, ctypes.c_double] + [_c_dp] * 2 +
+                                      [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, _c_dp, ctypes.c_int64] + [_c_dp] * 10 +
+                                      [ctypes.c_int64, ctypes.c_int, ctypes.c_void_p] + [_c_dp] * 4),
 }
 
 
@@ -287,6 +307,13 @@ _TRACED_COST_PLAIN = ["tcost" if k == "cost" else k for k in _SOLVE_PLAIN]
 TRACED_COST_SOLVE_ARGS = {
     "zm_traced_cost_solve_f64": _TRACED_COST_PLAIN,
     "zm_traced_cost_solve_trace_f64": _TRACED_COST_PLAIN + _SOLVE_TRACE,
+}
+
+# the solves with recorded constraints: the state entries' names with `con` in place of `sbox` and no input box
+_TRACED_CON_STATE = ["con" if k == "sbox" else k for k in _SOLVE_STATE if k not in ("box", "qp_capped")]
+TRACED_CON_SOLVE_ARGS = {
+    "zm_traced_con_solve_f64": _TRACED_CON_STATE,
+    "zm_traced_con_solve_trace_f64": _TRACED_CON_STATE + _SOLVE_TRACE + ["violation_trace", "mu_trace"],
 }
 
 

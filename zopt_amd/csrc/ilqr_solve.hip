@@ -20,6 +20,7 @@
 #include "quad_derivs_gen.h"
 #include "state_box.h"
 #include "track_cost.h"
+#include "traced_con.h"
 #include "traced_cost.h"
 #include "zm_common.h"
 
@@ -167,6 +168,18 @@ struct IlqrCost : CostRef {
     // recorded cost (zm_traced_cost_solve_f64; nullptr: none): its own line search and expansion, per-point Hessians conditioned in
     // every iteration, the list sweeps with shared_hessian = 0; there are then no weights, no box and no penalty
     const zm_tracedcost_t* traced = nullptr;
+    // recorded constraints (zm_traced_con_solve_f64; nullptr: none): their own penalty line search, the cost's expansion followed by the
+    // penalty's into per-point Hessians (shared conditioned set + Gauss-Newton addend), the list sweeps with shared_hessian = 0
+    const struct ConPen* con = nullptr;
+};
+// One inner solve of the augmented-Lagrangian loop on recorded constraints (zm_traced_con_solve_f64): StatePen's part there.
+struct ConPen {
+    const zm_tracedcon_t* tc;
+    double *sc_xx, *sc_ux, *sc_uu, *sv_xx;   // the shared Hessians of the quadratic cost, PD-conditioned once per inner solve
+    double* Jcost;              // (batch) the cost without the penalty, written by the line search's store pass
+    int32_t* visits;            // (batch, optional) += 1 per iteration of the loop over the trajectory
+    const int32_t* init_mask;   // (batch) the trajectories this inner solve covers
+    const double* uStart;       // (batch, T, m) the inputs it starts from
 };
 // psd.hip: the projections of zm_condition_cost_f64 / zm_psd_project_f64 over the listed trajectories' per-point Hessians
 int condition_cost_listed(double* c_xx, double* c_ux, double* c_uu, const int* list, long count, int T, int n, int m, double eps,
@@ -180,6 +193,10 @@ static int cost_linesearch(const IlqrCost& ck, const zm_model_t* model, const do
     if (ck.traced)
         return zm_traced_cost_linesearch_list_f64(model, ck.traced, x0, l, L, xPrev, uPrev, alphas, n_alpha, list, count, active, xTraj,
                                                   uTraj, J, alpha_idx, batch, T, stream);
+    if (ck.con)
+        return zm_traced_con_linesearch_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.con->tc, x0, l, L, xPrev, uPrev, alphas,
+                                                 n_alpha, list, count, active, xTraj, uTraj, J, ck.con->Jcost, alpha_idx, batch, T,
+                                                 stream);
     if (ck.pen)
         return zm_rollout_linesearch_state_list_f64(model, ck.track ? nullptr : &ck.w, ck.track, ck.box, ck.pen->sbox, x0, l, L, xPrev,
                                                     uPrev, alphas, n_alpha, list, count, active, xTraj, uTraj, J, ck.pen->Jcost,
@@ -265,7 +282,7 @@ static SweepPlan sweep_plan(const zm_model_t* model, const IlqrCost& ck, double*
     const bool windy = model->wind_ned[0] != 0.0 || model->wind_ned[1] != 0.0 || model->wind_ned[2] != 0.0;
     SweepPlan p;
     p.ddp = ddp, p.npairs = npairs;
-    p.packed = !ck.box && !ck.pen && !ck.traced && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 &&
+    p.packed = !ck.box && !ck.pen && !ck.traced && !ck.con && !packed_off && model->kind == ZM_MODEL_QUADCOPTER && model->dt != 0.0 &&
                (((uintptr_t)ws) & 15) == 0 && (!ddp || npairs == 28);
     p.sparse_h = p.packed && ddp && !sparse_off;
     p.f_ux = (need_ux && npairs == 0) ? ws + w.f_ux : nullptr;
@@ -284,7 +301,7 @@ static int backward_sweep(const SweepPlan& p, const IlqrCost& ck, const zm_model
                           const double* curU, const int32_t* list, int64_t count, const int32_t* active, double* L, int64_t batch, int T,
                           hipStream_t st) {
     const int n = model->n, m = model->m;
-    const int shared = ck.traced ? 0 : 1;   // shared_hessian of the plain sweeps: a recorded cost has per-point Hessians
+    const int shared = (ck.traced || ck.con) ? 0 : 1;   // shared_hessian of the plain sweeps: a recorded cost or constraint has per-point Hessians
     int rc = ZM_OK;
     if (p.packed) {
         if (p.sparse_h)
@@ -471,6 +488,10 @@ static int ilqr_solve_impl(const SolveCall& c) {
     if (ck.traced && (cost || ck.track || ck.box || ck.pen || n != ck.traced->n || m != ck.traced->m))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_traced_cost_solve_f64: a recorded cost of the model's (n, m) and nothing else (weights, "
                                               "input box and state box next to a recorded cost are not built)");
+    if (ck.con && (ddp || cost == nullptr || ck.box || ck.pen || ck.traced || n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM))
+        return zm::set_error(ZM_EUNSUPPORTED, "zm_traced_con_solve_f64: iLQR on a quadratic or tracking cost with n<=12, m<=4 and nothing "
+                                              "else (DDP, input box, state box and a recorded cost next to a recorded constraint are not "
+                                              "built)");
     if (model->kind == ZM_MODEL_TRACED && (ck.track || ck.box || ck.pen))
         return zm::set_error(ZM_EUNSUPPORTED, "zm_ilqr_solve_f64: a traced model takes a zm_quadcost_t and no bounds (tracking cost, input "
                                               "box and state box on the tape interpreter are not built)");
@@ -493,7 +514,7 @@ static int ilqr_solve_impl(const SolveCall& c) {
         if (rc) return rc;
     }
     const int need_ux = (mask >> n) != 0;   // a model affine in its controls has f_ux = f_uu = 0: neither written nor read
-    const zm::IlqrWs w = zm::carve(model, batch, T, ddp, need_ux, npairs, ck.traced != nullptr);
+    const zm::IlqrWs w = zm::carve(model, batch, T, ddp, need_ux, npairs, ck.traced != nullptr || ck.con != nullptr);
     if (c.workspace_doubles < w.total)
         return zm::set_error(ZM_EINVAL, "zm_ilqr_solve_f64: workspace of %lld doubles, %lld needed", (long long)c.workspace_doubles,
                              (long long)w.total);
@@ -507,8 +528,10 @@ static int ilqr_solve_impl(const SolveCall& c) {
 
     // policy = (uGuess, 0); traj_prev = zeros; step sizes; masks                                     (ilqrUtils.py:293-294, :145)
     int32_t* where = (int32_t*)(ws + w.where);
-    if (ck.pen) {
-        const int ri = zm::ilqr_init_masked(ck.pen->init_mask, ws + w.l, ck.pen->uStart, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, active,
+    const bool al = ck.pen || ck.con;   // an inner solve of an augmented-Lagrangian loop: masked start
+    if (al) {
+        const int ri = zm::ilqr_init_masked(ck.pen ? ck.pen->init_mask : ck.con->init_mask, ws + w.l,
+                                            ck.pen ? ck.pen->uStart : ck.con->uStart, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, active,
                                             c.converged, where, batch, T, n, m, st);
         if (ri) return ri;
     } else {
@@ -520,17 +543,20 @@ static int ilqr_solve_impl(const SolveCall& c) {
     }
     // initial rollout (alpha = 1) from the zero trajectory and its cost                                (:297-298)
     int rc = zm::cost_linesearch(ck, model, c.x0, ws + w.l, L, ws + w.xT2, ws + w.uT2, ws + w.alphas, 1, nullptr, 0,
-                                 ck.pen ? active : nullptr, xTraj, uTraj, J, nullptr, batch, T, st);
+                                 al ? active : nullptr, xTraj, uTraj, J, nullptr, batch, T, st);
     if (rc) return rc;
     // trajectory-independent Hessians of the quadratic cost, PD-conditioned once                         (:309-313)
     // (a recorded cost: per-point Hessians, expanded and conditioned in every iteration below)
+    // (recorded constraints: the same shared set, kept beside the per-point arrays that the penalty expansion fills from it)
     if (!ck.traced) {
-        rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws + w.c_xx,
-                                    ws + w.c_ux, ws + w.c_uu, ws + w.v_xx, 0, T, st);
+        double *const s_xx = ck.con ? ck.con->sc_xx : ws + w.c_xx, *const s_ux = ck.con ? ck.con->sc_ux : ws + w.c_ux,
+                     *const s_uu = ck.con ? ck.con->sc_uu : ws + w.c_uu, *const s_vxx = ck.con ? ck.con->sv_xx : ws + w.v_xx;
+        rc = zm_quadratize_cost_f64(cost, n, m, xTraj, uTraj, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, s_xx, s_ux, s_uu,
+                                    s_vxx, 0, T, st);
         if (rc) return rc;
-        rc = zm_condition_cost_f64(ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, 1, n, m, 1e-3, st);
+        rc = zm_condition_cost_f64(s_xx, s_ux, s_uu, 1, n, m, 1e-3, st);
         if (rc) return rc;
-        rc = zm_psd_project_f64(ws + w.v_xx, 1, n, 1e-3, st);
+        rc = zm_psd_project_f64(s_vxx, 1, n, 1e-3, st);
         if (rc) return rc;
     }
 
@@ -595,6 +621,12 @@ static int ilqr_solve_impl(const SolveCall& c) {
         if (ck.pen) {   // (behind the round trip: the list and its count are this iteration's)
             rc = zm::state_penalty_expand(ck.pen->sbox, curX, list, count, active, ws + w.c_x, ws + w.v_x, ck.pen->h, ck.pen->visits, batch,
                                           T, n, st);
+            if (rc) return rc;
+        }
+        if (ck.con) {   // (likewise; no projection behind it: the addend is positive semidefinite, the shared set conditioned)
+            const zm::ConPen& cp = *ck.con;
+            rc = zm::traced_con_expand(cp.tc, curX, curU, list, count, active, cp.sc_xx, cp.sc_ux, cp.sc_uu, cp.sv_xx, ws + w.c_x,
+                                       ws + w.c_u, ws + w.v_x, ws + w.c_xx, ws + w.c_ux, ws + w.c_uu, ws + w.v_xx, cp.visits, batch, T, st);
             if (rc) return rc;
         }
         if (ck.traced) {   // the PD projections of the listed trajectories' Hessians, per iteration                 (:312-313)
@@ -767,6 +799,42 @@ struct StateWs {
     }
 };
 
+// The outer loop of the two augmented-Lagrangian entries (zm_ilqr_solve_state_f64, zm_traced_con_solve_f64): per outer iteration
+// `bind(j)` points the call's cost at this iteration's penalty record, the inner solve runs over the trajectories that are not done,
+// `update(more)` is the entry's multiplier update (more: another outer iteration may follow), and the host learns how many go on.
+struct AlTraces {
+    double* J_trace;
+    int32_t* alpha_trace;
+    double *violation_trace, *mu_trace;
+};
+template <class Bind, class Update>
+static int al_outer_loop(SolveCall& c, int outer, const double* mu, const double* violation, int32_t* remaining, int32_t* iterations,
+                         const AlTraces& tr, Bind bind, Update update) {
+    hipStream_t st = (hipStream_t)c.stream;
+    const int64_t batch = c.batch;
+    int ran = 0;
+    for (int j = 0; j < outer; ++j) {
+        bind(j);
+        c.J_trace = tr.J_trace ? tr.J_trace + (long)j * c.max_iter * batch : nullptr;
+        c.alpha_trace = tr.alpha_trace ? tr.alpha_trace + (long)j * c.max_iter * batch : nullptr;
+        if (tr.mu_trace) ZM_HIP_CHECK(hipMemcpyAsync(tr.mu_trace + (long)j * batch, mu, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+        int rc = ilqr_solve_impl(c);
+        if (rc) return rc;
+        ZM_HIP_CHECK(hipMemsetAsync(remaining, 0, sizeof(int32_t), st));
+        rc = update(j + 1 < outer ? 1 : 0);
+        if (rc) return rc;
+        if (tr.violation_trace)
+            ZM_HIP_CHECK(hipMemcpyAsync(tr.violation_trace + (long)j * batch, violation, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+        int32_t left = 0;
+        ZM_HIP_CHECK(hipMemcpyAsync(&left, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ZM_HIP_CHECK(hipStreamSynchronize(st));
+        ran = j + 1;
+        if (left == 0) break;
+    }
+    if (iterations) *iterations = ran;
+    return ZM_OK;
+}
+
 extern "C" int64_t zm_ilqr_solve_state_workspace_f64(const zm_model_t* model, int64_t batch, int T) {
     const StateWs s(model, batch, T);
     return s.base < 0 ? -1 : s.total;
@@ -829,30 +897,17 @@ extern "C" int zm_ilqr_solve_state_trace_f64(const zm_model_t* model, const zm_q
     c.J = workspace + sw.Jal;
     c.ck.box = box;
     c.ck.qp_capped = box ? qp_capped : nullptr;
-    int ran = 0;
-    for (int j = 0; j < outer; ++j) {
-        const zm::StatePen pen{sbox, h, J, inner_iterations ? inner_iterations + (long)j * batch : nullptr, notdone,
-                               j == 0 ? uGuess : uTraj};
-        c.ck.pen = &pen;
-        c.J_trace = J_trace ? J_trace + (long)j * max_iter * batch : nullptr;
-        c.alpha_trace = alpha_trace ? alpha_trace + (long)j * max_iter * batch : nullptr;
-        if (mu_trace) ZM_HIP_CHECK(hipMemcpyAsync(mu_trace + (long)j * batch, sbox->mu, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
-        int rc = ilqr_solve_impl(c);
-        if (rc) return rc;
-        ZM_HIP_CHECK(hipMemsetAsync(remaining, 0, sizeof(int32_t), st));
-        rc = zm_state_multiplier_update_f64(sbox, xTraj, notdone, converged, violation, outer_iterations, remaining, ctol, growth, mu_max,
-                                            j + 1 < outer ? 1 : 0, batch, T, n, stream);
-        if (rc) return rc;
-        if (violation_trace)
-            ZM_HIP_CHECK(hipMemcpyAsync(violation_trace + (long)j * batch, violation, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
-        int32_t left = 0;
-        ZM_HIP_CHECK(hipMemcpyAsync(&left, remaining, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ZM_HIP_CHECK(hipStreamSynchronize(st));
-        ran = j + 1;
-        if (left == 0) break;
-    }
-    if (iterations) *iterations = ran;
-    return ZM_OK;
+    zm::StatePen pen{};
+    return al_outer_loop(
+        c, outer, sbox->mu, violation, remaining, iterations, AlTraces{J_trace, alpha_trace, violation_trace, mu_trace},
+        [&](int j) {
+            pen = zm::StatePen{sbox, h, J, inner_iterations ? inner_iterations + (long)j * batch : nullptr, notdone, j == 0 ? uGuess : uTraj};
+            c.ck.pen = &pen;
+        },
+        [&](int update) {
+            return zm_state_multiplier_update_f64(sbox, xTraj, notdone, converged, violation, outer_iterations, remaining, ctol, growth,
+                                                  mu_max, update, batch, T, n, stream);
+        });
 }
 
 extern "C" int zm_ilqr_solve_state_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
@@ -866,6 +921,112 @@ extern "C" int zm_ilqr_solve_state_f64(const zm_model_t* model, const zm_quadcos
                                          sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged, violation,
                                          outer_iterations, inner_iterations, iterations, qp_capped, batch, T, stream, nullptr, nullptr,
                                          nullptr, nullptr);
+}
+
+// Extension; the reference has no counterpart: AL-iLQR on recorded inequality constraints (zm_tracedcon_t; traced_con.hip) -- the outer
+// loop of zm_ilqr_solve_state_f64 with the constraint's line search, expansion and multiplier update in place of the state box's.
+// What the solve carves behind the inner solve's workspace (offsets in doubles from its start).
+struct ConWs {
+    int64_t base;       // the inner solve's own workspace with per-point Hessians (zm_traced_cost_solve_workspace_f64's size); -1: cannot
+    int64_t sc_xx, sc_ux, sc_uu, sv_xx;   // the shared conditioned Hessians of the quadratic cost
+    int64_t Jal;        // (batch) J_AL
+    int64_t notdone;    // int32 (batch): the trajectories that are not done
+    int64_t remaining;  // int32: how many of them go on
+    int64_t total;
+    ConWs(const zm_model_t* model, int64_t batch, int T)
+        : base((model && batch >= 0 && T >= 1) ? zm::carve(model, batch, T, 0, 0, 0, true).total : -1) {
+        const int64_t n = model ? model->n : 0, m = model ? model->m : 0;
+        auto even = [](int64_t v) { return (v + 1) & ~(int64_t)1; };
+        sc_xx = base;
+        sc_ux = sc_xx + even(n * n);
+        sc_uu = sc_ux + even(m * n);
+        sv_xx = sc_uu + even(m * m);
+        Jal = sv_xx + even(n * n);
+        notdone = Jal + even(batch);
+        remaining = notdone + (batch + 1) / 2;   // (behind the mask: int32 index (batch + 1) & ~1 of its piece)
+        total = remaining + 3;
+    }
+};
+
+extern "C" int64_t zm_traced_con_solve_workspace_f64(const zm_model_t* model, int64_t batch, int T) {
+    const ConWs s(model, batch, T);
+    return s.base < 0 ? -1 : s.total;
+}
+
+extern "C" int zm_traced_con_solve_trace_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                             const zm_tracedcon_t* con, double mu0, double growth, double mu_max, int outer, double ctol,
+                                             const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every,
+                                             double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj,
+                                             double* L, double* J, int32_t* converged, double* violation, int32_t* outer_iterations,
+                                             int32_t* inner_iterations, int32_t* iterations, int64_t batch, int T, void* stream,
+                                             double* J_trace, int32_t* alpha_trace, double* violation_trace, double* mu_trace) {
+    const char* who = "zm_traced_con_solve_f64";
+    if (batch == 0) return ZM_OK;
+    // every argument is checked here, before the first launch (also what the kernels' own entry points would refuse behind it)
+    if (!model || !con || !x0 || !uGuess || !workspace || !iwork || !xTraj || !uTraj || !L || !J || !converged || !violation)
+        return zm::set_error(ZM_EINVAL, "%s: null pointer", who);
+    SolveCall c{model, {}, x0, uGuess, 0, max_iter, tol, sync_every, workspace, 0, iwork, xTraj, uTraj, L, nullptr, converged, nullptr,
+                batch, T, stream};
+    if (const int rc = zm::cost_resolve(cost, track, zm::CostArg::exactly_one, who, &c.ck)) return rc;
+    if (ddp != 0) return zm::set_error(ZM_EUNSUPPORTED, "%s: DDP with recorded constraints is not built (ddp must be 0)", who);
+    if (batch < 0 || T < 1 || max_iter < 0 || sync_every < 1) return zm::set_error(ZM_EINVAL, "%s: bad size", who);
+    if (!(mu0 > 0.0) || !(growth >= 1.0) || !(mu_max >= mu0) || outer < 1 || !(ctol >= 0.0))
+        return zm::set_error(ZM_EINVAL, "%s: need mu0 > 0, growth >= 1, mu_max >= mu0, outer >= 1, ctol >= 0", who);
+    if (cost && (!cost->Q || !cost->R || !cost->Qf)) return zm::set_error(ZM_EINVAL, "%s: cost needs Q, R, Qf", who);
+    zm_model_t md;
+    if (const int rc = zm::model_check(model, who, &md)) return rc;
+    const int n = md.n, m = md.m;
+    if (model->n != n || model->m != m) return zm::set_error(ZM_EINVAL, "%s: the model's kind is (%d, %d)", who, n, m);
+    if (n < 1 || n > zm::MAXN || m < 1 || m > zm::MAXM)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: (n=%d, m=%d) not covered (traced constraint: n<=12, m<=4)", who, n, m);
+    if (md.kind == ZM_MODEL_TRACED && track)
+        return zm::set_error(ZM_EUNSUPPORTED, "%s: a traced model takes a zm_quadcost_t (the tracking cost on the tape interpreter is not "
+                                              "built)", who);
+    if (const int rc = zm::tracedcon_check(con, n, m, true, who)) return rc;
+    if ((int64_t)T * n * n >= (int64_t)1 << 31 || batch >= ((int64_t)1 << 31)) return zm::set_error(ZM_EUNSUPPORTED, "%s: T*n*n or batch too large", who);
+    const ConWs sw(model, batch, T);
+    if (sw.base < 0 || workspace_doubles < sw.total)
+        return zm::set_error(ZM_EINVAL, "%s: workspace of %lld doubles, %lld needed", who, (long long)workspace_doubles,
+                             (long long)(sw.base < 0 ? -1 : sw.total));
+    hipStream_t st = (hipStream_t)stream;
+    // the mask of the trajectories that are not done: the inner solve's own `active` mask (iwork) also drops what merely converged
+    int32_t* notdone = (int32_t*)(workspace + sw.notdone);
+    int32_t* remaining = (int32_t*)(workspace + sw.remaining);
+    const unsigned fb = (unsigned)((batch + 255) / 256);
+    hipLaunchKernelGGL(zm::fill_i32_kernel, dim3(fb), dim3(256), 0, st, (int*)notdone, (long)batch, 1);
+    hipLaunchKernelGGL(zm::fill_f64_kernel, dim3(fb), dim3(256), 0, st, con->mu, (long)batch, mu0);
+    if (con->n_con > 0) ZM_HIP_CHECK(hipMemsetAsync(con->lam, 0, sizeof(double) * batch * T * con->n_con, st));
+    if (con->n_con_terminal > 0) ZM_HIP_CHECK(hipMemsetAsync(con->lam_terminal, 0, sizeof(double) * batch * con->n_con_terminal, st));
+    ZM_HIP_CHECK(hipMemsetAsync(converged, 0, sizeof(int32_t) * batch, st));
+    if (outer_iterations) ZM_HIP_CHECK(hipMemsetAsync(outer_iterations, 0, sizeof(int32_t) * batch, st));
+    if (inner_iterations) ZM_HIP_CHECK(hipMemsetAsync(inner_iterations, 0, sizeof(int32_t) * batch * outer, st));
+    // the inner solves: the loop above on J_AL (written to the workspace; the caller's J receives the cost without the penalty)
+    c.workspace_doubles = sw.base;
+    c.J = workspace + sw.Jal;
+    zm::ConPen pen{};
+    return al_outer_loop(
+        c, outer, con->mu, violation, remaining, iterations, AlTraces{J_trace, alpha_trace, violation_trace, mu_trace},
+        [&](int j) {
+            pen = zm::ConPen{con, workspace + sw.sc_xx, workspace + sw.sc_ux, workspace + sw.sc_uu, workspace + sw.sv_xx, J,
+                             inner_iterations ? inner_iterations + (long)j * batch : nullptr, notdone, j == 0 ? uGuess : uTraj};
+            c.ck.con = &pen;
+        },
+        [&](int update) {
+            return zm_traced_con_multiplier_update_f64(con, xTraj, uTraj, notdone, converged, violation, outer_iterations, remaining, ctol,
+                                                       growth, mu_max, update, batch, T, stream);
+        });
+}
+
+extern "C" int zm_traced_con_solve_f64(const zm_model_t* model, const zm_quadcost_t* cost, const zm_trackcost_t* track,
+                                       const zm_tracedcon_t* con, double mu0, double growth, double mu_max, int outer, double ctol,
+                                       const double* x0, const double* uGuess, int ddp, int max_iter, double tol, int sync_every,
+                                       double* workspace, int64_t workspace_doubles, int32_t* iwork, double* xTraj, double* uTraj, double* L,
+                                       double* J, int32_t* converged, double* violation, int32_t* outer_iterations,
+                                       int32_t* inner_iterations, int32_t* iterations, int64_t batch, int T, void* stream) {
+    return zm_traced_con_solve_trace_f64(model, cost, track, con, mu0, growth, mu_max, outer, ctol, x0, uGuess, ddp, max_iter, tol,
+                                         sync_every, workspace, workspace_doubles, iwork, xTraj, uTraj, L, J, converged, violation,
+                                         outer_iterations, inner_iterations, iterations, batch, T, stream, nullptr, nullptr, nullptr,
+                                         nullptr);
 }
 
 extern "C" int zm_shutdown(void) { return zm::release_host_slots(); }

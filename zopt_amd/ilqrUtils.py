@@ -286,8 +286,26 @@ class ConstraintInfo(NamedTuple):
     innerIterations: object
 
 
+class TracedConstraintInfo(NamedTuple):
+    """`ConstraintInfo` of a `models.TracedConstraint` solve: per trajectory the largest pos(g) over the stage rows k = 0..N-1 and the
+    terminal row, the final penalty, the multipliers of the stage rows (..., N, n_con) and of the terminal row (..., n_con_terminal),
+    the outer iterations it took part in and its iLQR iterations in each of them (..., outer)."""
+    violation: object
+    mu: object
+    lam: object
+    lam_terminal: object
+    outerIterations: object
+    innerIterations: object
+
+
 def _rollout(x0, dynFun, policy, trajPrev, alphas, costFun):
     """Shared driver of trajectoryRollout / forwardPass2 on the rollout_linesearch kernel."""
+    if isinstance(dynFun, _models.TracedConstraint):
+        if costFun is not None:
+            raise ValueError("forwardPass2 takes no TracedConstraint: its cost would silently omit the constraints' penalty (the line "
+                             "search on the augmented-Lagrangian cost runs inside iterativeLqr / constrainedIterativeLqr; an array-level "
+                             "form is the follow-up)")
+        dynFun = dynFun.model         # the dynamics are unchanged
     if isinstance(dynFun, _models.StateBox):
         if costFun is not None:
             raise ValueError("forwardPass2 takes no StateBox: its cost would silently omit the state box's penalty (the line search on "
@@ -571,9 +589,13 @@ def constrainedIterativeLqr(dynamics, runningCost, terminalCost, x0, uGuess, max
     `|J_AL - J_AL,new| <= tol`) on the cost plus the penalty of the state box, then the multiplier and penalty update; a trajectory is
     done (`converged`) when its inner solve converged and its violation is <= the StateBox's `ctol`, and is not touched again.
 
-    Returns (traj, L, J, converged, info): `J` is the plain cost of the returned trajectory, `info` a `ConstraintInfo`."""
-    if not isinstance(dynamics, _models.StateBox):
-        raise TypeError("constrainedIterativeLqr: dynamics must be a zopt_amd.models.StateBox")
+    `dynamics` may also be a `models.TracedConstraint` (user-written constraints g(x, u) <= 0, terminal(x) <= 0 around a registered
+    model or a `TracedModel`): the same loop on the penalty of the recorded constraints.
+
+    Returns (traj, L, J, converged, info): `J` is the plain cost of the returned trajectory, `info` a `ConstraintInfo` (a
+    `TracedConstraintInfo` for a TracedConstraint)."""
+    if not isinstance(dynamics, (_models.StateBox, _models.TracedConstraint)):
+        raise TypeError("constrainedIterativeLqr: dynamics must be a zopt_amd.models.StateBox or a zopt_amd.models.TracedConstraint")
     return _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp=False, info=True)
 
 
@@ -610,6 +632,15 @@ def _ilqr_or_ddp_generic(dynamics, runningCost, terminalCost, x0, uGuess, maxIte
 
 def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, ddp, info=False):
     model = dynamics
+    con = model if isinstance(model, _models.TracedConstraint) else None
+    if con is not None:               # (before anything touches the device)
+        if ddp:
+            raise ValueError("differentialDynamicProgramming takes no TracedConstraint: DDP with recorded constraints is the follow-up "
+                             "to the augmented-Lagrangian iLQR (use iterativeLqr / constrainedIterativeLqr)")
+        if _models.traced_cost_of(runningCost, terminalCost) is not None:
+            raise TypeError("iterativeLqr: a TracedConstraint takes a QuadraticCost or a TrackingCost -- a TracedCost next to recorded "
+                            "constraints (per-point cost Hessians under the penalty's addend) is the follow-up")
+        model = con.model
     sbox = model if isinstance(model, _models.StateBox) else None
     if sbox is not None:
         if ddp:                       # (before anything touches the device)
@@ -652,6 +683,8 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     if tracking and (cost.n != n or cost.m != m):
         raise ValueError(f"the TrackingCost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
     md = _models.model_struct(model, lead)
+    if (tracking or not traced_cost) and (cost.n != n or cost.m != m) and con is not None:
+        raise ValueError(f"the cost is (n={cost.n}, m={cost.m}), the model (n={n}, m={m})")
     cs = cost.tcost_struct(tuple(lead)) if traced_cost else cost.track_struct(tuple(lead), N) if tracking else cost.c_struct()
     i32 = torch.int32
     L = torch.empty((B, N, m, n), dtype=dt, device=dev)
@@ -666,6 +699,14 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         viol = torch.zeros(B, dtype=dt, device=dev)
         outer_its = torch.zeros(B, dtype=i32, device=dev)
         inner_its = torch.zeros((sbox.outer, B), dtype=i32, device=dev)
+    if con is not None:               # likewise (TracedConstraintInfo)
+        lam = torch.zeros((B, N, con.n_con), dtype=dt, device=dev)
+        lam_t = torch.zeros((B, con.n_con_terminal), dtype=dt, device=dev)
+        mu = torch.empty(B, dtype=dt, device=dev)
+        viol = torch.zeros(B, dtype=dt, device=dev)
+        outer_its = torch.zeros(B, dtype=i32, device=dev)
+        inner_its = torch.zeros((con.outer, B), dtype=i32, device=dev)
+    al = sbox if sbox is not None else con      # the augmented-Lagrangian wrapper, if any
     if B:
         # The whole loop -- initial rollout (:293-298), per iteration expansions, PD-conditioned Hessians, backward pass, 16-way
         # line search, `converged = |J - J_new| <= tol` (:305-322) over the compacted list of still-active trajectories -- is ONE
@@ -678,8 +719,11 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         entry = f"zm_ilqr_solve_{family}{'trace_' if _TRACE is not None else ''}f64"
         if traced_cost:               # a recorded cost: the same loop behind its own entries (`tcost` in place of `cost`)
             entry = f"zm_traced_cost_solve_{'trace_' if _TRACE is not None else ''}f64"
+        if con is not None:           # recorded constraints: the state entries' loop behind its own (`con` in place of `sbox`)
+            entry = f"zm_traced_con_solve_{'trace_' if _TRACE is not None else ''}f64"
         pmd, pcs = ctypes.addressof(md), ctypes.addressof(cs)
-        nws = int(lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N) if sbox is not None else
+        nws = int(lib.zm_traced_con_solve_workspace_f64(pmd, B, N) if con is not None else
+                  lib.zm_ilqr_solve_state_workspace_f64(pmd, B, N) if sbox is not None else
                   lib.zm_traced_cost_solve_workspace_f64(pmd, pcs, B, N, 1 if ddp else 0) if traced_cost else
                   lib.zm_ilqr_solve_workspace_f64(pmd, B, N, 1 if ddp else 0))
         if nws < 0:
@@ -687,7 +731,8 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
         ws = torch.empty(nws, dtype=dt, device=dev)
         iwork = torch.empty(2 * B + 2, dtype=i32, device=dev)
         its = ctypes.c_int32(0)
-        d = {"model": pmd, "cost": None if tracking and family in ("state_", "box_") else pcs, "track": pcs if tracking else None,
+        d = {"model": pmd, "cost": None if tracking and (family in ("state_", "box_") or con is not None) else pcs,
+             "track": pcs if tracking else None,
              "tcost": pcs if traced_cost else None,
              "x0": dx0.data_ptr(), "uGuess": dug.data_ptr(), "ddp": 1 if ddp else 0, "max_iter": int(maxIter), "tol": float(tol),
              "sync_every": max(1, int(os.environ.get("ZOPT_AMD_ILQR_SYNC", "4"))), "workspace": ws.data_ptr(),
@@ -701,25 +746,30 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
             ss = sbox.statebox_struct(tuple(lead), lam_lb, lam_ub, mu)
             d.update(sbox=ctypes.addressof(ss), mu0=sbox.mu0, growth=sbox.growth, mu_max=sbox.mu_max, outer=sbox.outer, ctol=sbox.ctol,
                      violation=viol.data_ptr(), outer_iterations=outer_its.data_ptr(), inner_iterations=inner_its.data_ptr())
+        if con is not None:
+            cc = con.con_struct(tuple(lead), lam, lam_t, mu)
+            d.update(con=ctypes.addressof(cc), mu0=con.mu0, growth=con.growth, mu_max=con.mu_max, outer=con.outer, ctol=con.ctol,
+                     violation=viol.data_ptr(), outer_iterations=outer_its.data_ptr(), inner_iterations=inner_its.data_ptr())
         if _TRACE is not None:        # (outer, maxIter, batch) rows for a state box, (maxIter, batch) otherwise
-            outer = sbox.outer if sbox is not None else 1
+            outer = al.outer if al is not None else 1
             Jtr = torch.full((outer * max(int(maxIter), 1), B), float("nan"), dtype=dt, device=dev)
             atr = torch.full((outer * max(int(maxIter), 1), B), -1, dtype=i32, device=dev)
             d.update(J_trace=Jtr.data_ptr(), alpha_trace=atr.data_ptr())
-            if sbox is not None:
+            if al is not None:
                 vtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
                 mtr = torch.full((outer, B), float("nan"), dtype=dt, device=dev)
                 d.update(violation_trace=vtr.data_ptr(), mu_trace=mtr.data_ptr())
-        rc = getattr(lib, entry)(*[d[k] for k in (_lib.TRACED_COST_SOLVE_ARGS if traced_cost else _lib.SOLVE_ARGS)[entry]])
+        names = _lib.TRACED_CON_SOLVE_ARGS if con is not None else _lib.TRACED_COST_SOLVE_ARGS if traced_cost else _lib.SOLVE_ARGS
+        rc = getattr(lib, entry)(*[d[k] for k in names[entry]])
         _lib.check(rc, "differentialDynamicProgramming" if ddp else "iterativeLqr")
         if _TRACE is not None:
             o = int(its.value)        # iLQR / DDP iterations; outer iterations of a state-box solve
-            if sbox is not None:
+            if al is not None:
                 Jtr, atr = Jtr.reshape(outer, -1, B), atr.reshape(outer, -1, B)
             _TRACE.append(("iterations", o))
             _TRACE.append(("J_trace", Jtr[:o].cpu().numpy()))
             _TRACE.append(("alpha_trace", atr[:o].cpu().numpy()))
-            if sbox is not None:
+            if al is not None:
                 _TRACE.append(("violation_trace", vtr[:o].cpu().numpy()))
                 _TRACE.append(("mu_trace", mtr[:o].cpu().numpy()))
                 _TRACE.append(("inner_trace", inner_its[:o].cpu().numpy()))
@@ -735,11 +785,13 @@ def _ilqr_or_ddp(dynamics, runningCost, terminalCost, x0, uGuess, maxIter, tol, 
     if not arr.is_torch(tmpl) and len(lead) == 0:
         Jo, co = float(Jo), bool(co)
     if info:
-        fl = [viol.reshape(lead), mu.reshape(lead), lam_lb.reshape(lead + (N + 1, n)), lam_ub.reshape(lead + (N + 1, n))]
+        fl = [viol.reshape(lead), mu.reshape(lead)]
+        fl += ([lam.reshape(lead + (N, con.n_con)), lam_t.reshape(lead + (con.n_con_terminal,))] if con is not None else
+               [lam_lb.reshape(lead + (N + 1, n)), lam_ub.reshape(lead + (N + 1, n))])
         if fp32_in:
             fl = [o.to(torch.float32) for o in fl]
         res = [arr.result_like(o, tmpl) for o in fl]
         res += [arr.result_like(outer_its.reshape(lead), tmpl),
-                arr.result_like(inner_its.transpose(0, 1).contiguous().reshape(lead + (sbox.outer,)), tmpl)]
-        return Trajectory(xo, uo), Lo, Jo, co, ConstraintInfo(*res)
+                arr.result_like(inner_its.transpose(0, 1).contiguous().reshape(lead + (al.outer,)), tmpl)]
+        return Trajectory(xo, uo), Lo, Jo, co, (TracedConstraintInfo if con is not None else ConstraintInfo)(*res)
     return Trajectory(xo, uo), Lo, Jo, co

@@ -150,6 +150,13 @@ def model_struct(model, lead):
     return model.c_struct(tuple(lead)) if isinstance(model, TracedModel) else model.c_struct()
 
 
+def refuse_traced_constraint(model, who):
+    """A TracedConstraint inside a box, refused before anything touches the device"""
+    if isinstance(model, TracedConstraint):
+        raise TypeError(f"{who}: a TracedConstraint takes no InputBox / StateBox around it -- clipped inputs and a state box next to "
+                        "recorded constraints are the follow-up (write the bounds as rows of g)")
+
+
 def refuse_traced(model, who, follow_up):
     """The combinations a TracedModel is not built for yet, refused before anything touches the device"""
     if isinstance(model, TracedModel):
@@ -538,6 +545,7 @@ class InputBox:
             raise TypeError("InputBox: the model is an InputBox already")
         if isinstance(model, StateBox):
             raise TypeError("InputBox: a StateBox is the outer wrapper -- write StateBox(InputBox(model, u_lb, u_ub), x_lb, x_ub)")
+        refuse_traced_constraint(model, "InputBox")
         refuse_traced(model, "InputBox", "the box-QP line search and sweeps on the tape interpreter are the follow-up")
         if not hasattr(model, "c_struct"):
             raise TypeError("InputBox wraps a registered device model (zopt_amd.models.*); the generic-callable path has no box: clip "
@@ -674,6 +682,7 @@ class StateBox:
     def __init__(self, model, x_lb, x_ub, mu0=1.0, growth=10.0, mu_max=1e8, outer=10, ctol=1e-4):
         if isinstance(model, StateBox):
             raise TypeError("StateBox: the model is a StateBox already")
+        refuse_traced_constraint(model, "StateBox")
         inner = model.model if isinstance(model, InputBox) else model
         if isinstance(model, InputBox) and model.stage_varying:
             raise TypeError("StateBox: a stage-varying InputBox inside a StateBox is the follow-up -- the penalty line search and sweep "
@@ -728,3 +737,136 @@ class StateBox:
         st = zm_statebox_t(lb.data_ptr(), ub.data_ptr(), stride, lam_lb.data_ptr(), lam_ub.data_ptr(), mu.data_ptr())
         st._owner = (self, lb, ub, lam_lb, lam_ub, mu)      # raw device addresses: keep the arrays behind them alive with the struct
         return st
+
+
+class zm_tracedcon_t(ctypes.Structure):
+    _fields_ = [("stage", zm_traced_t), ("terminal", zm_traced_t), ("n", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("n_con", ctypes.c_int32), ("n_con_terminal", ctypes.c_int32), ("lam", ctypes.c_void_p),
+                ("lam_terminal", ctypes.c_void_p), ("mu", ctypes.c_void_p)]
+
+
+TRACEDCON_MAX = 8     # rows per tape (ZM_TRACEDCON_MAX)
+
+
+class TracedConstraint:
+    """A registered model or a `TracedModel` with user-written inequality constraints: `g(x, u)` or `g(x, u, p)` returns `n_con`
+    values, enforced as `g <= 0` at every stage k = 0..N-1 on (x_k, u_k) (stage 0 included: u_0 is free); `terminal(x)` or
+    `terminal(x, p)` returns `n_con_terminal` values, enforced on x_N.  At least one of the two is given (`g=None`: n_con = 0).  Both
+    are recorded ONCE by the recorder of `TracedModel` (zopt_amd/tape.py: `+ - * /`, unary minus, `** k`, np.sin / cos / tan / sqrt,
+    indexing, np.array, np.concatenate, `@`, np.cross; no branches on the data) and evaluated by the tape interpreter inside the
+    line-search, expansion and multiplier-update kernels of an augmented-Lagrangian loop around the fused iLQR (AL-iLQR, as `StateBox`):
+    penalty sum_i (pos(lam_i + mu g_i)^2 - lam_i^2) / (2 mu), its gradient G^T pos(s) and Gauss-Newton Hessian mu G^T diag(s > 0) G on
+    dual numbers (no second derivatives of g).  An extension: the reference's iLQR is unconstrained (ilqrUtils.py:260-327).
+
+    params: None, (np,) or (..., np) with leading axes that broadcast to the batch of the call, as `TracedCost.params`: per-problem
+    constants (an obstacle centre and radius per trajectory), np <= 8.  Caps: those of `TracedModel` per tape (n <= 12, m <= 4, 1024
+    instructions, 64 live slots, 256 constants), n_con <= 8, n_con_terminal <= 8: ValueError beyond.
+    mu0, growth, mu_max, outer, ctol: as `StateBox`.
+
+    Accepted by `iterativeLqr` and `constrainedIterativeLqr` with a `QuadraticCost` or (registered models) a `TrackingCost`.
+    `trajectoryRollout` and the simulator unwrap it.  Refused (the follow-up): `differentialDynamicProgramming`, `forwardPass2`, a
+    `TracedCost` next to it, an `InputBox` or `StateBox` inside or around it, the generic torch-callable path."""
+
+    def __init__(self, model, g, n_con, terminal=None, n_con_terminal=0, params=None, mu0=1.0, growth=10.0, mu_max=1e8, outer=10,
+                 ctol=1e-4):
+        from . import tape as _tape
+        if isinstance(model, (InputBox, StateBox, TracedConstraint)):
+            raise TypeError("TracedConstraint: an InputBox / StateBox / TracedConstraint inside a TracedConstraint is the follow-up -- "
+                            "the penalty line search takes no clipped inputs and no second penalty (write the bounds as rows of g)")
+        if not hasattr(model, "c_struct"):
+            raise TypeError("TracedConstraint wraps a registered device model (zopt_amd.models.*) or a TracedModel; constraints on the "
+                            "generic torch-callable path are the follow-up")
+        if g is None and terminal is None:
+            raise ValueError("TracedConstraint: give g, terminal, or both")
+        if not (g is None or callable(g)) or not (terminal is None or callable(terminal)):
+            raise TypeError("TracedConstraint: g must be a callable g(x, u) or g(x, u, p), terminal a callable t(x) or t(x, p), or None")
+        self.model, self.n, self.m = model, int(model.n), int(model.m)
+        self.n_con = 0 if g is None else int(n_con)
+        self.n_con_terminal = 0 if terminal is None else int(n_con_terminal)
+        if g is not None and not 1 <= self.n_con <= TRACEDCON_MAX:
+            raise ValueError(f"TracedConstraint: n_con = {self.n_con}, need 1 <= n_con <= {TRACEDCON_MAX}")
+        if terminal is not None and not 1 <= self.n_con_terminal <= TRACEDCON_MAX:
+            raise ValueError(f"TracedConstraint: n_con_terminal = {self.n_con_terminal}, need 1 <= n_con_terminal <= {TRACEDCON_MAX}")
+        self.mu0, self.growth, self.mu_max, self.outer, self.ctol = float(mu0), float(growth), float(mu_max), int(outer), float(ctol)
+        if not self.mu0 > 0 or not self.growth >= 1 or not self.mu_max >= self.mu0 or self.outer < 1 or not self.ctol >= 0:
+            raise ValueError("TracedConstraint: need mu0 > 0, growth >= 1, mu_max >= mu0, outer >= 1, ctol >= 0")
+        self.params = None
+        if params is not None:
+            self.params = params if arr.is_torch(params) else np.asarray(params, dtype=np.float64)
+            if len(self.params.shape) < 1 or self.params.shape[-1] < 1:
+                raise ValueError(f"TracedConstraint: params has shape {tuple(self.params.shape)}, expected (np,) or (..., np)")
+        self.n_params = 0 if self.params is None else int(self.params.shape[-1])
+        self._g, self._terminal = g, terminal
+        self.stage_tape = None if g is None else _tape.record(g, self.n, self.m, self.n_params, n_out=self.n_con, who="TracedConstraint")
+        self.terminal_tape = None if terminal is None else _tape.record(terminal, self.n, self.m, self.n_params,
+                                                                        n_out=self.n_con_terminal, controls=False,
+                                                                        who="TracedConstraint")
+        self._dev = {}
+
+    def _row(self, p):
+        if p is None:
+            p = self.params.detach().cpu().numpy() if arr.is_torch(self.params) else self.params
+            if p.ndim != 1:
+                raise ValueError("TracedConstraint: pass the parameter row p of this point (params has batch axes)")
+        return p
+
+    def g(self, x, u, p=None):
+        """the stage callable itself on numeric arrays"""
+        return np.asarray(self._g(x, u, self._row(p)) if self.n_params else self._g(x, u), dtype=np.float64).reshape(-1)
+
+    def terminal(self, x, p=None):
+        return np.asarray(self._terminal(x, self._row(p)) if self.n_params else self._terminal(x), dtype=np.float64).reshape(-1)
+
+    def con_struct(self, lead, lam=None, lam_terminal=None, mu=None):
+        """zm_tracedcon_t for a call with batch axes `lead` on the caller's device arrays for the multipliers and the penalty (None:
+        a call that reads none of them)"""
+        import torch
+        from . import tape as _tape
+        pdev, stride = None, 0
+        if self.n_params:
+            shp = tuple(int(d) for d in self.params.shape)
+            if all(d == 1 for d in shp[:-1]):
+                key = "shared"
+                if key not in self._dev:
+                    self._dev[key] = arr.to_device(self.params, torch.float64).reshape(self.n_params).contiguous()
+            else:
+                key = tuple(int(d) for d in lead)
+                if key not in self._dev:
+                    full = key + (self.n_params,)
+                    if len(shp) > len(full) or any(a != 1 and a != b for a, b in zip(shp[::-1], full[::-1])):
+                        raise ValueError(f"TracedConstraint: leading axes {shp[:-1]} of params do not broadcast to the batch {key}")
+                    self._dev[key] = arr.to_device(self.params, torch.float64).expand(full).reshape(-1, self.n_params).contiguous()
+                stride = self.n_params
+            pdev = self._dev[key]
+        if "blobs" not in self._dev:
+            self._dev["blobs"] = tuple(None if t is None else arr.to_device(_tape.blob(t).view(np.float64), torch.float64)
+                                       for t in (self.stage_tape, self.terminal_tape))
+        blobs = self._dev["blobs"]
+        pp = None if pdev is None else pdev.data_ptr()
+        tapes = [zm_traced_t(None, None, 0, 0, 0, 0, 0) if t is None else
+                 zm_traced_t(b.data_ptr(), pp, stride, len(t.code), len(t.consts), t.n_slots, self.n_params)
+                 for b, t in zip(blobs, (self.stage_tape, self.terminal_tape))]
+        ptr = lambda t: None if t is None else t.data_ptr()                                                    # noqa: E731
+        st = zm_tracedcon_t(tapes[0], tapes[1], self.n, self.m, self.n_con, self.n_con_terminal, ptr(lam), ptr(lam_terminal), ptr(mu))
+        st._owner = (self, blobs, pdev, lam, lam_terminal, mu)      # raw device addresses: keep the arrays behind them alive
+        return st
+
+    def values(self, xTraj, uTraj):
+        """(g (..., N, n_con), terminal (..., n_con_terminal)) along trajectories xTraj (..., N+1, n), uTraj (..., N, m), evaluated on
+        the device by the interpreter (the bits of a host build of it); NumPy in -> NumPy out, torch in -> torch out"""
+        import torch
+        from . import _lib
+        shp = tuple(arr.shape(uTraj))
+        lead, (N, m) = shp[:-2], shp[-2:]
+        if m != self.m or tuple(arr.shape(xTraj)) != lead + (N + 1, self.n):
+            raise ValueError(f"TracedConstraint.values: xTraj {tuple(arr.shape(xTraj))} / uTraj {shp} do not match (n={self.n}, m={self.m})")
+        cs = self.con_struct(lead)            # (the parameter rows are checked before anything else touches the device)
+        dx, du = (arr.to_device(X, torch.float64).contiguous() for X in (xTraj, uTraj))
+        B = arr.batch(lead)
+        gs = torch.zeros(lead + (N, self.n_con), dtype=torch.float64, device=dx.device)
+        gt = torch.zeros(lead + (self.n_con_terminal,), dtype=torch.float64, device=dx.device)
+        rc = _lib.lib().zm_traced_con_values_f64(ctypes.addressof(cs), dx.data_ptr(), du.data_ptr(), gs.data_ptr() if self.n_con else None,
+                                                 gt.data_ptr() if self.n_con_terminal else None, B, N,
+                                                 ctypes.c_void_p(arr.stream_ptr(dx)))
+        _lib.check(rc, "TracedConstraint.values")
+        return arr.result_like(gs, uTraj), arr.result_like(gt, uTraj)

@@ -16,7 +16,8 @@ names the n slots that hold x+ at the end.  An operand flagged as a constant ind
 
 `models.TracedCost` records its two cost callables with the same recorder (`record(..., n_out=1)`: one output; `controls=False` for
 terminalCost(x[, p]), whose tape keeps the control slots reserved and unread so that both tapes share the layout x, u, p); the device
-side is zopt_amd/csrc/tape_cost.h.
+side is zopt_amd/csrc/tape_cost.h.  `models.TracedConstraint` records g(x, u[, p]) and terminal(x[, p]) likewise, with `n_out = n_con`
+resp. `n_con_terminal` outputs (device side: zopt_amd/csrc/tape_con.h).
 """
 from __future__ import annotations
 
