@@ -312,23 +312,40 @@ class _Sym:
         return _Sym(sympy.sqrt(self.e))
 
 
-def sympy_call(f, xs, us):
+def sympy_call(f, xs, us, ps=None):
+    """the expressions `f` builds, one per output (an output that is a plain number becomes a sympy number)"""
     box = lambda a: np.array([_Sym(v) for v in a] + [None], dtype=object)[:-1]          # noqa: E731
-    return [o.e for o in f(box(xs), box(us))]
+    out = f(box(xs), box(us)) if ps is None else f(box(xs), box(us), box(ps))
+    return [o.e if isinstance(o, _Sym) else _Sym._e(o) for o in np.asarray(out, dtype=object).reshape(-1)]
 
 
-def sympy_hessian(f, n, m, x, u):
-    """H (P, n, n + m, n + m) in long double: sympy derivatives of the expression `f` builds (constants at their float64 values)"""
+def _mp_to_ld(v):
+    hi = float(v)
+    return np.longdouble(hi) + np.longdouble(float(v - hi)) if np.isfinite(hi) else np.longdouble(hi)
+
+
+def sympy_hessian(f, n, m, x, u, p=None, exact=False):
+    """H (P, n_out, n + m, n + m) in long double: sympy derivatives of the expression `f` builds (constants at their float64 values).
+    The default evaluation is the lambdified NumPy code on long-double arrays, whose numeric literals are float64: a constant that
+    sympy folded from two of the callable's (0.3 * 0.4) is rounded to 2^-53.  exact=True evaluates with mpmath at 128 bits instead, the
+    result rounded once to long double (slow: a few points of a small model)."""
     import sympy
     z = sympy.symbols(f"z0:{n + m}", real=True)
-    exprs = sympy_call(f, z[:n], z[n:])
-    zz = np.concatenate([x, u], 1)
-    Hs = np.zeros((len(x), n, n + m, n + m), dtype=np.longdouble)
-    for i in range(n):
+    q = sympy.symbols(f"q0:{max(1, 0 if p is None else np.shape(p)[-1])}", real=True)
+    exprs = sympy_call(f, z[:n], z[n:], None if p is None else q)
+    zz = np.concatenate([x, u] + ([] if p is None else [np.broadcast_to(np.atleast_2d(p), (len(x), np.shape(p)[-1]))]), 1)
+    syms = tuple(z) + (() if p is None else tuple(q))
+    Hs = np.zeros((len(x), len(exprs), n + m, n + m), dtype=np.longdouble)
+    for i in range(len(exprs)):
         for a in range(n + m):
             for b in range(a, n + m):
                 d = sympy.diff(exprs[i], z[a], z[b])
-                if d != 0:
-                    fn = sympy.lambdify(z, d, modules="numpy")
-                    Hs[:, i, a, b] = Hs[:, i, b, a] = fn(*[zz[:, k].astype(np.longdouble) for k in range(n + m)])
+                if d != 0 and exact:
+                    import mpmath
+                    fn = sympy.lambdify(syms, d, modules="mpmath")
+                    with mpmath.workprec(128):
+                        Hs[:, i, a, b] = Hs[:, i, b, a] = [_mp_to_ld(fn(*[mpmath.mpf(float(v)) for v in row])) for row in zz]
+                elif d != 0:
+                    fn = sympy.lambdify(syms, d, modules="numpy")
+                    Hs[:, i, a, b] = Hs[:, i, b, a] = fn(*[zz[:, k].astype(np.longdouble) for k in range(zz.shape[1])])
     return Hs

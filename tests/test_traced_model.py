@@ -16,6 +16,7 @@ from oracle import zopt_oracle as zo
 from tests import model_hp_ref as hp
 from tests import tape_ref as R
 from tests import trig_host
+from tests.tape_fuzz import Boxed            # (the operator-protocol float64; `**` is the recorder's product for k = 1..8)
 from zopt_amd import models, tape as T
 
 WIND = np.array([3.0, 1.0, 0.0])
@@ -26,33 +27,6 @@ FUNCS = {
     "car": (R.car, 4, 2),
     "cartpole": (R.cartpole, 4, 1),
 }
-
-
-class Boxed:
-    """a float64 behind the operator protocol the recording goes through (NumPy object arrays call these per element)"""
-    __slots__ = ("v",)
-
-    def __init__(self, v):
-        self.v = np.float64(v)
-
-    @staticmethod
-    def _v(o):
-        return o.v if isinstance(o, Boxed) else np.float64(o)
-
-    def __add__(self, o): return Boxed(self.v + self._v(o))
-    def __radd__(self, o): return Boxed(self._v(o) + self.v)
-    def __sub__(self, o): return Boxed(self.v - self._v(o))
-    def __rsub__(self, o): return Boxed(self._v(o) - self.v)
-    def __mul__(self, o): return Boxed(self.v * self._v(o))
-    def __rmul__(self, o): return Boxed(self._v(o) * self.v)
-    def __truediv__(self, o): return Boxed(self.v / self._v(o))
-    def __rtruediv__(self, o): return Boxed(self._v(o) / self.v)
-    def __neg__(self): return Boxed(-self.v)
-    def __pow__(self, k): return Boxed(self.v * self.v) if k == 2 else NotImplemented
-    def sin(self): return Boxed(np.sin(self.v))
-    def cos(self): return Boxed(np.cos(self.v))
-    def tan(self): return Boxed(np.tan(self.v))
-    def sqrt(self): return Boxed(np.sqrt(self.v))
 
 
 def boxed_call(f, x, u):
